@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- BASELINE.json's headline metric on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
   N > 1: one rank per GPU under torch.distributed.run.  Started WITHOUT the torchrun
   environment (WORLD_SIZE unset) the script starts the N ranks itself, as fresh child
   processes, before anything in this process touches the GPU, and exits with their code.
@@ -19,6 +19,10 @@ Prints ONE JSON line (rank 0) with the contract fields plus
                its mean duration from HIP events on the launch stream; peak 8 TB/s
   cpu_baseline the oracle's C port (scalar, 1 thread) on a bounded sample of the
                same batch, timed on this box's host cores (rank 0, N == 1 only)
+
+--dump-outputs DIR writes what rank 0's last timed step computed (see dump_outputs) so
+that two builds can be compared output for output; the batch is seeded, so the same
+arguments give the same inputs on every run.
 """
 from __future__ import annotations
 
@@ -34,6 +38,11 @@ sys.path.insert(0, ROOT)
 
 PATTERN = b"[a-z]+\\d+"
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak, /opt/skills/guides/MI355X_MICROARCH.md
+# --dump-outputs: rows kept per array.  Float64 values plus float64 row numbers when sampled:
+# 2^21 x 8 B x 2 (counts_prefix) + 2^20 x 16 B + 2^20 x 8 B (spans) = 56 MiB, under the 64 MB cap.
+DUMP_PREFIX_ROWS = 1 << 21
+DUMP_SPAN_ROWS = 1 << 20
+DUMP_SEED = 20260103
 
 
 def _host_info():
@@ -172,6 +181,43 @@ def measured_traffic(n: int, L: int):
     return best
 
 
+def _sample_rows(t, max_rows: int, seed: int):
+    """(rows of device tensor t as float64 numpy, their row numbers or None).  Every row when t has at most
+    max_rows of them; otherwise one row drawn uniformly (fixed seed) from each of max_rows equal strata, so the
+    sample is sorted, has no repeats and depends only on the seed and t's row count."""
+    import numpy as np
+    import torch
+    m = t.shape[0]
+    if m <= max_rows:
+        return t.double().cpu().numpy(), None
+    k = np.arange(max_rows + 1, dtype=np.int64)
+    lo = k[:-1] * m // max_rows
+    width = k[1:] * m // max_rows - lo
+    rows = lo + (np.random.default_rng(seed).random(max_rows) * width).astype(np.int64)
+    return t.index_select(0, torch.from_numpy(rows).to(t.device)).double().cpu().numpy(), rows
+
+
+def dump_outputs(out_dir: str, prefix, spans, n: int):
+    """What the caller of findall_async receives, as DIR/<name>.npy in float64:
+      counts_prefix  int64[n + 1] CSR offsets (text i's spans are rows prefix[i] .. prefix[i + 1] - 1 of spans)
+      spans          int32[total, 2] [start, end) byte offsets of every match, total = prefix[n]
+    An array longer than its row budget (DUMP_*_ROWS) is a fixed seeded sample of its rows, and <name>_rows.npy
+    holds the row numbers taken.  Returns {name: shape} of the files written."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    total = int(prefix[n].item())
+    written = {}
+    for name, t, cap in (("counts_prefix", prefix[: n + 1], DUMP_PREFIX_ROWS),
+                         ("spans", spans[:total], DUMP_SPAN_ROWS)):
+        vals, rows = _sample_rows(t, cap, DUMP_SEED)
+        np.save(os.path.join(out_dir, name + ".npy"), vals)
+        written[name] = list(vals.shape)
+        if rows is not None:
+            np.save(os.path.join(out_dir, name + "_rows.npy"), rows.astype(np.float64))
+            written[name + "_rows"] = list(rows.shape)
+    return written
+
+
 def launch_ranks(n: int, share: bool) -> int:
     """Start `python -m torch.distributed.run --nproc-per-node n bench.py <same args>` as a child
     process (one rank per GPU over RCCL) and return its exit code.  Called before this process has
@@ -224,10 +270,16 @@ def main():
     ap.add_argument("--no-extras", action="store_true",
                     help="N > 1: skip the extra legs (results exchange on the headline batch, config 3's per-GPU share)")
     ap.add_argument("--c3-texts", type=int, default=1 << 23, help="texts per GPU of the config-3 leg (256 B each)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what rank 0's last timed step computed as DIR/<name>.npy "
+                         "(float64, at most 64 MB in all; a larger array is a fixed seeded sample of its rows, "
+                         "their row numbers in DIR/<name>_rows.npy)")
     args = ap.parse_args()
 
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0 or args.settle < 0:
+        raise SystemExit("--steps must be >= 1, --warmup and --settle >= 0")
     share = bool(os.environ.get("MRX_BENCH_SHARE_GPU"))
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # Not under torchrun: start the ranks as fresh children.  Nothing in this process has
@@ -309,6 +361,10 @@ def main():
     total = int(prefix[n].item())
     if total > span_cap:
         raise SystemExit("span buffer too small (%d > %d): result incomplete, run invalid" % (total, span_cap))
+    # read back now, outside the timed region: the legs below write into the same buffers
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, *outs[(args.steps - 1) % nstreams], n)
 
     agg = D.combine(world, elapsed, {"bytes": float(n) * L * args.steps,
                                      "matches": float(total) * args.steps},
@@ -447,6 +503,8 @@ def main():
             line["other_ops"] = other
         if strong_info is not None:
             line["strong"] = strong_info
+        if dumped is not None:
+            line["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
 
     # ---- scan + results exchange (results stay sharded in the headline) -----------------------------
     # the one optional exchange step, "results only".  With the nccl backend it runs behind the
