@@ -254,6 +254,45 @@ int mrx_split_strided_dev(const mrx_handle* h, const uint8_t* d_data, int64_t st
                           int64_t n, int64_t maxsplit, int64_t* d_piece_prefix, int32_t* d_pieces, int64_t piece_cap,
                           int64_t* total, void* stream);
 
+/* ---- pattern sets: one batch against k patterns in one call ------------------------------------------------------
+ * The reference matches one pattern per call; a set answers k of them per text.  Member j's answer for text i is
+ * exactly what the single-pattern call on member j's own handle returns for it (so: what the reference's search /
+ * len(findall) returns).  Members whose single-pattern search or count runs the streaming kernel's one
+ * left-to-right walk share ONE pass over the texts (several for more than 32 such members: each pass reads the
+ * batch again); every other member runs its own single-pattern call into scratch.  Which of the two a call takes
+ * depends only on the set, the operation and the batch shape, never on timing; as measured so far the members' own
+ * calls win at every set size, so they are the default for every member.  The results never depend on it.  Layouts and argument rules are those of the single-pattern _dev entry points.
+ *
+ * Compile: options are those of the single-pattern compile, applied to every member; 1 <= k <= 256
+ * (MRX_E_ARGUMENT otherwise).  A syntax error in any member fails the whole compile with MRX_E_SYNTAX, and the
+ * message reads "member j: <the reference's message>".  A member that refuses an operation makes the operation
+ * MRX_E_UNSUPPORTED for the set ("member j: <reason>"), reported before anything is enqueued.
+ *
+ * Output layout: text-major, text i / member j at i*k + j.  search: d_start / d_end int32[n][k], -1/-1 = no match.
+ * count: int32[n][k] matches per member (len(findall)).  matches: uint64 words, ceil(k/64) per text; bit j % 64 of
+ * word d_bits[i * ceil(k/64) + j / 64] is set when member j's search finds a match in text i.  That is a SEARCH
+ * hit, not the single-pattern is_match operation, whose DFA first-byte quirk (dfa.mojo:1815-1849) answers some texts
+ * differently.  Nothing is synchronised: the calls enqueue their work on `stream` and return. */
+typedef struct mrx_set mrx_set;
+int mrx_set_compile(const char* const* patterns, const size_t* lens, int32_t k, uint32_t options, mrx_set** out);
+void mrx_set_free(mrx_set* s);
+int32_t mrx_set_size(const mrx_set* s);
+/* per member: its route for each operation ("shared(pass P/p, column g.m | class c)" or "own" with the reason);
+ * returns the bytes needed (excluding NUL), writes at most cap */
+size_t mrx_set_describe(const mrx_set* s, char* buf, size_t cap);
+int mrx_set_search_dev(const mrx_set* s, const uint8_t* d_data, const int64_t* d_offsets, int64_t n,
+                       int32_t* d_start, int32_t* d_end, void* stream);
+int mrx_set_search_strided_dev(const mrx_set* s, const uint8_t* d_data, int64_t stride, const int32_t* d_lens,
+                               int32_t len, int64_t n, int32_t* d_start, int32_t* d_end, void* stream);
+int mrx_set_count_dev(const mrx_set* s, const uint8_t* d_data, const int64_t* d_offsets, int64_t n,
+                      int32_t* d_counts, void* stream);
+int mrx_set_count_strided_dev(const mrx_set* s, const uint8_t* d_data, int64_t stride, const int32_t* d_lens,
+                              int32_t len, int64_t n, int32_t* d_counts, void* stream);
+int mrx_set_matches_dev(const mrx_set* s, const uint8_t* d_data, const int64_t* d_offsets, int64_t n,
+                        uint64_t* d_bits, void* stream);
+int mrx_set_matches_strided_dev(const mrx_set* s, const uint8_t* d_data, int64_t stride, const int32_t* d_lens,
+                                int32_t len, int64_t n, uint64_t* d_bits, void* stream);
+
 /* ---- host-buffer convenience wrappers (copy in, run, copy out) -------------- */
 int mrx_match_first_batch(const mrx_handle* h, const uint8_t* data,
                           const int64_t* offsets, int64_t n, int32_t* start,

@@ -96,6 +96,15 @@ int mrx_testing_comm_shift(const int64_t* d_prefix, int64_t n_local, const int64
 int mrx_testing_comm_compact(const int64_t* d_meta_all, int meta_stride, int nranks, const int64_t* d_stage_prefix, int64_t P,
                              const int32_t* d_stage_spans, int64_t cap, int64_t* d_gprefix, int64_t gprefix_cap,
                              int32_t* d_gspans, int64_t gspans_cap, int32_t* d_status, void* stream);
+/* Pattern sets (include/mrx.h): 0 = the route rule (the members' own calls: measured faster at every set size), 1 = the
+ * shared pass for every member that is eligible whatever the
+ * batch shape, 2 = every member through its own single-pattern call.  Results are the same. */
+void mrx_debug_set_route(int mode);
+/* The packed tables of a set walked on the CPU over ONE text, as the shared-pass kernel walks them, for tests that pin
+ * the packing to the oracle without a GPU.  op: 0 count (out[k]), 1 search (out[2 k]: start, end), 2 matches (out[k]:
+ * 0 / 1).  Members outside the shared pass of that operation get -2. */
+struct mrx_set;
+int mrx_testing_set_run(const struct mrx_set* s, int op, const uint8_t* text, int len, int32_t* out);
 /* Bytes of device memory the calling thread's scratch arenas hold (see mrx_release_scratch). */
 size_t mrx_debug_scratch_bytes(void);
 

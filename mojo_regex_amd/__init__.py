@@ -16,6 +16,7 @@ argument meaning, a *batch* of texts instead of one text:
     match_first / search / findall    :1325-1415  match_first / search / findall
     split / sub                       :1357,1857  split / sub
     clear_regex_cache()               :1318       clear_regex_cache()
+    (none: one pattern per call)                  PatternSet / compile_set(patterns): k at once
 
 All matching runs in the HIP kernels of libmrx_hip.so.  There is no CPU
 fallback: if the library is missing or no GPU is usable, calls raise.
@@ -26,10 +27,12 @@ from .api import (  # noqa: F401
     CompiledRegex,
     DeviceBatch,
     MrxError,
+    PatternSet,
     RegexSyntaxError,
     UnsupportedPattern,
     clear_regex_cache,
     compile_regex,
+    compile_set,
     findall,
     library_path,
     load_library,

@@ -149,6 +149,19 @@ def load_library():
         "mrx_testing_comm_shift": (C.c_int, [i64p, C.c_int64, i64p, C.c_int, C.c_int, i64p, C.c_int64, C.c_void_p]),
         "mrx_testing_comm_compact": (C.c_int, [i64p, C.c_int, C.c_int, i64p, C.c_int64, i32p, C.c_int64, i64p, C.c_int64,
                                                i32p, C.c_int64, i32p, C.c_void_p]),
+        # pattern sets
+        "mrx_set_compile": (C.c_int, [C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int32, C.c_uint32, C.POINTER(H)]),
+        "mrx_set_free": (None, [H]),
+        "mrx_set_size": (C.c_int32, [H]),
+        "mrx_set_describe": (C.c_size_t, [H, C.c_char_p, C.c_size_t]),
+        "mrx_set_search_dev": (C.c_int, [H, u8p, i64p, C.c_int64, i32p, i32p, C.c_void_p]),
+        "mrx_set_search_strided_dev": (C.c_int, [H, u8p, C.c_int64, i32p, C.c_int32, C.c_int64, i32p, i32p, C.c_void_p]),
+        "mrx_set_count_dev": (C.c_int, [H, u8p, i64p, C.c_int64, i32p, C.c_void_p]),
+        "mrx_set_count_strided_dev": (C.c_int, [H, u8p, C.c_int64, i32p, C.c_int32, C.c_int64, i32p, C.c_void_p]),
+        "mrx_set_matches_dev": (C.c_int, [H, u8p, i64p, C.c_int64, i64p, C.c_void_p]),
+        "mrx_set_matches_strided_dev": (C.c_int, [H, u8p, C.c_int64, i32p, C.c_int32, C.c_int64, i64p, C.c_void_p]),
+        "mrx_debug_set_route": (None, [C.c_int]),
+        "mrx_testing_set_run": (C.c_int, [H, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_int32)]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch
@@ -169,12 +182,16 @@ EXPORTED_SYMBOLS = [
     "mrx_search_at_strided_dev", "mrx_is_match_at_strided_dev",
     "mrx_sub_dev", "mrx_sub_known_dev", "mrx_sub_strided_dev", "mrx_split_dev", "mrx_split_strided_dev", "mrx_split_batch", "mrx_match_first_batch", "mrx_search_batch", "mrx_is_match_batch",
     "mrx_findall_batch", "mrx_captures_batch", "mrx_sub_batch", "mrx_version", "mrx_release_scratch",
+    "mrx_set_compile", "mrx_set_free", "mrx_set_size", "mrx_set_describe", "mrx_set_search_dev",
+    "mrx_set_search_strided_dev", "mrx_set_count_dev", "mrx_set_count_strided_dev", "mrx_set_matches_dev",
+    "mrx_set_matches_strided_dev",
 ]
 TESTING_SYMBOLS = [
     "mrx_timing_reset", "mrx_timing_enable", "mrx_timing_scan_ms", "mrx_last_kernel_name",
     "mrx_debug_force_generic", "mrx_debug_long_text_kernels", "mrx_debug_scratch_bytes",
     "mrx_debug_fused_findall", "mrx_debug_stream_bits", "mrx_debug_stream_bits_trace", "mrx_debug_dynamic_texts", "mrx_debug_subs_group",
     "mrx_debug_split_findall", "mrx_debug_dense_rows", "mrx_debug_tries_always", "mrx_debug_chain_sub_general", "mrx_testing_emptywalk_findall", "mrx_debug_litscan_pieces", "mrx_debug_multiwalk", "mrx_debug_rec_skew", "mrx_testing_comm_shift", "mrx_testing_comm_compact",
+    "mrx_debug_set_route", "mrx_testing_set_run",
 ]
 COMM_SYMBOLS = [
     "mrx_comm_unique_id", "mrx_comm_init", "mrx_comm_free", "mrx_comm_rank", "mrx_comm_size",
@@ -690,6 +707,99 @@ class CompiledRegex:
             _check(self._lib.mrx_count_strided_dev(self._h, _ptr(batch.data), batch.stride, _ptr(batch.lens),
                                                    batch.length, batch.n, _ptr(counts), self._stream_ptr()))
         return counts
+
+
+class PatternSet:
+    """k patterns answered together over one batch (include/mrx.h, "pattern sets"; Rust's RegexSet idea).
+
+    Member j's answer for text i is exactly CompiledRegex(patterns[j]).match_next / count for that text.  `texts` is a
+    DeviceBatch (results: device tensors [n, k]) or a list of bytes (copied in; results: numpy arrays [n, k])."""
+
+    def __init__(self, patterns, *, lazydfa_semantics: bool = False, bitset_nfa: bool = False):
+        self._lib = load_library()
+        self._h = None
+        self.patterns = [_b(p) for p in patterns]
+        k = len(self.patterns)
+        arr = (C.c_char_p * max(k, 1))(*self.patterns)
+        lens = (C.c_size_t * max(k, 1))(*[len(p) for p in self.patterns])
+        h = C.c_void_p()
+        _check(self._lib.mrx_set_compile(arr, lens, k, (1 if lazydfa_semantics else 0) | (2 if bitset_nfa else 0),
+                                         C.byref(h)))
+        self._h = h
+
+    def __del__(self):
+        try:
+            if self._h is not None:
+                self._lib.mrx_set_free(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+    def __len__(self) -> int:
+        return int(self._lib.mrx_set_size(self._h))
+
+    def describe(self) -> str:
+        need = self._lib.mrx_set_describe(self._h, None, 0)
+        buf = C.create_string_buffer(need + 1)
+        self._lib.mrx_set_describe(self._h, buf, need + 1)
+        return buf.value.decode("utf-8", "replace")
+
+    def _run(self, op: str, texts):
+        import torch
+        host = not isinstance(texts, DeviceBatch)
+        batch = DeviceBatch.from_texts(list(texts)) if host else texts
+        k, n, dev = len(self), batch.n, batch.data.device
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        csr = batch.offsets is not None
+        head = (self._h, _ptr(batch.data), _ptr(batch.offsets), n) if csr else \
+            (self._h, _ptr(batch.data), batch.stride, _ptr(batch.lens), batch.length, n)
+        L = self._lib
+        if op == "search":
+            s = torch.empty((n, k), dtype=torch.int32, device=dev)
+            e = torch.empty((n, k), dtype=torch.int32, device=dev)
+            fn = L.mrx_set_search_dev if csr else L.mrx_set_search_strided_dev
+            _check(fn(*head, _ptr(s), _ptr(e), stream))
+            return (s.cpu().numpy(), e.cpu().numpy()) if host else (s, e)
+        if op == "count":
+            c = torch.empty((n, k), dtype=torch.int32, device=dev)
+            fn = L.mrx_set_count_dev if csr else L.mrx_set_count_strided_dev
+            _check(fn(*head, _ptr(c), stream))
+            return c.cpu().numpy() if host else c
+        words = (k + 63) // 64
+        w = torch.empty((n, words), dtype=torch.int64, device=dev)
+        fn = L.mrx_set_matches_dev if csr else L.mrx_set_matches_strided_dev
+        _check(fn(*head, _ptr(w), stream))
+        if host:
+            u = w.cpu().numpy().view(np.uint64)
+            bits = (u[:, :, None] >> np.arange(64, dtype=np.uint64)) & np.uint64(1)
+            return bits.reshape(n, words * 64)[:, :k].astype(bool)
+        shifts = torch.arange(64, dtype=torch.int64, device=dev)
+        bits = (w.unsqueeze(-1) >> shifts) & 1
+        return bits.reshape(n, words * 64)[:, :k].bool()
+
+    def search(self, texts):
+        """(start, end) int32 [n, k] per member: regex.search, -1/-1 when member j finds nothing in text i."""
+        return self._run("search", texts)
+
+    def count(self, texts):
+        """int32 [n, k]: len(findall(member j, text i))."""
+        return self._run("count", texts)
+
+    def matches(self, texts):
+        """bool [n, k]: member j's search finds a match in text i (a search hit, not is_match)."""
+        return self._run("matches", texts)
+
+    def _host_run(self, op: int, text: bytes):
+        """Testing: the packed set tables walked on the CPU for one text (mrx_testing_set_run); -2 = not in a shared
+        pass for that operation."""
+        k = len(self)
+        out = (C.c_int32 * (2 * k))()
+        _check(self._lib.mrx_testing_set_run(self._h, op, bytes(text), len(text), out))
+        return list(out)[: (2 * k if op == 1 else k)]
+
+
+def compile_set(patterns, *, lazydfa_semantics: bool = False, bitset_nfa: bool = False) -> PatternSet:
+    return PatternSet(patterns, lazydfa_semantics=lazydfa_semantics, bitset_nfa=bitset_nfa)
 
 
 # ---------------------------------------------------------------------------------

@@ -4,6 +4,7 @@
 #include <cstdint>
 #include <string>
 
+struct mrx_handle;
 namespace mrx {
 // records the calling thread's last error message (mrx_last_error()) and returns `code`
 int internal_fail(int code, const std::string& msg);
@@ -25,4 +26,23 @@ int stream_bits_init(int64_t n, int64_t max_len, int64_t* d_prefix, int32_t* d_s
                      void* d_args, void* stream);
 int stream_bits_scan(const DevPlan& p, const uint8_t* d_blob, const uint8_t* data, int64_t stride, const int32_t* lens,
                      int32_t len, int64_t max_len, int64_t n, const void* d_args, void* stream);
+
+// ---- mrx_set.hip: pattern sets over the handles of their members ----------------------------------------------
+struct HostPlan;
+const HostPlan& handle_plan(const mrx_handle* h);
+// the single-pattern count / search of this handle take the streaming kernel's restart-per-position walk
+// (not the anchored automaton) -- what a set may run in its shared pass
+bool handle_count_streams(const mrx_handle* h);
+bool handle_search_streams(const mrx_handle* h);
+// why the handle's count / search would be refused before any work is enqueued ("" = it would run)
+std::string handle_refusal(const mrx_handle* h);
+void set_last_kernel(const char* name);
+// per-call scratch of the calling thread on `stream` (see mrx_release_scratch); a set call opens one scope around
+// its own allocations and the single-pattern calls it makes
+void scratch_scope_enter(void* stream);
+void scratch_scope_leave(void* stream);
+void* scratch_get(size_t bytes, void* stream);   // nullptr: HIP error
+// the scan timer of mrx_timing_scan_ms around a launch sequence: begin returns a token for end
+void* scan_timer_begin(void* stream);
+void scan_timer_end(void* token);
 }  // namespace mrx

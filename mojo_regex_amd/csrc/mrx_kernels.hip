@@ -7847,3 +7847,34 @@ void mrx_release_scratch(void) { scratch_release_all(); }
 size_t mrx_debug_scratch_bytes(void) { return scratch_bytes_reserved(); }
 
 }  // extern "C"
+
+// ---- mrx_internal.hpp: what pattern sets (mrx_set.hip) need of a handle, the scratch arena and the scan timer ----
+namespace mrx {
+const HostPlan& handle_plan(const mrx_handle* h) { return h->hp; }
+bool handle_count_streams(const mrx_handle* h) { return !anchored_at_zero(h) && (h->hp.dev.flags & PF_STREAMABLE); }
+bool handle_search_streams(const mrx_handle* h) { return !anchored_at_zero(h) && (h->hp.dev.flags & PF_STREAM_SEARCH); }
+std::string handle_refusal(const mrx_handle* h) {
+  if (!h->hp.why_no_search.empty()) return h->hp.why_no_search;
+  if (check_lds(h) != MRX_OK) return g_err;
+  return std::string();
+}
+void set_last_kernel(const char* name) { g_last_kernel = name; }
+void scratch_scope_enter(void* st) { ++scratch_arena((hipStream_t)st).depth; }
+void scratch_scope_leave(void* st) {
+  ScratchArena& a = scratch_arena((hipStream_t)st);
+  if (--a.depth == 0 && a.live != 0) {
+    a.live = 0;
+    for (auto& c : a.chunks) c.used = 0;
+  }
+}
+void* scratch_get(size_t bytes, void* st) {
+  void* p = nullptr;
+  return scratch_alloc(&p, bytes, (hipStream_t)st) == hipSuccess ? p : nullptr;
+}
+void* scan_timer_begin(void* st) { return new ScanTimer((hipStream_t)st); }
+void scan_timer_end(void* tok) {
+  ScanTimer* t = (ScanTimer*)tok;
+  t->stop();
+  delete t;
+}
+}  // namespace mrx

@@ -1357,6 +1357,8 @@ void build_plan(const std::string& pattern, HostPlan& hp, bool force_nfa, bool f
   auto emit_stream_tables = [&](const std::vector<std::array<uint16_t, 256>>& E,
                                 const std::vector<uint8_t>& live_acc) {
     const int nlive = (int)E.size();
+    hp.st_entries = E;
+    hp.st_live_acc = live_acc;
     const uint32_t fl = PF_STREAMABLE | ((d.flags & PF_PREFILTER) ? 0u : (uint32_t)PF_STREAM_SEARCH);
     d.st_nstates = nlive;
     {

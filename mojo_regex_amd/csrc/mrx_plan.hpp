@@ -226,6 +226,10 @@ struct HostPlan {
   DevPlan dev{};
   std::vector<uint8_t> blob;
   std::string streamable_why_not;
+  // the search automaton emit_stream_tables() was given (PF_STREAMABLE plans): entry matrix over its live states,
+  // E[q][byte] = next << 2 | EMIT << 1 | NEWSTART (state 0 = idle), and their accept flags; pattern sets pack it
+  std::vector<std::array<uint16_t, 256>> st_entries;
+  std::vector<uint8_t> st_live_acc;
   std::string mwalk_why_not, mwalk_req_why_not, backset_why_not;
   std::string first_stream_why_not;
 };

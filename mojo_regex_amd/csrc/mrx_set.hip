@@ -1,0 +1,715 @@
+// Pattern sets (include/mrx.h, "pattern sets"): search / count / matches of k patterns over one batch.
+//
+// The reference matches one pattern per call; a caller with k rules makes k calls, and each of them reads the whole
+// batch from HBM.  A set runs the members whose single-pattern call would take the streaming kernel's one
+// left-to-right walk (check_streamable(), mrx_plan.cpp: PF_STREAMABLE for count, PF_STREAM_SEARCH for search) side
+// by side in ONE pass over the texts, k_set_scan: the texts are staged through LDS once and every member takes its
+// table step on every byte.  Every other member (prefilter search, anchored automaton, stepper, multi-walk, bitset,
+// backtracker, `$`-LazyDFA, `.*`) runs its own single-pattern entry point into scratch, and k_set_scatter writes the
+// answer into its column.  Member j's answer for text i is therefore exactly the single-pattern call's.
+//
+// Set plan (per operation; search and matches share theirs):
+//   - a shared member's walk is the entry matrix E of its search automaton (HostPlan::st_entries:
+//     E[q][byte] = next << 2 | EMIT << 1 | NEWSTART over the live states, 0 = idle), packed as
+//       column slot: at most 4 live states; four members share one u64[256] column table, member m of the group
+//         owns bits 16 m .. 16 m + 15, state q the 4-bit field at 16 m + 4 q.  The lane keeps the field's bit
+//         offset, so a step is `f = col >> sh & 15; sh = 16 m + (f & 12)`: one ds_read_b64 per byte feeds four walks;
+//       class member: more live states (the wide-column and class-table plans): cls u8[256] | trans u16[live][2^cshift]
+//         (entry = row of the next state << 2 | EMIT << 1 | NEWSTART, row = state << cshift) | accept u8[live];
+//         at most kSetClsEntries entries, otherwise the member keeps its own route.
+//   - a pass holds at most 32 members, 8 column groups, 8 class members and kSetTableBudget bytes of tables, so that
+//     tables + four 9 KiB text tiles stay within 64 KiB of LDS and the per-lane state (three registers per member for
+//     search) within ~170 VGPRs.  Larger sets run several passes; each pass reads the texts again.
+//
+// Route rule (a pure function of set, operation and batch shape -- nothing is timed): the MEMBER LOOP, for every
+// batch shape.  The k-sweep (tools/bench_set.py, profiles/set_scan.md) measured the shared pass slower than the k
+// single-pattern calls at every k from 1 to 64, for count, search and matches, pitch and ragged: this kernel is bound
+// by instruction issue (every column slot of a group and a uniform branch per group are paid on every byte; search
+// with more than two class members runs the spilling <8, 8> instantiation), not by the bytes it saves.  The shared
+// pass stays available (mrx_debug_set_route(1)) and tested until a faster kernel earns the rule back.
+// Bytes outside a text (the CSR frame: a text is staged from the 16-byte boundary below its first byte, and a
+// chunk may reach past its end) are not stepped at all: chunks in which every lane of the wavefront lies inside its
+// text run the unmasked loop, the others the masked one (the member states are held), as ST_FIRST's probe does.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <atomic>
+#include <cstdint>
+#include <cstring>
+#include <map>
+#include <mutex>
+#include <sstream>
+#include <string>
+#include <type_traits>
+#include <vector>
+
+#include "../../include/mrx.h"
+#include "../../include/mrx_testing.h"
+#include "mrx_internal.hpp"
+#include "mrx_plan.hpp"
+
+namespace mrx {
+namespace {
+
+constexpr int kSetMaxK = 256;
+constexpr int kSetPassMembers = 32;
+constexpr int kSetMaxCG = 8;                  // column groups (4 members each) per pass
+constexpr int kSetMaxCM = 8;                  // class members per pass
+constexpr int kSetTableBudget = 20 * 1024;    // LDS bytes of one pass's tables
+constexpr int kSetClsEntries = 2048;          // class member: live states x padded classes
+constexpr int kSetWaves = 4;
+constexpr int kSetChunk = 128;                // bytes of every text staged per step: one cache line
+constexpr int kSetPitch = kSetChunk + 16;     // +16: the per-lane 16-byte read-back is bank-conflict free
+constexpr int kSetTile = 64 * kSetPitch;      // 9216
+constexpr int kSetFrameBytes = 64 * 16;       // per wavefront: base and end address of its 64 texts
+typedef uint32_t set_u32x4 __attribute__((ext_vector_type(4)));   // (the non-temporal load takes native vectors)
+enum { SET_COUNT = 0, SET_SEARCH = 1, SET_MATCHES = 2 };
+const char* const kSetOpName[3] = {"count", "search", "matches"};
+
+std::atomic<int> g_set_route{0};   // mrx_debug_set_route(): 0 rule, 1 shared wherever eligible, 2 own route always
+
+// one pass, by value to the kernel
+struct SetPassDev {
+  int32_t ncg, ncm, table_bytes, k, words;
+  int32_t col_j[kSetMaxCG * 4];     // set member of each column slot (-1: padding)
+  int32_t col_fixed[kSetMaxCG * 4]; // > 0: the member's matches are [end - fixed, end) (exact-literal KMP automaton)
+  uint32_t col_acc[kSetMaxCG];      // bit 4 m + q: state q of slot m accepts
+  int32_t cm_j[kSetMaxCM], cm_fixed[kSetMaxCM], cm_cls[kSetMaxCM], cm_trans[kSetMaxCM], cm_acc[kSetMaxCM],
+      cm_shift[kSetMaxCM];
+};
+
+// ---------------------------------------------------------------------------------------------------------------
+// kernel
+// ---------------------------------------------------------------------------------------------------------------
+template <int MODE, int NCG, int NCM>
+__global__ __launch_bounds__(64 * kSetWaves) void k_set_scan(const SetPassDev P, const uint8_t* __restrict__ blob,
+                                                             const uint8_t* __restrict__ data,
+                                                             const int64_t* __restrict__ offsets, int64_t stride,
+                                                             const int32_t* __restrict__ lens, int32_t len, int64_t n,
+                                                             int32_t* __restrict__ o0, int32_t* __restrict__ o1,
+                                                             uint64_t* __restrict__ bits) {
+  constexpr int NS = NCG * 4 + NCM;   // member slots: columns first, then class members
+  extern __shared__ __align__(16) uint8_t lds[];
+  for (int o = (int)threadIdx.x * 16; o < P.table_bytes; o += 64 * kSetWaves * 16)
+    *(uint4*)(lds + o) = *(const uint4*)(blob + o);
+  __syncthreads();
+  const int wave = (int)threadIdx.x >> 6, lane = (int)threadIdx.x & 63;
+  uint8_t* tile = lds + P.table_bytes + wave * kSetTile;
+  uint64_t* fb = (uint64_t*)(lds + P.table_bytes + kSetWaves * kSetTile + wave * kSetFrameBytes);   // [64] base, [64] end
+  const uint64_t* cols = (const uint64_t*)lds;
+  const int64_t ntask = (n + 63) / 64;
+  for (int64_t task = (int64_t)blockIdx.x * kSetWaves + wave; task < ntask; task += (int64_t)gridDim.x * kSetWaves) {
+    const int64_t i = task * 64 + lane;
+    const bool live = i < n;
+    int64_t a = 0;
+    int32_t L = 0;
+    if (live) {
+      if (offsets) { a = offsets[i]; L = (int32_t)(offsets[i + 1] - a); }
+      else { a = i * stride; L = lens ? lens[i] : len; }
+    }
+    const uint64_t ptr = (uint64_t)(uintptr_t)(data + a);
+    const uint64_t base = ptr & ~(uint64_t)15;
+    const int skew = live ? (int)(ptr - base) : 0;
+    const int flen = live ? skew + L : 0;
+    __builtin_amdgcn_wave_barrier();
+    fb[lane] = base;
+    fb[64 + lane] = live ? ptr + (uint64_t)L : base;   // no word at or past a text's end is loaded
+    int nch = (flen + kSetChunk - 1) / kSetChunk;
+#pragma unroll
+    for (int d = 32; d; d >>= 1) nch = max(nch, __shfl_xor(nch, d));
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+
+    uint32_t sh[NCG * 4 > 0 ? NCG * 4 : 1];   // column slots: bit offset of the state's field in the group's column
+    uint32_t row[NCM > 0 ? NCM : 1];          // class members: row offset of the state
+    int32_t cnt[NS], st[NS], re[NS];          // count / start of the current walk / end of the first match (-1 none)
+    uint64_t used = 0, hit = 0;   // per slot (40 slots at most)
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+      const bool u = s < NCG * 4 ? (s < 4 * P.ncg && P.col_j[s] >= 0) : (s - NCG * 4 < P.ncm);
+      if (u) used |= 1ull << s;
+      cnt[s] = 0;
+      st[s] = -1;
+      re[s] = u ? -1 : 0;
+      if (s < NCG * 4) sh[s < NCG * 4 ? s : 0] = 16 * (s & 3);
+      else row[s - NCG * 4 < NCM ? s - NCG * 4 : 0] = 0;
+    }
+    auto step = [&](uint32_t byte, int p) {
+#pragma unroll
+      for (int g = 0; g < NCG; ++g) {
+        if (g < P.ncg) {
+          const uint64_t col = cols[g * 256 + byte];
+#pragma unroll
+          for (int m = 0; m < 4; ++m) {
+            const int s = g * 4 + m;
+            const uint32_t f = (uint32_t)(col >> sh[s]) & 15u;
+            sh[s] = 16u * m + (f & 12u);
+            if constexpr (MODE == SET_COUNT) cnt[s] += (f >> 1) & 1u;
+            if constexpr (MODE == SET_SEARCH) {
+              if ((f & 2u) && re[s] < 0) re[s] = p;
+              if ((f & 1u) && re[s] < 0) st[s] = p;
+            }
+            if constexpr (MODE == SET_MATCHES) hit |= (uint64_t)((f >> 1) & 1u) << s;
+          }
+        }
+      }
+#pragma unroll
+      for (int c = 0; c < NCM; ++c) {
+        if (c < P.ncm) {
+          const int s = NCG * 4 + c;
+          const uint32_t cl = lds[P.cm_cls[c] + byte];
+          const uint32_t e = *(const uint16_t*)(lds + P.cm_trans[c] + 2 * (row[c] + cl));
+          row[c] = e >> 2;
+          if constexpr (MODE == SET_COUNT) cnt[s] += (e >> 1) & 1u;
+          if constexpr (MODE == SET_SEARCH) {
+            if ((e & 2u) && re[s] < 0) re[s] = p;
+            if ((e & 1u) && re[s] < 0) st[s] = p;
+          }
+          if constexpr (MODE == SET_MATCHES) hit |= (uint64_t)((e >> 1) & 1u) << s;
+        }
+      }
+    };
+    uint4 r[8];
+    auto load = [&](int c) {
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        const int t = k * 8 + (lane >> 3);
+        const uint64_t addr = fb[t] + (uint64_t)c * kSetChunk + 16u * (lane & 7);
+        uint4 v = make_uint4(0, 0, 0, 0);
+        if (addr < fb[64 + t]) {
+          const set_u32x4 x = __builtin_nontemporal_load((const set_u32x4*)(uintptr_t)addr);
+          v = make_uint4(x.x, x.y, x.z, x.w);
+        }
+        r[k] = v;
+      }
+    };
+    if (nch > 0) load(0);
+    for (int c = 0; c < nch; ++c) {
+#pragma unroll
+      for (int k = 0; k < 8; ++k) *(uint4*)(tile + (k * 8 + (lane >> 3)) * kSetPitch + 16 * (lane & 7)) = r[k];
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      if (c + 1 < nch) load(c + 1);
+      const int p0 = c * kSetChunk - skew;   // text position of the chunk's first byte
+      auto body = [&](auto masked) {
+        for (int q = 0; q < kSetChunk / 16; ++q) {
+          const uint4 v = *(const uint4*)(tile + lane * kSetPitch + 16 * q);
+          const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+          for (int b = 0; b < 16; ++b) {
+            const uint32_t byte = (w[b >> 2] >> (8 * (b & 3))) & 0xFFu;
+            const int p = p0 + 16 * q + b;
+            if constexpr (decltype(masked)::value) {
+              if (p >= 0 && p < L) step(byte, p);
+            } else {
+              step(byte, p);
+            }
+          }
+        }
+      };
+      if (__all(!live || (skew == 0 && p0 + kSetChunk <= L))) body(std::false_type{});
+      else body(std::true_type{});
+      __builtin_amdgcn_wave_barrier();   // (the tile is rewritten by the next chunk)
+      if constexpr (MODE != SET_COUNT) {
+        bool done = !live || (c + 1) * kSetChunk >= flen;
+        if constexpr (MODE == SET_SEARCH) {
+          bool all = true;
+#pragma unroll
+          for (int s = 0; s < NS; ++s) all = all && re[s] >= 0;
+          done = done || all;
+        } else {
+          done = done || (hit & used) == used;
+        }
+        if (__all(done)) break;
+      }
+    }
+    if (!live) continue;
+    // end of the text: an accepting walk is a match that ends there
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+      if (!((used >> s) & 1ull)) continue;
+      uint32_t acc;
+      int j, fixed;
+      if (s < NCG * 4) {
+        const int g = s >> 2;
+        acc = (P.col_acc[g] >> (sh[s < NCG * 4 ? s : 0] >> 2)) & 1u;
+        j = P.col_j[s];
+        fixed = P.col_fixed[s];
+      } else {
+        const int c = s - NCG * 4 < NCM ? s - NCG * 4 : 0;
+        acc = lds[P.cm_acc[c] + (row[c] >> P.cm_shift[c])];
+        j = P.cm_j[c];
+        fixed = P.cm_fixed[c];
+      }
+      const int64_t o = i * P.k + j;
+      if constexpr (MODE == SET_COUNT) o0[o] = cnt[s] + (int32_t)acc;
+      if constexpr (MODE == SET_SEARCH) {
+        if (acc && re[s] < 0) re[s] = L;
+        o0[o] = re[s] < 0 ? -1 : fixed > 0 ? re[s] - fixed : st[s];
+        o1[o] = re[s];
+      }
+      if constexpr (MODE == SET_MATCHES) {
+        if (((hit >> s) & 1ull) || acc) bits[i * P.words + (j >> 6)] |= 1ull << (j & 63);
+      }
+    }
+  }
+}
+
+// own-route member j: its single-pattern answer (scratch, n entries) into column j
+__global__ __launch_bounds__(256) void k_set_scatter(int mode, int64_t n, int k, int words, int j,
+                                                     const int32_t* __restrict__ a, const int32_t* __restrict__ b,
+                                                     int32_t* __restrict__ o0, int32_t* __restrict__ o1,
+                                                     uint64_t* __restrict__ bits) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    if (mode == SET_MATCHES) {
+      if (a[i] >= 0) bits[i * words + (j >> 6)] |= 1ull << (j & 63);
+    } else {
+      o0[i * k + j] = a[i];
+      if (mode == SET_SEARCH) o1[i * k + j] = b[i];
+    }
+  }
+}
+
+}  // namespace
+}  // namespace mrx
+
+using namespace mrx;
+
+// ---------------------------------------------------------------------------------------------------------------
+// host: the set plan
+// ---------------------------------------------------------------------------------------------------------------
+struct mrx_set {
+  struct Pass {
+    SetPassDev dv{};
+    std::vector<uint8_t> blob;    // LDS image, a multiple of 16 bytes
+    std::vector<int> members;
+  };
+  struct Plan {                   // one per operation family: [0] count, [1] search and matches
+    std::vector<Pass> passes;
+    std::vector<int> pass_of, slot_of;   // per member: pass / slot (-1: own route)
+    std::vector<std::string> why_own;    // per member: why it keeps its own route
+    std::string refusal;                 // "member j: reason" -- the operation is refused for the set
+  };
+  std::vector<mrx_handle*> members;
+  std::vector<std::string> patterns;
+  uint32_t options = 0;
+  Plan plan[2];
+  std::mutex mu;
+  std::map<std::pair<int, int>, uint8_t*> d_blobs;   // (device, plan * 4096 + pass) -> uploaded table image
+  ~mrx_set() {
+    for (auto& kv : d_blobs) (void)hipFree(kv.second);
+    for (mrx_handle* h : members) mrx_free(h);
+  }
+};
+
+namespace {
+
+// the member's walk as a column slot (u16[256]) or a class member (cls | trans | acc); false: too large for a pass
+struct MemberTables {
+  bool column = false;
+  std::array<uint16_t, 256> col{};
+  uint32_t acc_bits = 0;   // column: bit q = state q accepts
+  std::array<uint8_t, 256> cls{};
+  int cshift = 0;
+  std::vector<uint16_t> trans;
+  std::vector<uint8_t> acc;
+  int fixed = 0;
+  size_t bytes() const { return column ? 0 : (size_t)((256 + trans.size() * 2 + acc.size() + 15) & ~size_t(15)); }
+};
+
+bool member_tables(const HostPlan& hp, MemberTables& t, std::string& why) {
+  const auto& E = hp.st_entries;
+  const int nlive = (int)E.size();
+  if (nlive == 0 || hp.st_live_acc.size() != E.size()) { why = "no search automaton"; return false; }
+  t.fixed = hp.dev.st_fixed_len;
+  if (nlive <= 4) {
+    t.column = true;
+    for (int c = 0; c < 256; ++c)
+      for (int q = 0; q < nlive; ++q) t.col[c] |= (uint16_t)((E[q][c] & 0xF) << (4 * q));
+    for (int q = 0; q < nlive; ++q)
+      if (hp.st_live_acc[q]) t.acc_bits |= 1u << q;
+    return true;
+  }
+  std::map<std::vector<uint16_t>, int> seen;
+  int ncls = 0;
+  for (int c = 0; c < 256; ++c) {
+    std::vector<uint16_t> colv(nlive);
+    for (int q = 0; q < nlive; ++q) colv[q] = E[q][c];
+    auto it = seen.find(colv);
+    if (it == seen.end()) it = seen.emplace(colv, ncls++).first;
+    t.cls[c] = (uint8_t)it->second;
+  }
+  while ((1 << t.cshift) < ncls) ++t.cshift;
+  const int ncp = 1 << t.cshift;
+  if ((int64_t)nlive * ncp > kSetClsEntries) { why = "search automaton too large for a set pass's LDS tables"; return false; }
+  t.trans.assign((size_t)nlive * ncp, 0);
+  for (int c = 0; c < 256; ++c)
+    for (int q = 0; q < nlive; ++q) {
+      const uint16_t e = E[q][c];
+      t.trans[(size_t)q * ncp + t.cls[c]] = (uint16_t)((((e >> 2) << t.cshift) << 2) | (e & 3));
+    }
+  t.acc = hp.st_live_acc;
+  return true;
+}
+
+void put(std::vector<uint8_t>& b, const void* p, size_t n) {
+  const uint8_t* q = (const uint8_t*)p;
+  b.insert(b.end(), q, q + n);
+}
+void pad16(std::vector<uint8_t>& b) { b.resize((b.size() + 15) & ~size_t(15), 0); }
+
+// packs the eligible members of one operation family into passes (in member order)
+void build_set_plan(mrx_set& s, int fam) {
+  mrx_set::Plan& pl = s.plan[fam];
+  const int k = (int)s.members.size();
+  pl.pass_of.assign(k, -1);
+  pl.slot_of.assign(k, -1);
+  pl.why_own.assign(k, std::string());
+  std::vector<MemberTables> tabs(k);
+  std::vector<int> cols, clsm;
+  for (int j = 0; j < k; ++j) {
+    const mrx_handle* h = s.members[j];
+    const bool streams = fam == 0 ? handle_count_streams(h) : handle_search_streams(h);
+    if (!streams) {
+      const HostPlan& hp = handle_plan(h);
+      pl.why_own[j] = fam == 1 && (hp.dev.flags & PF_STREAMABLE) ? "search is not the streaming walk (prefilter)"
+                      : hp.streamable_why_not.empty() ? "not streamable" : hp.streamable_why_not;
+      continue;
+    }
+    if (!member_tables(handle_plan(h), tabs[j], pl.why_own[j])) continue;
+    (tabs[j].column ? cols : clsm).push_back(j);
+  }
+  // passes: column groups first (four members per group), then class members, within the pass budgets
+  size_t ci = 0, mi = 0;
+  while (ci < cols.size() || mi < clsm.size()) {
+    mrx_set::Pass ps;
+    SetPassDev& d = ps.dv;
+    for (int x = 0; x < kSetMaxCG * 4; ++x) d.col_j[x] = -1;
+    for (int x = 0; x < kSetMaxCM; ++x) d.cm_j[x] = -1;
+    int members = 0;
+    size_t bytes = 0;
+    std::vector<std::array<uint64_t, 256>> groups;
+    while (ci < cols.size() && members < kSetPassMembers && (int)groups.size() < kSetMaxCG && bytes + 2048 <= (size_t)kSetTableBudget) {
+      groups.emplace_back();
+      auto& G = groups.back();
+      G.fill(0);
+      const int g = (int)groups.size() - 1;
+      for (int m = 0; m < 4 && ci < cols.size() && members < kSetPassMembers; ++m, ++ci, ++members) {
+        const int j = cols[ci];
+        for (int c = 0; c < 256; ++c) G[c] |= (uint64_t)tabs[j].col[c] << (16 * m);
+        d.col_j[g * 4 + m] = j;
+        d.col_fixed[g * 4 + m] = tabs[j].fixed;
+        d.col_acc[g] |= tabs[j].acc_bits << (4 * m);
+        pl.pass_of[j] = (int)s.plan[fam].passes.size();
+        pl.slot_of[j] = g * 4 + m;
+        ps.members.push_back(j);
+      }
+      bytes += 2048;
+    }
+    d.ncg = (int)groups.size();
+    for (auto& G : groups) put(ps.blob, G.data(), 2048);
+    while (mi < clsm.size() && members < kSetPassMembers && d.ncm < kSetMaxCM &&
+           bytes + tabs[clsm[mi]].bytes() <= (size_t)kSetTableBudget) {
+      const int j = clsm[mi++];
+      const MemberTables& t = tabs[j];
+      const int c = d.ncm++;
+      d.cm_j[c] = j;
+      d.cm_fixed[c] = t.fixed;
+      d.cm_shift[c] = t.cshift;
+      d.cm_cls[c] = (int)ps.blob.size();
+      put(ps.blob, t.cls.data(), 256);
+      d.cm_trans[c] = (int)ps.blob.size();
+      put(ps.blob, t.trans.data(), t.trans.size() * 2);
+      d.cm_acc[c] = (int)ps.blob.size();
+      put(ps.blob, t.acc.data(), t.acc.size());
+      pad16(ps.blob);
+      bytes = ps.blob.size();
+      pl.pass_of[j] = (int)s.plan[fam].passes.size();
+      pl.slot_of[j] = kSetMaxCG * 4 + c;
+      ps.members.push_back(j);
+      ++members;
+    }
+    pad16(ps.blob);
+    d.table_bytes = (int)ps.blob.size();
+    d.k = k;
+    d.words = (k + 63) / 64;
+    pl.passes.push_back(std::move(ps));
+  }
+}
+
+// CPU walk of one pass's packed tables over one text (mrx_testing_set_run): the kernel's arithmetic, byte by byte
+void set_pass_run_host(const mrx_set::Pass& ps, int mode, const uint8_t* text, int len, int32_t* out) {
+  const SetPassDev& d = ps.dv;
+  const uint8_t* lds = ps.blob.data();
+  auto finish = [&](int j, uint32_t acc, int32_t cnt, int32_t st, int32_t re, bool hit, int fixed) {
+    if (mode == SET_COUNT) out[j] = cnt + (int32_t)acc;
+    if (mode == SET_SEARCH) {
+      if (acc && re < 0) re = len;
+      out[2 * j] = re < 0 ? -1 : fixed > 0 ? re - fixed : st;
+      out[2 * j + 1] = re;
+    }
+    if (mode == SET_MATCHES) out[j] = (hit || acc) ? 1 : 0;
+  };
+  for (int s = 0; s < d.ncg * 4; ++s) {
+    if (d.col_j[s] < 0) continue;
+    const int g = s >> 2, m = s & 3;
+    uint32_t sh = 16u * m;
+    int32_t cnt = 0, st = -1, re = -1;
+    bool hit = false;
+    for (int p = 0; p < len; ++p) {
+      uint64_t col;
+      memcpy(&col, lds + (size_t)(g * 256 + text[p]) * 8, 8);
+      const uint32_t f = (uint32_t)(col >> sh) & 15u;
+      sh = 16u * m + (f & 12u);
+      cnt += (f >> 1) & 1u;
+      hit = hit || (f & 2u);
+      if ((f & 2u) && re < 0) re = p;
+      if ((f & 1u) && re < 0) st = p;
+    }
+    finish(d.col_j[s], (d.col_acc[g] >> (sh >> 2)) & 1u, cnt, st, re, hit, d.col_fixed[s]);
+  }
+  for (int c = 0; c < d.ncm; ++c) {
+    uint32_t row = 0;
+    int32_t cnt = 0, st = -1, re = -1;
+    bool hit = false;
+    for (int p = 0; p < len; ++p) {
+      const uint32_t cl = lds[d.cm_cls[c] + text[p]];
+      uint16_t e;
+      memcpy(&e, lds + d.cm_trans[c] + 2 * (row + cl), 2);
+      row = e >> 2;
+      cnt += (e >> 1) & 1u;
+      hit = hit || (e & 2u);
+      if ((e & 2u) && re < 0) re = p;
+      if ((e & 1u) && re < 0) st = p;
+    }
+    finish(d.cm_j[c], lds[d.cm_acc[c] + (row >> d.cm_shift[c])], cnt, st, re, hit, d.cm_fixed[c]);
+  }
+}
+
+// the route rule: shared pass for this batch shape?  Never by default (see the head of this file).
+bool set_shared_route(const int64_t* /*offsets*/, int64_t /*stride*/, const int32_t* /*lens*/, int32_t /*len*/,
+                      int64_t /*n*/) {
+  return g_set_route.load(std::memory_order_relaxed) == 1;
+}
+
+hipError_t set_upload(mrx_set* s, int fam, int pi, int dev, const uint8_t** out) {
+  std::lock_guard<std::mutex> g(s->mu);
+  auto key = std::make_pair(dev, fam * 4096 + pi);
+  auto it = s->d_blobs.find(key);
+  if (it != s->d_blobs.end()) { *out = it->second; return hipSuccess; }
+  const auto& b = s->plan[fam].passes[pi].blob;
+  uint8_t* p = nullptr;
+  hipError_t e = hipMalloc((void**)&p, std::max<size_t>(b.size(), 16));
+  if (e != hipSuccess) return e;
+  e = hipMemcpy(p, b.data(), b.size(), hipMemcpyHostToDevice);
+  if (e != hipSuccess) { (void)hipFree(p); return e; }
+  s->d_blobs[key] = p;
+  *out = p;
+  return hipSuccess;
+}
+
+#define SET_TRY(expr)                                                                               \
+  do {                                                                                              \
+    hipError_t e_ = (expr);                                                                         \
+    if (e_ != hipSuccess) return internal_fail(MRX_E_NO_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
+  } while (0)
+
+template <int MODE>
+void launch_pass(const SetPassDev& d, const uint8_t* blob, const uint8_t* data, const int64_t* offsets, int64_t stride,
+                 const int32_t* lens, int32_t len, int64_t n, int32_t* o0, int32_t* o1, uint64_t* bits, hipStream_t s) {
+  const int64_t ntask = (n + 63) / 64;
+  int64_t grid = (ntask + kSetWaves - 1) / kSetWaves;
+  if (grid > 4096) grid = 4096;
+  const size_t lds = (size_t)d.table_bytes + kSetWaves * (kSetTile + kSetFrameBytes);
+  if (d.ncg <= 2 && d.ncm <= 2)
+    hipLaunchKernelGGL((k_set_scan<MODE, 2, 2>), dim3((unsigned)grid), dim3(64 * kSetWaves), lds, s, d, blob, data, offsets,
+                       stride, lens, len, n, o0, o1, bits);
+  else
+    hipLaunchKernelGGL((k_set_scan<MODE, kSetMaxCG, kSetMaxCM>), dim3((unsigned)grid), dim3(64 * kSetWaves), lds, s, d, blob,
+                       data, offsets, stride, lens, len, n, o0, o1, bits);
+}
+
+int set_run(const mrx_set* sc, int mode, const uint8_t* data, const int64_t* offsets, int64_t stride, const int32_t* lens,
+            int32_t len, int64_t n, int32_t* o0, int32_t* o1, uint64_t* bits, void* st) {
+  if (!sc) return internal_fail(MRX_E_ARGUMENT, "null set");
+  mrx_set* s = const_cast<mrx_set*>(sc);
+  if (n < 0) return internal_fail(MRX_E_ARGUMENT, "n must be >= 0");
+  if (!offsets) {
+    if (stride <= 0) return internal_fail(MRX_E_ARGUMENT, "stride must be positive");
+    if (!lens && (len < 0 || len > stride)) return internal_fail(MRX_E_ARGUMENT, "len must be in [0, stride]");
+  }
+  if (n > 0 && (!data || (mode == SET_MATCHES ? !bits : (!o0 || (mode == SET_SEARCH && !o1)))))
+    return internal_fail(MRX_E_ARGUMENT, "null argument");
+  const int fam = mode == SET_COUNT ? 0 : 1;
+  const mrx_set::Plan& pl = s->plan[fam];
+  const int k = (int)s->members.size();
+  // refusals before anything is enqueued
+  for (int j = 0; j < k; ++j) {
+    const std::string why = handle_refusal(s->members[j]);
+    if (!why.empty()) return internal_fail(MRX_E_UNSUPPORTED, "member " + std::to_string(j) + ": " + why);
+  }
+  int dev = 0;
+  SET_TRY(hipGetDevice(&dev));
+  if (n == 0) return MRX_OK;
+  hipStream_t hs = (hipStream_t)st;
+  const bool shared = set_shared_route(offsets, stride, lens, len, n);
+  const int words = (k + 63) / 64;
+  scratch_scope_enter(st);
+  struct Leave { void* st; ~Leave() { scratch_scope_leave(st); } } leave_{st};
+  if (mode == SET_MATCHES) SET_TRY(hipMemsetAsync(bits, 0, sizeof(uint64_t) * (size_t)n * words, hs));
+  int32_t* a = nullptr;
+  int32_t* b = nullptr;
+  for (int j = 0; j < k; ++j) {
+    if (shared && pl.pass_of[j] >= 0) continue;
+    if (!a) {
+      a = (int32_t*)scratch_get(sizeof(int32_t) * 2 * (size_t)n, st);
+      if (!a) return internal_fail(MRX_E_NO_DEVICE, "scratch allocation failed");
+      b = a + n;
+    }
+    const mrx_handle* h = s->members[j];
+    int rc;
+    if (mode == SET_COUNT)
+      rc = offsets ? mrx_count_dev(h, data, offsets, n, a, st) : mrx_count_strided_dev(h, data, stride, lens, len, n, a, st);
+    else
+      rc = offsets ? mrx_search_dev(h, data, offsets, n, a, b, st)
+                   : mrx_search_strided_dev(h, data, stride, lens, len, n, a, b, st);
+    if (rc != MRX_OK) return internal_fail(rc, "member " + std::to_string(j) + ": " + mrx_last_error());
+    int64_t g = (n + 255) / 256;
+    if (g > 4096) g = 4096;
+    hipLaunchKernelGGL(k_set_scatter, dim3((unsigned)g), dim3(256), 0, hs, mode, n, k, words, j, a, b, o0, o1, bits);
+    SET_TRY(hipGetLastError());
+  }
+  if (shared && !pl.passes.empty()) {
+    void* tm = scan_timer_begin(st);
+    for (int pi = 0; pi < (int)pl.passes.size(); ++pi) {
+      const uint8_t* d_blob = nullptr;
+      SET_TRY(set_upload(s, fam, pi, dev, &d_blob));
+      const SetPassDev& d = pl.passes[pi].dv;
+      if (mode == SET_COUNT) launch_pass<SET_COUNT>(d, d_blob, data, offsets, stride, lens, len, n, o0, o1, bits, hs);
+      else if (mode == SET_SEARCH) launch_pass<SET_SEARCH>(d, d_blob, data, offsets, stride, lens, len, n, o0, o1, bits, hs);
+      else launch_pass<SET_MATCHES>(d, d_blob, data, offsets, stride, lens, len, n, o0, o1, bits, hs);
+      SET_TRY(hipGetLastError());
+    }
+    scan_timer_end(tm);
+    set_last_kernel("k_set_scan");
+  } else {
+    set_last_kernel("k_set_member_loop");
+  }
+  return MRX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mrx_set_compile(const char* const* patterns, const size_t* lens, int32_t k, uint32_t options, mrx_set** out) {
+  if (!out) return internal_fail(MRX_E_ARGUMENT, "null argument");
+  *out = nullptr;
+  if (k < 1 || k > kSetMaxK) return internal_fail(MRX_E_ARGUMENT, "set size must be in [1, 256]");
+  if (!patterns || !lens) return internal_fail(MRX_E_ARGUMENT, "null argument");
+  mrx_set* s = new mrx_set();
+  s->options = options;
+  for (int j = 0; j < k; ++j) {
+    mrx_handle* h = nullptr;
+    const int rc = mrx_compile_ex(patterns[j], lens[j], options, &h);
+    if (rc != MRX_OK) {
+      const std::string msg = mrx_last_error();
+      delete s;
+      return internal_fail(rc, "member " + std::to_string(j) + ": " + msg);
+    }
+    s->members.push_back(h);
+    s->patterns.emplace_back(patterns[j] ? std::string(patterns[j], lens[j]) : std::string());
+  }
+  try {
+    build_set_plan(*s, 0);
+    build_set_plan(*s, 1);
+  } catch (const std::exception& e) {
+    delete s;
+    return internal_fail(MRX_E_UNSUPPORTED, e.what());
+  }
+  *out = s;
+  return MRX_OK;
+}
+
+void mrx_set_free(mrx_set* s) { delete s; }
+
+int32_t mrx_set_size(const mrx_set* s) { return s ? (int32_t)s->members.size() : 0; }
+
+size_t mrx_set_describe(const mrx_set* s, char* buf, size_t cap) {
+  std::ostringstream o;
+  if (s) {
+    o << "set k=" << s->members.size() << " count_passes=" << s->plan[0].passes.size()
+      << " search_passes=" << s->plan[1].passes.size() << "\n";
+    for (size_t j = 0; j < s->members.size(); ++j) {
+      o << "member " << j << ":";
+      for (int op = 0; op < 3; ++op) {
+        const mrx_set::Plan& pl = s->plan[op == 0 ? 0 : 1];
+        o << " " << kSetOpName[op] << "=";
+        if (pl.pass_of[j] >= 0) {
+          const int sl = pl.slot_of[j];
+          o << "shared(pass " << pl.passes.size() << "/" << pl.pass_of[j] << ", ";
+          if (sl < kSetMaxCG * 4) o << "column " << sl / 4 << "." << sl % 4 << ")";
+          else o << "class " << sl - kSetMaxCG * 4 << ")";
+        } else {
+          o << "own";
+        }
+      }
+      const std::string& w0 = s->plan[0].why_own[j];
+      const std::string& w1 = s->plan[1].why_own[j];
+      if (!w0.empty()) o << " count_own_why=\"" << w0 << "\"";
+      if (!w1.empty()) o << " search_own_why=\"" << w1 << "\"";
+      o << "\n";
+    }
+  }
+  const std::string t = o.str();
+  if (buf && cap) {
+    const size_t m = std::min(cap - 1, t.size());
+    memcpy(buf, t.data(), m);
+    buf[m] = 0;
+  }
+  return t.size();
+}
+
+int mrx_set_search_dev(const mrx_set* s, const uint8_t* d_data, const int64_t* d_offsets, int64_t n, int32_t* d_start,
+                       int32_t* d_end, void* stream) {
+  if (!d_offsets) return internal_fail(MRX_E_ARGUMENT, "null offsets");
+  return set_run(s, SET_SEARCH, d_data, d_offsets, 0, nullptr, 0, n, d_start, d_end, nullptr, stream);
+}
+int mrx_set_search_strided_dev(const mrx_set* s, const uint8_t* d_data, int64_t stride, const int32_t* d_lens,
+                               int32_t len, int64_t n, int32_t* d_start, int32_t* d_end, void* stream) {
+  return set_run(s, SET_SEARCH, d_data, nullptr, stride, d_lens, len, n, d_start, d_end, nullptr, stream);
+}
+int mrx_set_count_dev(const mrx_set* s, const uint8_t* d_data, const int64_t* d_offsets, int64_t n, int32_t* d_counts,
+                      void* stream) {
+  if (!d_offsets) return internal_fail(MRX_E_ARGUMENT, "null offsets");
+  return set_run(s, SET_COUNT, d_data, d_offsets, 0, nullptr, 0, n, d_counts, nullptr, nullptr, stream);
+}
+int mrx_set_count_strided_dev(const mrx_set* s, const uint8_t* d_data, int64_t stride, const int32_t* d_lens,
+                              int32_t len, int64_t n, int32_t* d_counts, void* stream) {
+  return set_run(s, SET_COUNT, d_data, nullptr, stride, d_lens, len, n, d_counts, nullptr, nullptr, stream);
+}
+int mrx_set_matches_dev(const mrx_set* s, const uint8_t* d_data, const int64_t* d_offsets, int64_t n, uint64_t* d_bits,
+                        void* stream) {
+  if (!d_offsets) return internal_fail(MRX_E_ARGUMENT, "null offsets");
+  return set_run(s, SET_MATCHES, d_data, d_offsets, 0, nullptr, 0, n, nullptr, nullptr, d_bits, stream);
+}
+int mrx_set_matches_strided_dev(const mrx_set* s, const uint8_t* d_data, int64_t stride, const int32_t* d_lens,
+                                int32_t len, int64_t n, uint64_t* d_bits, void* stream) {
+  return set_run(s, SET_MATCHES, d_data, nullptr, stride, d_lens, len, n, nullptr, nullptr, d_bits, stream);
+}
+
+void mrx_debug_set_route(int mode) { g_set_route = (mode == 1 || mode == 2) ? mode : 0; }
+
+int mrx_testing_set_run(const mrx_set* s, int op, const uint8_t* text, int len, int32_t* out) {
+  if (!s || op < 0 || op > 2 || len < 0 || (!text && len) || !out) return internal_fail(MRX_E_ARGUMENT, "bad argument");
+  const int k = (int)s->members.size();
+  const int per = op == SET_SEARCH ? 2 : 1;
+  for (int x = 0; x < per * k; ++x) out[x] = -2;
+  const mrx_set::Plan& pl = s->plan[op == SET_COUNT ? 0 : 1];
+  for (const auto& ps : pl.passes) set_pass_run_host(ps, op, text, len, out);
+  return MRX_OK;
+}
+
+}  // extern "C"
