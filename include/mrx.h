@@ -245,7 +245,11 @@ int mrx_sub_strided_dev(const mrx_handle* h, const char* repl, size_t repl_len, 
  * > 0: at most that many splits per text, the rest of the text is the last piece; < 0: no split at all (the whole text
  * is the only piece) -- the reference's loop `if maxsplit != 0 and splits_done >= maxsplit: break`.
  *   d_piece_prefix[n + 1]  CSR offsets of the texts' pieces (text i has min(matches, maxsplit) + 1 of them)
- *   d_pieces[piece_cap][2] byte ranges [start, end) within the piece's own text, text order then position
+ *   d_pieces[piece_cap][2] byte ranges [start, end) within the piece's own text, text order then position;
+ *                          always 0 <= start <= end <= len.  The exact-literal route finds the overlapping
+ *                          occurrences of a self-overlapping literal, as the reference's findall does
+ *                          (matcher.mojo:815-847; 22 x "a" in 23 x "a": (0, 22), (1, 23)); the piece between two
+ *                          overlapping matches is the empty range [end of the first, end of the first).
  * *total (host, may be NULL) = number of pieces; MRX_E_CAPACITY when piece_cap does not hold them (what fits is not
  * written then; *total holds the need when the limit is off, a lower bound otherwise).  One stream synchronisation. */
 int mrx_split_dev(const mrx_handle* h, const uint8_t* d_data, const int64_t* d_offsets, int64_t n, int64_t maxsplit,

@@ -7347,7 +7347,9 @@ __global__ __launch_bounds__(kBlock) void k_split_pieces(Layout lay, int64_t n, 
     const int32_t* sp = spans + 2 * prefix[i];
     const int a = q == 0 ? 0 : sp[2 * (q - 1) + 1];
     const int b = q < kept ? sp[2 * q] : lay.text(i).len;
-    *(int2*)(pieces + 2 * j) = make_int2(a, b);
+    // exact-literal plans return overlapping spans (findall of a self-overlapping literal), so match q may begin
+    // before match q-1 ends: that piece is empty, [a, a), never a reversed range
+    *(int2*)(pieces + 2 * j) = make_int2(a, b > a ? b : a);
   }
 }
 

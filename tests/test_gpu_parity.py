@@ -26,6 +26,7 @@ from mrx_ref import hybrid as O  # noqa: E402  (oracle: checker only)
 from mrx_ref import UnsupportedByOracle, RegexSyntaxError as OracleSyntaxError  # noqa: E402
 from vector_eval import load_vectors, evaluate, Unsupported  # noqa: E402
 from mojo_regex_amd.workloads import make_c2_batch  # noqa: E402
+from layouts import split_ranges  # noqa: E402
 
 
 def _need_gpu():
@@ -2732,7 +2733,8 @@ def test_dense_matches_decode_in_row_windows(pat):
         assert [tuple(int(x) for x in r) for r in sp_h[pre_h[i]:pre_h[i + 1]]] == O.findall(pat, t), (pat, i)
 
 
-@pytest.mark.parametrize("pat", [b"[, ]+", b"\\d+", b"ab", b"[a-z]+\\d+", b"x*", b"(\\d{3})(\\d{3})(\\d{4})", b"hello.*world"])
+@pytest.mark.parametrize("pat", [b"[, ]+", b"\\d+", b"ab", b"[a-z]+\\d+", b"x*", b"(\\d{3})(\\d{3})(\\d{4})", b"hello.*world",
+                                 b"a" * 22, b"xy" * 13])
 @pytest.mark.parametrize("maxsplit", [0, 1, 3, -1])
 def test_split_behind_the_c_abi_equals_the_oracle(pat, maxsplit):
     """regex.split (matcher.mojo:1357-1393) through mrx_split_batch / mrx_split_dev / mrx_split_strided_dev: pieces as
@@ -2743,6 +2745,8 @@ def test_split_behind_the_c_abi_equals_the_oracle(pat, maxsplit):
     rng = np.random.default_rng(zlib.crc32(pat) + maxsplit + 7)
     al = b"ab12, xhelloworld" + bytes(c for c in pat if chr(c).isalnum())
     texts = _random_texts(rng, 400, 90, al) + [b"", b",", b",,a,,", b"a,b", b"12ab34", b"hello big world, hello world"]
+    # self-overlapping exact literals: findall returns overlapping occurrences (matcher.mojo:815-847)
+    texts += [b"a" * 25 + b" x " + b"a" * 22, b"a" * 23, b"xy" * 14, b"xy" * 15 + b"a" * 24]
     rx = M.compile_regex(pat)
     try:
         want = [O.split(pat, t, maxsplit) for t in texts]
@@ -2755,6 +2759,10 @@ def test_split_behind_the_c_abi_equals_the_oracle(pat, maxsplit):
     assert total == int(pre[-1]) == sum(len(w) for w in want)
     for i, t in enumerate(texts):
         assert [t[int(a):int(b)] for a, b in pc[pre[i]:pre[i + 1]]] == want[i], (pat, maxsplit, i, t)
+        # the raw ranges: [start, end) with 0 <= start <= end <= len, the ones findall's spans give
+        ranges = [(int(a), int(b)) for a, b in pc[pre[i]:pre[i + 1]]]
+        assert all(0 <= a <= b <= len(t) for a, b in ranges), (pat, maxsplit, i, t, ranges)
+        assert ranges == split_ranges(O.findall(pat, t), len(t), maxsplit), (pat, maxsplit, i, t, ranges)
     # fixed pitch with per-text lengths
     pitch = 96
     arr = np.zeros((len(texts), pitch), dtype=np.uint8)
