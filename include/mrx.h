@@ -258,6 +258,37 @@ int mrx_split_strided_dev(const mrx_handle* h, const uint8_t* d_data, int64_t st
                           int64_t n, int64_t maxsplit, int64_t* d_piece_prefix, int32_t* d_pieces, int64_t piece_cap,
                           int64_t* total, void* stream);
 
+/* captures_all: the capture groups of every match, Python's [m.groups() for m in re.finditer(p, t)] per text.
+ * The reference has no such call; its one loop over every match with groups is the loop of sub() with a template that
+ * names a group (_sub_impl_with_repl, matcher.mojo:1679-1854).  The matches are exactly the ones that loop visits, with
+ * the groups it reads:
+ *   - fixed-width form (a pattern of (\d{N}) groups and literals): match_next from pos; group j at
+ *     match start + its offset, of its width.  A "concat" pattern (groups only) on a text of exactly its total width
+ *     takes the whole-text shortcut: one match at 0 if every byte is a digit, else none;
+ *   - otherwise NFAEngine.match_next_with_groups from pos; a group without an entry is (-1, -1);
+ *   - after an empty match pos = end + 1; a match that lies in front of pos ends the text's list (the reference does
+ *     not terminate there); an empty text has no match.
+ * These are NOT findall's spans where the groups run on the backtracker: it is greedy and the first alternative wins,
+ * while findall takes the hybrid engines' leftmost-longest walk ('(a|ab)(c|bcd)(d*)' on "abcd": findall (0, 4),
+ * captures_all no match).  Exact literals differ too: findall returns overlapping occurrences, this loop does not.
+ *   d_match_prefix[n + 1]  CSR offsets of the texts' matches, at most `count` per text when count > 0 (0 = all)
+ *   d_groups               match k (text order, then match order) holds g + 1 pairs, g = mrx_num_groups(h): groups 1..g,
+ *                          then group 0 (the whole match), the order and raw (unclamped) spans of mrx_captures_dev:
+ *                          d_groups[((k * (g + 1)) + j) * 2 + {0, 1}].  A text's first row is its mrx_captures_dev row
+ *                          (outside the whole-text shortcut)
+ *   *total (host, not NULL) the number of matches; one stream synchronisation returns it.  MRX_E_CAPACITY when it
+ *                          exceeds match_cap; no row at or beyond match_cap is ever written.
+ * Negative n, count or match_cap, and null pointers: MRX_E_ARGUMENT.  A pattern that sub() with a group template refuses
+ * (beyond the flat program's limits) is refused the same way, MRX_E_UNSUPPORTED, before anything is enqueued.  Routes
+ *  are those of sub() with a group template; results never depend on them. */
+int mrx_captures_all_dev(const mrx_handle* h, const uint8_t* d_data, const int64_t* d_offsets, int64_t n, int64_t count,
+                         int64_t* d_match_prefix, int32_t* d_groups, int64_t match_cap, int64_t* total, void* stream);
+/* Same, texts at a fixed pitch (as mrx_sub_strided_dev: rows without padding take every route of the CSR form, padded
+ * rows the lane-per-text kernels). */
+int mrx_captures_all_strided_dev(const mrx_handle* h, const uint8_t* d_data, int64_t stride, const int32_t* d_lens,
+                                 int32_t len, int64_t n, int64_t count, int64_t* d_match_prefix, int32_t* d_groups,
+                                 int64_t match_cap, int64_t* total, void* stream);
+
 /* ---- pattern sets: one batch against k patterns in one call ------------------------------------------------------
  * The reference matches one pattern per call; a set answers k of them per text.  Member j's answer for text i is
  * exactly what the single-pattern call on member j's own handle returns for it (so: what the reference's search /
@@ -312,6 +343,9 @@ int mrx_findall_batch(const mrx_handle* h, const uint8_t* data, const int64_t* o
                       int64_t span_cap, int64_t* total);
 int mrx_captures_batch(const mrx_handle* h, const uint8_t* data, const int64_t* offsets,
                        int64_t n, int32_t* spans);
+/* mrx_captures_all_dev on host buffers: groups holds match_cap rows of g + 1 pairs (copied out only when all fit) */
+int mrx_captures_all_batch(const mrx_handle* h, const uint8_t* data, const int64_t* offsets, int64_t n, int64_t count,
+                           int64_t* match_prefix, int32_t* groups, int64_t match_cap, int64_t* total);
 int mrx_sub_batch(const mrx_handle* h, const char* repl, size_t repl_len, int64_t count,
                   const uint8_t* data, const int64_t* offsets, int64_t n,
                   int64_t* out_offsets, uint8_t* out_data, int64_t out_cap,

@@ -14,6 +14,7 @@ argument meaning, a *batch* of texts instead of one text:
     CompiledRegex.sub(repl, text)     :1118       CompiledRegex.sub(repl, texts)
     CompiledRegex.get_stats()         :1139       CompiledRegex.get_stats()
     match_first / search / findall    :1325-1415  match_first / search / findall
+    (none: sub()'s loop with groups)  :1679-1854  captures_all / CompiledRegex.captures_all
     split / sub                       :1357,1857  split / sub
     clear_regex_cache()               :1318       clear_regex_cache()
     (none: one pattern per call)                  PatternSet / compile_set(patterns): k at once
@@ -30,6 +31,7 @@ from .api import (  # noqa: F401
     PatternSet,
     RegexSyntaxError,
     UnsupportedPattern,
+    captures_all,
     clear_regex_cache,
     compile_regex,
     compile_set,

@@ -92,6 +92,12 @@ def load_library():
         "mrx_count_strided_dev": (C.c_int, [H, u8p, C.c_int64, i32p, C.c_int32, C.c_int64, i32p, C.c_void_p]),
         "mrx_captures_strided_dev": (C.c_int, [H, u8p, C.c_int64, i32p, C.c_int32, C.c_int64, i32p, C.c_void_p]),
         "mrx_captures_dev": (C.c_int, [H, u8p, i64p, C.c_int64, i32p, C.c_void_p]),
+        "mrx_captures_all_dev": (C.c_int, [H, u8p, i64p, C.c_int64, C.c_int64, i64p, i32p, C.c_int64,
+                                           C.POINTER(C.c_int64), C.c_void_p]),
+        "mrx_captures_all_strided_dev": (C.c_int, [H, u8p, C.c_int64, i32p, C.c_int32, C.c_int64, C.c_int64, i64p, i32p,
+                                                   C.c_int64, C.POINTER(C.c_int64), C.c_void_p]),
+        "mrx_captures_all_batch": (C.c_int, [H, u8p, i64p, C.c_int64, C.c_int64, i64p, i32p, C.c_int64,
+                                             C.POINTER(C.c_int64)]),
         "mrx_sub_dev": (C.c_int, [H, C.c_char_p, C.c_size_t, C.c_int64, u8p, i64p, C.c_int64, i64p,
                                   u8p, C.c_int64, C.POINTER(C.c_int64), C.c_void_p]),
         "mrx_sub_known_dev": (C.c_int, [H, C.c_char_p, C.c_size_t, C.c_int64, u8p, i64p, C.c_int64, C.c_int64, C.c_int64,
@@ -178,6 +184,7 @@ EXPORTED_SYMBOLS = [
     "mrx_search_strided_dev", "mrx_is_match_dev", "mrx_is_match_strided_dev",
     "mrx_findall_dev", "mrx_findall_known_dev", "mrx_findall_strided_dev", "mrx_count_dev", "mrx_count_strided_dev",
     "mrx_captures_strided_dev", "mrx_captures_dev",
+    "mrx_captures_all_dev", "mrx_captures_all_strided_dev", "mrx_captures_all_batch",
     "mrx_match_first_at_dev", "mrx_search_at_dev", "mrx_is_match_at_dev", "mrx_match_first_at_strided_dev",
     "mrx_search_at_strided_dev", "mrx_is_match_at_strided_dev",
     "mrx_sub_dev", "mrx_sub_known_dev", "mrx_sub_strided_dev", "mrx_split_dev", "mrx_split_strided_dev", "mrx_split_batch", "mrx_match_first_batch", "mrx_search_batch", "mrx_is_match_batch",
@@ -565,6 +572,50 @@ class CompiledRegex:
                                             out.ctypes.data))
         return out
 
+    def captures_all(self, texts, count: int = 0):
+        """Capture groups of every match: the matches of sub()'s loop with a group template, at most `count` per text
+        (0 = all; include/mrx.h, mrx_captures_all_dev).  (match_prefix int64[n+1], groups int32[total, g+1, 2]), rows in
+        the order of captures(): groups 1..g, then group 0.  Host texts give numpy arrays, a DeviceBatch device tensors."""
+        g = self.num_groups
+        if isinstance(texts, DeviceBatch):
+            return self._captures_all_dev(texts, count)
+        data, offsets = pack_texts(texts)
+        n = len(offsets) - 1
+        prefix = np.zeros(n + 1, np.int64)
+        cap = max(64, int(offsets[-1]) // 8 + n)
+        while True:
+            groups = np.empty((cap, g + 1, 2), np.int32)
+            total = C.c_int64(0)
+            rc = self._lib.mrx_captures_all_batch(self._h, data.ctypes.data, offsets.ctypes.data, n, int(count),
+                                                  prefix.ctypes.data, groups.ctypes.data, cap, C.byref(total))
+            if rc == MRX_E_CAPACITY and int(total.value) > cap:
+                cap = int(total.value)
+                continue
+            _check(rc)
+            return prefix, groups[: total.value]
+
+    def _captures_all_dev(self, batch: "DeviceBatch", count: int = 0, match_cap: Optional[int] = None):
+        import torch
+        dev = batch.data.device
+        g = self.num_groups
+        prefix = torch.empty(batch.n + 1, dtype=torch.int64, device=dev)
+        cap = int(match_cap) if match_cap is not None else max(64, batch.data.numel() // 8 + batch.n)
+        while True:
+            groups = torch.empty((cap, g + 1, 2), dtype=torch.int32, device=dev)
+            total = C.c_int64(0)
+            if batch.offsets is not None:
+                rc = self._lib.mrx_captures_all_dev(self._h, _ptr(batch.data), _ptr(batch.offsets), batch.n, int(count),
+                                                    _ptr(prefix), _ptr(groups), cap, C.byref(total), self._stream_ptr())
+            else:
+                rc = self._lib.mrx_captures_all_strided_dev(self._h, _ptr(batch.data), batch.stride, _ptr(batch.lens),
+                                                            batch.length, batch.n, int(count), _ptr(prefix), _ptr(groups),
+                                                            cap, C.byref(total), self._stream_ptr())
+            if rc == MRX_E_CAPACITY and match_cap is None and int(total.value) > cap:
+                cap = int(total.value)
+                continue
+            _check(rc)
+            return prefix, groups[: total.value]
+
     def sub(self, repl, texts, count: int = 0) -> List[bytes]:
         repl = _b(repl)
         data, offsets = pack_texts(texts)
@@ -832,6 +883,11 @@ def search(pattern, texts):
 
 def findall(pattern, texts):
     return compile_regex(pattern).match_all(texts)
+
+
+def captures_all(pattern, texts, count: int = 0):
+    """Capture groups of every match per text: (match_prefix int64[n+1], groups int32[total, g+1, 2])."""
+    return compile_regex(pattern).captures_all(texts, count)
 
 
 def sub(pattern, repl, texts, count: int = 0) -> List[bytes]:
