@@ -307,7 +307,7 @@ int mrx_captures_all_strided_dev(const mrx_handle* h, const uint8_t* d_data, int
  * count: int32[n][k] matches per member (len(findall)).  matches: uint64 words, ceil(k/64) per text; bit j % 64 of
  * word d_bits[i * ceil(k/64) + j / 64] is set when member j's search finds a match in text i.  That is a SEARCH
  * hit, not the single-pattern is_match operation, whose DFA first-byte quirk (dfa.mojo:1815-1849) answers some texts
- * differently.  Nothing is synchronised: the calls enqueue their work on `stream` and return. */
+ * differently.  search, count and matches synchronise nothing: they enqueue their work on `stream` and return. */
 typedef struct mrx_set mrx_set;
 int mrx_set_compile(const char* const* patterns, const size_t* lens, int32_t k, uint32_t options, mrx_set** out);
 void mrx_set_free(mrx_set* s);
@@ -327,6 +327,32 @@ int mrx_set_matches_dev(const mrx_set* s, const uint8_t* d_data, const int64_t* 
                         uint64_t* d_bits, void* stream);
 int mrx_set_matches_strided_dev(const mrx_set* s, const uint8_t* d_data, int64_t stride, const int32_t* d_lens,
                                 int32_t len, int64_t n, uint64_t* d_bits, void* stream);
+/* findall of every member, text-major (the members' findall spans regrouped by text):
+ *   d_text_prefix int64[n + 1]  CSR over texts: text i's hits are [d_text_prefix[i], d_text_prefix[i + 1])
+ *   d_members int32[total]      the member of each hit
+ *   d_spans int32[total][2]     start, end of each hit, text-relative, raw as mrx_findall_dev returns them; a span is
+ *                               one 8-byte word, so d_spans must be 8-byte aligned
+ * Within text i come member 0's findall spans for text i in match order, then member 1's, and so on: d_members never
+ * decreases within a text, and the run of member j in text i is exactly what mrx_findall_dev on member j's handle
+ * returns for that text (overlapping occurrences of a self-overlapping exact literal, empty matches and the `$`-LazyDFA
+ * contract included), so its length is cell (i, j) of mrx_set_count_dev.  Hits are not ordered by position across
+ * members.
+ * span_cap = capacity of d_members and d_spans in hits.  total > span_cap: MRX_E_CAPACITY, with *total and
+ * d_text_prefix valid once the stream drains (retry with *total); nothing is written at or beyond span_cap.
+ * The call synchronises the stream once (the members' totals size the second phase); a CSR batch
+ * without known bounds adds one synchronisation per call for its byte count and longest text -- the _known form, as
+ * mrx_findall_known_dev, spares it.  total may be NULL.  n == 0 gives d_text_prefix = {0}.  Negative n or span_cap,
+ * and null pointers: MRX_E_ARGUMENT.  A member whose search / findall is refused makes the call MRX_E_UNSUPPORTED
+ * ("member j: <reason>") before anything is enqueued or written. */
+int mrx_set_findall_dev(const mrx_set* s, const uint8_t* d_data, const int64_t* d_offsets, int64_t n,
+                        int64_t* d_text_prefix, int32_t* d_members, int32_t* d_spans, int64_t span_cap, int64_t* total,
+                        void* stream);
+int mrx_set_findall_known_dev(const mrx_set* s, const uint8_t* d_data, const int64_t* d_offsets, int64_t n,
+                              int64_t end_offset, int64_t max_text_len, int64_t* d_text_prefix, int32_t* d_members,
+                              int32_t* d_spans, int64_t span_cap, int64_t* total, void* stream);
+int mrx_set_findall_strided_dev(const mrx_set* s, const uint8_t* d_data, int64_t stride, const int32_t* d_lens,
+                                int32_t len, int64_t n, int64_t* d_text_prefix, int32_t* d_members, int32_t* d_spans,
+                                int64_t span_cap, int64_t* total, void* stream);
 
 /* ---- host-buffer convenience wrappers (copy in, run, copy out) -------------- */
 int mrx_match_first_batch(const mrx_handle* h, const uint8_t* data,
@@ -346,6 +372,9 @@ int mrx_captures_batch(const mrx_handle* h, const uint8_t* data, const int64_t* 
 /* mrx_captures_all_dev on host buffers: groups holds match_cap rows of g + 1 pairs (copied out only when all fit) */
 int mrx_captures_all_batch(const mrx_handle* h, const uint8_t* data, const int64_t* offsets, int64_t n, int64_t count,
                            int64_t* match_prefix, int32_t* groups, int64_t match_cap, int64_t* total);
+/* mrx_set_findall_dev on host buffers: members and spans are copied out only when all hits fit */
+int mrx_set_findall_batch(const mrx_set* s, const uint8_t* data, const int64_t* offsets, int64_t n,
+                          int64_t* text_prefix, int32_t* members, int32_t* spans, int64_t span_cap, int64_t* total);
 int mrx_sub_batch(const mrx_handle* h, const char* repl, size_t repl_len, int64_t count,
                   const uint8_t* data, const int64_t* offsets, int64_t n,
                   int64_t* out_offsets, uint8_t* out_data, int64_t out_cap,

@@ -166,6 +166,13 @@ def load_library():
         "mrx_set_count_strided_dev": (C.c_int, [H, u8p, C.c_int64, i32p, C.c_int32, C.c_int64, i32p, C.c_void_p]),
         "mrx_set_matches_dev": (C.c_int, [H, u8p, i64p, C.c_int64, i64p, C.c_void_p]),
         "mrx_set_matches_strided_dev": (C.c_int, [H, u8p, C.c_int64, i32p, C.c_int32, C.c_int64, i64p, C.c_void_p]),
+        "mrx_set_findall_dev": (C.c_int, [H, u8p, i64p, C.c_int64, i64p, i32p, i32p, C.c_int64, C.POINTER(C.c_int64),
+                                          C.c_void_p]),
+        "mrx_set_findall_known_dev": (C.c_int, [H, u8p, i64p, C.c_int64, C.c_int64, C.c_int64, i64p, i32p, i32p,
+                                                C.c_int64, C.POINTER(C.c_int64), C.c_void_p]),
+        "mrx_set_findall_strided_dev": (C.c_int, [H, u8p, C.c_int64, i32p, C.c_int32, C.c_int64, i64p, i32p, i32p,
+                                                  C.c_int64, C.POINTER(C.c_int64), C.c_void_p]),
+        "mrx_set_findall_batch": (C.c_int, [H, u8p, i64p, C.c_int64, i64p, i32p, i32p, C.c_int64, C.POINTER(C.c_int64)]),
         "mrx_debug_set_route": (None, [C.c_int]),
         "mrx_testing_set_run": (C.c_int, [H, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_int32)]),
     }
@@ -191,7 +198,8 @@ EXPORTED_SYMBOLS = [
     "mrx_findall_batch", "mrx_captures_batch", "mrx_sub_batch", "mrx_version", "mrx_release_scratch",
     "mrx_set_compile", "mrx_set_free", "mrx_set_size", "mrx_set_describe", "mrx_set_search_dev",
     "mrx_set_search_strided_dev", "mrx_set_count_dev", "mrx_set_count_strided_dev", "mrx_set_matches_dev",
-    "mrx_set_matches_strided_dev",
+    "mrx_set_matches_strided_dev", "mrx_set_findall_dev", "mrx_set_findall_known_dev", "mrx_set_findall_strided_dev",
+    "mrx_set_findall_batch",
 ]
 TESTING_SYMBOLS = [
     "mrx_timing_reset", "mrx_timing_enable", "mrx_timing_scan_ms", "mrx_last_kernel_name",
@@ -769,6 +777,7 @@ class PatternSet:
     def __init__(self, patterns, *, lazydfa_semantics: bool = False, bitset_nfa: bool = False):
         self._lib = load_library()
         self._h = None
+        self._hits_per_byte = 0.0   # findall: hits per input byte of the last call (sizes the next call's capacity)
         self.patterns = [_b(p) for p in patterns]
         k = len(self.patterns)
         arr = (C.c_char_p * max(k, 1))(*self.patterns)
@@ -839,6 +848,72 @@ class PatternSet:
     def matches(self, texts):
         """bool [n, k]: member j's search finds a match in text i (a search hit, not is_match)."""
         return self._run("matches", texts)
+
+    def findall(self, texts, span_cap: Optional[int] = None):
+        """Every member's findall, text-major (include/mrx.h, mrx_set_findall_dev): (text_prefix int64[n+1],
+        members int32[total], spans int32[total, 2]).  Text i's hits are [text_prefix[i], text_prefix[i+1]): member
+        0's findall spans of text i in match order, then member 1's, and so on.  A list of bytes gives numpy arrays, a
+        DeviceBatch device tensors.  Without span_cap the call retries once with the total it needs."""
+        if isinstance(texts, DeviceBatch):
+            return self._findall_dev(texts, span_cap)
+        data, offsets = pack_texts(texts)
+        n = len(offsets) - 1
+        prefix = np.zeros(n + 1, np.int64)
+        cap = int(span_cap) if span_cap is not None else self._default_cap(int(offsets[-1]), n)
+        while True:
+            members = np.empty(max(cap, 1), np.int32)
+            spans = np.empty((max(cap, 1), 2), np.int32)
+            total = C.c_int64(0)
+            rc = self._lib.mrx_set_findall_batch(self._h, data.ctypes.data, offsets.ctypes.data, n, prefix.ctypes.data,
+                                                 members.ctypes.data, spans.ctypes.data, cap, C.byref(total))
+            if rc == MRX_E_CAPACITY and span_cap is None and int(total.value) > cap:
+                cap = int(total.value)
+                continue
+            _check(rc)
+            self._hits_per_byte = int(total.value) / max(1, int(offsets[-1]))
+            return prefix, members[: total.value], spans[: total.value]
+
+    def _default_cap(self, nbytes: int, n: int) -> int:
+        """Span capacity without a caller's cap: one hit per 8 bytes, or the density of this set's previous call (+1/8)
+        where that was higher, so that a dense rule set does not pay the retry on every call."""
+        by_last = int(nbytes * self._hits_per_byte * 1.125)
+        return max(64, nbytes // 8 + n, by_last + n + 64)
+
+    def _findall_dev(self, batch: "DeviceBatch", span_cap: Optional[int] = None):
+        import torch
+        dev = batch.data.device
+        n = batch.n
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        prefix = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        cap = int(span_cap) if span_cap is not None else self._default_cap(batch.data.numel(), n)
+        L = self._lib
+        while True:
+            members = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
+            spans = torch.empty((max(cap, 1), 2), dtype=torch.int32, device=dev)
+            total = C.c_int64(0)
+            tail = (_ptr(prefix), _ptr(members), _ptr(spans), cap, C.byref(total), stream)
+            if batch.offsets is not None and batch._end_offset is not None:
+                rc = L.mrx_set_findall_known_dev(self._h, _ptr(batch.data), _ptr(batch.offsets), n, batch._end_offset,
+                                                 batch._max_len, *tail)
+            elif batch.offsets is not None:
+                rc = L.mrx_set_findall_dev(self._h, _ptr(batch.data), _ptr(batch.offsets), n, *tail)
+            else:
+                rc = L.mrx_set_findall_strided_dev(self._h, _ptr(batch.data), batch.stride, _ptr(batch.lens),
+                                                   batch.length, n, *tail)
+            if rc == MRX_E_CAPACITY and span_cap is None and int(total.value) > cap:
+                cap = int(total.value)
+                continue
+            _check(rc)
+            self._hits_per_byte = int(total.value) / max(1, batch.data.numel())
+            return prefix, members[: total.value], spans[: total.value]
+
+    def findall_lists(self, texts) -> List[List[Tuple[int, int, int]]]:
+        """findall() as a list per text of (member, start, end) tuples."""
+        prefix, members, spans = self.findall(texts)
+        if not isinstance(prefix, np.ndarray):
+            prefix, members, spans = prefix.cpu().numpy(), members.cpu().numpy(), spans.cpu().numpy()
+        return [[(int(members[q]), int(spans[q, 0]), int(spans[q, 1])) for q in range(prefix[i], prefix[i + 1])]
+                for i in range(len(prefix) - 1)]
 
     def _host_run(self, op: int, text: bytes):
         """Testing: the packed set tables walked on the CPU for one text (mrx_testing_set_run); -2 = not in a shared

@@ -3,6 +3,7 @@
 #include <cstddef>
 #include <cstdint>
 #include <string>
+#include <vector>
 
 struct mrx_handle;
 namespace mrx {
@@ -42,6 +43,25 @@ void set_last_kernel(const char* name);
 void scratch_scope_enter(void* stream);
 void scratch_scope_leave(void* stream);
 void* scratch_get(size_t bytes, void* stream);   // nullptr: HIP error
+// a position in the calling thread's arena on `stream`: a set call rewinds to it behind each member's call (the
+// next member's work runs after it on the same stream), so that its scratch does not grow with the set size
+struct ScratchMark {
+  std::vector<size_t> used;
+  int live = 0;
+};
+ScratchMark scratch_mark(void* stream);
+void scratch_rewind(void* stream, const ScratchMark& m);
+// byte count (d_offsets[n]) and longest text of a CSR batch: one small kernel and one stream synchronisation
+int batch_bounds(const int64_t* d_offsets, int64_t n, void* stream, int64_t* total, int64_t* max_len);
+// exclusive prefix sum of n int64 into d_prefix[n + 1]; *d_total receives the sum
+int exclusive_scan(const int64_t* d_in, int64_t n, int64_t* d_prefix, int64_t* d_total, void* stream);
+// mrx_count_dev / mrx_findall_known_dev (total == NULL: asynchronous) of one handle, CSR (offsets) or fixed pitch;
+// known_total / known_max: the CSR batch's bounds (< 0: not known)
+int member_count(const mrx_handle* h, const uint8_t* data, const int64_t* offsets, int64_t stride, const int32_t* lens,
+                 int32_t len, int64_t n, int32_t* counts, void* stream, int64_t known_total, int64_t known_max);
+int member_findall(const mrx_handle* h, const uint8_t* data, const int64_t* offsets, int64_t stride, const int32_t* lens,
+                   int32_t len, int64_t n, int64_t* d_prefix, int32_t* d_spans, int64_t span_cap, void* stream,
+                   int64_t known_total, int64_t known_max);
 // the scan timer of mrx_timing_scan_ms around a launch sequence: begin returns a token for end
 void* scan_timer_begin(void* stream);
 void scan_timer_end(void* token);

@@ -7417,7 +7417,9 @@ int mrx_split_strided_dev(const mrx_handle* h, const uint8_t* d, int64_t stride,
   return run_split(h, Layout{d, nullptr, stride, lens, len}, n, maxsplit, d_piece_prefix, d_pieces, piece_cap, total, st);
 }
 
-static int run_count_any(const mrx_handle* h, const Layout& lay, int64_t n, int32_t* counts, void* st) {
+// known_total / known_max: csr_stats() of a CSR batch when the caller has them already (< 0: not; pattern-set findall)
+static int run_count_any(const mrx_handle* h, const Layout& lay, int64_t n, int32_t* counts, void* st,
+                         int64_t known_total = -1, int64_t known_max = -1) {
   ScratchScope scratch_scope_((hipStream_t)st);
   if (!h) return fail(MRX_E_ARGUMENT, "null handle");
   if (int rc = check_search_supported(h)) return rc;
@@ -7440,7 +7442,7 @@ static int run_count_any(const mrx_handle* h, const Layout& lay, int64_t n, int3
   ScanTimer tm(s);
   if (!g_force_generic && (h->hp.dev.flags & PF_STREAMABLE) && stream_layout_ok(lay, n)) {
     Pieces pc;
-    if (int rc = pieces_prepare(h, lay, n, s, &pc)) return rc;
+    if (int rc = pieces_prepare(h, lay, n, s, &pc, known_total, known_max)) return rc;
     if (pc.on) {   // long texts: count per piece, then add up each text's pieces
       int32_t* d_vcounts = nullptr;
       HIP_TRY(scratch_alloc((void**)&d_vcounts, sizeof(int32_t) * pc.nv, s));
@@ -7485,7 +7487,7 @@ static int run_count_any(const mrx_handle* h, const Layout& lay, int64_t n, int3
         (!use_req_route || g_long_text_mode == 1)) {
       // long texts: disjoint pieces between synchronising bytes, one lane each (see run_findall)
       Pieces spc;
-      if (int rc = pieces_prepare(h, lay, n, s, &spc, -1, -1, /*disjoint=*/true, wstep_mwalk)) return rc;
+      if (int rc = pieces_prepare(h, lay, n, s, &spc, known_total, known_max, /*disjoint=*/true, wstep_mwalk)) return rc;
       if (spc.on && !wstep_mwalk) {
         bool dense = true;
         if (int rc = dense_candidates(h, lay, n, s, &dense)) return rc;
@@ -8262,6 +8264,34 @@ void scratch_scope_leave(void* st) {
 void* scratch_get(size_t bytes, void* st) {
   void* p = nullptr;
   return scratch_alloc(&p, bytes, (hipStream_t)st) == hipSuccess ? p : nullptr;
+}
+ScratchMark scratch_mark(void* st) {
+  ScratchArena& a = scratch_arena((hipStream_t)st);
+  ScratchMark m;
+  m.live = a.live;
+  for (auto& c : a.chunks) m.used.push_back(c.used);
+  return m;
+}
+void scratch_rewind(void* st, const ScratchMark& m) {
+  ScratchArena& a = scratch_arena((hipStream_t)st);
+  a.live = m.live;
+  for (size_t c = 0; c < a.chunks.size(); ++c) a.chunks[c].used = c < m.used.size() ? m.used[c] : 0;
+}
+int batch_bounds(const int64_t* d_offsets, int64_t n, void* st, int64_t* total, int64_t* max_len) {
+  return csr_stats(Layout{nullptr, d_offsets, 0, nullptr, 0}, n, (hipStream_t)st, total, max_len);
+}
+int exclusive_scan(const int64_t* d_in, int64_t n, int64_t* d_prefix, int64_t* d_total, void* st) {
+  return device_scan<int64_t>(d_in, n, d_prefix, d_total, (hipStream_t)st);
+}
+int member_count(const mrx_handle* h, const uint8_t* data, const int64_t* offsets, int64_t stride, const int32_t* lens,
+                 int32_t len, int64_t n, int32_t* counts, void* st, int64_t known_total, int64_t known_max) {
+  return run_count_any(h, Layout{data, offsets, stride, lens, len}, n, counts, st, known_total, known_max);
+}
+int member_findall(const mrx_handle* h, const uint8_t* data, const int64_t* offsets, int64_t stride, const int32_t* lens,
+                   int32_t len, int64_t n, int64_t* d_prefix, int32_t* d_spans, int64_t span_cap, void* st,
+                   int64_t known_total, int64_t known_max) {
+  return run_findall(h, Layout{data, offsets, stride, lens, len}, n, d_prefix, d_spans, span_cap, nullptr, st, false,
+                     known_total, known_max);
 }
 void* scan_timer_begin(void* st) { return new ScanTimer((hipStream_t)st); }
 void scan_timer_end(void* tok) {
