@@ -353,6 +353,50 @@ int mrx_set_findall_known_dev(const mrx_set* s, const uint8_t* d_data, const int
 int mrx_set_findall_strided_dev(const mrx_set* s, const uint8_t* d_data, int64_t stride, const int32_t* d_lens,
                                 int32_t len, int64_t n, int64_t* d_text_prefix, int32_t* d_members, int32_t* d_spans,
                                 int64_t span_cap, int64_t* total, void* stream);
+/* sub of a set: replace the hits of every member in one call.  Defined on the hits that mrx_set_findall_dev returns,
+ * not on the reference's sub() loop (the reference has no multi-pattern call).  For text i:
+ *   1. the candidates are every member's findall hits in text i, (s, j, e) = start, member, end -- overlapping
+ *      occurrences of a self-overlapping exact literal, empty matches and the `$`-LazyDFA contract included, exactly as
+ *      set findall returns them;
+ *   2. walk the candidates in ascending (s, j) order (then e), pos = 0: a candidate is SELECTED iff s >= pos, and then
+ *      pos = max(e, s + 1); stop after `count` selections when count > 0;
+ *   3. the output is the text with each selected [s, e) replaced by member j's replacement; every other byte is copied.
+ * So at equal start the lower member wins (member order is priority order); a hit that overlaps a selected one is
+ * dropped and its member is NOT searched again behind the selected hit; an empty hit is selected where no earlier
+ * selection covers its position (findall of `z*` on "ab" is (0,0) (1,1) (2,2): replacement "-" gives "-a-b-"; on ""
+ * it is (0,0), which gives "-").
+ * A one-member set differs from mrx_sub_dev exactly where the reference's sub() loop does not visit findall's list:
+ * exact literals (findall overlaps, the set drops the overlap: sub() searches again behind each match); empty
+ * matches (sub() copies text[pos] behind an empty match found beyond pos, oracle/mrx_ref/hybrid.py:668, and returns
+ * an empty text unchanged); and any other route whose sub is not served from findall's spans.
+ * repls[k], repl_lens[k] (k = mrx_set_size): member j's replacement, bytes taken verbatim (as a single sub template
+ * without group references); an entry may be NULL when its length is 0, and repls itself when every length is 0.
+ * A replacement that holds a group reference \1..\9 is refused, MRX_E_UNSUPPORTED ("member j: group references are
+ * not supported in a set's sub"), before anything is enqueued; no length is refused.
+ *   d_out_offsets int64[n + 1], d_out_data: the output CSR, as mrx_sub_dev writes it.
+ *   d_nsub int32[n] (may be NULL): the number of replacements in each text.
+ *   *total_bytes (may be NULL): the output size.  Above out_cap: MRX_E_CAPACITY, nothing written at or beyond
+ *   out_cap, d_out_offsets (and d_nsub) valid once the stream drains, for a retry.
+ * Synchronisations: two per call -- the set findall's first phase (its member totals), and the output size -- plus,
+ * for a CSR batch without known bounds, the one that reads its byte count and longest text (the _known form spares
+ * it).  The output bytes are complete when the stream reaches the point of return.
+ * Scratch: 12 bytes per hit of the set's findall (member and span), O(n) words, and the densest member's spans
+ * while the members' findall runs: about 30 GB for 2.5 * 10^9 hits.
+ * Negative n, count or out_cap, a null required pointer (set, repl_lens, d_offsets, d_out_offsets, d_out_data when
+ * out_cap > 0) and a NULL entry of nonzero length: MRX_E_ARGUMENT.  (d_data may be NULL when every text is empty.)  A member whose search /
+ * findall is refused makes the call MRX_E_UNSUPPORTED ("member j: <reason>"), as set findall.  n == 0 gives
+ * d_out_offsets = {0}. */
+int mrx_set_sub_dev(const mrx_set* s, const char* const* repls, const size_t* repl_lens, int64_t count,
+                    const uint8_t* d_data, const int64_t* d_offsets, int64_t n, int64_t* d_out_offsets,
+                    uint8_t* d_out_data, int64_t out_cap, int32_t* d_nsub, int64_t* total_bytes, void* stream);
+int mrx_set_sub_known_dev(const mrx_set* s, const char* const* repls, const size_t* repl_lens, int64_t count,
+                          const uint8_t* d_data, const int64_t* d_offsets, int64_t n, int64_t end_offset,
+                          int64_t max_text_len, int64_t* d_out_offsets, uint8_t* d_out_data, int64_t out_cap,
+                          int32_t* d_nsub, int64_t* total_bytes, void* stream);
+int mrx_set_sub_strided_dev(const mrx_set* s, const char* const* repls, const size_t* repl_lens, int64_t count,
+                            const uint8_t* d_data, int64_t stride, const int32_t* d_lens, int32_t len, int64_t n,
+                            int64_t* d_out_offsets, uint8_t* d_out_data, int64_t out_cap, int32_t* d_nsub,
+                            int64_t* total_bytes, void* stream);
 
 /* ---- host-buffer convenience wrappers (copy in, run, copy out) -------------- */
 int mrx_match_first_batch(const mrx_handle* h, const uint8_t* data,
@@ -375,6 +419,10 @@ int mrx_captures_all_batch(const mrx_handle* h, const uint8_t* data, const int64
 /* mrx_set_findall_dev on host buffers: members and spans are copied out only when all hits fit */
 int mrx_set_findall_batch(const mrx_set* s, const uint8_t* data, const int64_t* offsets, int64_t n,
                           int64_t* text_prefix, int32_t* members, int32_t* spans, int64_t span_cap, int64_t* total);
+/* mrx_set_sub_dev on host buffers: out_data is copied out only when all output fits; nsub (int32[n]) may be NULL */
+int mrx_set_sub_batch(const mrx_set* s, const char* const* repls, const size_t* repl_lens, int64_t count,
+                      const uint8_t* data, const int64_t* offsets, int64_t n, int64_t* out_offsets, uint8_t* out_data,
+                      int64_t out_cap, int32_t* nsub, int64_t* total_bytes);
 int mrx_sub_batch(const mrx_handle* h, const char* repl, size_t repl_len, int64_t count,
                   const uint8_t* data, const int64_t* offsets, int64_t n,
                   int64_t* out_offsets, uint8_t* out_data, int64_t out_cap,

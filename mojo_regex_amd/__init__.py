@@ -18,6 +18,7 @@ argument meaning, a *batch* of texts instead of one text:
     split / sub                       :1357,1857  split / sub
     clear_regex_cache()               :1318       clear_regex_cache()
     (none: one pattern per call)                  PatternSet / compile_set(patterns): k at once
+    (none: k sub() calls in a row)                PatternSet.sub(repls, texts): k patterns' hits, one call
 
 All matching runs in the HIP kernels of libmrx_hip.so.  There is no CPU
 fallback: if the library is missing or no GPU is usable, calls raise.

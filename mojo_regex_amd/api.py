@@ -173,6 +173,14 @@ def load_library():
         "mrx_set_findall_strided_dev": (C.c_int, [H, u8p, C.c_int64, i32p, C.c_int32, C.c_int64, i64p, i32p, i32p,
                                                   C.c_int64, C.POINTER(C.c_int64), C.c_void_p]),
         "mrx_set_findall_batch": (C.c_int, [H, u8p, i64p, C.c_int64, i64p, i32p, i32p, C.c_int64, C.POINTER(C.c_int64)]),
+        "mrx_set_sub_dev": (C.c_int, [H, C.c_void_p, C.c_void_p, C.c_int64, u8p, i64p, C.c_int64, i64p, u8p, C.c_int64,
+                                      i32p, C.POINTER(C.c_int64), C.c_void_p]),
+        "mrx_set_sub_known_dev": (C.c_int, [H, C.c_void_p, C.c_void_p, C.c_int64, u8p, i64p, C.c_int64, C.c_int64,
+                                            C.c_int64, i64p, u8p, C.c_int64, i32p, C.POINTER(C.c_int64), C.c_void_p]),
+        "mrx_set_sub_strided_dev": (C.c_int, [H, C.c_void_p, C.c_void_p, C.c_int64, u8p, C.c_int64, i32p, C.c_int32,
+                                              C.c_int64, i64p, u8p, C.c_int64, i32p, C.POINTER(C.c_int64), C.c_void_p]),
+        "mrx_set_sub_batch": (C.c_int, [H, C.c_void_p, C.c_void_p, C.c_int64, u8p, i64p, C.c_int64, i64p, u8p, C.c_int64,
+                                        i32p, C.POINTER(C.c_int64)]),
         "mrx_debug_set_route": (None, [C.c_int]),
         "mrx_testing_set_run": (C.c_int, [H, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_int32)]),
     }
@@ -199,7 +207,7 @@ EXPORTED_SYMBOLS = [
     "mrx_set_compile", "mrx_set_free", "mrx_set_size", "mrx_set_describe", "mrx_set_search_dev",
     "mrx_set_search_strided_dev", "mrx_set_count_dev", "mrx_set_count_strided_dev", "mrx_set_matches_dev",
     "mrx_set_matches_strided_dev", "mrx_set_findall_dev", "mrx_set_findall_known_dev", "mrx_set_findall_strided_dev",
-    "mrx_set_findall_batch",
+    "mrx_set_findall_batch", "mrx_set_sub_dev", "mrx_set_sub_known_dev", "mrx_set_sub_strided_dev", "mrx_set_sub_batch",
 ]
 TESTING_SYMBOLS = [
     "mrx_timing_reset", "mrx_timing_enable", "mrx_timing_scan_ms", "mrx_last_kernel_name",
@@ -914,6 +922,83 @@ class PatternSet:
             prefix, members, spans = prefix.cpu().numpy(), members.cpu().numpy(), spans.cpu().numpy()
         return [[(int(members[q]), int(spans[q, 0]), int(spans[q, 1])) for q in range(prefix[i], prefix[i + 1])]
                 for i in range(len(prefix) - 1)]
+
+    def _repl_table(self, repl):
+        """(repls, repl_lens, keep-alive) for the C call: one replacement for every member, or a sequence of k."""
+        k = len(self)
+        if isinstance(repl, (bytes, bytearray, memoryview, str)):
+            reps = [_b(repl)] * k
+        else:
+            reps = [_b(r) for r in repl]
+            if len(reps) != k:
+                raise MrxError("repl: %d replacements for a set of %d members" % (len(reps), k))
+        arr = (C.c_char_p * max(k, 1))(*reps)
+        lens = (C.c_size_t * max(k, 1))(*[len(r) for r in reps])
+        return C.cast(arr, C.c_void_p), C.cast(lens, C.c_void_p), (arr, lens, reps)
+
+    def sub(self, repl, texts, count: int = 0, out_cap: Optional[int] = None):
+        """Replace the hits of every member in one call (include/mrx.h, mrx_set_sub_dev): the candidates are the
+        members' findall hits; in ascending (start, member) order a hit is selected when it starts at or after the end
+        of the last selected one (an empty hit: one past it), and replaced by its member's replacement.  `repl` is
+        bytes / str for every member or a sequence of k.  A list of texts gives List[bytes], a DeviceBatch
+        (out_offsets int64[n+1], out_data uint8[total]) device tensors.  Without out_cap the call retries once with the
+        size it needs."""
+        return self._sub(repl, texts, count, out_cap)[:2] if isinstance(texts, DeviceBatch) else \
+            self._sub(repl, texts, count, out_cap)[0]
+
+    def subn(self, repl, texts, count: int = 0, out_cap: Optional[int] = None):
+        """sub(), plus the number of replacements in each text, int32[n]: (List[bytes], numpy) for a list of texts,
+        (out_offsets, out_data, nsub) device tensors for a DeviceBatch."""
+        return self._sub(repl, texts, count, out_cap)
+
+    def _sub(self, repl, texts, count: int, out_cap: Optional[int]):
+        repls, lens, keep = self._repl_table(repl)   # (keep: the ctypes tables live until the call returns)
+        longest = max((len(r) for r in keep[2]), default=0)
+        if isinstance(texts, DeviceBatch):
+            return self._sub_dev(repls, lens, longest, texts, count, out_cap)
+        data, offsets = pack_texts(texts)
+        n = len(offsets) - 1
+        out_off = np.zeros(n + 1, np.int64)
+        nsub = np.zeros(max(n, 1), np.int32)
+        cap = int(out_cap) if out_cap is not None else int(offsets[-1]) * 2 + (16 + longest) * n + 64
+        while True:
+            out = np.empty(max(cap, 1), np.uint8)
+            total = C.c_int64(0)
+            rc = self._lib.mrx_set_sub_batch(self._h, repls, lens, count, data.ctypes.data, offsets.ctypes.data, n,
+                                             out_off.ctypes.data, out.ctypes.data, cap, nsub.ctypes.data, C.byref(total))
+            if rc == MRX_E_CAPACITY and out_cap is None and int(total.value) > cap:
+                cap = int(total.value)
+                continue
+            _check(rc)
+            raw = out[: total.value].tobytes()
+            return [raw[out_off[i]:out_off[i + 1]] for i in range(n)], nsub[:n]
+
+    def _sub_dev(self, repls, lens, longest: int, batch: "DeviceBatch", count: int, out_cap: Optional[int]):
+        import torch
+        dev = batch.data.device
+        n = batch.n
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        out_off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        nsub = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+        cap = int(out_cap) if out_cap is not None else int(batch.data.numel()) * 2 + (16 + longest) * n + 64
+        L = self._lib
+        while True:
+            out = torch.empty(max(cap, 1), dtype=torch.uint8, device=dev)
+            total = C.c_int64(0)
+            tail = (_ptr(out_off), _ptr(out), cap, _ptr(nsub), C.byref(total), stream)
+            if batch.offsets is not None and batch._end_offset is not None:
+                rc = L.mrx_set_sub_known_dev(self._h, repls, lens, count, _ptr(batch.data), _ptr(batch.offsets), n,
+                                             batch._end_offset, batch._max_len, *tail)
+            elif batch.offsets is not None:
+                rc = L.mrx_set_sub_dev(self._h, repls, lens, count, _ptr(batch.data), _ptr(batch.offsets), n, *tail)
+            else:
+                rc = L.mrx_set_sub_strided_dev(self._h, repls, lens, count, _ptr(batch.data), batch.stride,
+                                               _ptr(batch.lens), batch.length, n, *tail)
+            if rc == MRX_E_CAPACITY and out_cap is None and int(total.value) > cap:
+                cap = int(total.value)
+                continue
+            _check(rc)
+            return out_off, out[: total.value], nsub[:n]
 
     def _host_run(self, op: int, text: bytes):
         """Testing: the packed set tables walked on the CPU for one text (mrx_testing_set_run); -2 = not in a shared

@@ -352,6 +352,260 @@ __global__ __launch_bounds__(256) void k_setfa_advance(int64_t n, const int64_t*
     before[i] += prefix_j[i + 1] - prefix_j[i];
 }
 
+// ---- sub of a set (mrx_set_sub_dev): the set's findall hits -> one selection per text -> output bytes -----------
+// One wavefront per text walks it in windows of W positions (0 .. L: an empty hit may sit at L; W = the batch's
+// longest text + 1 rounded up to 64, at most kSetSubMaxW).  Per window, the lanes stride over the text's hits
+// (contiguous in the set's findall output) and every hit that starts in the window at or after `pos` does
+// best[s - w0] = min(best, member << 32 | end): the candidate that the contract's ascending (s, j, e) order puts
+// first at that start.  Then 64 positions at a time, one per lane, a ballot of the occupied positions drives the walk
+// with wave-uniform values only: next occupied position >= pos (s_ff1), select it, pos = max(e, s + 1) read from that
+// lane.  pos, the replacement count and (emit) the input / output cursors carry across windows, so a text of any
+// length is served; each window re-reads all of the text's hits, so a text's cost grows as L / W x its hits.
+// A text without hits takes neither window nor walk.
+// select: the output size and the replacement count of every text.  emit: the same walk, behind the scan of the
+// sizes, also assembles the bytes in a per-wavefront LDS ring of kSetSubRing bytes indexed by the output's address:
+// every position not inside a selected hit is copied from the input to the offset that the last selected hit at or
+// before it leaves, each selected hit writes its member's replacement (a lane alone up to 64 bytes, the whole
+// wavefront beyond).  The ring goes to global memory as whole aligned 16-byte words, bytes only at the ends of a
+// text's output row (its neighbours' words belong to other wavefronts).  A chunk whose output does not fit the ring
+// (long replacements) is written byte by byte.  The walk is repeated rather than stored, so the hits are the only
+// per-hit scratch.  Reads stay inside a text, writes inside its output row.
+constexpr int kSetSubMaxW = 1536;             // positions per window at most: u64 best[W] per wavefront, 12 KiB
+constexpr int kSetSubWaves = 4;
+constexpr int kSetSubRing = 2048;             // emit: output ring per wavefront
+constexpr int kSetSubFlushAt = 1024;          // ... flushed once this many bytes are pending
+constexpr int kSetSubReplLds = 4096;          // the replacement table is staged in LDS up to this many bytes
+
+struct SetSubArgs {
+  const uint8_t* data;
+  const int64_t* offsets;   // CSR, or NULL: fixed pitch
+  int64_t stride;
+  const int32_t* lens;
+  int32_t len;
+  int64_t n;
+  const int64_t* text_prefix;   // the set's findall: text CSR, member and span of each hit
+  const int32_t* members;
+  const int32_t* spans;
+  const uint8_t* rtab;      // the members' replacements back to back; member j's are [roff[j], roff[j + 1])
+  const int64_t* roff;
+  int64_t rbytes;
+  int64_t count;            // > 0: at most count replacements per text
+  int32_t k;
+  int32_t W;                // window: a multiple of 64, at most kSetSubMaxW
+};
+
+__device__ __forceinline__ int64_t setsub_readlane64(int64_t v, int h) {
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, h);
+  const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)((uint64_t)v >> 32), h);
+  return (int64_t)(((uint64_t)hi << 32) | lo);
+}
+__device__ __forceinline__ int64_t setsub_shfl64(int64_t v, int src) {
+  const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)v, src);
+  const uint32_t hi = (uint32_t)__shfl((int)(uint32_t)((uint64_t)v >> 32), src);
+  return (int64_t)(((uint64_t)hi << 32) | lo);
+}
+__device__ __forceinline__ void setsub_lds_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+template <bool EMIT>
+__device__ void setsub_text(const SetSubArgs& A, int64_t i, uint64_t* best, uint8_t* ring, const uint8_t* R, int lane,
+                            int64_t* __restrict__ sizes, int32_t* __restrict__ nsub, const int64_t* __restrict__ out_off,
+                            uint8_t* __restrict__ out) {
+  int64_t a0;
+  int32_t L;
+  if (A.offsets) { a0 = A.offsets[i]; L = (int32_t)(A.offsets[i + 1] - a0); }
+  else { a0 = i * A.stride; L = A.lens ? A.lens[i] : A.len; }
+  const uint8_t* text = A.data + a0;
+  const int64_t ha = A.text_prefix[i], hb = A.text_prefix[i + 1];
+  if constexpr (!EMIT) {
+    if (ha >= hb) {   // no hit: the text is its output
+      if (lane == 0) { sizes[i] = L; nsub[i] = 0; }
+      return;
+    }
+  }
+  int64_t olen = 0;
+  uint64_t ob = 0;           // emit: address of the text's output row
+  if constexpr (EMIT) { ob = (uint64_t)(uintptr_t)(out + out_off[i]); olen = out_off[i + 1] - out_off[i]; }
+  int64_t pend = 0, oend = 0;   // emit: the output before pend is in global memory, before oend in the ring
+  // emit: [pend, upto) of the row from the ring to global memory: bytes up to the first 16-byte boundary, whole words,
+  // and (final) the bytes behind the last boundary; else they wait for the next flush
+  auto flush = [&](int64_t upto, bool final) {
+    setsub_lds_sync();
+    const uint64_t a = ob + (uint64_t)pend, b = ob + (uint64_t)upto;
+    const uint64_t wa = (a + 15) & ~(uint64_t)15, wb = b & ~(uint64_t)15;
+    const uint64_t hend = wa < b ? wa : b;
+    for (uint64_t x = a + lane; x < hend; x += 64) *(uint8_t*)(uintptr_t)x = ring[x & (kSetSubRing - 1)];
+    for (uint64_t w = wa + 16 * (uint64_t)lane; w + 16 <= wb; w += 1024)
+      *(uint4*)(uintptr_t)w = *(const uint4*)(ring + (w & (kSetSubRing - 1)));
+    uint64_t np = wb > hend ? wb : hend;
+    if (final) {
+      for (uint64_t x = np + lane; x < b; x += 64) *(uint8_t*)(uintptr_t)x = ring[x & (kSetSubRing - 1)];
+      np = b;
+    }
+    pend = (int64_t)(np - ob);
+    setsub_lds_sync();
+  };
+  int32_t pos = 0;           // no candidate that starts before pos can be selected
+  int64_t reps = 0;
+  bool live = ha < hb;       // replacements are still being selected (hits left, count not reached)
+  int32_t cur = 0;           // emit: the input before cur is consumed ...
+  int64_t ocur = 0;          // ... and fills the output before ocur
+  int64_t delta = 0;         // select, per lane: replacement bytes minus matched bytes of its selected hits
+  const int32_t W = A.W;
+  for (int32_t w0 = 0; w0 <= L; w0 += W) {
+    const int32_t wn = min(W, L + 1 - w0);
+    const bool walk = live && pos < w0 + wn;
+    if constexpr (!EMIT) {
+      if (!live) break;
+      if (!walk) continue;
+    }
+    if (walk) {
+      const int wc = (wn + 63) & ~63;
+      for (int x = lane; x < wc; x += 64) best[x] = ~0ull;
+      setsub_lds_sync();
+      const int32_t lo = max(w0, pos), hi = w0 + wn;
+      for (int64_t q = ha + lane; q < hb; q += 64) {
+        const int2 sp = *(const int2*)(A.spans + 2 * q);
+        if (sp.x >= lo && sp.x < hi) {
+          const int32_t j = A.members[q];
+          const int32_t e = min(max(sp.y, sp.x), L);
+          if ((uint32_t)j < (uint32_t)A.k)
+            atomicMin((unsigned long long*)&best[sp.x - w0], ((unsigned long long)(uint32_t)j << 32) | (uint32_t)e);
+        }
+      }
+      setsub_lds_sync();
+    }
+    const int32_t c0 = EMIT ? 0 : ((max(pos, w0) - w0) & ~63);
+    for (int32_t c = c0; c < wn; c += 64) {
+      const int32_t p = w0 + c + lane;
+      uint32_t byte = 0;
+      if constexpr (EMIT) {
+        if (p < L) byte = text[p];
+      }
+      const int32_t cur_in = cur;
+      const int64_t ocur_in = ocur;
+      uint64_t sel = 0;
+      int32_t e = 0, j = 0;
+      int64_t rl = 0, my_o = 0;
+      if (walk && live && pos < w0 + c + 64) {
+        const uint64_t key = c + lane < wn ? best[c + lane] : ~0ull;
+        const bool occupied = key != ~0ull;
+        const uint64_t occ = __ballot(occupied);
+        e = (int32_t)(uint32_t)key;
+        j = occupied ? (int32_t)(key >> 32) : 0;
+        if (occupied) rl = A.roff[j + 1] - A.roff[j];
+        const int32_t nxt = max(e, p + 1);
+        while (true) {
+          const int32_t rel = pos - (w0 + c);
+          if (rel >= 64) break;
+          const uint64_t m = rel <= 0 ? occ : (occ & (~0ull << rel));
+          if (!m) break;
+          const int h = __builtin_ctzll(m);
+          sel |= 1ull << h;
+          pos = __builtin_amdgcn_readlane(nxt, h);
+          if constexpr (EMIT) {
+            const int64_t o = ocur + (int64_t)(w0 + c + h - cur);
+            if (lane == h) my_o = o;
+            ocur = o + setsub_readlane64(rl, h);
+            cur = __builtin_amdgcn_readlane(e, h);
+          }
+          ++reps;
+          if (A.count > 0 && reps >= A.count) { live = false; break; }
+        }
+      }
+      const bool mine = (sel >> lane) & 1ull;
+      if constexpr (!EMIT) {
+        if (mine) delta += rl - (int64_t)(e - p);
+      } else {
+        // this chunk writes the output [oend, oend_new): into the ring, or byte by byte when it does not fit
+        const int32_t cend = min(w0 + c + 64, L);
+        const int64_t oend_new = cur >= cend ? ocur : ocur + (cend - cur);
+        bool direct = false;
+        if (oend_new - pend > kSetSubRing) {
+          flush(oend, false);
+          if (oend_new - pend > kSetSubRing) {
+            flush(oend, true);
+            direct = true;
+          }
+        }
+        auto put = [&](int64_t o, uint8_t v) {
+          if (o < olen) {
+            const uint64_t x = ob + (uint64_t)o;
+            if (direct) *(uint8_t*)(uintptr_t)x = v;
+            else ring[x & (kSetSubRing - 1)] = v;
+          }
+        };
+        // the member's replacement at my_o
+        const uint8_t* rp = R + (mine ? A.roff[j] : 0);
+        if (mine && rl <= 64)
+          for (int64_t t = 0; t < rl; ++t) put(my_o + t, rp[t]);
+        uint64_t longm = __ballot(mine && rl > 64);
+        while (longm) {
+          const int h = __builtin_ctzll(longm);
+          longm &= longm - 1;
+          const int64_t o = setsub_readlane64(my_o, h), n_r = setsub_readlane64(rl, h);
+          const int32_t jh = __builtin_amdgcn_readlane(j, h);
+          const uint8_t* src = R + A.roff[jh];
+          for (int64_t t = lane; t < n_r; t += 64) put(o + t, src[t]);
+        }
+        // my byte: copied unless a selected hit covers it, behind the last selected hit at or before it
+        const uint64_t upto = sel & (lane == 63 ? ~0ull : ((2ull << lane) - 1));
+        const int src = upto ? 63 - __builtin_clzll(upto) : lane;
+        const int32_t e_src = __shfl(e, src);
+        const int64_t o_src = setsub_shfl64(my_o + rl, src);
+        const int32_t cs = upto ? e_src : cur_in;
+        const int64_t os = upto ? o_src : ocur_in;
+        if (p < L && p >= cs) put(os + (p - cs), (uint8_t)byte);
+        oend = oend_new;
+        if (direct) pend = oend;
+        else if (oend - pend >= kSetSubFlushAt) flush(oend, false);
+      }
+    }
+    if (walk) setsub_lds_sync();   // (best[] is rewritten by the next window)
+  }
+  if constexpr (EMIT) {
+    flush(oend < olen ? oend : olen, true);
+  } else {
+#pragma unroll
+    for (int d = 32; d; d >>= 1) delta += setsub_shfl64(delta, lane ^ d);
+    if (lane == 0) {
+      sizes[i] = (int64_t)L + delta;
+      nsub[i] = (int32_t)reps;
+    }
+  }
+}
+
+__device__ __forceinline__ const uint8_t* setsub_stage_repl(const SetSubArgs& A, uint8_t* lds_r) {
+  if (A.rbytes > kSetSubReplLds) return A.rtab;
+  for (int64_t x = threadIdx.x; x < A.rbytes; x += blockDim.x) lds_r[x] = A.rtab[x];
+  __syncthreads();
+  return lds_r;
+}
+
+// LDS: u64 best[W] per wavefront; emit adds a ring per wavefront and the replacement table (when it fits)
+__global__ __launch_bounds__(64 * kSetSubWaves) void k_setsub_select(const SetSubArgs A, int64_t* __restrict__ sizes,
+                                                                     int32_t* __restrict__ nsub) {
+  extern __shared__ __align__(16) uint8_t lds[];
+  const int wave = (int)threadIdx.x >> 6, lane = (int)threadIdx.x & 63;
+  uint64_t* best = (uint64_t*)lds + wave * A.W;
+  for (int64_t i = (int64_t)blockIdx.x * kSetSubWaves + wave; i < A.n; i += (int64_t)gridDim.x * kSetSubWaves)
+    setsub_text<false>(A, i, best, nullptr, nullptr, lane, sizes, nsub, nullptr, nullptr);
+}
+
+__global__ __launch_bounds__(64 * kSetSubWaves) void k_setsub_emit(const SetSubArgs A, const int64_t* __restrict__ out_off,
+                                                                   uint8_t* __restrict__ out) {
+  extern __shared__ __align__(16) uint8_t lds[];
+  const int wave = (int)threadIdx.x >> 6, lane = (int)threadIdx.x & 63;
+  uint64_t* best = (uint64_t*)lds + wave * A.W;
+  uint8_t* rings = lds + sizeof(uint64_t) * kSetSubWaves * A.W;
+  const uint8_t* R = setsub_stage_repl(A, rings + kSetSubWaves * kSetSubRing);
+  for (int64_t i = (int64_t)blockIdx.x * kSetSubWaves + wave; i < A.n; i += (int64_t)gridDim.x * kSetSubWaves)
+    setsub_text<true>(A, i, best, rings + wave * kSetSubRing, R, lane, nullptr, nullptr, out_off, out);
+}
+
 }  // namespace
 }  // namespace mrx
 
@@ -688,7 +942,77 @@ unsigned set_grid(int64_t items) {
 // Two phases: every member's count sizes each text's row and each member's total (one stream
 // synchronisation); then every member with a match runs its findall into scratch of exactly its total, and
 // k_setfa_place moves the spans into the text-major output.  Scratch: O(n) words plus the densest member's spans,
-// whatever k is (the arena is rewound behind each member's call).
+// whatever k is (the arena is rewound behind each member's call).  The phases are separate calls so that a caller
+// (set sub) can allocate the hits' buffers once their total is known; both run inside the caller's scratch scope.
+struct SetFaRun {
+  int64_t kt = -1, km = -1;      // the CSR batch's byte count and longest text, once for every member
+  int64_t* before = nullptr;     // [n] spans of the members placed so far, per text
+  int64_t* pre_j = nullptr;      // [n + 1] one member's findall CSR
+  std::vector<int64_t> h_mt;     // [k] member totals, [k] the total
+  int64_t total() const { return h_mt.back(); }
+};
+
+// phase 1: counts -> d_text_prefix[n + 1] and the member totals (one synchronisation); n > 0
+int set_findall_count(const mrx_set* sc, const uint8_t* data, const int64_t* offsets, int64_t stride, const int32_t* lens,
+                      int32_t len, int64_t n, int64_t known_total, int64_t known_max, int64_t* d_text_prefix,
+                      SetFaRun& r, void* st) {
+  const int k = (int)sc->members.size();
+  hipStream_t hs = (hipStream_t)st;
+  if (offsets) {
+    if (known_total >= 0 && known_max >= 0) { r.kt = known_total; r.km = known_max; }
+    else if (int rc = batch_bounds(offsets, n, st, &r.kt, &r.km)) return rc;
+  }
+  int32_t* cnt = (int32_t*)scratch_get(sizeof(int32_t) * (size_t)n, st);
+  int64_t* row = (int64_t*)scratch_get(sizeof(int64_t) * (size_t)n, st);
+  r.before = (int64_t*)scratch_get(sizeof(int64_t) * (size_t)n, st);
+  r.pre_j = (int64_t*)scratch_get(sizeof(int64_t) * (size_t)(n + 1), st);
+  int64_t* mt = (int64_t*)scratch_get(sizeof(int64_t) * (size_t)(k + 1), st);   // [k] member totals, [k] the total
+  if (!cnt || !row || !r.before || !r.pre_j || !mt) return internal_fail(MRX_E_NO_DEVICE, "scratch allocation failed");
+  SET_TRY(hipMemsetAsync(row, 0, sizeof(int64_t) * (size_t)n, hs));
+  SET_TRY(hipMemsetAsync(mt, 0, sizeof(int64_t) * (size_t)(k + 1), hs));
+  const ScratchMark mark = scratch_mark(st);
+  for (int j = 0; j < k; ++j) {
+    const int rc = member_count(sc->members[j], data, offsets, stride, lens, len, n, cnt, st, r.kt, r.km);
+    if (rc != MRX_OK) return internal_fail(rc, "member " + std::to_string(j) + ": " + mrx_last_error());
+    hipLaunchKernelGGL(k_setfa_add, dim3(std::min(set_grid(n), 1024u)), dim3(256), 0, hs, n, cnt, row,
+                       (unsigned long long*)(mt + j));
+    SET_TRY(hipGetLastError());
+    scratch_rewind(st, mark);
+  }
+  if (int rc = exclusive_scan(row, n, d_text_prefix, mt + k, st)) return rc;
+  r.h_mt.assign((size_t)k + 1, 0);
+  SET_TRY(hipMemcpyAsync(r.h_mt.data(), mt, sizeof(int64_t) * (size_t)(k + 1), hipMemcpyDeviceToHost, hs));
+  SET_TRY(hipStreamSynchronize(hs));
+  return MRX_OK;
+}
+
+// phase 2: the spans of the members that match, into d_members / d_spans (capacity span_cap >= r.total())
+int set_findall_place(const mrx_set* sc, const uint8_t* data, const int64_t* offsets, int64_t stride, const int32_t* lens,
+                      int32_t len, int64_t n, const SetFaRun& r, const int64_t* d_text_prefix, int32_t* d_members,
+                      int32_t* d_spans, int64_t span_cap, void* st) {
+  const int k = (int)sc->members.size();
+  hipStream_t hs = (hipStream_t)st;
+  const int64_t densest = *std::max_element(r.h_mt.begin(), r.h_mt.begin() + k);
+  int32_t* sp_j = (int32_t*)scratch_get(sizeof(int32_t) * 2 * (size_t)densest, st);
+  if (!sp_j) return internal_fail(MRX_E_NO_DEVICE, "scratch allocation failed");
+  SET_TRY(hipMemsetAsync(r.before, 0, sizeof(int64_t) * (size_t)n, hs));
+  const ScratchMark mark2 = scratch_mark(st);
+  for (int j = 0; j < k; ++j) {
+    const int64_t m = r.h_mt[j];
+    if (m == 0) continue;
+    const int rc = member_findall(sc->members[j], data, offsets, stride, lens, len, n, r.pre_j, sp_j, m, st, r.kt, r.km);
+    if (rc == MRX_E_CAPACITY)
+      return internal_fail(MRX_E_NO_DEVICE, "internal error: member " + std::to_string(j) + ": findall disagrees with count");
+    if (rc != MRX_OK) return internal_fail(rc, "member " + std::to_string(j) + ": " + mrx_last_error());
+    hipLaunchKernelGGL(k_setfa_place, dim3(set_grid(m)), dim3(256), 0, hs, n, j, m, r.pre_j, sp_j, d_text_prefix, r.before,
+                       span_cap, d_members, d_spans);
+    hipLaunchKernelGGL(k_setfa_advance, dim3(set_grid(n)), dim3(256), 0, hs, n, r.pre_j, r.before);
+    SET_TRY(hipGetLastError());
+    scratch_rewind(st, mark2);
+  }
+  return MRX_OK;
+}
+
 int set_findall(const mrx_set* sc, const uint8_t* data, const int64_t* offsets, int64_t stride, const int32_t* lens,
                 int32_t len, int64_t n, int64_t known_total, int64_t known_max, int64_t* d_text_prefix, int32_t* d_members,
                 int32_t* d_spans, int64_t span_cap, int64_t* total, void* st) {
@@ -717,71 +1041,126 @@ int set_findall(const mrx_set* sc, const uint8_t* data, const int64_t* offsets, 
   }
   scratch_scope_enter(st);
   struct Leave { void* st; ~Leave() { scratch_scope_leave(st); } } leave_{st};
-  int64_t kt = -1, km = -1;   // the CSR batch's byte count and longest text, once for every member
-  if (offsets) {
-    if (known_total >= 0 && known_max >= 0) { kt = known_total; km = known_max; }
-    else if (int rc = batch_bounds(offsets, n, st, &kt, &km)) return rc;
-  }
-  int32_t* cnt = (int32_t*)scratch_get(sizeof(int32_t) * (size_t)n, st);
-  int64_t* row = (int64_t*)scratch_get(sizeof(int64_t) * (size_t)n, st);
-  int64_t* before = (int64_t*)scratch_get(sizeof(int64_t) * (size_t)n, st);
-  int64_t* pre_j = (int64_t*)scratch_get(sizeof(int64_t) * (size_t)(n + 1), st);
-  int64_t* mt = (int64_t*)scratch_get(sizeof(int64_t) * (size_t)(k + 1), st);   // [k] member totals, [k] the total
-  if (!cnt || !row || !before || !pre_j || !mt) return internal_fail(MRX_E_NO_DEVICE, "scratch allocation failed");
-  SET_TRY(hipMemsetAsync(row, 0, sizeof(int64_t) * (size_t)n, hs));
-  SET_TRY(hipMemsetAsync(mt, 0, sizeof(int64_t) * (size_t)(k + 1), hs));
-  // phase 1: counts
-  const ScratchMark mark = scratch_mark(st);
-  for (int j = 0; j < k; ++j) {
-    const int rc = member_count(sc->members[j], data, offsets, stride, lens, len, n, cnt, st, kt, km);
-    if (rc != MRX_OK) return internal_fail(rc, "member " + std::to_string(j) + ": " + mrx_last_error());
-    hipLaunchKernelGGL(k_setfa_add, dim3(std::min(set_grid(n), 1024u)), dim3(256), 0, hs, n, cnt, row,
-                       (unsigned long long*)(mt + j));
-    SET_TRY(hipGetLastError());
-    scratch_rewind(st, mark);
-  }
-  if (int rc = exclusive_scan(row, n, d_text_prefix, mt + k, st)) return rc;
-  std::vector<int64_t> h_mt((size_t)k + 1);
-  SET_TRY(hipMemcpyAsync(h_mt.data(), mt, sizeof(int64_t) * (size_t)(k + 1), hipMemcpyDeviceToHost, hs));
-  SET_TRY(hipStreamSynchronize(hs));
-  const int64_t tot = h_mt[k];
+  SetFaRun r;
+  if (int rc = set_findall_count(sc, data, offsets, stride, lens, len, n, known_total, known_max, d_text_prefix, r, st))
+    return rc;
+  const int64_t tot = r.total();
   if (total) *total = tot;
   if (tot > span_cap)
     return internal_fail(MRX_E_CAPACITY, "span buffer too small: need " + std::to_string(tot));
   set_last_kernel("k_set_findall");
   if (tot == 0) return MRX_OK;
-  // phase 2: spans, for the members that match
-  const int64_t densest = *std::max_element(h_mt.begin(), h_mt.begin() + k);
-  int32_t* sp_j = (int32_t*)scratch_get(sizeof(int32_t) * 2 * (size_t)densest, st);
-  if (!sp_j) return internal_fail(MRX_E_NO_DEVICE, "scratch allocation failed");
-  SET_TRY(hipMemsetAsync(before, 0, sizeof(int64_t) * (size_t)n, hs));
-  const ScratchMark mark2 = scratch_mark(st);
-  for (int j = 0; j < k; ++j) {
-    const int64_t m = h_mt[j];
-    if (m == 0) continue;
-    const int rc = member_findall(sc->members[j], data, offsets, stride, lens, len, n, pre_j, sp_j, m, st, kt, km);
-    if (rc == MRX_E_CAPACITY)
-      return internal_fail(MRX_E_NO_DEVICE, "internal error: member " + std::to_string(j) + ": findall disagrees with count");
-    if (rc != MRX_OK) return internal_fail(rc, "member " + std::to_string(j) + ": " + mrx_last_error());
-    hipLaunchKernelGGL(k_setfa_place, dim3(set_grid(m)), dim3(256), 0, hs, n, j, m, pre_j, sp_j, d_text_prefix, before,
-                       span_cap, d_members, d_spans);
-    hipLaunchKernelGGL(k_setfa_advance, dim3(set_grid(n)), dim3(256), 0, hs, n, pre_j, before);
-    SET_TRY(hipGetLastError());
-    scratch_rewind(st, mark2);
-  }
+  if (int rc = set_findall_place(sc, data, offsets, stride, lens, len, n, r, d_text_prefix, d_members, d_spans, span_cap, st))
+    return rc;
   set_last_kernel("k_set_findall");
   return MRX_OK;
 }
 
-// host buffers for mrx_set_findall_batch
+// sub of a set: the set's findall into scratch (12 bytes per hit), k_setsub_select -> sizes and
+// replacement counts, the device scan -> output offsets, one synchronisation for the output size, k_setsub_emit.
+// Scratch: the hits, O(n) words and, while the members' findall runs, the densest member's spans.
+int set_sub(const mrx_set* sc, const char* const* repls, const size_t* repl_lens, int64_t count, const uint8_t* data,
+            const int64_t* offsets, int64_t stride, const int32_t* lens, int32_t len, int64_t n, int64_t known_total,
+            int64_t known_max, int64_t* d_out_off, uint8_t* d_out, int64_t out_cap, int32_t* d_nsub, int64_t* total_bytes,
+            void* st) {
+  if (!sc) return internal_fail(MRX_E_ARGUMENT, "null set");
+  if (n < 0) return internal_fail(MRX_E_ARGUMENT, "n must be >= 0");
+  if (count < 0) return internal_fail(MRX_E_ARGUMENT, "count must be >= 0");
+  if (out_cap < 0) return internal_fail(MRX_E_ARGUMENT, "out_cap must be >= 0");
+  if (!offsets) {
+    if (stride <= 0) return internal_fail(MRX_E_ARGUMENT, "stride must be positive");
+    if (!lens && (len < 0 || len > stride)) return internal_fail(MRX_E_ARGUMENT, "len must be in [0, stride]");
+  }
+  const int k = (int)sc->members.size();
+  if (!repl_lens || !d_out_off || (out_cap > 0 && !d_out))
+    return internal_fail(MRX_E_ARGUMENT, "null argument");
+  std::vector<int64_t> roff((size_t)k + 1, 0);
+  for (int j = 0; j < k; ++j) {
+    if (repl_lens[j] > 0 && (!repls || !repls[j]))
+      return internal_fail(MRX_E_ARGUMENT, "member " + std::to_string(j) + ": null replacement of nonzero length");
+    roff[j + 1] = roff[j] + (int64_t)repl_lens[j];
+  }
+  // refusals before anything is enqueued: group references, then the members' own
+  for (int j = 0; j < k; ++j)
+    if (repl_lens[j] > 0 && repl_has_group_refs(std::string(repls[j], repl_lens[j])))
+      return internal_fail(MRX_E_UNSUPPORTED,
+                           "member " + std::to_string(j) + ": group references are not supported in a set's sub");
+  for (int j = 0; j < k; ++j) {
+    const std::string why = handle_refusal(sc->members[j]);
+    if (!why.empty()) return internal_fail(MRX_E_UNSUPPORTED, "member " + std::to_string(j) + ": " + why);
+  }
+  int dev = 0;
+  SET_TRY(hipGetDevice(&dev));
+  hipStream_t hs = (hipStream_t)st;
+  if (total_bytes) *total_bytes = 0;
+  if (n == 0) {
+    SET_TRY(hipMemsetAsync(d_out_off, 0, sizeof(int64_t), hs));
+    set_last_kernel("k_set_sub");
+    return MRX_OK;
+  }
+  scratch_scope_enter(st);
+  struct Leave { void* st; ~Leave() { scratch_scope_leave(st); } } leave_{st};
+  // the set's findall, into scratch
+  int64_t* text_prefix = (int64_t*)scratch_get(sizeof(int64_t) * (size_t)(n + 1), st);
+  if (!text_prefix) return internal_fail(MRX_E_NO_DEVICE, "scratch allocation failed");
+  SetFaRun r;
+  if (int rc = set_findall_count(sc, data, offsets, stride, lens, len, n, known_total, known_max, text_prefix, r, st))
+    return rc;
+  const int64_t hits = r.total();
+  int32_t* members = (int32_t*)scratch_get(sizeof(int32_t) * (size_t)std::max<int64_t>(hits, 1), st);
+  int32_t* spans = (int32_t*)scratch_get(sizeof(int32_t) * 2 * (size_t)std::max<int64_t>(hits, 1), st);
+  int64_t* sizes = (int64_t*)scratch_get(sizeof(int64_t) * (size_t)n, st);
+  int64_t* d_total = (int64_t*)scratch_get(sizeof(int64_t), st);
+  int64_t* d_roff = (int64_t*)scratch_get(sizeof(int64_t) * (size_t)(k + 1), st);
+  uint8_t* d_rtab = (uint8_t*)scratch_get((size_t)roff[k] + 16, st);
+  int32_t* nsub = d_nsub ? d_nsub : (int32_t*)scratch_get(sizeof(int32_t) * (size_t)n, st);
+  if (!members || !spans || !sizes || !d_total || !d_roff || !d_rtab || !nsub)
+    return internal_fail(MRX_E_NO_DEVICE, "scratch allocation failed");
+  if (hits > 0)
+    if (int rc = set_findall_place(sc, data, offsets, stride, lens, len, n, r, text_prefix, members, spans, hits, st))
+      return rc;
+  std::vector<uint8_t> rtab((size_t)roff[k] + 1);
+  for (int j = 0; j < k; ++j)
+    if (repl_lens[j]) memcpy(rtab.data() + roff[j], repls[j], repl_lens[j]);
+  SET_TRY(hipMemcpyAsync(d_roff, roff.data(), sizeof(int64_t) * (size_t)(k + 1), hipMemcpyHostToDevice, hs));
+  if (roff[k]) SET_TRY(hipMemcpyAsync(d_rtab, rtab.data(), (size_t)roff[k], hipMemcpyHostToDevice, hs));
+  // the window: the longest text + 1 positions, rounded up to 64, at most kSetSubMaxW
+  const int64_t longest = offsets ? r.km : (lens ? stride : (int64_t)len);
+  const int32_t W = (int32_t)std::min<int64_t>(kSetSubMaxW, std::max<int64_t>(64, (longest + 1 + 63) & ~int64_t(63)));
+  SetSubArgs A{data, offsets, stride, lens, len, n, text_prefix, members, spans, d_rtab, d_roff, roff[k], count, k, W};
+  int64_t g = (n + kSetSubWaves - 1) / kSetSubWaves;
+  if (g > 4096) g = 4096;
+  const size_t lds_best = sizeof(uint64_t) * kSetSubWaves * (size_t)W;
+  const size_t lds_ring = (size_t)kSetSubWaves * kSetSubRing;
+  const size_t lds_repl = roff[k] <= kSetSubReplLds ? (size_t)((roff[k] + 15) & ~int64_t(15)) : 0;
+  hipLaunchKernelGGL(k_setsub_select, dim3((unsigned)g), dim3(64 * kSetSubWaves), lds_best, hs, A, sizes, nsub);
+  SET_TRY(hipGetLastError());
+  if (int rc = exclusive_scan(sizes, n, d_out_off, d_total, st)) return rc;
+  int64_t tot = 0;
+  SET_TRY(hipMemcpyAsync(&tot, d_total, sizeof tot, hipMemcpyDeviceToHost, hs));
+  SET_TRY(hipStreamSynchronize(hs));
+  if (total_bytes) *total_bytes = tot;
+  set_last_kernel("k_set_sub");
+  if (tot > out_cap) return internal_fail(MRX_E_CAPACITY, "output buffer too small: need " + std::to_string(tot));
+  if (tot > 0) {
+    hipLaunchKernelGGL(k_setsub_emit, dim3((unsigned)g), dim3(64 * kSetSubWaves), lds_best + lds_ring + lds_repl, hs, A, d_out_off,
+                       d_out);
+    SET_TRY(hipGetLastError());
+  }
+  return MRX_OK;
+}
+
+// host buffers for mrx_set_findall_batch and mrx_set_sub_batch
 struct HostBatchBufs {
   uint8_t* data = nullptr;
   int64_t* off = nullptr;
   int64_t* prefix = nullptr;
   int32_t* members = nullptr;
   int32_t* spans = nullptr;
+  uint8_t* out = nullptr;     // mrx_set_sub_batch: output bytes and replacement counts
+  int32_t* nsub = nullptr;
   ~HostBatchBufs() {
-    for (void* p : {(void*)data, (void*)off, (void*)prefix, (void*)members, (void*)spans})
+    for (void* p : {(void*)data, (void*)off, (void*)prefix, (void*)members, (void*)spans, (void*)out, (void*)nsub})
       if (p) (void)hipFree(p);
   }
 };
@@ -945,6 +1324,76 @@ int mrx_set_findall_batch(const mrx_set* s, const uint8_t* data, const int64_t* 
     SET_TRY(hipMemcpy(members, b.members, sizeof(int32_t) * (size_t)tot, hipMemcpyDeviceToHost));
     SET_TRY(hipMemcpy(spans, b.spans, sizeof(int32_t) * 2 * (size_t)tot, hipMemcpyDeviceToHost));
   }
+  return rc;
+}
+
+int mrx_set_sub_dev(const mrx_set* s, const char* const* repls, const size_t* repl_lens, int64_t count,
+                    const uint8_t* d_data, const int64_t* d_offsets, int64_t n, int64_t* d_out_offsets, uint8_t* d_out_data,
+                    int64_t out_cap, int32_t* d_nsub, int64_t* total_bytes, void* stream) {
+  if (!d_offsets) return internal_fail(MRX_E_ARGUMENT, "null offsets");
+  return set_sub(s, repls, repl_lens, count, d_data, d_offsets, 0, nullptr, 0, n, -1, -1, d_out_offsets, d_out_data,
+                 out_cap, d_nsub, total_bytes, stream);
+}
+int mrx_set_sub_known_dev(const mrx_set* s, const char* const* repls, const size_t* repl_lens, int64_t count,
+                          const uint8_t* d_data, const int64_t* d_offsets, int64_t n, int64_t end_offset,
+                          int64_t max_text_len, int64_t* d_out_offsets, uint8_t* d_out_data, int64_t out_cap,
+                          int32_t* d_nsub, int64_t* total_bytes, void* stream) {
+  if (!d_offsets) return internal_fail(MRX_E_ARGUMENT, "null offsets");
+  if (end_offset < 0 || max_text_len < 0)
+    return internal_fail(MRX_E_ARGUMENT, "end_offset and max_text_len must not be negative");
+  return set_sub(s, repls, repl_lens, count, d_data, d_offsets, 0, nullptr, 0, n, end_offset, max_text_len,
+                 d_out_offsets, d_out_data, out_cap, d_nsub, total_bytes, stream);
+}
+int mrx_set_sub_strided_dev(const mrx_set* s, const char* const* repls, const size_t* repl_lens, int64_t count,
+                            const uint8_t* d_data, int64_t stride, const int32_t* d_lens, int32_t len, int64_t n,
+                            int64_t* d_out_offsets, uint8_t* d_out_data, int64_t out_cap, int32_t* d_nsub,
+                            int64_t* total_bytes, void* stream) {
+  return set_sub(s, repls, repl_lens, count, d_data, nullptr, stride, d_lens, len, n, -1, -1, d_out_offsets, d_out_data,
+                 out_cap, d_nsub, total_bytes, stream);
+}
+int mrx_set_sub_batch(const mrx_set* s, const char* const* repls, const size_t* repl_lens, int64_t count,
+                      const uint8_t* data, const int64_t* offsets, int64_t n, int64_t* out_offsets, uint8_t* out_data,
+                      int64_t out_cap, int32_t* nsub, int64_t* total_bytes) {
+  if (!s || n < 0 || !offsets || !out_offsets || !repl_lens || (out_cap > 0 && !out_data))
+    return internal_fail(MRX_E_ARGUMENT, "null argument");
+  if (count < 0 || out_cap < 0) return internal_fail(MRX_E_ARGUMENT, "count and out_cap must be >= 0");
+  // argument errors and refusals before any device work, as the _dev entry points
+  for (size_t j = 0; j < s->members.size(); ++j)
+    if (repl_lens[j] > 0 && (!repls || !repls[j]))
+      return internal_fail(MRX_E_ARGUMENT, "member " + std::to_string(j) + ": null replacement of nonzero length");
+  for (size_t j = 0; j < s->members.size(); ++j)
+    if (repl_lens[j] > 0 && repl_has_group_refs(std::string(repls[j], repl_lens[j])))
+      return internal_fail(MRX_E_UNSUPPORTED,
+                           "member " + std::to_string(j) + ": group references are not supported in a set's sub");
+  for (size_t j = 0; j < s->members.size(); ++j) {
+    const std::string why = handle_refusal(s->members[j]);
+    if (!why.empty()) return internal_fail(MRX_E_UNSUPPORTED, "member " + std::to_string(j) + ": " + why);
+  }
+  const int64_t base = offsets[0], nbytes = offsets[n] - base;
+  if (nbytes < 0) return internal_fail(MRX_E_ARGUMENT, "offsets must not decrease");
+  if (nbytes > 0 && !data) return internal_fail(MRX_E_ARGUMENT, "null argument");
+  std::vector<int64_t> rel((size_t)n + 1);
+  int64_t longest = 0;
+  for (int64_t i = 0; i <= n; ++i) {
+    rel[i] = offsets[i] - base;
+    if (i > 0) longest = std::max(longest, rel[i] - rel[i - 1]);
+  }
+  HostBatchBufs b;
+  SET_TRY(hipMalloc((void**)&b.data, (size_t)nbytes + 64));
+  SET_TRY(hipMalloc((void**)&b.off, sizeof(int64_t) * (size_t)(n + 1)));
+  SET_TRY(hipMalloc((void**)&b.prefix, sizeof(int64_t) * (size_t)(n + 1)));
+  SET_TRY(hipMalloc((void**)&b.out, (size_t)std::max<int64_t>(out_cap, 1)));
+  if (nsub) SET_TRY(hipMalloc((void**)&b.nsub, sizeof(int32_t) * (size_t)std::max<int64_t>(n, 1)));
+  if (nbytes) SET_TRY(hipMemcpy(b.data, data + base, (size_t)nbytes, hipMemcpyHostToDevice));
+  SET_TRY(hipMemcpy(b.off, rel.data(), sizeof(int64_t) * (size_t)(n + 1), hipMemcpyHostToDevice));
+  int64_t tot = 0;
+  const int rc = mrx_set_sub_known_dev(s, repls, repl_lens, count, b.data, b.off, n, nbytes, longest, b.prefix, b.out,
+                                       out_cap, b.nsub, &tot, nullptr);
+  if (total_bytes) *total_bytes = tot;
+  if (rc != MRX_OK && rc != MRX_E_CAPACITY) return rc;
+  SET_TRY(hipMemcpy(out_offsets, b.prefix, sizeof(int64_t) * (size_t)(n + 1), hipMemcpyDeviceToHost));
+  if (nsub && n > 0) SET_TRY(hipMemcpy(nsub, b.nsub, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost));
+  if (rc == MRX_OK && tot > 0) SET_TRY(hipMemcpy(out_data, b.out, (size_t)tot, hipMemcpyDeviceToHost));
   return rc;
 }
 
