@@ -348,6 +348,27 @@ class DeviceBatch:
         b._max_len = int(np.diff(offs).max()) if n > 0 else 0
         return b
 
+    _entry_points = {}   # call(): an operation's entry points, resolved once per stem
+
+    def call(self, lib, op, head, tail):
+        """One C call on this batch: op is an operation's stem ("mrx_findall", "mrx_set_sub", ...) or the pair
+        (fn_csr, fn_strided).  Picks <stem>_strided_dev for a fixed pitch, <stem>_known_dev where the library has it and
+        the batch knows its bounds, else <stem>_dev, and lays the batch out as the ABI does between the arguments in
+        front of it (`head`) and those behind it (`tail`).  Returns the return code."""
+        if isinstance(op, str):
+            fns = self._entry_points.get(op)
+            if fns is None:
+                fns = self._entry_points[op] = (getattr(lib, op + "_dev"), getattr(lib, op + "_known_dev", None),
+                                                getattr(lib, op + "_strided_dev"))
+            fn_csr, fn_known, fn_strided = fns
+        else:
+            (fn_csr, fn_strided), fn_known = op, None
+        if self.offsets is None:
+            return fn_strided(*head, _ptr(self.data), self.stride, _ptr(self.lens), self.length, self.n, *tail)
+        if fn_known is not None and self._end_offset is not None:
+            return fn_known(*head, _ptr(self.data), _ptr(self.offsets), self.n, self._end_offset, self._max_len, *tail)
+        return fn_csr(*head, _ptr(self.data), _ptr(self.offsets), self.n, *tail)
+
     def csr_offsets(self):
         """CSR offsets for the generic kernels (built on device for strided batches)."""
         import torch
@@ -361,6 +382,21 @@ class DeviceBatch:
 
 def _ptr(t) -> int:
     return 0 if t is None else int(t.data_ptr())
+
+
+def _grow_call(cap, alloc, call, grow=True, only_larger=False):
+    """Allocate alloc(cap), rc = call(buffers, cap, byref(total)); on MRX_E_CAPACITY grow to the reported total and
+    repeat -- if `grow` (a caller's own capacity is not outgrown) and, with only_larger, only when the total exceeds
+    the capacity.  Returns (buffers, total)."""
+    while True:
+        bufs = alloc(cap)
+        total = C.c_int64(0)
+        rc = call(bufs, cap, C.byref(total))
+        if rc == MRX_E_CAPACITY and grow and (not only_larger or int(total.value) > cap):
+            cap = int(total.value)
+            continue
+        _check(rc)
+        return bufs, int(total.value)
 
 
 class CompiledRegex:
@@ -439,12 +475,7 @@ class CompiledRegex:
         if isinstance(texts, DeviceBatch):   # device tensor uint8[n]
             import torch
             f = torch.empty(texts.n, dtype=torch.uint8, device=texts.data.device)
-            if texts.offsets is not None:
-                _check(self._lib.mrx_is_match_dev(self._h, _ptr(texts.data), _ptr(texts.offsets), texts.n, _ptr(f),
-                                                  self._stream_ptr()))
-            else:
-                _check(self._lib.mrx_is_match_strided_dev(self._h, _ptr(texts.data), texts.stride, _ptr(texts.lens),
-                                                          texts.length, texts.n, _ptr(f), self._stream_ptr()))
+            _check(texts.call(self._lib, "mrx_is_match", (self._h,), (_ptr(f), self._stream_ptr())))
             return f
         data, offsets = pack_texts(texts)
         n = len(offsets) - 1
@@ -469,18 +500,14 @@ class CompiledRegex:
             d_starts = d_starts.to(device=dev, dtype=torch.int32).contiguous()
             if d_starts.numel() != batch.n:
                 raise MrxError("starts needs one entry per text")
-        csr = batch.offsets is not None
-        lay = ([_ptr(batch.data), _ptr(batch.offsets), batch.n] if csr else
-               [_ptr(batch.data), batch.stride, _ptr(batch.lens), batch.length, batch.n])
         if op == "is_match":
             f = torch.empty(batch.n, dtype=torch.uint8, device=dev)
-            fn = self._lib.mrx_is_match_at_dev if csr else self._lib.mrx_is_match_at_strided_dev
-            _check(fn(self._h, *lay, s0, _ptr(d_starts), _ptr(f), self._stream_ptr()))
+            _check(batch.call(self._lib, "mrx_is_match_at", (self._h,), (s0, _ptr(d_starts), _ptr(f), self._stream_ptr())))
             return f if isinstance(texts, DeviceBatch) else f.cpu().numpy()
         s = torch.empty(batch.n, dtype=torch.int32, device=dev)
         e = torch.empty(batch.n, dtype=torch.int32, device=dev)
-        name = "mrx_%s_at_%sdev" % ("match_first" if op == "match_first" else "search", "" if csr else "strided_")
-        _check(getattr(self._lib, name)(self._h, *lay, s0, _ptr(d_starts), _ptr(s), _ptr(e), self._stream_ptr()))
+        _check(batch.call(self._lib, "mrx_match_first_at" if op == "match_first" else "mrx_search_at", (self._h,),
+                          (s0, _ptr(d_starts), _ptr(s), _ptr(e), self._stream_ptr())))
         return (s, e) if isinstance(texts, DeviceBatch) else (s.cpu().numpy(), e.cpu().numpy())
 
     def match_first_at(self, texts, start):
@@ -510,18 +537,11 @@ class CompiledRegex:
         data, offsets = pack_texts(texts)
         n = len(offsets) - 1
         prefix = np.zeros(n + 1, np.int64)
-        cap = max(64, int(offsets[-1]) // 4 + n)
-        while True:
-            spans = np.empty((cap, 2), np.int32)
-            total = C.c_int64(0)
-            rc = self._lib.mrx_findall_batch(self._h, data.ctypes.data, offsets.ctypes.data, n,
-                                             prefix.ctypes.data, spans.ctypes.data, cap,
-                                             C.byref(total))
-            if rc == MRX_E_CAPACITY:
-                cap = int(total.value)
-                continue
-            _check(rc)
-            return prefix, spans[: total.value]
+        spans, total = _grow_call(
+            max(64, int(offsets[-1]) // 4 + n), lambda cap: np.empty((cap, 2), np.int32),
+            lambda spans, cap, total: self._lib.mrx_findall_batch(self._h, data.ctypes.data, offsets.ctypes.data, n,
+                                                                  prefix.ctypes.data, spans.ctypes.data, cap, total))
+        return prefix, spans[:total]
 
     findall = match_all
 
@@ -538,17 +558,11 @@ class CompiledRegex:
         data, offsets = pack_texts(bs)
         n = len(bs)
         prefix = np.zeros(n + 1, dtype=np.int64)
-        cap = max(16, 2 * n + len(data) // 8)
-        total = C.c_int64(0)
-        while True:
-            pieces = np.empty((cap, 2), dtype=np.int32)
-            rc = self._lib.mrx_split_batch(self._h, data.ctypes.data, offsets.ctypes.data, n, int(maxsplit), prefix.ctypes.data,
-                                           pieces.ctypes.data, cap, C.byref(total))
-            if rc == MRX_E_CAPACITY and int(total.value) > cap:
-                cap = int(total.value)
-                continue
-            _check(rc)
-            break
+        pieces, _ = _grow_call(
+            max(16, 2 * n + len(data) // 8), lambda cap: np.empty((cap, 2), dtype=np.int32),
+            lambda pieces, cap, total: self._lib.mrx_split_batch(self._h, data.ctypes.data, offsets.ctypes.data, n,
+                                                                 int(maxsplit), prefix.ctypes.data, pieces.ctypes.data,
+                                                                 cap, total), only_larger=True)
         out = []
         for i, t in enumerate(bs):
             out.append([t[int(a):int(b)] for a, b in pieces[prefix[i]:prefix[i + 1]]])
@@ -560,22 +574,14 @@ class CompiledRegex:
         dev = batch.data.device
         n = batch.n
         prefix = torch.empty(n + 1, dtype=torch.int64, device=dev)
-        cap = piece_cap if piece_cap is not None else max(16, 2 * n + batch.data.numel() // 8)
-        total = C.c_int64(0)
-        while True:
-            pieces = torch.empty((cap, 2), dtype=torch.int32, device=dev)
-            if batch.offsets is not None:
-                rc = self._lib.mrx_split_dev(self._h, _ptr(batch.data), _ptr(batch.offsets), n, int(maxsplit), _ptr(prefix),
-                                             _ptr(pieces), cap, C.byref(total), self._stream_ptr())
-            else:
-                rc = self._lib.mrx_split_strided_dev(self._h, _ptr(batch.data), batch.stride, _ptr(batch.lens), batch.length, n,
-                                                     int(maxsplit), _ptr(prefix), _ptr(pieces), cap, C.byref(total), self._stream_ptr())
-            if rc == MRX_E_CAPACITY and piece_cap is None and int(total.value) > cap:
-                cap = int(total.value)
-                continue
-            _check(rc)
-            break
-        return prefix, pieces, int(total.value)
+        pieces, total = _grow_call(
+            piece_cap if piece_cap is not None else max(16, 2 * n + batch.data.numel() // 8),
+            lambda cap: torch.empty((cap, 2), dtype=torch.int32, device=dev),
+            lambda pieces, cap, total: batch.call(self._lib, "mrx_split", (self._h,),
+                                                  (int(maxsplit), _ptr(prefix), _ptr(pieces), cap, total,
+                                                   self._stream_ptr())),
+            grow=piece_cap is None, only_larger=True)
+        return prefix, pieces, total
 
     def captures(self, texts) -> np.ndarray:
         """search + capture groups, int32[n, g+1, 2] in the order the reference's
@@ -598,100 +604,62 @@ class CompiledRegex:
         data, offsets = pack_texts(texts)
         n = len(offsets) - 1
         prefix = np.zeros(n + 1, np.int64)
-        cap = max(64, int(offsets[-1]) // 8 + n)
-        while True:
-            groups = np.empty((cap, g + 1, 2), np.int32)
-            total = C.c_int64(0)
-            rc = self._lib.mrx_captures_all_batch(self._h, data.ctypes.data, offsets.ctypes.data, n, int(count),
-                                                  prefix.ctypes.data, groups.ctypes.data, cap, C.byref(total))
-            if rc == MRX_E_CAPACITY and int(total.value) > cap:
-                cap = int(total.value)
-                continue
-            _check(rc)
-            return prefix, groups[: total.value]
+        groups, total = _grow_call(
+            max(64, int(offsets[-1]) // 8 + n), lambda cap: np.empty((cap, g + 1, 2), np.int32),
+            lambda groups, cap, total: self._lib.mrx_captures_all_batch(self._h, data.ctypes.data, offsets.ctypes.data, n,
+                                                                        int(count), prefix.ctypes.data,
+                                                                        groups.ctypes.data, cap, total),
+            only_larger=True)
+        return prefix, groups[:total]
 
     def _captures_all_dev(self, batch: "DeviceBatch", count: int = 0, match_cap: Optional[int] = None):
         import torch
         dev = batch.data.device
         g = self.num_groups
         prefix = torch.empty(batch.n + 1, dtype=torch.int64, device=dev)
-        cap = int(match_cap) if match_cap is not None else max(64, batch.data.numel() // 8 + batch.n)
-        while True:
-            groups = torch.empty((cap, g + 1, 2), dtype=torch.int32, device=dev)
-            total = C.c_int64(0)
-            if batch.offsets is not None:
-                rc = self._lib.mrx_captures_all_dev(self._h, _ptr(batch.data), _ptr(batch.offsets), batch.n, int(count),
-                                                    _ptr(prefix), _ptr(groups), cap, C.byref(total), self._stream_ptr())
-            else:
-                rc = self._lib.mrx_captures_all_strided_dev(self._h, _ptr(batch.data), batch.stride, _ptr(batch.lens),
-                                                            batch.length, batch.n, int(count), _ptr(prefix), _ptr(groups),
-                                                            cap, C.byref(total), self._stream_ptr())
-            if rc == MRX_E_CAPACITY and match_cap is None and int(total.value) > cap:
-                cap = int(total.value)
-                continue
-            _check(rc)
-            return prefix, groups[: total.value]
+        groups, total = _grow_call(
+            int(match_cap) if match_cap is not None else max(64, batch.data.numel() // 8 + batch.n),
+            lambda cap: torch.empty((cap, g + 1, 2), dtype=torch.int32, device=dev),
+            lambda groups, cap, total: batch.call(self._lib, "mrx_captures_all", (self._h,),
+                                                  (int(count), _ptr(prefix), _ptr(groups), cap, total,
+                                                   self._stream_ptr())),
+            grow=match_cap is None, only_larger=True)
+        return prefix, groups[:total]
 
     def sub(self, repl, texts, count: int = 0) -> List[bytes]:
         repl = _b(repl)
         data, offsets = pack_texts(texts)
         n = len(offsets) - 1
         out_off = np.zeros(n + 1, np.int64)
-        cap = max(64, int(offsets[-1]) * 2 + 16 * n)
-        while True:
-            out = np.empty(cap, np.uint8)
-            total = C.c_int64(0)
-            rc = self._lib.mrx_sub_batch(self._h, repl, len(repl), count, data.ctypes.data,
-                                         offsets.ctypes.data, n, out_off.ctypes.data,
-                                         out.ctypes.data, cap, C.byref(total))
-            if rc == MRX_E_CAPACITY:
-                cap = int(total.value)
-                continue
-            _check(rc)
-            raw = out[: total.value].tobytes()
-            return [raw[out_off[i]:out_off[i + 1]] for i in range(n)]
+        out, total = _grow_call(
+            max(64, int(offsets[-1]) * 2 + 16 * n), lambda cap: np.empty(cap, np.uint8),
+            lambda out, cap, total: self._lib.mrx_sub_batch(self._h, repl, len(repl), count, data.ctypes.data,
+                                                            offsets.ctypes.data, n, out_off.ctypes.data, out.ctypes.data,
+                                                            cap, total))
+        raw = out[:total].tobytes()
+        return [raw[out_off[i]:out_off[i + 1]] for i in range(n)]
 
     def captures_dev(self, batch: "DeviceBatch"):
         """search + capture groups on a device-resident batch: int32[n, g+1, 2] (device tensor)."""
         import torch
         g = self.num_groups
         out = torch.empty((batch.n, g + 1, 2), dtype=torch.int32, device=batch.data.device)
-        if batch.offsets is not None:
-            _check(self._lib.mrx_captures_dev(self._h, _ptr(batch.data), _ptr(batch.offsets), batch.n, _ptr(out),
-                                              self._stream_ptr()))
-        else:
-            _check(self._lib.mrx_captures_strided_dev(self._h, _ptr(batch.data), batch.stride, _ptr(batch.lens),
-                                                      batch.length, batch.n, _ptr(out), self._stream_ptr()))
+        _check(batch.call(self._lib, "mrx_captures", (self._h,), (_ptr(out), self._stream_ptr())))
         return out
 
     def sub_dev(self, repl, batch: "DeviceBatch", count: int = 0, out_cap: Optional[int] = None):
-        """regex.sub on a device-resident batch (CSR, or fixed pitch: mrx_sub_strided_dev):
+        """regex.sub on a device-resident batch (CSR, or fixed pitch, padded or not):
         (out_offsets int64[n+1], out_data uint8[total])."""
         import torch
         repl = _b(repl)
         dev = batch.data.device
-        off = batch.csr_offsets() if batch.offsets is not None else None
-        cap = int(out_cap) if out_cap else int(batch.data.numel()) * 2 + 16 * batch.n + 64
         out_off = torch.empty(batch.n + 1, dtype=torch.int64, device=dev)
-        while True:
-            out = torch.empty(cap, dtype=torch.uint8, device=dev)
-            total = C.c_int64(0)
-            if off is None:
-                rc = self._lib.mrx_sub_strided_dev(self._h, repl, len(repl), count, _ptr(batch.data), batch.stride,
-                                                   _ptr(batch.lens), batch.length, batch.n, _ptr(out_off), _ptr(out),
-                                                   cap, C.byref(total), self._stream_ptr())
-            elif batch.offsets is not None and batch._end_offset is not None:
-                rc = self._lib.mrx_sub_known_dev(self._h, repl, len(repl), count, _ptr(batch.data), _ptr(off), batch.n,
-                                                 batch._end_offset, batch._max_len, _ptr(out_off), _ptr(out), cap,
-                                                 C.byref(total), self._stream_ptr())
-            else:
-                rc = self._lib.mrx_sub_dev(self._h, repl, len(repl), count, _ptr(batch.data), _ptr(off), batch.n,
-                                           _ptr(out_off), _ptr(out), cap, C.byref(total), self._stream_ptr())
-            if rc == MRX_E_CAPACITY:
-                cap = int(total.value)
-                continue
-            _check(rc)
-            return out_off, out[: total.value]
+        out, total = _grow_call(
+            int(out_cap) if out_cap else int(batch.data.numel()) * 2 + 16 * batch.n + 64,
+            lambda cap: torch.empty(cap, dtype=torch.uint8, device=dev),
+            lambda out, cap, total: batch.call(self._lib, "mrx_sub", (self._h, repl, len(repl), count),
+                                               (_ptr(out_off), _ptr(out), cap, total, self._stream_ptr())))
+        return out_off, out[:total]
 
     # -- device-resident batches (torch tensors) ------------------------------------
     def _stream_ptr(self):
@@ -702,12 +670,7 @@ class CompiledRegex:
         import torch
         s = torch.empty(batch.n, dtype=torch.int32, device=batch.data.device)
         e = torch.empty(batch.n, dtype=torch.int32, device=batch.data.device)
-        if batch.offsets is not None:
-            _check(fn_csr(self._h, _ptr(batch.data), _ptr(batch.offsets), batch.n, _ptr(s), _ptr(e),
-                          self._stream_ptr()))
-        else:
-            _check(fn_strided(self._h, _ptr(batch.data), batch.stride, _ptr(batch.lens), batch.length,
-                              batch.n, _ptr(s), _ptr(e), self._stream_ptr()))
+        _check(batch.call(self._lib, (fn_csr, fn_strided), (self._h,), (_ptr(s), _ptr(e), self._stream_ptr())))
         return s, e
 
     def findall_async(self, batch: DeviceBatch, out):
@@ -715,20 +678,8 @@ class CompiledRegex:
         out = (counts_prefix int64[n+1], spans int32[cap, 2]) device tensors; the total
         is counts_prefix[n] once the stream has drained (check it against cap)."""
         prefix, spans = out
-        if batch.offsets is not None and batch._end_offset is not None:
-            rc = self._lib.mrx_findall_known_dev(self._h, _ptr(batch.data), _ptr(batch.offsets), batch.n,
-                                                 batch._end_offset, batch._max_len, _ptr(prefix), _ptr(spans),
-                                                 spans.shape[0], None, self._stream_ptr())
-        elif batch.offsets is not None:
-            rc = self._lib.mrx_findall_dev(self._h, _ptr(batch.data), _ptr(batch.offsets), batch.n,
-                                           _ptr(prefix), _ptr(spans), spans.shape[0], None,
-                                           self._stream_ptr())
-        else:
-            rc = self._lib.mrx_findall_strided_dev(self._h, _ptr(batch.data), batch.stride,
-                                                   _ptr(batch.lens), batch.length, batch.n,
-                                                   _ptr(prefix), _ptr(spans), spans.shape[0], None,
-                                                   self._stream_ptr())
-        _check(rc)
+        _check(batch.call(self._lib, "mrx_findall", (self._h,),
+                          (_ptr(prefix), _ptr(spans), spans.shape[0], None, self._stream_ptr())))
 
     def _dev_findall(self, batch: DeviceBatch, span_cap: Optional[int] = None, out=None):
         """Returns (counts_prefix int64[n+1], spans int32[cap, 2], total) on device."""
@@ -742,37 +693,18 @@ class CompiledRegex:
         else:
             prefix, spans = out
             span_cap = spans.shape[0]
-        total = C.c_int64(0)
-        while True:
-            if batch.offsets is not None and batch._end_offset is not None:
-                rc = self._lib.mrx_findall_known_dev(self._h, _ptr(batch.data), _ptr(batch.offsets), batch.n,
-                                                     batch._end_offset, batch._max_len, _ptr(prefix), _ptr(spans),
-                                                     span_cap, C.byref(total), self._stream_ptr())
-            elif batch.offsets is not None:
-                rc = self._lib.mrx_findall_dev(self._h, _ptr(batch.data), _ptr(batch.offsets), batch.n,
-                                               _ptr(prefix), _ptr(spans), span_cap, C.byref(total),
-                                               self._stream_ptr())
-            else:
-                rc = self._lib.mrx_findall_strided_dev(self._h, _ptr(batch.data), batch.stride,
-                                                       _ptr(batch.lens), batch.length, batch.n,
-                                                       _ptr(prefix), _ptr(spans), span_cap,
-                                                       C.byref(total), self._stream_ptr())
-            if rc == MRX_E_CAPACITY and out is None:
-                span_cap = int(total.value)
-                spans = torch.empty((span_cap, 2), dtype=torch.int32, device=dev)
-                continue
-            _check(rc)
-            return prefix, spans, int(total.value)
+        ready = [spans]   # (the first call's buffer is there already)
+        spans, total = _grow_call(
+            span_cap, lambda cap: ready.pop() if ready else torch.empty((cap, 2), dtype=torch.int32, device=dev),
+            lambda spans, cap, total: batch.call(self._lib, "mrx_findall", (self._h,),
+                                                 (_ptr(prefix), _ptr(spans), cap, total, self._stream_ptr())),
+            grow=out is None)
+        return prefix, spans, total
 
     def count(self, batch: DeviceBatch):
         import torch
         counts = torch.empty(batch.n, dtype=torch.int32, device=batch.data.device)
-        if batch.offsets is not None:
-            _check(self._lib.mrx_count_dev(self._h, _ptr(batch.data), _ptr(batch.offsets), batch.n,
-                                           _ptr(counts), self._stream_ptr()))
-        else:
-            _check(self._lib.mrx_count_strided_dev(self._h, _ptr(batch.data), batch.stride, _ptr(batch.lens),
-                                                   batch.length, batch.n, _ptr(counts), self._stream_ptr()))
+        _check(batch.call(self._lib, "mrx_count", (self._h,), (_ptr(counts), self._stream_ptr())))
         return counts
 
 
@@ -818,25 +750,18 @@ class PatternSet:
         batch = DeviceBatch.from_texts(list(texts)) if host else texts
         k, n, dev = len(self), batch.n, batch.data.device
         stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        csr = batch.offsets is not None
-        head = (self._h, _ptr(batch.data), _ptr(batch.offsets), n) if csr else \
-            (self._h, _ptr(batch.data), batch.stride, _ptr(batch.lens), batch.length, n)
-        L = self._lib
         if op == "search":
             s = torch.empty((n, k), dtype=torch.int32, device=dev)
             e = torch.empty((n, k), dtype=torch.int32, device=dev)
-            fn = L.mrx_set_search_dev if csr else L.mrx_set_search_strided_dev
-            _check(fn(*head, _ptr(s), _ptr(e), stream))
+            _check(batch.call(self._lib, "mrx_set_search", (self._h,), (_ptr(s), _ptr(e), stream)))
             return (s.cpu().numpy(), e.cpu().numpy()) if host else (s, e)
         if op == "count":
             c = torch.empty((n, k), dtype=torch.int32, device=dev)
-            fn = L.mrx_set_count_dev if csr else L.mrx_set_count_strided_dev
-            _check(fn(*head, _ptr(c), stream))
+            _check(batch.call(self._lib, "mrx_set_count", (self._h,), (_ptr(c), stream)))
             return c.cpu().numpy() if host else c
         words = (k + 63) // 64
         w = torch.empty((n, words), dtype=torch.int64, device=dev)
-        fn = L.mrx_set_matches_dev if csr else L.mrx_set_matches_strided_dev
-        _check(fn(*head, _ptr(w), stream))
+        _check(batch.call(self._lib, "mrx_set_matches", (self._h,), (_ptr(w), stream)))
         if host:
             u = w.cpu().numpy().view(np.uint64)
             bits = (u[:, :, None] >> np.arange(64, dtype=np.uint64)) & np.uint64(1)
@@ -867,19 +792,15 @@ class PatternSet:
         data, offsets = pack_texts(texts)
         n = len(offsets) - 1
         prefix = np.zeros(n + 1, np.int64)
-        cap = int(span_cap) if span_cap is not None else self._default_cap(int(offsets[-1]), n)
-        while True:
-            members = np.empty(max(cap, 1), np.int32)
-            spans = np.empty((max(cap, 1), 2), np.int32)
-            total = C.c_int64(0)
-            rc = self._lib.mrx_set_findall_batch(self._h, data.ctypes.data, offsets.ctypes.data, n, prefix.ctypes.data,
-                                                 members.ctypes.data, spans.ctypes.data, cap, C.byref(total))
-            if rc == MRX_E_CAPACITY and span_cap is None and int(total.value) > cap:
-                cap = int(total.value)
-                continue
-            _check(rc)
-            self._hits_per_byte = int(total.value) / max(1, int(offsets[-1]))
-            return prefix, members[: total.value], spans[: total.value]
+        (members, spans), total = _grow_call(
+            int(span_cap) if span_cap is not None else self._default_cap(int(offsets[-1]), n),
+            lambda cap: (np.empty(max(cap, 1), np.int32), np.empty((max(cap, 1), 2), np.int32)),
+            lambda ms, cap, total: self._lib.mrx_set_findall_batch(self._h, data.ctypes.data, offsets.ctypes.data, n,
+                                                                   prefix.ctypes.data, ms[0].ctypes.data,
+                                                                   ms[1].ctypes.data, cap, total),
+            grow=span_cap is None, only_larger=True)
+        self._hits_per_byte = total / max(1, int(offsets[-1]))
+        return prefix, members[:total], spans[:total]
 
     def _default_cap(self, nbytes: int, n: int) -> int:
         """Span capacity without a caller's cap: one hit per 8 bytes, or the density of this set's previous call (+1/8)
@@ -893,27 +814,15 @@ class PatternSet:
         n = batch.n
         stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
         prefix = torch.empty(n + 1, dtype=torch.int64, device=dev)
-        cap = int(span_cap) if span_cap is not None else self._default_cap(batch.data.numel(), n)
-        L = self._lib
-        while True:
-            members = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
-            spans = torch.empty((max(cap, 1), 2), dtype=torch.int32, device=dev)
-            total = C.c_int64(0)
-            tail = (_ptr(prefix), _ptr(members), _ptr(spans), cap, C.byref(total), stream)
-            if batch.offsets is not None and batch._end_offset is not None:
-                rc = L.mrx_set_findall_known_dev(self._h, _ptr(batch.data), _ptr(batch.offsets), n, batch._end_offset,
-                                                 batch._max_len, *tail)
-            elif batch.offsets is not None:
-                rc = L.mrx_set_findall_dev(self._h, _ptr(batch.data), _ptr(batch.offsets), n, *tail)
-            else:
-                rc = L.mrx_set_findall_strided_dev(self._h, _ptr(batch.data), batch.stride, _ptr(batch.lens),
-                                                   batch.length, n, *tail)
-            if rc == MRX_E_CAPACITY and span_cap is None and int(total.value) > cap:
-                cap = int(total.value)
-                continue
-            _check(rc)
-            self._hits_per_byte = int(total.value) / max(1, batch.data.numel())
-            return prefix, members[: total.value], spans[: total.value]
+        (members, spans), total = _grow_call(
+            int(span_cap) if span_cap is not None else self._default_cap(batch.data.numel(), n),
+            lambda cap: (torch.empty(max(cap, 1), dtype=torch.int32, device=dev),
+                         torch.empty((max(cap, 1), 2), dtype=torch.int32, device=dev)),
+            lambda ms, cap, total: batch.call(self._lib, "mrx_set_findall", (self._h,),
+                                              (_ptr(prefix), _ptr(ms[0]), _ptr(ms[1]), cap, total, stream)),
+            grow=span_cap is None, only_larger=True)
+        self._hits_per_byte = total / max(1, batch.data.numel())
+        return prefix, members[:total], spans[:total]
 
     def findall_lists(self, texts) -> List[List[Tuple[int, int, int]]]:
         """findall() as a list per text of (member, start, end) tuples."""
@@ -960,18 +869,15 @@ class PatternSet:
         n = len(offsets) - 1
         out_off = np.zeros(n + 1, np.int64)
         nsub = np.zeros(max(n, 1), np.int32)
-        cap = int(out_cap) if out_cap is not None else int(offsets[-1]) * 2 + (16 + longest) * n + 64
-        while True:
-            out = np.empty(max(cap, 1), np.uint8)
-            total = C.c_int64(0)
-            rc = self._lib.mrx_set_sub_batch(self._h, repls, lens, count, data.ctypes.data, offsets.ctypes.data, n,
-                                             out_off.ctypes.data, out.ctypes.data, cap, nsub.ctypes.data, C.byref(total))
-            if rc == MRX_E_CAPACITY and out_cap is None and int(total.value) > cap:
-                cap = int(total.value)
-                continue
-            _check(rc)
-            raw = out[: total.value].tobytes()
-            return [raw[out_off[i]:out_off[i + 1]] for i in range(n)], nsub[:n]
+        out, total = _grow_call(
+            int(out_cap) if out_cap is not None else int(offsets[-1]) * 2 + (16 + longest) * n + 64,
+            lambda cap: np.empty(max(cap, 1), np.uint8),
+            lambda out, cap, total: self._lib.mrx_set_sub_batch(self._h, repls, lens, count, data.ctypes.data,
+                                                                offsets.ctypes.data, n, out_off.ctypes.data,
+                                                                out.ctypes.data, cap, nsub.ctypes.data, total),
+            grow=out_cap is None, only_larger=True)
+        raw = out[:total].tobytes()
+        return [raw[out_off[i]:out_off[i + 1]] for i in range(n)], nsub[:n]
 
     def _sub_dev(self, repls, lens, longest: int, batch: "DeviceBatch", count: int, out_cap: Optional[int]):
         import torch
@@ -980,25 +886,13 @@ class PatternSet:
         stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
         out_off = torch.empty(n + 1, dtype=torch.int64, device=dev)
         nsub = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
-        cap = int(out_cap) if out_cap is not None else int(batch.data.numel()) * 2 + (16 + longest) * n + 64
-        L = self._lib
-        while True:
-            out = torch.empty(max(cap, 1), dtype=torch.uint8, device=dev)
-            total = C.c_int64(0)
-            tail = (_ptr(out_off), _ptr(out), cap, _ptr(nsub), C.byref(total), stream)
-            if batch.offsets is not None and batch._end_offset is not None:
-                rc = L.mrx_set_sub_known_dev(self._h, repls, lens, count, _ptr(batch.data), _ptr(batch.offsets), n,
-                                             batch._end_offset, batch._max_len, *tail)
-            elif batch.offsets is not None:
-                rc = L.mrx_set_sub_dev(self._h, repls, lens, count, _ptr(batch.data), _ptr(batch.offsets), n, *tail)
-            else:
-                rc = L.mrx_set_sub_strided_dev(self._h, repls, lens, count, _ptr(batch.data), batch.stride,
-                                               _ptr(batch.lens), batch.length, n, *tail)
-            if rc == MRX_E_CAPACITY and out_cap is None and int(total.value) > cap:
-                cap = int(total.value)
-                continue
-            _check(rc)
-            return out_off, out[: total.value], nsub[:n]
+        out, total = _grow_call(
+            int(out_cap) if out_cap is not None else int(batch.data.numel()) * 2 + (16 + longest) * n + 64,
+            lambda cap: torch.empty(max(cap, 1), dtype=torch.uint8, device=dev),
+            lambda out, cap, total: batch.call(self._lib, "mrx_set_sub", (self._h, repls, lens, count),
+                                               (_ptr(out_off), _ptr(out), cap, _ptr(nsub), total, stream)),
+            grow=out_cap is None, only_larger=True)
+        return out_off, out[:total], nsub[:n]
 
     def _host_run(self, op: int, text: bytes):
         """Testing: the packed set tables walked on the CPU for one text (mrx_testing_set_run); -2 = not in a shared

@@ -1,0 +1,56 @@
+// Host-buffer staging of the mrx_*_batch wrappers (mrx_kernels.hip, mrx_set.hip): a CSR batch copied to the device
+// with offsets made relative to its first byte, and device buffers for the outputs, all freed on every way out.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "../../include/mrx.h"
+#include "mrx_internal.hpp"
+
+#define MRX_HIP_TRY(expr)                                                                                    \
+  do {                                                                                                       \
+    hipError_t e_ = (expr);                                                                                  \
+    if (e_ != hipSuccess)                                                                                    \
+      return mrx::internal_fail(MRX_E_NO_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_));         \
+  } while (0)
+
+namespace mrx {
+struct DevBatch {
+  uint8_t* data = nullptr;
+  int64_t* offsets = nullptr;
+  int64_t nbytes = 0;    // after measure(): bytes of the batch, and its longest text
+  int64_t longest = 0;
+  std::vector<int64_t> rel;
+  ~DevBatch() { if (data) (void)hipFree(data); if (offsets) (void)hipFree(offsets); }
+  // host work only, so that a wrapper can still refuse (nbytes < 0: the offsets decrease) before anything is allocated
+  int measure(const int64_t* h_off, int64_t n) {
+    if (n < 0 || !h_off) return internal_fail(MRX_E_ARGUMENT, "bad batch");
+    rel.resize((size_t)n + 1);
+    for (int64_t i = 0; i <= n; ++i) {
+      rel[i] = h_off[i] - h_off[0];
+      if (i > 0) longest = std::max(longest, rel[i] - rel[i - 1]);
+    }
+    nbytes = rel[n];
+    return MRX_OK;
+  }
+  int upload(const uint8_t* h_data, const int64_t* h_off, int64_t n) {
+    if (rel.empty())
+      if (int rc = measure(h_off, n)) return rc;
+    MRX_HIP_TRY(hipMalloc((void**)&data, (size_t)nbytes + 64));
+    MRX_HIP_TRY(hipMalloc((void**)&offsets, sizeof(int64_t) * (n + 1)));
+    if (nbytes) MRX_HIP_TRY(hipMemcpy(data, h_data + h_off[0], (size_t)nbytes, hipMemcpyHostToDevice));
+    MRX_HIP_TRY(hipMemcpy(offsets, rel.data(), sizeof(int64_t) * (n + 1), hipMemcpyHostToDevice));
+    return MRX_OK;
+  }
+};
+template <class T>
+struct DevBuf {
+  T* p = nullptr;
+  ~DevBuf() { if (p) (void)hipFree(p); }
+  int alloc(size_t count) { MRX_HIP_TRY(hipMalloc((void**)&p, sizeof(T) * (count ? count : 1))); return MRX_OK; }
+};
+}  // namespace mrx

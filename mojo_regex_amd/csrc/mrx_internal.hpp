@@ -5,10 +5,47 @@
 #include <string>
 #include <vector>
 
+#if defined(__HIPCC__)
+#define MRX_HD __host__ __device__ __forceinline__
+#else
+#define MRX_HD inline
+#endif
+
 struct mrx_handle;
 namespace mrx {
 // records the calling thread's last error message (mrx_last_error()) and returns `code`
 int internal_fail(int code, const std::string& msg);
+
+// ---- where the texts of a batch live: the one form that entry points, host code and kernels pass on ------------
+// CSR (offsets != nullptr: text i is data[offsets[i], offsets[i + 1])) or fixed pitch (text i begins at data + i * stride
+// and is lens[i], or without lens `len`, bytes long).  The kernels' Layout (mrx_kernels.hip) begins with these fields.
+struct TextBatch {
+  const uint8_t* data = nullptr;
+  const int64_t* offsets = nullptr;
+  int64_t stride = 0;
+  const int32_t* lens = nullptr;
+  int32_t len = 0;
+  MRX_HD const uint8_t* text(int64_t i, int32_t* L) const {   // first byte and length of text i
+    if (offsets) {
+      const int64_t a = offsets[i];
+      *L = (int32_t)(offsets[i + 1] - a);
+      return data + a;
+    }
+    *L = lens ? lens[i] : len;
+    return data + i * stride;
+  }
+  int64_t pitch_longest() const { return lens ? stride : (int64_t)len; }   // fixed pitch: no text is longer
+};
+inline TextBatch csr(const uint8_t* data, const int64_t* offsets) { return TextBatch{data, offsets, 0, nullptr, 0}; }
+inline TextBatch strided(const uint8_t* data, int64_t stride, const int32_t* lens, int32_t len) {
+  return TextBatch{data, nullptr, stride, lens, len};
+}
+// The one check of a caller's batch, MRX_OK or MRX_E_ARGUMENT with the message that the entry point has always
+// given: BATCH_CSR refuses null offsets; BATCH_PITCH checks the pitch and the common length of a batch without
+// offsets (one with offsets passes), BATCH_PITCH_TERSE (sub and captures_all of one pattern) with one message for
+// both.  mrx_findall*_dev, mrx_split_dev and mrx_sub*_dev have never checked their offsets and pass csr() on as it is.
+enum BatchForm { BATCH_CSR, BATCH_PITCH, BATCH_PITCH_TERSE };
+int check_batch(const TextBatch& b, BatchForm form);
 
 // ---- mrx_stream_bits.hip: findall of short fixed-pitch texts in one launch, events kept in registers ----------
 struct DevPlan;
@@ -42,6 +79,16 @@ void set_last_kernel(const char* name);
 // its own allocations and the single-pattern calls it makes
 void scratch_scope_enter(void* stream);
 void scratch_scope_leave(void* stream);
+// One per API call (entry points nest: sub -> findall, a set -> its members): whatever exit path the outermost call
+// takes, bad-argument and HIP-error returns included, its allocations are returned to the arena, so the next call
+// reuses the same bytes instead of growing the arena.
+struct ScratchScope {
+  void* stream;
+  explicit ScratchScope(void* st) : stream(st) { scratch_scope_enter(stream); }
+  ~ScratchScope() { scratch_scope_leave(stream); }
+  ScratchScope(const ScratchScope&) = delete;
+  ScratchScope& operator=(const ScratchScope&) = delete;
+};
 void* scratch_get(size_t bytes, void* stream);   // nullptr: HIP error
 // a position in the calling thread's arena on `stream`: a set call rewinds to it behind each member's call (the
 // next member's work runs after it on the same stream), so that its scratch does not grow with the set size
@@ -55,13 +102,12 @@ void scratch_rewind(void* stream, const ScratchMark& m);
 int batch_bounds(const int64_t* d_offsets, int64_t n, void* stream, int64_t* total, int64_t* max_len);
 // exclusive prefix sum of n int64 into d_prefix[n + 1]; *d_total receives the sum
 int exclusive_scan(const int64_t* d_in, int64_t n, int64_t* d_prefix, int64_t* d_total, void* stream);
-// mrx_count_dev / mrx_findall_known_dev (total == NULL: asynchronous) of one handle, CSR (offsets) or fixed pitch;
+// mrx_count_dev / mrx_findall_known_dev (total == NULL: asynchronous) of one handle on a checked batch;
 // known_total / known_max: the CSR batch's bounds (< 0: not known)
-int member_count(const mrx_handle* h, const uint8_t* data, const int64_t* offsets, int64_t stride, const int32_t* lens,
-                 int32_t len, int64_t n, int32_t* counts, void* stream, int64_t known_total, int64_t known_max);
-int member_findall(const mrx_handle* h, const uint8_t* data, const int64_t* offsets, int64_t stride, const int32_t* lens,
-                   int32_t len, int64_t n, int64_t* d_prefix, int32_t* d_spans, int64_t span_cap, void* stream,
-                   int64_t known_total, int64_t known_max);
+int member_count(const mrx_handle* h, const TextBatch& b, int64_t n, int32_t* counts, void* stream, int64_t known_total,
+                 int64_t known_max);
+int member_findall(const mrx_handle* h, const TextBatch& b, int64_t n, int64_t* d_prefix, int32_t* d_spans,
+                   int64_t span_cap, void* stream, int64_t known_total, int64_t known_max);
 // the scan timer of mrx_timing_scan_ms around a launch sequence: begin returns a token for end
 void* scan_timer_begin(void* stream);
 void scan_timer_end(void* token);

@@ -29,6 +29,7 @@
 #include "../../include/mrx.h"
 #include "../../include/mrx_testing.h"
 #include "mrx_device.hpp"
+#include "mrx_host_batch.hpp"
 #include "mrx_internal.hpp"
 #include "mrx_lookback.hpp"
 
@@ -41,12 +42,9 @@ namespace {
 
 constexpr int kBlock = 256;  // 4 wavefronts
 
-struct Layout {  // where text i lives
-  const uint8_t* data;
-  const int64_t* offsets;  // CSR layout when non-null
-  int64_t stride;          // fixed pitch otherwise
-  const int32_t* lens;     // optional per-text length (fixed pitch)
-  int32_t len;             // common length when lens == nullptr
+struct Layout : TextBatch {  // where text i lives (TextBatch: data, offsets, stride, lens, len), and what kernels add
+  Layout() = default;
+  Layout(const TextBatch& b) : TextBatch(b) {}
   // Stepper kernels only (ragged batches with a few very long texts): k_wstep leaves texts of at least
   // `split` bytes to k_req_wave, which in turn skips the shorter ones; 0 = no split
   int32_t split = 0;
@@ -90,6 +88,13 @@ struct Layout {  // where text i lives
     return t;
   }
 };
+// every kernel's argument block holds a Layout: its size and field offsets are part of the device code
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winvalid-offsetof"
+static_assert(sizeof(Layout) == 96 && offsetof(Layout, data) == 0 && offsetof(Layout, len) == 32 &&
+                  offsetof(Layout, split) == 36 && offsetof(Layout, bm_cnt) == 88,
+              "Layout must keep its layout");
+#pragma clang diagnostic pop
 
 __device__ __forceinline__ Ctx stage_tables(const DevPlan& p, const uint8_t* __restrict__ blob,
                                             uint8_t* lds) {
@@ -4320,7 +4325,18 @@ int fail(int code, const std::string& msg) {
 }
 
 }  // namespace
-namespace mrx { int internal_fail(int code, const std::string& msg) { return fail(code, msg); } }   // mrx_internal.hpp
+namespace mrx {   // mrx_internal.hpp
+int internal_fail(int code, const std::string& msg) { return fail(code, msg); }
+int check_batch(const TextBatch& b, BatchForm form) {
+  if (form == BATCH_CSR) return b.offsets ? MRX_OK : fail(MRX_E_ARGUMENT, "null offsets");
+  if (b.offsets) return MRX_OK;
+  const bool terse = form == BATCH_PITCH_TERSE;
+  if (b.stride <= 0) return fail(MRX_E_ARGUMENT, terse ? "bad pitch / length" : "stride must be positive");
+  if (!b.lens && (b.len < 0 || b.len > b.stride))
+    return fail(MRX_E_ARGUMENT, terse ? "bad pitch / length" : "len must be in [0, stride]");
+  return MRX_OK;
+}
+}  // namespace mrx
 namespace {
 
 #define HIP_TRY(expr)                                                                  \
@@ -4389,21 +4405,6 @@ hipError_t scratch_free(void* p, hipStream_t s) {
     for (auto& c : a.chunks) c.used = 0;
   return hipSuccess;
 }
-// One per API call (entry points nest: sub -> findall): whatever exit path the outermost call takes,
-// bad-argument and HIP-error returns included, its allocations are returned to the arena, so the
-// next call reuses the same bytes instead of growing the arena.
-struct ScratchScope {
-  ScratchArena& a;
-  explicit ScratchScope(hipStream_t s) : a(scratch_arena(s)) { ++a.depth; }
-  ~ScratchScope() {
-    if (--a.depth == 0 && a.live != 0) {
-      a.live = 0;
-      for (auto& c : a.chunks) c.used = 0;
-    }
-  }
-  ScratchScope(const ScratchScope&) = delete;
-  ScratchScope& operator=(const ScratchScope&) = delete;
-};
 size_t scratch_bytes_reserved() {   // testing: total bytes held by the calling thread's arenas
   size_t t = 0;
   for (auto& kv : g_scratch) for (auto& c : kv.second.chunks) t += c.cap;
@@ -5264,7 +5265,7 @@ int pieces_prepare(const mrx_handle* h, const Layout& lay, int64_t n, hipStream_
   hipLaunchKernelGGL(k_virt_fill, dim3(grid_for(pc->nv, kBlock)), dim3(kBlock), 0, s, lay, n, pc->vfirst, pc->nv, C,
                      pc->back, pc->vstart, pc->vlen, pc->vskip, pc->vbase, disjoint ? 1 : 0);
   HIP_TRY(hipGetLastError());
-  pc->lay = Layout{lay.data, pc->vstart, 0, nullptr, 0};
+  pc->lay = csr(lay.data, pc->vstart);
   if (disjoint) pc->lay.vlen = pc->vlen;   // a view: the stepper's kernels read the pieces through Layout::text()
   pc->on = true;
   return MRX_OK;
@@ -6860,32 +6861,6 @@ int sub_chain_from_spans(const mrx_handle* h, const Layout& lay, int64_t n, cons
 }
 }  // namespace
 
-namespace {
-struct DevBatch {
-  uint8_t* data = nullptr;
-  int64_t* offsets = nullptr;
-  int64_t nbytes = 0;
-  ~DevBatch() { if (data) (void)hipFree(data); if (offsets) (void)hipFree(offsets); }
-  int upload(const uint8_t* h_data, const int64_t* h_off, int64_t n) {
-    if (n < 0 || !h_off) return fail(MRX_E_ARGUMENT, "bad batch");
-    nbytes = h_off[n];
-    HIP_TRY(hipMalloc((void**)&data, (size_t)nbytes + 64));
-    HIP_TRY(hipMalloc((void**)&offsets, sizeof(int64_t) * (n + 1)));
-    if (nbytes) HIP_TRY(hipMemcpy(data, h_data + h_off[0], (size_t)(nbytes - h_off[0]), hipMemcpyHostToDevice));
-    std::vector<int64_t> rel(n + 1);
-    for (int64_t i = 0; i <= n; ++i) rel[i] = h_off[i] - h_off[0];
-    HIP_TRY(hipMemcpy(offsets, rel.data(), sizeof(int64_t) * (n + 1), hipMemcpyHostToDevice));
-    return MRX_OK;
-  }
-};
-template <class T>
-struct DevBuf {
-  T* p = nullptr;
-  ~DevBuf() { if (p) (void)hipFree(p); }
-  int alloc(size_t count) { HIP_TRY(hipMalloc((void**)&p, sizeof(T) * (count ? count : 1))); return MRX_OK; }
-};
-}  // namespace
-
 extern "C" {
 
 int mrx_compile(const char* pattern, size_t pattern_len, mrx_handle** out) {
@@ -7013,7 +6988,7 @@ static int run_search_any(const mrx_handle* h, const Layout& lay, int64_t n, int
     }
     hipLaunchKernelGGL(k_view_build, dim3(grid_for(n + 1, kBlock)), dim3(kBlock), 0, s, lay, n, 0, d_cand, vstart, vlen, vskip, 0);
     HIP_TRY(hipGetLastError());
-    Layout view{lay.data, vstart, 0, nullptr, 0};
+    Layout view{csr(lay.data, vstart)};
     view.vlen = vlen;
     view.vskip = vskip;
     t_prefilter_done = true;
@@ -7091,26 +7066,28 @@ static int run_first_any(const mrx_handle* h, const Layout& lay, int64_t n, int3
 
 int mrx_match_first_dev(const mrx_handle* h, const uint8_t* d, const int64_t* off, int64_t n,
                         int32_t* s, int32_t* e, void* st) {
-  if (!off) return fail(MRX_E_ARGUMENT, "null offsets");
-  return run_first_any(h, Layout{d, off, 0, nullptr, 0}, n, s, e, st);
+  const TextBatch b = csr(d, off);
+  if (int rc = check_batch(b, BATCH_CSR)) return rc;
+  return run_first_any(h, b, n, s, e, st);
 }
 int mrx_search_dev(const mrx_handle* h, const uint8_t* d, const int64_t* off, int64_t n, int32_t* s,
                    int32_t* e, void* st) {
-  if (!off) return fail(MRX_E_ARGUMENT, "null offsets");
-  return run_search_any(h, Layout{d, off, 0, nullptr, 0}, n, s, e, st);
+  const TextBatch b = csr(d, off);
+  if (int rc = check_batch(b, BATCH_CSR)) return rc;
+  return run_search_any(h, b, n, s, e, st);
 }
 int mrx_search_strided_dev(const mrx_handle* h, const uint8_t* d, int64_t stride, const int32_t* lens,
                            int32_t len, int64_t n, int32_t* ds, int32_t* de, void* st) {
-  if (stride <= 0) return fail(MRX_E_ARGUMENT, "stride must be positive");
-  if (!lens && (len < 0 || len > stride)) return fail(MRX_E_ARGUMENT, "len must be in [0, stride]");
-  return run_search_any(h, Layout{d, nullptr, stride, lens, len}, n, ds, de, st);
+  const TextBatch b = strided(d, stride, lens, len);
+  if (int rc = check_batch(b, BATCH_PITCH)) return rc;
+  return run_search_any(h, b, n, ds, de, st);
 }
 int mrx_match_first_strided_dev(const mrx_handle* h, const uint8_t* d, int64_t stride,
                                 const int32_t* lens, int32_t len, int64_t n, int32_t* ds,
                                 int32_t* de, void* st) {
-  if (stride <= 0) return fail(MRX_E_ARGUMENT, "stride must be positive");
-  if (!lens && (len < 0 || len > stride)) return fail(MRX_E_ARGUMENT, "len must be in [0, stride]");
-  return run_first_any(h, Layout{d, nullptr, stride, lens, len}, n, ds, de, st);
+  const TextBatch b = strided(d, stride, lens, len);
+  if (int rc = check_batch(b, BATCH_PITCH)) return rc;
+  return run_first_any(h, b, n, ds, de, st);
 }
 static int run_is_match_any(const mrx_handle* h, const Layout& lay, int64_t n, uint8_t* f, void* st) {
   ScratchScope scratch_scope_((hipStream_t)st);
@@ -7147,14 +7124,15 @@ static int run_is_match_any(const mrx_handle* h, const Layout& lay, int64_t n, u
 }
 int mrx_is_match_dev(const mrx_handle* h, const uint8_t* d, const int64_t* off, int64_t n,
                      uint8_t* f, void* st) {
-  if (!off) return fail(MRX_E_ARGUMENT, "null offsets");
-  return run_is_match_any(h, Layout{d, off, 0, nullptr, 0}, n, f, st);
+  const TextBatch b = csr(d, off);
+  if (int rc = check_batch(b, BATCH_CSR)) return rc;
+  return run_is_match_any(h, b, n, f, st);
 }
 int mrx_is_match_strided_dev(const mrx_handle* h, const uint8_t* d, int64_t stride, const int32_t* lens,
                              int32_t len, int64_t n, uint8_t* f, void* st) {
-  if (stride <= 0) return fail(MRX_E_ARGUMENT, "stride must be positive");
-  if (!lens && (len < 0 || len > stride)) return fail(MRX_E_ARGUMENT, "len must be in [0, stride]");
-  return run_is_match_any(h, Layout{d, nullptr, stride, lens, len}, n, f, st);
+  const TextBatch b = strided(d, stride, lens, len);
+  if (int rc = check_batch(b, BATCH_PITCH)) return rc;
+  return run_is_match_any(h, b, n, f, st);
 }
 // match_first / match_next / is_match at a start position (see k_view_build): the operation runs on a
 // view of the batch, k_view_fix turns the view's answers into the text's.
@@ -7194,7 +7172,7 @@ static int run_at(int op, const mrx_handle* h, const Layout& lay, int64_t n, int
   const bool bt_first = op != AT_SEARCH && (h->hp.dev.flags & PF_BT_FIRST) && plan_uses_backtracker(h);
   hipLaunchKernelGGL(k_view_build, dim3(grid_for(n + 1, kBlock)), dim3(kBlock), 0, s, lay, n, start, d_starts, vstart, vlen, vskip,
                      bt_first ? 1 : 0);
-  Layout view{lay.data, vstart, 0, nullptr, 0};
+  Layout view{csr(lay.data, vstart)};
   view.vlen = vlen;
   view.vskip = vskip;
   const HostPlan& hp = h->hp;
@@ -7225,40 +7203,42 @@ static int run_at(int op, const mrx_handle* h, const Layout& lay, int64_t n, int
   HIP_TRY(scratch_free(vskip, s));
   return rc;
 }
-#define MRX_CHECK_STRIDED()                                                                        \
-  if (stride <= 0) return fail(MRX_E_ARGUMENT, "stride must be positive");                         \
-  if (!lens && (len < 0 || len > stride)) return fail(MRX_E_ARGUMENT, "len must be in [0, stride]")
 int mrx_match_first_at_dev(const mrx_handle* h, const uint8_t* d, const int64_t* off, int64_t n, int32_t start,
                            const int32_t* d_starts, int32_t* s, int32_t* e, void* st) {
-  if (!off) return fail(MRX_E_ARGUMENT, "null offsets");
-  return run_at(AT_FIRST, h, Layout{d, off, 0, nullptr, 0}, n, start, d_starts, s, e, nullptr, st);
+  const TextBatch b = csr(d, off);
+  if (int rc = check_batch(b, BATCH_CSR)) return rc;
+  return run_at(AT_FIRST, h, b, n, start, d_starts, s, e, nullptr, st);
 }
 int mrx_search_at_dev(const mrx_handle* h, const uint8_t* d, const int64_t* off, int64_t n, int32_t start,
                       const int32_t* d_starts, int32_t* s, int32_t* e, void* st) {
-  if (!off) return fail(MRX_E_ARGUMENT, "null offsets");
-  return run_at(AT_SEARCH, h, Layout{d, off, 0, nullptr, 0}, n, start, d_starts, s, e, nullptr, st);
+  const TextBatch b = csr(d, off);
+  if (int rc = check_batch(b, BATCH_CSR)) return rc;
+  return run_at(AT_SEARCH, h, b, n, start, d_starts, s, e, nullptr, st);
 }
 int mrx_is_match_at_dev(const mrx_handle* h, const uint8_t* d, const int64_t* off, int64_t n, int32_t start,
                         const int32_t* d_starts, uint8_t* f, void* st) {
-  if (!off) return fail(MRX_E_ARGUMENT, "null offsets");
-  return run_at(AT_IS_MATCH, h, Layout{d, off, 0, nullptr, 0}, n, start, d_starts, nullptr, nullptr, f, st);
+  const TextBatch b = csr(d, off);
+  if (int rc = check_batch(b, BATCH_CSR)) return rc;
+  return run_at(AT_IS_MATCH, h, b, n, start, d_starts, nullptr, nullptr, f, st);
 }
 int mrx_match_first_at_strided_dev(const mrx_handle* h, const uint8_t* d, int64_t stride, const int32_t* lens, int32_t len,
                                    int64_t n, int32_t start, const int32_t* d_starts, int32_t* s, int32_t* e, void* st) {
-  MRX_CHECK_STRIDED();
-  return run_at(AT_FIRST, h, Layout{d, nullptr, stride, lens, len}, n, start, d_starts, s, e, nullptr, st);
+  const TextBatch b = strided(d, stride, lens, len);
+  if (int rc = check_batch(b, BATCH_PITCH)) return rc;
+  return run_at(AT_FIRST, h, b, n, start, d_starts, s, e, nullptr, st);
 }
 int mrx_search_at_strided_dev(const mrx_handle* h, const uint8_t* d, int64_t stride, const int32_t* lens, int32_t len,
                               int64_t n, int32_t start, const int32_t* d_starts, int32_t* s, int32_t* e, void* st) {
-  MRX_CHECK_STRIDED();
-  return run_at(AT_SEARCH, h, Layout{d, nullptr, stride, lens, len}, n, start, d_starts, s, e, nullptr, st);
+  const TextBatch b = strided(d, stride, lens, len);
+  if (int rc = check_batch(b, BATCH_PITCH)) return rc;
+  return run_at(AT_SEARCH, h, b, n, start, d_starts, s, e, nullptr, st);
 }
 int mrx_is_match_at_strided_dev(const mrx_handle* h, const uint8_t* d, int64_t stride, const int32_t* lens, int32_t len,
                                 int64_t n, int32_t start, const int32_t* d_starts, uint8_t* f, void* st) {
-  MRX_CHECK_STRIDED();
-  return run_at(AT_IS_MATCH, h, Layout{d, nullptr, stride, lens, len}, n, start, d_starts, nullptr, nullptr, f, st);
+  const TextBatch b = strided(d, stride, lens, len);
+  if (int rc = check_batch(b, BATCH_PITCH)) return rc;
+  return run_at(AT_IS_MATCH, h, b, n, start, d_starts, nullptr, nullptr, f, st);
 }
-#undef MRX_CHECK_STRIDED
 
 static int run_captures_any(const mrx_handle* h, const Layout& lay, int64_t n, int32_t* spans, void* st) {
   ScratchScope scratch_scope_((hipStream_t)st);
@@ -7285,30 +7265,31 @@ static int run_captures_any(const mrx_handle* h, const Layout& lay, int64_t n, i
 }
 int mrx_captures_dev(const mrx_handle* h, const uint8_t* d, const int64_t* off, int64_t n,
                      int32_t* spans, void* st) {
-  if (!off) return fail(MRX_E_ARGUMENT, "null offsets");
-  return run_captures_any(h, Layout{d, off, 0, nullptr, 0}, n, spans, st);
+  const TextBatch b = csr(d, off);
+  if (int rc = check_batch(b, BATCH_CSR)) return rc;
+  return run_captures_any(h, b, n, spans, st);
 }
 int mrx_captures_strided_dev(const mrx_handle* h, const uint8_t* d, int64_t stride, const int32_t* lens,
                              int32_t len, int64_t n, int32_t* spans, void* st) {
-  if (stride <= 0) return fail(MRX_E_ARGUMENT, "stride must be positive");
-  if (!lens && (len < 0 || len > stride)) return fail(MRX_E_ARGUMENT, "len must be in [0, stride]");
-  return run_captures_any(h, Layout{d, nullptr, stride, lens, len}, n, spans, st);
+  const TextBatch b = strided(d, stride, lens, len);
+  if (int rc = check_batch(b, BATCH_PITCH)) return rc;
+  return run_captures_any(h, b, n, spans, st);
 }
 int mrx_findall_dev(const mrx_handle* h, const uint8_t* d, const int64_t* off, int64_t n,
                     int64_t* prefix, int32_t* spans, int64_t cap, int64_t* total, void* st) {
-  return run_findall(h, Layout{d, off, 0, nullptr, 0}, n, prefix, spans, cap, total, st);
+  return run_findall(h, csr(d, off), n, prefix, spans, cap, total, st);
 }
 int mrx_findall_known_dev(const mrx_handle* h, const uint8_t* d, const int64_t* off, int64_t n, int64_t end_offset,
                           int64_t max_text_len, int64_t* prefix, int32_t* spans, int64_t cap, int64_t* total, void* st) {
   if (end_offset < 0 || max_text_len < 0) return fail(MRX_E_ARGUMENT, "end_offset and max_text_len must not be negative");
-  return run_findall(h, Layout{d, off, 0, nullptr, 0}, n, prefix, spans, cap, total, st, false, end_offset, max_text_len);
+  return run_findall(h, csr(d, off), n, prefix, spans, cap, total, st, false, end_offset, max_text_len);
 }
 int mrx_findall_strided_dev(const mrx_handle* h, const uint8_t* d, int64_t stride,
                             const int32_t* lens, int32_t len, int64_t n, int64_t* prefix,
                             int32_t* spans, int64_t cap, int64_t* total, void* st) {
-  if (stride <= 0) return fail(MRX_E_ARGUMENT, "stride must be positive");
-  if (!lens && (len < 0 || len > stride)) return fail(MRX_E_ARGUMENT, "len must be in [0, stride]");
-  return run_findall(h, Layout{d, nullptr, stride, lens, len}, n, prefix, spans, cap, total, st);
+  const TextBatch b = strided(d, stride, lens, len);
+  if (int rc = check_batch(b, BATCH_PITCH)) return rc;
+  return run_findall(h, b, n, prefix, spans, cap, total, st);
 }
 
 }  // extern "C"
@@ -7408,13 +7389,13 @@ int run_split(const mrx_handle* h, const Layout& lay, int64_t n, int64_t maxspli
 extern "C" {
 int mrx_split_dev(const mrx_handle* h, const uint8_t* d, const int64_t* off, int64_t n, int64_t maxsplit,
                   int64_t* d_piece_prefix, int32_t* d_pieces, int64_t piece_cap, int64_t* total, void* st) {
-  return run_split(h, Layout{d, off, 0, nullptr, 0}, n, maxsplit, d_piece_prefix, d_pieces, piece_cap, total, st);
+  return run_split(h, csr(d, off), n, maxsplit, d_piece_prefix, d_pieces, piece_cap, total, st);
 }
 int mrx_split_strided_dev(const mrx_handle* h, const uint8_t* d, int64_t stride, const int32_t* lens, int32_t len, int64_t n,
                           int64_t maxsplit, int64_t* d_piece_prefix, int32_t* d_pieces, int64_t piece_cap, int64_t* total, void* st) {
-  if (stride <= 0) return fail(MRX_E_ARGUMENT, "stride must be positive");
-  if (!lens && (len < 0 || len > stride)) return fail(MRX_E_ARGUMENT, "len must be in [0, stride]");
-  return run_split(h, Layout{d, nullptr, stride, lens, len}, n, maxsplit, d_piece_prefix, d_pieces, piece_cap, total, st);
+  const TextBatch b = strided(d, stride, lens, len);
+  if (int rc = check_batch(b, BATCH_PITCH)) return rc;
+  return run_split(h, b, n, maxsplit, d_piece_prefix, d_pieces, piece_cap, total, st);
 }
 
 // known_total / known_max: csr_stats() of a CSR batch when the caller has them already (< 0: not; pattern-set findall)
@@ -7557,14 +7538,15 @@ static int run_count_any(const mrx_handle* h, const Layout& lay, int64_t n, int3
 }
 int mrx_count_dev(const mrx_handle* h, const uint8_t* d, const int64_t* off, int64_t n,
                   int32_t* counts, void* st) {
-  if (!off) return fail(MRX_E_ARGUMENT, "null offsets");
-  return run_count_any(h, Layout{d, off, 0, nullptr, 0}, n, counts, st);
+  const TextBatch b = csr(d, off);
+  if (int rc = check_batch(b, BATCH_CSR)) return rc;
+  return run_count_any(h, b, n, counts, st);
 }
 int mrx_count_strided_dev(const mrx_handle* h, const uint8_t* d, int64_t stride, const int32_t* lens,
                           int32_t len, int64_t n, int32_t* counts, void* st) {
-  if (stride <= 0) return fail(MRX_E_ARGUMENT, "stride must be positive");
-  if (!lens && (len < 0 || len > stride)) return fail(MRX_E_ARGUMENT, "len must be in [0, stride]");
-  return run_count_any(h, Layout{d, nullptr, stride, lens, len}, n, counts, st);
+  const TextBatch b = strided(d, stride, lens, len);
+  if (int rc = check_batch(b, BATCH_PITCH)) return rc;
+  return run_count_any(h, b, n, counts, st);
 }
 
 }  // extern "C"
@@ -7580,13 +7562,13 @@ extern "C" {
 int mrx_sub_dev(const mrx_handle* h, const char* repl, size_t repl_len, int64_t count,
                 const uint8_t* d, const int64_t* off, int64_t n, int64_t* out_off, uint8_t* out,
                 int64_t out_cap, int64_t* total_bytes, void* st) {
-  return sub_any(h, repl, repl_len, count, Layout{d, off, 0, nullptr, 0}, n, out_off, out, out_cap, total_bytes, st);
+  return sub_any(h, repl, repl_len, count, csr(d, off), n, out_off, out, out_cap, total_bytes, st);
 }
 int mrx_sub_known_dev(const mrx_handle* h, const char* repl, size_t repl_len, int64_t count,
                       const uint8_t* d, const int64_t* off, int64_t n, int64_t end_offset, int64_t max_text_len,
                       int64_t* out_off, uint8_t* out, int64_t out_cap, int64_t* total_bytes, void* st) {
   if (end_offset < 0 || max_text_len < 0) return fail(MRX_E_ARGUMENT, "negative end offset / text length");
-  return sub_any(h, repl, repl_len, count, Layout{d, off, 0, nullptr, 0}, n, out_off, out, out_cap, total_bytes, st,
+  return sub_any(h, repl, repl_len, count, csr(d, off), n, out_off, out, out_cap, total_bytes, st,
                  end_offset, max_text_len);
 }
 // Texts at a fixed pitch.  Rows without padding (len == stride, no per-text lengths) are a CSR batch whose offsets
@@ -7596,17 +7578,18 @@ int mrx_sub_strided_dev(const mrx_handle* h, const char* repl, size_t repl_len, 
                         const uint8_t* d, int64_t stride, const int32_t* d_lens, int32_t len, int64_t n,
                         int64_t* out_off, uint8_t* out, int64_t out_cap, int64_t* total_bytes, void* st) {
   // (`len` is ignored when d_lens is given, as in every other strided entry point)
-  if (stride <= 0 || (!d_lens && (len < 0 || len > stride))) return fail(MRX_E_ARGUMENT, "bad pitch / length");
+  const TextBatch b = strided(d, stride, d_lens, len);
+  if (int rc = check_batch(b, BATCH_PITCH_TERSE)) return rc;
   if (!d_lens && (int64_t)len == stride && n > 0) {
     ScratchScope scope_((hipStream_t)st);
     int64_t* d_off = nullptr;
     HIP_TRY(scratch_alloc((void**)&d_off, sizeof(int64_t) * (n + 1), (hipStream_t)st));
     hipLaunchKernelGGL(k_pitch_offsets, dim3(grid_for(n + 1, kBlock)), dim3(kBlock), 0, (hipStream_t)st, n, stride, d_off);
     HIP_TRY(hipGetLastError());
-    return sub_any(h, repl, repl_len, count, Layout{d, d_off, 0, nullptr, 0}, n, out_off, out, out_cap, total_bytes, st,
+    return sub_any(h, repl, repl_len, count, csr(d, d_off), n, out_off, out, out_cap, total_bytes, st,
                    n * stride, stride);
   }
-  return sub_any(h, repl, repl_len, count, Layout{d, nullptr, stride, d_lens, len}, n, out_off, out, out_cap, total_bytes, st);
+  return sub_any(h, repl, repl_len, count, b, n, out_off, out, out_cap, total_bytes, st);
 }
 }  // extern "C"
 static int sub_any(const mrx_handle* h, const char* repl, size_t repl_len, int64_t count, const Layout& lay_in,
@@ -7640,7 +7623,7 @@ static int sub_any(const mrx_handle* h, const char* repl, size_t repl_len, int64
   // leaves' runs (k_subc_sizes / k_subc_emit); batches with a text or an output beyond the tiles stay the interpreter's
   if (general_groups && h->hp.chain.ok && !g_force_generic && n > 0 && off && count >= 0 &&
       (h->hp.dev.flags & (PF_STREAM_SEARCH | PF_STEP_SEARCH)) && h->hp.why_no_search.empty()) {
-    const int rc = sub_chain_from_spans(h, Layout{d, off, 0, nullptr, 0}, n, r, tpl, count, out_off, out, out_cap,
+    const int rc = sub_chain_from_spans(h, csr(d, off), n, r, tpl, count, out_off, out, out_cap,
                                         total_bytes, s, known_bytes, known_max);
     if (rc != kSubsRetryGeneric) return rc;
   }
@@ -7675,7 +7658,7 @@ static int sub_any(const mrx_handle* h, const char* repl, size_t repl_len, int64
     // (nothing but (\d{N}) groups: every match is fixed_total bytes long and holds all its windows)
     if (h->hp.fixed_pure) group_reach = 0;
     if (rmap.size() <= 4096 && h->hp.fixed_total < 0x7FFF) {
-      const int rc = sub_from_spans(h, Layout{d, off, 0, nullptr, 0}, n, rmap, count, out_off, out, out_cap,
+      const int rc = sub_from_spans(h, csr(d, off), n, rmap, count, out_off, out, out_cap,
                                     total_bytes, s, group_reach, known_bytes, known_max);
       if (rc != kSubsRetryGeneric) return rc;   // else: a group reaches behind its text, the lane-per-text form cuts it
     }
@@ -8022,7 +8005,7 @@ static int captures_all_any(const mrx_handle* h, int64_t count, const Layout& la
                   h->hp.why_no_search.empty() && cg.nleaf <= kSubcLeaves && h->hp.bt.ngroups <= 9;
   for (int j = 1; chain_ok && j <= h->hp.bt.ngroups; ++j) chain_ok = cg.gopen[j] >= 0;
   if (chain_ok) {
-    const int rc = capall_from_spans(h, Layout{lay_in.data, off, 0, nullptr, 0}, n, count, true, d_prefix, d_groups,
+    const int rc = capall_from_spans(h, csr(lay_in.data, off), n, count, true, d_prefix, d_groups,
                                      match_cap, total, s, known_bytes, known_max);
     if (rc != kSubsRetryGeneric) return rc;
   }
@@ -8033,7 +8016,7 @@ static int captures_all_any(const mrx_handle* h, int64_t count, const Layout& la
                          (g_force_generic < 2 && (sfl & PF_STEP_SEARCH) && !(sfl & PF_PREFILTER)));
   const bool shortcut_differs = h->hp.fixed_concat && !h->hp.fixed_pure;
   if (spans_ok && !general && !shortcut_differs && n > 0 && off && h->hp.fixed_total < 0x7FFF)
-    return capall_from_spans(h, Layout{lay_in.data, off, 0, nullptr, 0}, n, count, false, d_prefix, d_groups, match_cap,
+    return capall_from_spans(h, csr(lay_in.data, off), n, count, false, d_prefix, d_groups, match_cap,
                              total, s, known_bytes, known_max);
   // route 3: sub_text()'s loop, a lane per text
   Layout lay = lay_in;
@@ -8080,25 +8063,27 @@ static int captures_all_any(const mrx_handle* h, int64_t count, const Layout& la
 extern "C" {
 int mrx_captures_all_dev(const mrx_handle* h, const uint8_t* d, const int64_t* off, int64_t n, int64_t count,
                          int64_t* d_match_prefix, int32_t* d_groups, int64_t match_cap, int64_t* total, void* st) {
-  if (!off) return fail(MRX_E_ARGUMENT, "null offsets");
-  return captures_all_any(h, count, Layout{d, off, 0, nullptr, 0}, n, d_match_prefix, d_groups, match_cap, total, st);
+  const TextBatch b = csr(d, off);
+  if (int rc = check_batch(b, BATCH_CSR)) return rc;
+  return captures_all_any(h, count, b, n, d_match_prefix, d_groups, match_cap, total, st);
 }
 // Texts at a fixed pitch, as mrx_sub_strided_dev: rows without padding are a CSR batch (offsets i * stride written on the
 // device) and take every route; padded rows take the lane-per-text kernels.
 int mrx_captures_all_strided_dev(const mrx_handle* h, const uint8_t* d, int64_t stride, const int32_t* d_lens, int32_t len,
                                  int64_t n, int64_t count, int64_t* d_match_prefix, int32_t* d_groups, int64_t match_cap,
                                  int64_t* total, void* st) {
-  if (stride <= 0 || (!d_lens && (len < 0 || len > stride))) return fail(MRX_E_ARGUMENT, "bad pitch / length");
+  const TextBatch b = strided(d, stride, d_lens, len);
+  if (int rc = check_batch(b, BATCH_PITCH_TERSE)) return rc;
   if (h && total && n > 0 && count >= 0 && !d_lens && (int64_t)len == stride) {
     ScratchScope scope_((hipStream_t)st);
     int64_t* d_off = nullptr;
     HIP_TRY(scratch_alloc((void**)&d_off, sizeof(int64_t) * (n + 1), (hipStream_t)st));
     hipLaunchKernelGGL(k_pitch_offsets, dim3(grid_for(n + 1, kBlock)), dim3(kBlock), 0, (hipStream_t)st, n, stride, d_off);
     HIP_TRY(hipGetLastError());
-    return captures_all_any(h, count, Layout{d, d_off, 0, nullptr, 0}, n, d_match_prefix, d_groups, match_cap, total, st,
+    return captures_all_any(h, count, csr(d, d_off), n, d_match_prefix, d_groups, match_cap, total, st,
                             n * stride, stride);
   }
-  return captures_all_any(h, count, Layout{d, nullptr, stride, d_lens, len}, n, d_match_prefix, d_groups, match_cap,
+  return captures_all_any(h, count, b, n, d_match_prefix, d_groups, match_cap,
                           total, st);
 }
 int mrx_captures_all_batch(const mrx_handle* h, const uint8_t* data, const int64_t* off, int64_t n, int64_t count,
@@ -8278,20 +8263,18 @@ void scratch_rewind(void* st, const ScratchMark& m) {
   for (size_t c = 0; c < a.chunks.size(); ++c) a.chunks[c].used = c < m.used.size() ? m.used[c] : 0;
 }
 int batch_bounds(const int64_t* d_offsets, int64_t n, void* st, int64_t* total, int64_t* max_len) {
-  return csr_stats(Layout{nullptr, d_offsets, 0, nullptr, 0}, n, (hipStream_t)st, total, max_len);
+  return csr_stats(csr(nullptr, d_offsets), n, (hipStream_t)st, total, max_len);
 }
 int exclusive_scan(const int64_t* d_in, int64_t n, int64_t* d_prefix, int64_t* d_total, void* st) {
   return device_scan<int64_t>(d_in, n, d_prefix, d_total, (hipStream_t)st);
 }
-int member_count(const mrx_handle* h, const uint8_t* data, const int64_t* offsets, int64_t stride, const int32_t* lens,
-                 int32_t len, int64_t n, int32_t* counts, void* st, int64_t known_total, int64_t known_max) {
-  return run_count_any(h, Layout{data, offsets, stride, lens, len}, n, counts, st, known_total, known_max);
+int member_count(const mrx_handle* h, const TextBatch& b, int64_t n, int32_t* counts, void* st, int64_t known_total,
+                 int64_t known_max) {
+  return run_count_any(h, b, n, counts, st, known_total, known_max);
 }
-int member_findall(const mrx_handle* h, const uint8_t* data, const int64_t* offsets, int64_t stride, const int32_t* lens,
-                   int32_t len, int64_t n, int64_t* d_prefix, int32_t* d_spans, int64_t span_cap, void* st,
-                   int64_t known_total, int64_t known_max) {
-  return run_findall(h, Layout{data, offsets, stride, lens, len}, n, d_prefix, d_spans, span_cap, nullptr, st, false,
-                     known_total, known_max);
+int member_findall(const mrx_handle* h, const TextBatch& b, int64_t n, int64_t* d_prefix, int32_t* d_spans,
+                   int64_t span_cap, void* st, int64_t known_total, int64_t known_max) {
+  return run_findall(h, b, n, d_prefix, d_spans, span_cap, nullptr, st, false, known_total, known_max);
 }
 void* scan_timer_begin(void* st) { return new ScanTimer((hipStream_t)st); }
 void scan_timer_end(void* tok) {

@@ -45,6 +45,7 @@
 
 #include "../../include/mrx.h"
 #include "../../include/mrx_testing.h"
+#include "mrx_host_batch.hpp"
 #include "mrx_internal.hpp"
 #include "mrx_plan.hpp"
 
@@ -83,9 +84,7 @@ struct SetPassDev {
 // ---------------------------------------------------------------------------------------------------------------
 template <int MODE, int NCG, int NCM>
 __global__ __launch_bounds__(64 * kSetWaves) void k_set_scan(const SetPassDev P, const uint8_t* __restrict__ blob,
-                                                             const uint8_t* __restrict__ data,
-                                                             const int64_t* __restrict__ offsets, int64_t stride,
-                                                             const int32_t* __restrict__ lens, int32_t len, int64_t n,
+                                                             const TextBatch B, int64_t n,
                                                              int32_t* __restrict__ o0, int32_t* __restrict__ o1,
                                                              uint64_t* __restrict__ bits) {
   constexpr int NS = NCG * 4 + NCM;   // member slots: columns first, then class members
@@ -101,13 +100,8 @@ __global__ __launch_bounds__(64 * kSetWaves) void k_set_scan(const SetPassDev P,
   for (int64_t task = (int64_t)blockIdx.x * kSetWaves + wave; task < ntask; task += (int64_t)gridDim.x * kSetWaves) {
     const int64_t i = task * 64 + lane;
     const bool live = i < n;
-    int64_t a = 0;
     int32_t L = 0;
-    if (live) {
-      if (offsets) { a = offsets[i]; L = (int32_t)(offsets[i + 1] - a); }
-      else { a = i * stride; L = lens ? lens[i] : len; }
-    }
-    const uint64_t ptr = (uint64_t)(uintptr_t)(data + a);
+    const uint64_t ptr = (uint64_t)(uintptr_t)(live ? B.text(i, &L) : B.data);
     const uint64_t base = ptr & ~(uint64_t)15;
     const int skew = live ? (int)(ptr - base) : 0;
     const int flen = live ? skew + L : 0;
@@ -376,7 +370,7 @@ constexpr int kSetSubRing = 2048;             // emit: output ring per wavefront
 constexpr int kSetSubFlushAt = 1024;          // ... flushed once this many bytes are pending
 constexpr int kSetSubReplLds = 4096;          // the replacement table is staged in LDS up to this many bytes
 
-struct SetSubArgs {
+struct SetSubArgs {   // (the batch's fields, not a TextBatch: with one, k_setsub_emit's scalar register count moved)
   const uint8_t* data;
   const int64_t* offsets;   // CSR, or NULL: fixed pitch
   int64_t stride;
@@ -823,8 +817,7 @@ void set_pass_run_host(const mrx_set::Pass& ps, int mode, const uint8_t* text, i
 }
 
 // the route rule: shared pass for this batch shape?  Never by default (see the head of this file).
-bool set_shared_route(const int64_t* /*offsets*/, int64_t /*stride*/, const int32_t* /*lens*/, int32_t /*len*/,
-                      int64_t /*n*/) {
+bool set_shared_route(const TextBatch& /*b*/, int64_t /*n*/) {
   return g_set_route.load(std::memory_order_relaxed) == 1;
 }
 
@@ -844,55 +837,53 @@ hipError_t set_upload(mrx_set* s, int fam, int pi, int dev, const uint8_t** out)
   return hipSuccess;
 }
 
-#define SET_TRY(expr)                                                                               \
-  do {                                                                                              \
-    hipError_t e_ = (expr);                                                                         \
-    if (e_ != hipSuccess) return internal_fail(MRX_E_NO_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-  } while (0)
-
-template <int MODE>
-void launch_pass(const SetPassDev& d, const uint8_t* blob, const uint8_t* data, const int64_t* offsets, int64_t stride,
-                 const int32_t* lens, int32_t len, int64_t n, int32_t* o0, int32_t* o1, uint64_t* bits, hipStream_t s) {
-  const int64_t ntask = (n + 63) / 64;
-  int64_t grid = (ntask + kSetWaves - 1) / kSetWaves;
-  if (grid > 4096) grid = 4096;
-  const size_t lds = (size_t)d.table_bytes + kSetWaves * (kSetTile + kSetFrameBytes);
-  if (d.ncg <= 2 && d.ncm <= 2)
-    hipLaunchKernelGGL((k_set_scan<MODE, 2, 2>), dim3((unsigned)grid), dim3(64 * kSetWaves), lds, s, d, blob, data, offsets,
-                       stride, lens, len, n, o0, o1, bits);
-  else
-    hipLaunchKernelGGL((k_set_scan<MODE, kSetMaxCG, kSetMaxCM>), dim3((unsigned)grid), dim3(64 * kSetWaves), lds, s, d, blob,
-                       data, offsets, stride, lens, len, n, o0, o1, bits);
+// blocks of `per` items each, at least one and at most 4096 (the kernels stride over what is left)
+unsigned set_grid(int64_t items, int per = 256) {
+  const int64_t g = (items + per - 1) / per;
+  return (unsigned)(g < 1 ? 1 : g > 4096 ? 4096 : g);
 }
 
-int set_run(const mrx_set* sc, int mode, const uint8_t* data, const int64_t* offsets, int64_t stride, const int32_t* lens,
-            int32_t len, int64_t n, int32_t* o0, int32_t* o1, uint64_t* bits, void* st) {
+// "member j: reason" if a member's count / search would be refused: asked before anything is enqueued
+std::string set_refusal(const mrx_set* s) {
+  for (size_t j = 0; j < s->members.size(); ++j) {
+    const std::string why = handle_refusal(s->members[j]);
+    if (!why.empty()) return "member " + std::to_string(j) + ": " + why;
+  }
+  return std::string();
+}
+
+template <int MODE>
+void launch_pass(const SetPassDev& d, const uint8_t* blob, const TextBatch& b, int64_t n, int32_t* o0, int32_t* o1,
+                 uint64_t* bits, hipStream_t s) {
+  const dim3 grid(set_grid((n + 63) / 64, kSetWaves)), block(64 * kSetWaves);
+  const size_t lds = (size_t)d.table_bytes + kSetWaves * (kSetTile + kSetFrameBytes);
+  if (d.ncg <= 2 && d.ncm <= 2)
+    hipLaunchKernelGGL((k_set_scan<MODE, 2, 2>), grid, block, lds, s, d, blob, b, n, o0, o1, bits);
+  else
+    hipLaunchKernelGGL((k_set_scan<MODE, kSetMaxCG, kSetMaxCM>), grid, block, lds, s, d, blob, b, n, o0, o1, bits);
+}
+
+int set_run(const mrx_set* sc, int mode, const TextBatch& tb, int64_t n, int32_t* o0, int32_t* o1, uint64_t* bits,
+            void* st) {
   if (!sc) return internal_fail(MRX_E_ARGUMENT, "null set");
   mrx_set* s = const_cast<mrx_set*>(sc);
   if (n < 0) return internal_fail(MRX_E_ARGUMENT, "n must be >= 0");
-  if (!offsets) {
-    if (stride <= 0) return internal_fail(MRX_E_ARGUMENT, "stride must be positive");
-    if (!lens && (len < 0 || len > stride)) return internal_fail(MRX_E_ARGUMENT, "len must be in [0, stride]");
-  }
-  if (n > 0 && (!data || (mode == SET_MATCHES ? !bits : (!o0 || (mode == SET_SEARCH && !o1)))))
+  if (int rc = check_batch(tb, BATCH_PITCH)) return rc;
+  if (n > 0 && (!tb.data || (mode == SET_MATCHES ? !bits : (!o0 || (mode == SET_SEARCH && !o1)))))
     return internal_fail(MRX_E_ARGUMENT, "null argument");
   const int fam = mode == SET_COUNT ? 0 : 1;
   const mrx_set::Plan& pl = s->plan[fam];
   const int k = (int)s->members.size();
-  // refusals before anything is enqueued
-  for (int j = 0; j < k; ++j) {
-    const std::string why = handle_refusal(s->members[j]);
-    if (!why.empty()) return internal_fail(MRX_E_UNSUPPORTED, "member " + std::to_string(j) + ": " + why);
-  }
+  const std::string refused = set_refusal(s);
+  if (!refused.empty()) return internal_fail(MRX_E_UNSUPPORTED, refused);
   int dev = 0;
-  SET_TRY(hipGetDevice(&dev));
+  MRX_HIP_TRY(hipGetDevice(&dev));
   if (n == 0) return MRX_OK;
   hipStream_t hs = (hipStream_t)st;
-  const bool shared = set_shared_route(offsets, stride, lens, len, n);
+  const bool shared = set_shared_route(tb, n);
   const int words = (k + 63) / 64;
-  scratch_scope_enter(st);
-  struct Leave { void* st; ~Leave() { scratch_scope_leave(st); } } leave_{st};
-  if (mode == SET_MATCHES) SET_TRY(hipMemsetAsync(bits, 0, sizeof(uint64_t) * (size_t)n * words, hs));
+  ScratchScope scope_(st);
+  if (mode == SET_MATCHES) MRX_HIP_TRY(hipMemsetAsync(bits, 0, sizeof(uint64_t) * (size_t)n * words, hs));
   int32_t* a = nullptr;
   int32_t* b = nullptr;
   for (int j = 0; j < k; ++j) {
@@ -905,26 +896,25 @@ int set_run(const mrx_set* sc, int mode, const uint8_t* data, const int64_t* off
     const mrx_handle* h = s->members[j];
     int rc;
     if (mode == SET_COUNT)
-      rc = offsets ? mrx_count_dev(h, data, offsets, n, a, st) : mrx_count_strided_dev(h, data, stride, lens, len, n, a, st);
+      rc = tb.offsets ? mrx_count_dev(h, tb.data, tb.offsets, n, a, st)
+                      : mrx_count_strided_dev(h, tb.data, tb.stride, tb.lens, tb.len, n, a, st);
     else
-      rc = offsets ? mrx_search_dev(h, data, offsets, n, a, b, st)
-                   : mrx_search_strided_dev(h, data, stride, lens, len, n, a, b, st);
+      rc = tb.offsets ? mrx_search_dev(h, tb.data, tb.offsets, n, a, b, st)
+                      : mrx_search_strided_dev(h, tb.data, tb.stride, tb.lens, tb.len, n, a, b, st);
     if (rc != MRX_OK) return internal_fail(rc, "member " + std::to_string(j) + ": " + mrx_last_error());
-    int64_t g = (n + 255) / 256;
-    if (g > 4096) g = 4096;
-    hipLaunchKernelGGL(k_set_scatter, dim3((unsigned)g), dim3(256), 0, hs, mode, n, k, words, j, a, b, o0, o1, bits);
-    SET_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_set_scatter, dim3(set_grid(n)), dim3(256), 0, hs, mode, n, k, words, j, a, b, o0, o1, bits);
+    MRX_HIP_TRY(hipGetLastError());
   }
   if (shared && !pl.passes.empty()) {
     void* tm = scan_timer_begin(st);
     for (int pi = 0; pi < (int)pl.passes.size(); ++pi) {
       const uint8_t* d_blob = nullptr;
-      SET_TRY(set_upload(s, fam, pi, dev, &d_blob));
+      MRX_HIP_TRY(set_upload(s, fam, pi, dev, &d_blob));
       const SetPassDev& d = pl.passes[pi].dv;
-      if (mode == SET_COUNT) launch_pass<SET_COUNT>(d, d_blob, data, offsets, stride, lens, len, n, o0, o1, bits, hs);
-      else if (mode == SET_SEARCH) launch_pass<SET_SEARCH>(d, d_blob, data, offsets, stride, lens, len, n, o0, o1, bits, hs);
-      else launch_pass<SET_MATCHES>(d, d_blob, data, offsets, stride, lens, len, n, o0, o1, bits, hs);
-      SET_TRY(hipGetLastError());
+      if (mode == SET_COUNT) launch_pass<SET_COUNT>(d, d_blob, tb, n, o0, o1, bits, hs);
+      else if (mode == SET_SEARCH) launch_pass<SET_SEARCH>(d, d_blob, tb, n, o0, o1, bits, hs);
+      else launch_pass<SET_MATCHES>(d, d_blob, tb, n, o0, o1, bits, hs);
+      MRX_HIP_TRY(hipGetLastError());
     }
     scan_timer_end(tm);
     set_last_kernel("k_set_scan");
@@ -932,11 +922,6 @@ int set_run(const mrx_set* sc, int mode, const uint8_t* data, const int64_t* off
     set_last_kernel("k_set_member_loop");
   }
   return MRX_OK;
-}
-
-unsigned set_grid(int64_t items) {
-  int64_t g = (items + 255) / 256;
-  return (unsigned)(g < 1 ? 1 : g > 4096 ? 4096 : g);
 }
 
 // Two phases: every member's count sizes each text's row and each member's total (one stream
@@ -953,14 +938,13 @@ struct SetFaRun {
 };
 
 // phase 1: counts -> d_text_prefix[n + 1] and the member totals (one synchronisation); n > 0
-int set_findall_count(const mrx_set* sc, const uint8_t* data, const int64_t* offsets, int64_t stride, const int32_t* lens,
-                      int32_t len, int64_t n, int64_t known_total, int64_t known_max, int64_t* d_text_prefix,
-                      SetFaRun& r, void* st) {
+int set_findall_count(const mrx_set* sc, const TextBatch& b, int64_t n, int64_t known_total, int64_t known_max,
+                      int64_t* d_text_prefix, SetFaRun& r, void* st) {
   const int k = (int)sc->members.size();
   hipStream_t hs = (hipStream_t)st;
-  if (offsets) {
+  if (b.offsets) {
     if (known_total >= 0 && known_max >= 0) { r.kt = known_total; r.km = known_max; }
-    else if (int rc = batch_bounds(offsets, n, st, &r.kt, &r.km)) return rc;
+    else if (int rc = batch_bounds(b.offsets, n, st, &r.kt, &r.km)) return rc;
   }
   int32_t* cnt = (int32_t*)scratch_get(sizeof(int32_t) * (size_t)n, st);
   int64_t* row = (int64_t*)scratch_get(sizeof(int64_t) * (size_t)n, st);
@@ -968,90 +952,79 @@ int set_findall_count(const mrx_set* sc, const uint8_t* data, const int64_t* off
   r.pre_j = (int64_t*)scratch_get(sizeof(int64_t) * (size_t)(n + 1), st);
   int64_t* mt = (int64_t*)scratch_get(sizeof(int64_t) * (size_t)(k + 1), st);   // [k] member totals, [k] the total
   if (!cnt || !row || !r.before || !r.pre_j || !mt) return internal_fail(MRX_E_NO_DEVICE, "scratch allocation failed");
-  SET_TRY(hipMemsetAsync(row, 0, sizeof(int64_t) * (size_t)n, hs));
-  SET_TRY(hipMemsetAsync(mt, 0, sizeof(int64_t) * (size_t)(k + 1), hs));
+  MRX_HIP_TRY(hipMemsetAsync(row, 0, sizeof(int64_t) * (size_t)n, hs));
+  MRX_HIP_TRY(hipMemsetAsync(mt, 0, sizeof(int64_t) * (size_t)(k + 1), hs));
   const ScratchMark mark = scratch_mark(st);
   for (int j = 0; j < k; ++j) {
-    const int rc = member_count(sc->members[j], data, offsets, stride, lens, len, n, cnt, st, r.kt, r.km);
+    const int rc = member_count(sc->members[j], b, n, cnt, st, r.kt, r.km);
     if (rc != MRX_OK) return internal_fail(rc, "member " + std::to_string(j) + ": " + mrx_last_error());
     hipLaunchKernelGGL(k_setfa_add, dim3(std::min(set_grid(n), 1024u)), dim3(256), 0, hs, n, cnt, row,
                        (unsigned long long*)(mt + j));
-    SET_TRY(hipGetLastError());
+    MRX_HIP_TRY(hipGetLastError());
     scratch_rewind(st, mark);
   }
   if (int rc = exclusive_scan(row, n, d_text_prefix, mt + k, st)) return rc;
   r.h_mt.assign((size_t)k + 1, 0);
-  SET_TRY(hipMemcpyAsync(r.h_mt.data(), mt, sizeof(int64_t) * (size_t)(k + 1), hipMemcpyDeviceToHost, hs));
-  SET_TRY(hipStreamSynchronize(hs));
+  MRX_HIP_TRY(hipMemcpyAsync(r.h_mt.data(), mt, sizeof(int64_t) * (size_t)(k + 1), hipMemcpyDeviceToHost, hs));
+  MRX_HIP_TRY(hipStreamSynchronize(hs));
   return MRX_OK;
 }
 
 // phase 2: the spans of the members that match, into d_members / d_spans (capacity span_cap >= r.total())
-int set_findall_place(const mrx_set* sc, const uint8_t* data, const int64_t* offsets, int64_t stride, const int32_t* lens,
-                      int32_t len, int64_t n, const SetFaRun& r, const int64_t* d_text_prefix, int32_t* d_members,
-                      int32_t* d_spans, int64_t span_cap, void* st) {
+int set_findall_place(const mrx_set* sc, const TextBatch& b, int64_t n, const SetFaRun& r, const int64_t* d_text_prefix,
+                      int32_t* d_members, int32_t* d_spans, int64_t span_cap, void* st) {
   const int k = (int)sc->members.size();
   hipStream_t hs = (hipStream_t)st;
   const int64_t densest = *std::max_element(r.h_mt.begin(), r.h_mt.begin() + k);
   int32_t* sp_j = (int32_t*)scratch_get(sizeof(int32_t) * 2 * (size_t)densest, st);
   if (!sp_j) return internal_fail(MRX_E_NO_DEVICE, "scratch allocation failed");
-  SET_TRY(hipMemsetAsync(r.before, 0, sizeof(int64_t) * (size_t)n, hs));
+  MRX_HIP_TRY(hipMemsetAsync(r.before, 0, sizeof(int64_t) * (size_t)n, hs));
   const ScratchMark mark2 = scratch_mark(st);
   for (int j = 0; j < k; ++j) {
     const int64_t m = r.h_mt[j];
     if (m == 0) continue;
-    const int rc = member_findall(sc->members[j], data, offsets, stride, lens, len, n, r.pre_j, sp_j, m, st, r.kt, r.km);
+    const int rc = member_findall(sc->members[j], b, n, r.pre_j, sp_j, m, st, r.kt, r.km);
     if (rc == MRX_E_CAPACITY)
       return internal_fail(MRX_E_NO_DEVICE, "internal error: member " + std::to_string(j) + ": findall disagrees with count");
     if (rc != MRX_OK) return internal_fail(rc, "member " + std::to_string(j) + ": " + mrx_last_error());
     hipLaunchKernelGGL(k_setfa_place, dim3(set_grid(m)), dim3(256), 0, hs, n, j, m, r.pre_j, sp_j, d_text_prefix, r.before,
                        span_cap, d_members, d_spans);
     hipLaunchKernelGGL(k_setfa_advance, dim3(set_grid(n)), dim3(256), 0, hs, n, r.pre_j, r.before);
-    SET_TRY(hipGetLastError());
+    MRX_HIP_TRY(hipGetLastError());
     scratch_rewind(st, mark2);
   }
   return MRX_OK;
 }
 
-int set_findall(const mrx_set* sc, const uint8_t* data, const int64_t* offsets, int64_t stride, const int32_t* lens,
-                int32_t len, int64_t n, int64_t known_total, int64_t known_max, int64_t* d_text_prefix, int32_t* d_members,
-                int32_t* d_spans, int64_t span_cap, int64_t* total, void* st) {
+int set_findall(const mrx_set* sc, const TextBatch& b, int64_t n, int64_t known_total, int64_t known_max,
+                int64_t* d_text_prefix, int32_t* d_members, int32_t* d_spans, int64_t span_cap, int64_t* total, void* st) {
   if (!sc) return internal_fail(MRX_E_ARGUMENT, "null set");
   if (n < 0) return internal_fail(MRX_E_ARGUMENT, "n must be >= 0");
   if (span_cap < 0) return internal_fail(MRX_E_ARGUMENT, "span_cap must be >= 0");
-  if (!offsets) {
-    if (stride <= 0) return internal_fail(MRX_E_ARGUMENT, "stride must be positive");
-    if (!lens && (len < 0 || len > stride)) return internal_fail(MRX_E_ARGUMENT, "len must be in [0, stride]");
-  }
+  if (int rc = check_batch(b, BATCH_PITCH)) return rc;
   if (!d_text_prefix || (n > 0 && span_cap > 0 && (!d_members || !d_spans)))
     return internal_fail(MRX_E_ARGUMENT, "null argument");
   if ((uintptr_t)d_spans & 7) return internal_fail(MRX_E_ARGUMENT, "d_spans must be 8-byte aligned");
-  const int k = (int)sc->members.size();
-  for (int j = 0; j < k; ++j) {
-    const std::string why = handle_refusal(sc->members[j]);
-    if (!why.empty()) return internal_fail(MRX_E_UNSUPPORTED, "member " + std::to_string(j) + ": " + why);
-  }
+  const std::string refused = set_refusal(sc);
+  if (!refused.empty()) return internal_fail(MRX_E_UNSUPPORTED, refused);
   int dev = 0;
-  SET_TRY(hipGetDevice(&dev));
+  MRX_HIP_TRY(hipGetDevice(&dev));
   hipStream_t hs = (hipStream_t)st;
   if (total) *total = 0;
   if (n == 0) {
-    SET_TRY(hipMemsetAsync(d_text_prefix, 0, sizeof(int64_t), hs));
+    MRX_HIP_TRY(hipMemsetAsync(d_text_prefix, 0, sizeof(int64_t), hs));
     return MRX_OK;
   }
-  scratch_scope_enter(st);
-  struct Leave { void* st; ~Leave() { scratch_scope_leave(st); } } leave_{st};
+  ScratchScope scope_(st);
   SetFaRun r;
-  if (int rc = set_findall_count(sc, data, offsets, stride, lens, len, n, known_total, known_max, d_text_prefix, r, st))
-    return rc;
+  if (int rc = set_findall_count(sc, b, n, known_total, known_max, d_text_prefix, r, st)) return rc;
   const int64_t tot = r.total();
   if (total) *total = tot;
   if (tot > span_cap)
     return internal_fail(MRX_E_CAPACITY, "span buffer too small: need " + std::to_string(tot));
   set_last_kernel("k_set_findall");
   if (tot == 0) return MRX_OK;
-  if (int rc = set_findall_place(sc, data, offsets, stride, lens, len, n, r, d_text_prefix, d_members, d_spans, span_cap, st))
-    return rc;
+  if (int rc = set_findall_place(sc, b, n, r, d_text_prefix, d_members, d_spans, span_cap, st)) return rc;
   set_last_kernel("k_set_findall");
   return MRX_OK;
 }
@@ -1059,18 +1032,14 @@ int set_findall(const mrx_set* sc, const uint8_t* data, const int64_t* offsets, 
 // sub of a set: the set's findall into scratch (12 bytes per hit), k_setsub_select -> sizes and
 // replacement counts, the device scan -> output offsets, one synchronisation for the output size, k_setsub_emit.
 // Scratch: the hits, O(n) words and, while the members' findall runs, the densest member's spans.
-int set_sub(const mrx_set* sc, const char* const* repls, const size_t* repl_lens, int64_t count, const uint8_t* data,
-            const int64_t* offsets, int64_t stride, const int32_t* lens, int32_t len, int64_t n, int64_t known_total,
-            int64_t known_max, int64_t* d_out_off, uint8_t* d_out, int64_t out_cap, int32_t* d_nsub, int64_t* total_bytes,
-            void* st) {
+int set_sub(const mrx_set* sc, const char* const* repls, const size_t* repl_lens, int64_t count, const TextBatch& b,
+            int64_t n, int64_t known_total, int64_t known_max, int64_t* d_out_off, uint8_t* d_out, int64_t out_cap,
+            int32_t* d_nsub, int64_t* total_bytes, void* st) {
   if (!sc) return internal_fail(MRX_E_ARGUMENT, "null set");
   if (n < 0) return internal_fail(MRX_E_ARGUMENT, "n must be >= 0");
   if (count < 0) return internal_fail(MRX_E_ARGUMENT, "count must be >= 0");
   if (out_cap < 0) return internal_fail(MRX_E_ARGUMENT, "out_cap must be >= 0");
-  if (!offsets) {
-    if (stride <= 0) return internal_fail(MRX_E_ARGUMENT, "stride must be positive");
-    if (!lens && (len < 0 || len > stride)) return internal_fail(MRX_E_ARGUMENT, "len must be in [0, stride]");
-  }
+  if (int rc = check_batch(b, BATCH_PITCH)) return rc;
   const int k = (int)sc->members.size();
   if (!repl_lens || !d_out_off || (out_cap > 0 && !d_out))
     return internal_fail(MRX_E_ARGUMENT, "null argument");
@@ -1085,27 +1054,23 @@ int set_sub(const mrx_set* sc, const char* const* repls, const size_t* repl_lens
     if (repl_lens[j] > 0 && repl_has_group_refs(std::string(repls[j], repl_lens[j])))
       return internal_fail(MRX_E_UNSUPPORTED,
                            "member " + std::to_string(j) + ": group references are not supported in a set's sub");
-  for (int j = 0; j < k; ++j) {
-    const std::string why = handle_refusal(sc->members[j]);
-    if (!why.empty()) return internal_fail(MRX_E_UNSUPPORTED, "member " + std::to_string(j) + ": " + why);
-  }
+  const std::string refused = set_refusal(sc);
+  if (!refused.empty()) return internal_fail(MRX_E_UNSUPPORTED, refused);
   int dev = 0;
-  SET_TRY(hipGetDevice(&dev));
+  MRX_HIP_TRY(hipGetDevice(&dev));
   hipStream_t hs = (hipStream_t)st;
   if (total_bytes) *total_bytes = 0;
   if (n == 0) {
-    SET_TRY(hipMemsetAsync(d_out_off, 0, sizeof(int64_t), hs));
+    MRX_HIP_TRY(hipMemsetAsync(d_out_off, 0, sizeof(int64_t), hs));
     set_last_kernel("k_set_sub");
     return MRX_OK;
   }
-  scratch_scope_enter(st);
-  struct Leave { void* st; ~Leave() { scratch_scope_leave(st); } } leave_{st};
+  ScratchScope scope_(st);
   // the set's findall, into scratch
   int64_t* text_prefix = (int64_t*)scratch_get(sizeof(int64_t) * (size_t)(n + 1), st);
   if (!text_prefix) return internal_fail(MRX_E_NO_DEVICE, "scratch allocation failed");
   SetFaRun r;
-  if (int rc = set_findall_count(sc, data, offsets, stride, lens, len, n, known_total, known_max, text_prefix, r, st))
-    return rc;
+  if (int rc = set_findall_count(sc, b, n, known_total, known_max, text_prefix, r, st)) return rc;
   const int64_t hits = r.total();
   int32_t* members = (int32_t*)scratch_get(sizeof(int32_t) * (size_t)std::max<int64_t>(hits, 1), st);
   int32_t* spans = (int32_t*)scratch_get(sizeof(int32_t) * 2 * (size_t)std::max<int64_t>(hits, 1), st);
@@ -1117,53 +1082,36 @@ int set_sub(const mrx_set* sc, const char* const* repls, const size_t* repl_lens
   if (!members || !spans || !sizes || !d_total || !d_roff || !d_rtab || !nsub)
     return internal_fail(MRX_E_NO_DEVICE, "scratch allocation failed");
   if (hits > 0)
-    if (int rc = set_findall_place(sc, data, offsets, stride, lens, len, n, r, text_prefix, members, spans, hits, st))
-      return rc;
+    if (int rc = set_findall_place(sc, b, n, r, text_prefix, members, spans, hits, st)) return rc;
   std::vector<uint8_t> rtab((size_t)roff[k] + 1);
   for (int j = 0; j < k; ++j)
     if (repl_lens[j]) memcpy(rtab.data() + roff[j], repls[j], repl_lens[j]);
-  SET_TRY(hipMemcpyAsync(d_roff, roff.data(), sizeof(int64_t) * (size_t)(k + 1), hipMemcpyHostToDevice, hs));
-  if (roff[k]) SET_TRY(hipMemcpyAsync(d_rtab, rtab.data(), (size_t)roff[k], hipMemcpyHostToDevice, hs));
+  MRX_HIP_TRY(hipMemcpyAsync(d_roff, roff.data(), sizeof(int64_t) * (size_t)(k + 1), hipMemcpyHostToDevice, hs));
+  if (roff[k]) MRX_HIP_TRY(hipMemcpyAsync(d_rtab, rtab.data(), (size_t)roff[k], hipMemcpyHostToDevice, hs));
   // the window: the longest text + 1 positions, rounded up to 64, at most kSetSubMaxW
-  const int64_t longest = offsets ? r.km : (lens ? stride : (int64_t)len);
+  const int64_t longest = b.offsets ? r.km : b.pitch_longest();
   const int32_t W = (int32_t)std::min<int64_t>(kSetSubMaxW, std::max<int64_t>(64, (longest + 1 + 63) & ~int64_t(63)));
-  SetSubArgs A{data, offsets, stride, lens, len, n, text_prefix, members, spans, d_rtab, d_roff, roff[k], count, k, W};
-  int64_t g = (n + kSetSubWaves - 1) / kSetSubWaves;
-  if (g > 4096) g = 4096;
+  SetSubArgs A{b.data, b.offsets, b.stride, b.lens, b.len, n, text_prefix, members, spans, d_rtab, d_roff, roff[k], count, k, W};
+  const dim3 g(set_grid(n, kSetSubWaves));
   const size_t lds_best = sizeof(uint64_t) * kSetSubWaves * (size_t)W;
   const size_t lds_ring = (size_t)kSetSubWaves * kSetSubRing;
   const size_t lds_repl = roff[k] <= kSetSubReplLds ? (size_t)((roff[k] + 15) & ~int64_t(15)) : 0;
-  hipLaunchKernelGGL(k_setsub_select, dim3((unsigned)g), dim3(64 * kSetSubWaves), lds_best, hs, A, sizes, nsub);
-  SET_TRY(hipGetLastError());
+  hipLaunchKernelGGL(k_setsub_select, g, dim3(64 * kSetSubWaves), lds_best, hs, A, sizes, nsub);
+  MRX_HIP_TRY(hipGetLastError());
   if (int rc = exclusive_scan(sizes, n, d_out_off, d_total, st)) return rc;
   int64_t tot = 0;
-  SET_TRY(hipMemcpyAsync(&tot, d_total, sizeof tot, hipMemcpyDeviceToHost, hs));
-  SET_TRY(hipStreamSynchronize(hs));
+  MRX_HIP_TRY(hipMemcpyAsync(&tot, d_total, sizeof tot, hipMemcpyDeviceToHost, hs));
+  MRX_HIP_TRY(hipStreamSynchronize(hs));
   if (total_bytes) *total_bytes = tot;
   set_last_kernel("k_set_sub");
   if (tot > out_cap) return internal_fail(MRX_E_CAPACITY, "output buffer too small: need " + std::to_string(tot));
   if (tot > 0) {
-    hipLaunchKernelGGL(k_setsub_emit, dim3((unsigned)g), dim3(64 * kSetSubWaves), lds_best + lds_ring + lds_repl, hs, A, d_out_off,
+    hipLaunchKernelGGL(k_setsub_emit, g, dim3(64 * kSetSubWaves), lds_best + lds_ring + lds_repl, hs, A, d_out_off,
                        d_out);
-    SET_TRY(hipGetLastError());
+    MRX_HIP_TRY(hipGetLastError());
   }
   return MRX_OK;
 }
-
-// host buffers for mrx_set_findall_batch and mrx_set_sub_batch
-struct HostBatchBufs {
-  uint8_t* data = nullptr;
-  int64_t* off = nullptr;
-  int64_t* prefix = nullptr;
-  int32_t* members = nullptr;
-  int32_t* spans = nullptr;
-  uint8_t* out = nullptr;     // mrx_set_sub_batch: output bytes and replacement counts
-  int32_t* nsub = nullptr;
-  ~HostBatchBufs() {
-    for (void* p : {(void*)data, (void*)off, (void*)prefix, (void*)members, (void*)spans, (void*)out, (void*)nsub})
-      if (p) (void)hipFree(p);
-  }
-};
 
 }  // namespace
 
@@ -1239,52 +1187,55 @@ size_t mrx_set_describe(const mrx_set* s, char* buf, size_t cap) {
 
 int mrx_set_search_dev(const mrx_set* s, const uint8_t* d_data, const int64_t* d_offsets, int64_t n, int32_t* d_start,
                        int32_t* d_end, void* stream) {
-  if (!d_offsets) return internal_fail(MRX_E_ARGUMENT, "null offsets");
-  return set_run(s, SET_SEARCH, d_data, d_offsets, 0, nullptr, 0, n, d_start, d_end, nullptr, stream);
+  const TextBatch b = csr(d_data, d_offsets);
+  if (int rc = check_batch(b, BATCH_CSR)) return rc;
+  return set_run(s, SET_SEARCH, b, n, d_start, d_end, nullptr, stream);
 }
 int mrx_set_search_strided_dev(const mrx_set* s, const uint8_t* d_data, int64_t stride, const int32_t* d_lens,
                                int32_t len, int64_t n, int32_t* d_start, int32_t* d_end, void* stream) {
-  return set_run(s, SET_SEARCH, d_data, nullptr, stride, d_lens, len, n, d_start, d_end, nullptr, stream);
+  return set_run(s, SET_SEARCH, strided(d_data, stride, d_lens, len), n, d_start, d_end, nullptr, stream);
 }
 int mrx_set_count_dev(const mrx_set* s, const uint8_t* d_data, const int64_t* d_offsets, int64_t n, int32_t* d_counts,
                       void* stream) {
-  if (!d_offsets) return internal_fail(MRX_E_ARGUMENT, "null offsets");
-  return set_run(s, SET_COUNT, d_data, d_offsets, 0, nullptr, 0, n, d_counts, nullptr, nullptr, stream);
+  const TextBatch b = csr(d_data, d_offsets);
+  if (int rc = check_batch(b, BATCH_CSR)) return rc;
+  return set_run(s, SET_COUNT, b, n, d_counts, nullptr, nullptr, stream);
 }
 int mrx_set_count_strided_dev(const mrx_set* s, const uint8_t* d_data, int64_t stride, const int32_t* d_lens,
                               int32_t len, int64_t n, int32_t* d_counts, void* stream) {
-  return set_run(s, SET_COUNT, d_data, nullptr, stride, d_lens, len, n, d_counts, nullptr, nullptr, stream);
+  return set_run(s, SET_COUNT, strided(d_data, stride, d_lens, len), n, d_counts, nullptr, nullptr, stream);
 }
 int mrx_set_matches_dev(const mrx_set* s, const uint8_t* d_data, const int64_t* d_offsets, int64_t n, uint64_t* d_bits,
                         void* stream) {
-  if (!d_offsets) return internal_fail(MRX_E_ARGUMENT, "null offsets");
-  return set_run(s, SET_MATCHES, d_data, d_offsets, 0, nullptr, 0, n, nullptr, nullptr, d_bits, stream);
+  const TextBatch b = csr(d_data, d_offsets);
+  if (int rc = check_batch(b, BATCH_CSR)) return rc;
+  return set_run(s, SET_MATCHES, b, n, nullptr, nullptr, d_bits, stream);
 }
 int mrx_set_matches_strided_dev(const mrx_set* s, const uint8_t* d_data, int64_t stride, const int32_t* d_lens,
                                 int32_t len, int64_t n, uint64_t* d_bits, void* stream) {
-  return set_run(s, SET_MATCHES, d_data, nullptr, stride, d_lens, len, n, nullptr, nullptr, d_bits, stream);
+  return set_run(s, SET_MATCHES, strided(d_data, stride, d_lens, len), n, nullptr, nullptr, d_bits, stream);
 }
 
 int mrx_set_findall_dev(const mrx_set* s, const uint8_t* d_data, const int64_t* d_offsets, int64_t n,
                         int64_t* d_text_prefix, int32_t* d_members, int32_t* d_spans, int64_t span_cap, int64_t* total,
                         void* stream) {
-  if (!d_offsets) return internal_fail(MRX_E_ARGUMENT, "null offsets");
-  return set_findall(s, d_data, d_offsets, 0, nullptr, 0, n, -1, -1, d_text_prefix, d_members, d_spans, span_cap, total,
-                     stream);
+  const TextBatch b = csr(d_data, d_offsets);
+  if (int rc = check_batch(b, BATCH_CSR)) return rc;
+  return set_findall(s, b, n, -1, -1, d_text_prefix, d_members, d_spans, span_cap, total, stream);
 }
 int mrx_set_findall_known_dev(const mrx_set* s, const uint8_t* d_data, const int64_t* d_offsets, int64_t n,
                               int64_t end_offset, int64_t max_text_len, int64_t* d_text_prefix, int32_t* d_members,
                               int32_t* d_spans, int64_t span_cap, int64_t* total, void* stream) {
-  if (!d_offsets) return internal_fail(MRX_E_ARGUMENT, "null offsets");
+  const TextBatch b = csr(d_data, d_offsets);
+  if (int rc = check_batch(b, BATCH_CSR)) return rc;
   if (end_offset < 0 || max_text_len < 0)
     return internal_fail(MRX_E_ARGUMENT, "end_offset and max_text_len must not be negative");
-  return set_findall(s, d_data, d_offsets, 0, nullptr, 0, n, end_offset, max_text_len, d_text_prefix, d_members, d_spans,
-                     span_cap, total, stream);
+  return set_findall(s, b, n, end_offset, max_text_len, d_text_prefix, d_members, d_spans, span_cap, total, stream);
 }
 int mrx_set_findall_strided_dev(const mrx_set* s, const uint8_t* d_data, int64_t stride, const int32_t* d_lens,
                                 int32_t len, int64_t n, int64_t* d_text_prefix, int32_t* d_members, int32_t* d_spans,
                                 int64_t span_cap, int64_t* total, void* stream) {
-  return set_findall(s, d_data, nullptr, stride, d_lens, len, n, -1, -1, d_text_prefix, d_members, d_spans, span_cap,
+  return set_findall(s, strided(d_data, stride, d_lens, len), n, -1, -1, d_text_prefix, d_members, d_spans, span_cap,
                      total, stream);
 }
 int mrx_set_findall_batch(const mrx_set* s, const uint8_t* data, const int64_t* offsets, int64_t n, int64_t* text_prefix,
@@ -1293,36 +1244,25 @@ int mrx_set_findall_batch(const mrx_set* s, const uint8_t* data, const int64_t* 
     return internal_fail(MRX_E_ARGUMENT, "null argument");
   if (span_cap < 0) return internal_fail(MRX_E_ARGUMENT, "span_cap must be >= 0");
   // refusals before any device work, as the _dev entry points
-  for (size_t j = 0; j < s->members.size(); ++j) {
-    const std::string why = handle_refusal(s->members[j]);
-    if (!why.empty()) return internal_fail(MRX_E_UNSUPPORTED, "member " + std::to_string(j) + ": " + why);
-  }
-  HostBatchBufs b;
-  const int64_t base = offsets[0], nbytes = offsets[n] - base;
-  if (nbytes < 0) return internal_fail(MRX_E_ARGUMENT, "offsets must not decrease");
-  if (nbytes > 0 && !data) return internal_fail(MRX_E_ARGUMENT, "null argument");
-  std::vector<int64_t> rel((size_t)n + 1);
-  int64_t longest = 0;
-  for (int64_t i = 0; i <= n; ++i) {
-    rel[i] = offsets[i] - base;
-    if (i > 0) longest = std::max(longest, rel[i] - rel[i - 1]);
-  }
-  SET_TRY(hipMalloc((void**)&b.data, (size_t)nbytes + 64));
-  SET_TRY(hipMalloc((void**)&b.off, sizeof(int64_t) * (size_t)(n + 1)));
-  SET_TRY(hipMalloc((void**)&b.prefix, sizeof(int64_t) * (size_t)(n + 1)));
-  SET_TRY(hipMalloc((void**)&b.members, sizeof(int32_t) * (size_t)std::max<int64_t>(span_cap, 1)));
-  SET_TRY(hipMalloc((void**)&b.spans, sizeof(int32_t) * 2 * (size_t)std::max<int64_t>(span_cap, 1)));
-  if (nbytes) SET_TRY(hipMemcpy(b.data, data + base, (size_t)nbytes, hipMemcpyHostToDevice));
-  SET_TRY(hipMemcpy(b.off, rel.data(), sizeof(int64_t) * (size_t)(n + 1), hipMemcpyHostToDevice));
+  const std::string refused = set_refusal(s);
+  if (!refused.empty()) return internal_fail(MRX_E_UNSUPPORTED, refused);
+  DevBatch b; DevBuf<int64_t> pre; DevBuf<int32_t> mem, sp;
+  if (int rc = b.measure(offsets, n)) return rc;
+  if (b.nbytes < 0) return internal_fail(MRX_E_ARGUMENT, "offsets must not decrease");
+  if (b.nbytes > 0 && !data) return internal_fail(MRX_E_ARGUMENT, "null argument");
+  if (int rc = b.upload(data, offsets, n)) return rc;
+  if (int rc = pre.alloc((size_t)n + 1)) return rc;
+  if (int rc = mem.alloc((size_t)span_cap)) return rc;
+  if (int rc = sp.alloc(2 * (size_t)std::max<int64_t>(span_cap, 1))) return rc;
   int64_t tot = 0;
-  const int rc = mrx_set_findall_known_dev(s, b.data, b.off, n, nbytes, longest, b.prefix, b.members, b.spans, span_cap,
+  const int rc = mrx_set_findall_known_dev(s, b.data, b.offsets, n, b.nbytes, b.longest, pre.p, mem.p, sp.p, span_cap,
                                            &tot, nullptr);
   if (total) *total = tot;
   if (rc != MRX_OK && rc != MRX_E_CAPACITY) return rc;
-  SET_TRY(hipMemcpy(text_prefix, b.prefix, sizeof(int64_t) * (size_t)(n + 1), hipMemcpyDeviceToHost));
+  MRX_HIP_TRY(hipMemcpy(text_prefix, pre.p, sizeof(int64_t) * (size_t)(n + 1), hipMemcpyDeviceToHost));
   if (rc == MRX_OK && tot > 0) {
-    SET_TRY(hipMemcpy(members, b.members, sizeof(int32_t) * (size_t)tot, hipMemcpyDeviceToHost));
-    SET_TRY(hipMemcpy(spans, b.spans, sizeof(int32_t) * 2 * (size_t)tot, hipMemcpyDeviceToHost));
+    MRX_HIP_TRY(hipMemcpy(members, mem.p, sizeof(int32_t) * (size_t)tot, hipMemcpyDeviceToHost));
+    MRX_HIP_TRY(hipMemcpy(spans, sp.p, sizeof(int32_t) * 2 * (size_t)tot, hipMemcpyDeviceToHost));
   }
   return rc;
 }
@@ -1330,25 +1270,26 @@ int mrx_set_findall_batch(const mrx_set* s, const uint8_t* data, const int64_t* 
 int mrx_set_sub_dev(const mrx_set* s, const char* const* repls, const size_t* repl_lens, int64_t count,
                     const uint8_t* d_data, const int64_t* d_offsets, int64_t n, int64_t* d_out_offsets, uint8_t* d_out_data,
                     int64_t out_cap, int32_t* d_nsub, int64_t* total_bytes, void* stream) {
-  if (!d_offsets) return internal_fail(MRX_E_ARGUMENT, "null offsets");
-  return set_sub(s, repls, repl_lens, count, d_data, d_offsets, 0, nullptr, 0, n, -1, -1, d_out_offsets, d_out_data,
-                 out_cap, d_nsub, total_bytes, stream);
+  const TextBatch b = csr(d_data, d_offsets);
+  if (int rc = check_batch(b, BATCH_CSR)) return rc;
+  return set_sub(s, repls, repl_lens, count, b, n, -1, -1, d_out_offsets, d_out_data, out_cap, d_nsub, total_bytes, stream);
 }
 int mrx_set_sub_known_dev(const mrx_set* s, const char* const* repls, const size_t* repl_lens, int64_t count,
                           const uint8_t* d_data, const int64_t* d_offsets, int64_t n, int64_t end_offset,
                           int64_t max_text_len, int64_t* d_out_offsets, uint8_t* d_out_data, int64_t out_cap,
                           int32_t* d_nsub, int64_t* total_bytes, void* stream) {
-  if (!d_offsets) return internal_fail(MRX_E_ARGUMENT, "null offsets");
+  const TextBatch b = csr(d_data, d_offsets);
+  if (int rc = check_batch(b, BATCH_CSR)) return rc;
   if (end_offset < 0 || max_text_len < 0)
     return internal_fail(MRX_E_ARGUMENT, "end_offset and max_text_len must not be negative");
-  return set_sub(s, repls, repl_lens, count, d_data, d_offsets, 0, nullptr, 0, n, end_offset, max_text_len,
-                 d_out_offsets, d_out_data, out_cap, d_nsub, total_bytes, stream);
+  return set_sub(s, repls, repl_lens, count, b, n, end_offset, max_text_len, d_out_offsets, d_out_data, out_cap, d_nsub,
+                 total_bytes, stream);
 }
 int mrx_set_sub_strided_dev(const mrx_set* s, const char* const* repls, const size_t* repl_lens, int64_t count,
                             const uint8_t* d_data, int64_t stride, const int32_t* d_lens, int32_t len, int64_t n,
                             int64_t* d_out_offsets, uint8_t* d_out_data, int64_t out_cap, int32_t* d_nsub,
                             int64_t* total_bytes, void* stream) {
-  return set_sub(s, repls, repl_lens, count, d_data, nullptr, stride, d_lens, len, n, -1, -1, d_out_offsets, d_out_data,
+  return set_sub(s, repls, repl_lens, count, strided(d_data, stride, d_lens, len), n, -1, -1, d_out_offsets, d_out_data,
                  out_cap, d_nsub, total_bytes, stream);
 }
 int mrx_set_sub_batch(const mrx_set* s, const char* const* repls, const size_t* repl_lens, int64_t count,
@@ -1365,35 +1306,25 @@ int mrx_set_sub_batch(const mrx_set* s, const char* const* repls, const size_t* 
     if (repl_lens[j] > 0 && repl_has_group_refs(std::string(repls[j], repl_lens[j])))
       return internal_fail(MRX_E_UNSUPPORTED,
                            "member " + std::to_string(j) + ": group references are not supported in a set's sub");
-  for (size_t j = 0; j < s->members.size(); ++j) {
-    const std::string why = handle_refusal(s->members[j]);
-    if (!why.empty()) return internal_fail(MRX_E_UNSUPPORTED, "member " + std::to_string(j) + ": " + why);
-  }
-  const int64_t base = offsets[0], nbytes = offsets[n] - base;
-  if (nbytes < 0) return internal_fail(MRX_E_ARGUMENT, "offsets must not decrease");
-  if (nbytes > 0 && !data) return internal_fail(MRX_E_ARGUMENT, "null argument");
-  std::vector<int64_t> rel((size_t)n + 1);
-  int64_t longest = 0;
-  for (int64_t i = 0; i <= n; ++i) {
-    rel[i] = offsets[i] - base;
-    if (i > 0) longest = std::max(longest, rel[i] - rel[i - 1]);
-  }
-  HostBatchBufs b;
-  SET_TRY(hipMalloc((void**)&b.data, (size_t)nbytes + 64));
-  SET_TRY(hipMalloc((void**)&b.off, sizeof(int64_t) * (size_t)(n + 1)));
-  SET_TRY(hipMalloc((void**)&b.prefix, sizeof(int64_t) * (size_t)(n + 1)));
-  SET_TRY(hipMalloc((void**)&b.out, (size_t)std::max<int64_t>(out_cap, 1)));
-  if (nsub) SET_TRY(hipMalloc((void**)&b.nsub, sizeof(int32_t) * (size_t)std::max<int64_t>(n, 1)));
-  if (nbytes) SET_TRY(hipMemcpy(b.data, data + base, (size_t)nbytes, hipMemcpyHostToDevice));
-  SET_TRY(hipMemcpy(b.off, rel.data(), sizeof(int64_t) * (size_t)(n + 1), hipMemcpyHostToDevice));
+  const std::string refused = set_refusal(s);
+  if (!refused.empty()) return internal_fail(MRX_E_UNSUPPORTED, refused);
+  DevBatch b; DevBuf<int64_t> oo; DevBuf<uint8_t> od; DevBuf<int32_t> ns;
+  if (int rc = b.measure(offsets, n)) return rc;
+  if (b.nbytes < 0) return internal_fail(MRX_E_ARGUMENT, "offsets must not decrease");
+  if (b.nbytes > 0 && !data) return internal_fail(MRX_E_ARGUMENT, "null argument");
+  if (int rc = b.upload(data, offsets, n)) return rc;
+  if (int rc = oo.alloc((size_t)n + 1)) return rc;
+  if (int rc = od.alloc((size_t)out_cap)) return rc;
+  if (nsub)
+    if (int rc = ns.alloc((size_t)n)) return rc;
   int64_t tot = 0;
-  const int rc = mrx_set_sub_known_dev(s, repls, repl_lens, count, b.data, b.off, n, nbytes, longest, b.prefix, b.out,
-                                       out_cap, b.nsub, &tot, nullptr);
+  const int rc = mrx_set_sub_known_dev(s, repls, repl_lens, count, b.data, b.offsets, n, b.nbytes, b.longest, oo.p, od.p,
+                                       out_cap, ns.p, &tot, nullptr);
   if (total_bytes) *total_bytes = tot;
   if (rc != MRX_OK && rc != MRX_E_CAPACITY) return rc;
-  SET_TRY(hipMemcpy(out_offsets, b.prefix, sizeof(int64_t) * (size_t)(n + 1), hipMemcpyDeviceToHost));
-  if (nsub && n > 0) SET_TRY(hipMemcpy(nsub, b.nsub, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost));
-  if (rc == MRX_OK && tot > 0) SET_TRY(hipMemcpy(out_data, b.out, (size_t)tot, hipMemcpyDeviceToHost));
+  MRX_HIP_TRY(hipMemcpy(out_offsets, oo.p, sizeof(int64_t) * (size_t)(n + 1), hipMemcpyDeviceToHost));
+  if (nsub && n > 0) MRX_HIP_TRY(hipMemcpy(nsub, ns.p, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost));
+  if (rc == MRX_OK && tot > 0) MRX_HIP_TRY(hipMemcpy(out_data, od.p, (size_t)tot, hipMemcpyDeviceToHost));
   return rc;
 }
 
