@@ -398,7 +398,69 @@ int mrx_set_sub_strided_dev(const mrx_set* s, const char* const* repls, const si
                             int64_t* d_out_offsets, uint8_t* d_out_data, int64_t out_cap, int32_t* d_nsub,
                             int64_t* total_bytes, void* stream);
 
+/* ---- filter: keep the matching texts as a new packed batch on the device ----
+ * Text i is KEPT when the pattern's search finds a match in it: the predicate of CompiledRegex.test
+ * (matcher.mojo:1091-1101), start[i] >= 0 of mrx_search_dev -- not the is_match operation.  MRX_FILTER_INVERT keeps
+ * exactly the other texts.  A set keeps a text when some member's search hits (a row of mrx_set_matches_dev with a bit
+ * set); with MRX_FILTER_ALL, when every member's does; MRX_FILTER_INVERT negates either, so "none" is the inverse of
+ * "any".  (One pattern ignores MRX_FILTER_ALL.)  Any other flag bit: MRX_E_ARGUMENT.
+ * The kept texts keep their order (ascending original index).  Outputs, all on the device:
+ *   d_kept_idx int64[n]         [0, kept): the original index of each kept text
+ *   d_out_offsets int64[n + 1]  [0, kept]: the CSR of the output batch; d_out_offsets[kept] = bytes.  A kept empty
+ *                               text contributes no byte and its offset repeats
+ *   d_out_data uint8[out_cap]   the kept texts back to back; any alignment
+ *   d_totals int64[2]           {kept, bytes}
+ * Entries of d_kept_idx and d_out_offsets past those are unspecified.  The output is CSR whatever the input form, so
+ * it is the input of a following call as it stands (with bytes and the input's longest text as its known bounds).
+ * No byte of d_out_data at or past bytes, nor at or past out_cap, is ever written.
+ * Capacity: out_cap = the input's byte count always suffices.  When bytes > out_cap the indices, the offsets and
+ * d_totals are still complete and correct, NO output byte is written, and a call with `totals` returns
+ * MRX_E_CAPACITY with totals filled.
+ * totals (host, int64[2], may be NULL) receives d_totals: the call then reads back once, at its end -- no host
+ * decision sits between its kernels.  With totals == NULL the call reads nothing back and is asynchronous, as findall
+ * with total == NULL: the gather decides on the device from d_totals, and the caller checks d_totals[1] against its
+ * out_cap once the stream has drained.
+ * The _known form takes a CSR batch's d_offsets[n] and longest text, as mrx_findall_known_dev, and needs no look at
+ * the device before its first kernel (without them a search over few long texts reads them back first).  Upper
+ * bounds are fine; neither may be too small.
+ * n == 0 gives kept = bytes = 0 and d_out_offsets = {0}.  Negative n or out_cap, unknown flag bits, a bad pitch and a
+ * null required pointer (handle, d_offsets, d_out_offsets, d_totals; d_kept_idx when n > 0; d_out_data when
+ * out_cap > 0): MRX_E_ARGUMENT.  A pattern (a member) whose search is refused is refused here, MRX_E_UNSUPPORTED with
+ * the same reason ("member j: <reason>" for a set), before anything is enqueued or written.
+ * Reads: a text's bytes are fetched as the aligned 16-byte words that hold them, so up to 15 bytes in front of a text's
+ * first byte and behind its last one are read (never used), as sub's byte mover does: the words around d_data's first
+ * and last text must be readable, which every hipMalloc'ed or pooled device buffer gives (256-byte granules).
+ * Scratch: 32 bytes per text and the predicate's own (8 bytes per text for one pattern; for a set its bit rows and
+ * one member's search), returned to the arena when the call returns. */
+enum { MRX_FILTER_INVERT = 1, MRX_FILTER_ALL = 2 };
+int mrx_filter_dev(const mrx_handle* h, uint32_t flags, const uint8_t* d_data, const int64_t* d_offsets, int64_t n,
+                   int64_t* d_kept_idx, int64_t* d_out_offsets, uint8_t* d_out_data, int64_t out_cap, int64_t* d_totals,
+                   int64_t* totals, void* stream);
+int mrx_filter_known_dev(const mrx_handle* h, uint32_t flags, const uint8_t* d_data, const int64_t* d_offsets, int64_t n,
+                         int64_t end_offset, int64_t max_text_len, int64_t* d_kept_idx, int64_t* d_out_offsets,
+                         uint8_t* d_out_data, int64_t out_cap, int64_t* d_totals, int64_t* totals, void* stream);
+int mrx_filter_strided_dev(const mrx_handle* h, uint32_t flags, const uint8_t* d_data, int64_t stride,
+                           const int32_t* d_lens, int32_t len, int64_t n, int64_t* d_kept_idx, int64_t* d_out_offsets,
+                           uint8_t* d_out_data, int64_t out_cap, int64_t* d_totals, int64_t* totals, void* stream);
+int mrx_set_filter_dev(const mrx_set* s, uint32_t flags, const uint8_t* d_data, const int64_t* d_offsets, int64_t n,
+                       int64_t* d_kept_idx, int64_t* d_out_offsets, uint8_t* d_out_data, int64_t out_cap,
+                       int64_t* d_totals, int64_t* totals, void* stream);
+int mrx_set_filter_known_dev(const mrx_set* s, uint32_t flags, const uint8_t* d_data, const int64_t* d_offsets, int64_t n,
+                             int64_t end_offset, int64_t max_text_len, int64_t* d_kept_idx, int64_t* d_out_offsets,
+                             uint8_t* d_out_data, int64_t out_cap, int64_t* d_totals, int64_t* totals, void* stream);
+int mrx_set_filter_strided_dev(const mrx_set* s, uint32_t flags, const uint8_t* d_data, int64_t stride,
+                               const int32_t* d_lens, int32_t len, int64_t n, int64_t* d_kept_idx,
+                               int64_t* d_out_offsets, uint8_t* d_out_data, int64_t out_cap, int64_t* d_totals,
+                               int64_t* totals, void* stream);
+
 /* ---- host-buffer convenience wrappers (copy in, run, copy out) -------------- */
+/* mrx_filter_dev / mrx_set_filter_dev on host buffers: kept_idx int64[n], out_offsets int64[n + 1], out_data
+ * uint8[out_cap], totals int64[2] = {kept, bytes} (may be NULL).  kept_idx[0, kept) and out_offsets[0, kept] are
+ * copied out, out_data only when all of it fits (MRX_E_CAPACITY otherwise). */
+int mrx_filter_batch(const mrx_handle* h, uint32_t flags, const uint8_t* data, const int64_t* offsets, int64_t n,
+                     int64_t* kept_idx, int64_t* out_offsets, uint8_t* out_data, int64_t out_cap, int64_t* totals);
+int mrx_set_filter_batch(const mrx_set* s, uint32_t flags, const uint8_t* data, const int64_t* offsets, int64_t n,
+                         int64_t* kept_idx, int64_t* out_offsets, uint8_t* out_data, int64_t out_cap, int64_t* totals);
 int mrx_match_first_batch(const mrx_handle* h, const uint8_t* data,
                           const int64_t* offsets, int64_t n, int32_t* start,
                           int32_t* end);

@@ -105,6 +105,11 @@ void mrx_debug_set_route(int mode);
  * 0 / 1).  Members outside the shared pass of that operation get -2. */
 struct mrx_set;
 int mrx_testing_set_run(const struct mrx_set* s, int op, const uint8_t* text, int len, int32_t* out);
+/* Filter (include/mrx.h): which kernel moves the kept bytes.  0 = the rule (k_filter_gather_text, 16 lanes per kept
+ * text, when the host knows the batch's longest text and it is at most 4 KiB; k_filter_gather, a lane per 16-byte
+ * output block, otherwise: profiles/filter.md), 1 = the block form always, 16 = the text form always.  Results are
+ * the same. */
+void mrx_debug_filter_form(int form);
 /* Bytes of device memory the calling thread's scratch arenas hold (see mrx_release_scratch). */
 size_t mrx_debug_scratch_bytes(void);
 

@@ -19,6 +19,8 @@ argument meaning, a *batch* of texts instead of one text:
     clear_regex_cache()               :1318       clear_regex_cache()
     (none: one pattern per call)                  PatternSet / compile_set(patterns): k at once
     (none: k sub() calls in a row)                PatternSet.sub(repls, texts): k patterns' hits, one call
+    CompiledRegex.test(text), per text :1091      filter_texts / CompiledRegex.filter / PatternSet.filter:
+                                                  the matching texts as a new packed batch
 
 All matching runs in the HIP kernels of libmrx_hip.so.  There is no CPU
 fallback: if the library is missing or no GPU is usable, calls raise.
@@ -36,6 +38,7 @@ from .api import (  # noqa: F401
     clear_regex_cache,
     compile_regex,
     compile_set,
+    filter_texts,
     findall,
     library_path,
     load_library,

@@ -181,6 +181,22 @@ def load_library():
                                               C.c_int64, i64p, u8p, C.c_int64, i32p, C.POINTER(C.c_int64), C.c_void_p]),
         "mrx_set_sub_batch": (C.c_int, [H, C.c_void_p, C.c_void_p, C.c_int64, u8p, i64p, C.c_int64, i64p, u8p, C.c_int64,
                                         i32p, C.POINTER(C.c_int64)]),
+        # filter: (handle, flags) | the batch | (kept_idx, out_offsets, out_data, out_cap, d_totals, totals, stream)
+        "mrx_filter_dev": (C.c_int, [H, C.c_uint32, u8p, i64p, C.c_int64, i64p, i64p, u8p, C.c_int64, i64p,
+                                     C.c_void_p, C.c_void_p]),
+        "mrx_filter_known_dev": (C.c_int, [H, C.c_uint32, u8p, i64p, C.c_int64, C.c_int64, C.c_int64, i64p, i64p, u8p,
+                                           C.c_int64, i64p, C.c_void_p, C.c_void_p]),
+        "mrx_filter_strided_dev": (C.c_int, [H, C.c_uint32, u8p, C.c_int64, i32p, C.c_int32, C.c_int64, i64p, i64p, u8p,
+                                             C.c_int64, i64p, C.c_void_p, C.c_void_p]),
+        "mrx_filter_batch": (C.c_int, [H, C.c_uint32, u8p, i64p, C.c_int64, i64p, i64p, u8p, C.c_int64, C.c_void_p]),
+        "mrx_set_filter_dev": (C.c_int, [H, C.c_uint32, u8p, i64p, C.c_int64, i64p, i64p, u8p, C.c_int64, i64p,
+                                         C.c_void_p, C.c_void_p]),
+        "mrx_set_filter_known_dev": (C.c_int, [H, C.c_uint32, u8p, i64p, C.c_int64, C.c_int64, C.c_int64, i64p, i64p,
+                                               u8p, C.c_int64, i64p, C.c_void_p, C.c_void_p]),
+        "mrx_set_filter_strided_dev": (C.c_int, [H, C.c_uint32, u8p, C.c_int64, i32p, C.c_int32, C.c_int64, i64p, i64p,
+                                                 u8p, C.c_int64, i64p, C.c_void_p, C.c_void_p]),
+        "mrx_set_filter_batch": (C.c_int, [H, C.c_uint32, u8p, i64p, C.c_int64, i64p, i64p, u8p, C.c_int64, C.c_void_p]),
+        "mrx_debug_filter_form": (None, [C.c_int]),
         "mrx_debug_set_route": (None, [C.c_int]),
         "mrx_testing_set_run": (C.c_int, [H, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_int32)]),
     }
@@ -208,13 +224,15 @@ EXPORTED_SYMBOLS = [
     "mrx_set_search_strided_dev", "mrx_set_count_dev", "mrx_set_count_strided_dev", "mrx_set_matches_dev",
     "mrx_set_matches_strided_dev", "mrx_set_findall_dev", "mrx_set_findall_known_dev", "mrx_set_findall_strided_dev",
     "mrx_set_findall_batch", "mrx_set_sub_dev", "mrx_set_sub_known_dev", "mrx_set_sub_strided_dev", "mrx_set_sub_batch",
+    "mrx_filter_dev", "mrx_filter_known_dev", "mrx_filter_strided_dev", "mrx_filter_batch",
+    "mrx_set_filter_dev", "mrx_set_filter_known_dev", "mrx_set_filter_strided_dev", "mrx_set_filter_batch",
 ]
 TESTING_SYMBOLS = [
     "mrx_timing_reset", "mrx_timing_enable", "mrx_timing_scan_ms", "mrx_last_kernel_name",
     "mrx_debug_force_generic", "mrx_debug_long_text_kernels", "mrx_debug_scratch_bytes",
     "mrx_debug_fused_findall", "mrx_debug_stream_bits", "mrx_debug_stream_bits_trace", "mrx_debug_dynamic_texts", "mrx_debug_subs_group",
     "mrx_debug_split_findall", "mrx_debug_dense_rows", "mrx_debug_tries_always", "mrx_debug_chain_sub_general", "mrx_testing_emptywalk_findall", "mrx_debug_litscan_pieces", "mrx_debug_multiwalk", "mrx_debug_rec_skew", "mrx_testing_comm_shift", "mrx_testing_comm_compact",
-    "mrx_debug_set_route", "mrx_testing_set_run",
+    "mrx_debug_set_route", "mrx_testing_set_run", "mrx_debug_filter_form",
 ]
 COMM_SYMBOLS = [
     "mrx_comm_unique_id", "mrx_comm_init", "mrx_comm_free", "mrx_comm_rank", "mrx_comm_size",
@@ -399,6 +417,68 @@ def _grow_call(cap, alloc, call, grow=True, only_larger=False):
         return bufs, int(total.value)
 
 
+MRX_FILTER_INVERT, MRX_FILTER_ALL = 1, 2
+
+
+def _filter_flags(mode: str = "any", invert: bool = False) -> int:
+    if mode not in ("any", "all"):
+        raise MrxError("mode must be 'any' or 'all'")
+    return (MRX_FILTER_INVERT if invert else 0) | (MRX_FILTER_ALL if mode == "all" else 0)
+
+
+def _filter(lib, stem: str, handle, flags: int, texts):
+    """filter of one pattern (stem "mrx_filter") or a set ("mrx_set_filter").  The capacity is the input's byte count,
+    which always suffices, so there is no retry."""
+    if isinstance(texts, DeviceBatch):
+        import torch
+        batch, dev, n = texts, texts.data.device, texts.n
+        cap = int(batch.data.numel())
+        out = (torch.empty(n, dtype=torch.int64, device=dev), torch.empty(n + 1, dtype=torch.int64, device=dev),
+               torch.empty(cap, dtype=torch.uint8, device=dev), torch.empty(2, dtype=torch.int64, device=dev))
+        totals = (C.c_int64 * 2)()
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        _check(batch.call(lib, stem, (handle, flags), (_ptr(out[0]), _ptr(out[1]), _ptr(out[2]), cap, _ptr(out[3]),
+                                                       C.cast(totals, C.c_void_p), stream)))
+        kept, nbytes = int(totals[0]), int(totals[1])
+        longest = batch._max_len if batch.offsets is not None else (batch.stride if batch.lens is not None else batch.length)
+        # The outputs were allocated for the worst case (every text kept).  A result that uses less than a quarter
+        # of them is copied out, so that a sparse filter does not pin the input's size for the result's lifetime;
+        # above that the views are returned as they are (at most four times the result's own bytes stay allocated).
+        trim = (lambda t, m: t[:m].clone()) if 4 * nbytes < cap else (lambda t, m: t[:m])
+        kept_batch = DeviceBatch(trim(out[2], nbytes), trim(out[1], kept + 1))
+        if longest is not None:   # known bounds: a following findall / sub / filter needs no read-back for them
+            kept_batch._end_offset, kept_batch._max_len = nbytes, int(longest)
+        return kept_batch, trim(out[0], kept)
+    bs = [_b(t) for t in texts]
+    data, offsets = pack_texts(bs)
+    n = len(bs)
+    idx = np.zeros(max(n, 1), np.int64)
+    out_off = np.zeros(n + 1, np.int64)
+    out = np.empty(max(int(offsets[-1]), 1), np.uint8)
+    totals = (C.c_int64 * 2)()
+    _check(getattr(lib, stem + "_batch")(handle, flags, data.ctypes.data, offsets.ctypes.data, n, idx.ctypes.data,
+                                         out_off.ctypes.data, out.ctypes.data, int(offsets[-1]),
+                                         C.cast(totals, C.c_void_p)))
+    kept = int(totals[0])
+    raw = out[:int(totals[1])].tobytes()
+    return [raw[out_off[r]:out_off[r + 1]] for r in range(kept)], idx[:kept].copy()
+
+
+def _filter_async(lib, stem: str, handle, flags: int, batch: "DeviceBatch", out):
+    import torch
+    kept_idx, out_offsets, out_data, totals = out
+    if kept_idx.numel() < batch.n or out_offsets.numel() < batch.n + 1 or totals.numel() < 2:
+        raise MrxError("out needs kept_idx int64[n], out_offsets int64[n + 1], out_data uint8[cap], totals int64[2]")
+    for t in (kept_idx, out_offsets, totals):
+        if t.dtype != torch.int64 or not t.is_contiguous():
+            raise MrxError("kept_idx, out_offsets and totals must be contiguous int64 tensors")
+    if out_data.dtype != torch.uint8 or not out_data.is_contiguous():
+        raise MrxError("out_data must be a contiguous uint8 tensor")
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    _check(batch.call(lib, stem, (handle, flags), (_ptr(kept_idx), _ptr(out_offsets), _ptr(out_data),
+                                                   int(out_data.numel()), _ptr(totals), None, stream)))
+
+
 class CompiledRegex:
     """Compile once, match many batches (reference: matcher.mojo:929-1163)."""
 
@@ -529,6 +609,23 @@ class CompiledRegex:
         if isinstance(texts, DeviceBatch):
             return s >= 0
         return (np.asarray(s) >= 0)
+
+    def filter(self, texts, invert: bool = False):
+        """The texts in which search() matches (test(); with invert, the others) as a new packed batch, in their order
+        (include/mrx.h, mrx_filter_dev).  A list of texts gives (kept List[bytes], idx numpy int64[kept]); a
+        DeviceBatch gives (DeviceBatch, idx) with device tensors: a CSR batch trimmed to the kept texts and their bytes.
+        It carries known bounds (its byte count, and the input's longest text as its own) when the input knows its
+        longest text -- a fixed pitch, from_texts / from_arrow / csr_known -- so that a following findall, sub or filter
+        needs no read-back for them; the result of a plain DeviceBatch(data, offsets) has none, as its input.  The
+        tensors are views of buffers sized for the whole input unless the result uses less than a quarter of them (then
+        they are copies of their own size).  idx holds the original indices."""
+        return _filter(self._lib, "mrx_filter", self._h, _filter_flags("any", invert), texts)
+
+    def filter_async(self, batch: "DeviceBatch", out, invert: bool = False):
+        """Enqueue filter on the current stream without reading anything back.  out = (kept_idx int64[n], out_offsets
+        int64[n + 1], out_data uint8[cap], totals int64[2]) device tensors of the caller; totals = {kept, bytes} once the
+        stream has drained.  No byte is written when bytes > cap (check totals[1]); cap = the input's bytes always fits."""
+        _filter_async(self._lib, "mrx_filter", self._h, _filter_flags("any", invert), batch, out)
 
     def match_all(self, texts):
         """regex.findall per text: (counts_prefix int64[n+1], spans int32[total, 2])."""
@@ -782,6 +879,17 @@ class PatternSet:
         """bool [n, k]: member j's search finds a match in text i (a search hit, not is_match)."""
         return self._run("matches", texts)
 
+    def filter(self, texts, mode: str = "any", invert: bool = False):
+        """The texts in which some member's search matches (mode="any") or every member's does (mode="all") -- with
+        invert, the others, so any + invert is "none" -- as a new packed batch in their order (include/mrx.h,
+        mrx_set_filter_dev).  Shapes as CompiledRegex.filter: (List[bytes], numpy idx) for a list of texts, (DeviceBatch,
+        idx) device tensors for a DeviceBatch."""
+        return _filter(self._lib, "mrx_set_filter", self._h, _filter_flags(mode, invert), texts)
+
+    def filter_async(self, batch: "DeviceBatch", out, mode: str = "any", invert: bool = False):
+        """filter() enqueued on the current stream without a read-back, as CompiledRegex.filter_async."""
+        _filter_async(self._lib, "mrx_set_filter", self._h, _filter_flags(mode, invert), batch, out)
+
     def findall(self, texts, span_cap: Optional[int] = None):
         """Every member's findall, text-major (include/mrx.h, mrx_set_findall_dev): (text_prefix int64[n+1],
         members int32[total], spans int32[total, 2]).  Text i's hits are [text_prefix[i], text_prefix[i+1]): member
@@ -946,6 +1054,11 @@ def captures_all(pattern, texts, count: int = 0):
 
 def sub(pattern, repl, texts, count: int = 0) -> List[bytes]:
     return compile_regex(pattern).sub(repl, texts, count)
+
+
+def filter_texts(pattern, texts, invert: bool = False):
+    """CompiledRegex.filter through the cache (the name leaves the builtin filter alone)."""
+    return compile_regex(pattern).filter(texts, invert)
 
 
 def split(pattern, texts, maxsplit: int = 0) -> List[List[bytes]]:

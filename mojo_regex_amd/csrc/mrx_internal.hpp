@@ -12,6 +12,7 @@
 #endif
 
 struct mrx_handle;
+struct mrx_set;
 namespace mrx {
 // records the calling thread's last error message (mrx_last_error()) and returns `code`
 int internal_fail(int code, const std::string& msg);
@@ -108,6 +109,14 @@ int member_count(const mrx_handle* h, const TextBatch& b, int64_t n, int32_t* co
                  int64_t known_max);
 int member_findall(const mrx_handle* h, const TextBatch& b, int64_t n, int64_t* d_prefix, int32_t* d_spans,
                    int64_t span_cap, void* stream, int64_t known_total, int64_t known_max);
+// mrx_search_dev of one handle on a checked batch (filter), with the CSR batch's bounds as above
+int member_search(const mrx_handle* h, const TextBatch& b, int64_t n, int32_t* d_start, int32_t* d_end, void* stream,
+                  int64_t known_total, int64_t known_max);
+// mrx_set.hip: "member j: reason" if a member's search would be refused ("" = the set's search would run)
+std::string set_members_refusal(const mrx_set* s);
+// mrx_set_matches_dev on a checked batch (set filter), with the CSR batch's bounds as above
+int set_matches(const mrx_set* s, const TextBatch& b, int64_t n, uint64_t* d_bits, void* stream, int64_t known_total,
+                int64_t known_max);
 // the scan timer of mrx_timing_scan_ms around a launch sequence: begin returns a token for end
 void* scan_timer_begin(void* stream);
 void scan_timer_end(void* token);

@@ -6946,8 +6946,9 @@ size_t mrx_describe(const mrx_handle* h, char* buf, size_t cap) {
 
 // regex.search / regex.match_first for any layout: the streaming kernel when the plan and the
 // layout allow it, the generic lane-per-text kernel otherwise
+// known_total / known_max: csr_stats() of a CSR batch when the caller has them already (< 0: not; filter)
 static int run_search_any(const mrx_handle* h, const Layout& lay, int64_t n, int32_t* ds, int32_t* de,
-                          void* st) {
+                          void* st, int64_t known_total = -1, int64_t known_max = -1) {
   ScratchScope scratch_scope_((hipStream_t)st);
   if (!h) return fail(MRX_E_ARGUMENT, "null handle");
   const DevPlan& p = h->hp.dev;
@@ -7007,7 +7008,7 @@ static int run_search_any(const mrx_handle* h, const Layout& lay, int64_t n, int
   hipStream_t s = (hipStream_t)st;
   Pieces pc;
   if (!lay.vlen)   // (a view is searched as it stands)
-    if (int rc = pieces_prepare(h, lay, n, s, &pc)) return rc;
+    if (int rc = pieces_prepare(h, lay, n, s, &pc, known_total, known_max)) return rc;
   if (pc.on) {   // long texts: search every piece, keep each text's first
     int32_t* d_vs = nullptr;
     HIP_TRY(scratch_alloc((void**)&d_vs, sizeof(int32_t) * 2 * pc.nv, s));
@@ -8275,6 +8276,10 @@ int member_count(const mrx_handle* h, const TextBatch& b, int64_t n, int32_t* co
 int member_findall(const mrx_handle* h, const TextBatch& b, int64_t n, int64_t* d_prefix, int32_t* d_spans,
                    int64_t span_cap, void* st, int64_t known_total, int64_t known_max) {
   return run_findall(h, b, n, d_prefix, d_spans, span_cap, nullptr, st, false, known_total, known_max);
+}
+int member_search(const mrx_handle* h, const TextBatch& b, int64_t n, int32_t* d_start, int32_t* d_end, void* st,
+                  int64_t known_total, int64_t known_max) {
+  return run_search_any(h, b, n, d_start, d_end, st, known_total, known_max);
 }
 void* scan_timer_begin(void* st) { return new ScanTimer((hipStream_t)st); }
 void scan_timer_end(void* tok) {

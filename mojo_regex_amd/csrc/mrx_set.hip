@@ -863,8 +863,9 @@ void launch_pass(const SetPassDev& d, const uint8_t* blob, const TextBatch& b, i
     hipLaunchKernelGGL((k_set_scan<MODE, kSetMaxCG, kSetMaxCM>), grid, block, lds, s, d, blob, b, n, o0, o1, bits);
 }
 
+// known_total / known_max: a CSR batch's bounds where the caller has them (< 0: not; set filter), for the members' search
 int set_run(const mrx_set* sc, int mode, const TextBatch& tb, int64_t n, int32_t* o0, int32_t* o1, uint64_t* bits,
-            void* st) {
+            void* st, int64_t known_total = -1, int64_t known_max = -1) {
   if (!sc) return internal_fail(MRX_E_ARGUMENT, "null set");
   mrx_set* s = const_cast<mrx_set*>(sc);
   if (n < 0) return internal_fail(MRX_E_ARGUMENT, "n must be >= 0");
@@ -899,8 +900,7 @@ int set_run(const mrx_set* sc, int mode, const TextBatch& tb, int64_t n, int32_t
       rc = tb.offsets ? mrx_count_dev(h, tb.data, tb.offsets, n, a, st)
                       : mrx_count_strided_dev(h, tb.data, tb.stride, tb.lens, tb.len, n, a, st);
     else
-      rc = tb.offsets ? mrx_search_dev(h, tb.data, tb.offsets, n, a, b, st)
-                      : mrx_search_strided_dev(h, tb.data, tb.stride, tb.lens, tb.len, n, a, b, st);
+      rc = member_search(h, tb, n, a, b, st, known_total, known_max);
     if (rc != MRX_OK) return internal_fail(rc, "member " + std::to_string(j) + ": " + mrx_last_error());
     hipLaunchKernelGGL(k_set_scatter, dim3(set_grid(n)), dim3(256), 0, hs, mode, n, k, words, j, a, b, o0, o1, bits);
     MRX_HIP_TRY(hipGetLastError());
@@ -1327,6 +1327,16 @@ int mrx_set_sub_batch(const mrx_set* s, const char* const* repls, const size_t* 
   if (rc == MRX_OK && tot > 0) MRX_HIP_TRY(hipMemcpy(out_data, od.p, (size_t)tot, hipMemcpyDeviceToHost));
   return rc;
 }
+
+}  // extern "C"
+namespace mrx {
+std::string set_members_refusal(const mrx_set* s) { return set_refusal(s); }
+int set_matches(const mrx_set* s, const TextBatch& b, int64_t n, uint64_t* d_bits, void* stream, int64_t known_total,
+                int64_t known_max) {
+  return set_run(s, SET_MATCHES, b, n, nullptr, nullptr, d_bits, stream, known_total, known_max);
+}
+}  // namespace mrx
+extern "C" {
 
 void mrx_debug_set_route(int mode) { g_set_route = (mode == 1 || mode == 2) ? mode : 0; }
 
