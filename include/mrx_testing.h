@@ -112,6 +112,9 @@ int mrx_testing_set_run(const struct mrx_set* s, int op, const uint8_t* text, in
 void mrx_debug_filter_form(int form);
 /* Bytes of device memory the calling thread's scratch arenas hold (see mrx_release_scratch). */
 size_t mrx_debug_scratch_bytes(void);
+/* ... and how many of them are handed out and not yet rewound.  Scratch belongs to the call's scope, so between calls
+ * this is 0 whichever way the last call returned. */
+size_t mrx_debug_scratch_in_use(void);
 
 #ifdef __cplusplus
 }

@@ -138,6 +138,7 @@ def load_library():
         "mrx_debug_rec_skew": (None, [C.c_int64]),
         "mrx_release_scratch": (None, []),
         "mrx_debug_scratch_bytes": (C.c_size_t, []),
+        "mrx_debug_scratch_in_use": (C.c_size_t, []),
         "mrx_version": (C.c_char_p, []),
         # include/mrx_comm.h: results exchange between ranks (RCCL, opened on first use)
         "mrx_comm_unique_id": (C.c_int, [C.c_void_p]),
@@ -230,6 +231,7 @@ EXPORTED_SYMBOLS = [
 TESTING_SYMBOLS = [
     "mrx_timing_reset", "mrx_timing_enable", "mrx_timing_scan_ms", "mrx_last_kernel_name",
     "mrx_debug_force_generic", "mrx_debug_long_text_kernels", "mrx_debug_scratch_bytes",
+    "mrx_debug_scratch_in_use",
     "mrx_debug_fused_findall", "mrx_debug_stream_bits", "mrx_debug_stream_bits_trace", "mrx_debug_dynamic_texts", "mrx_debug_subs_group",
     "mrx_debug_split_findall", "mrx_debug_dense_rows", "mrx_debug_tries_always", "mrx_debug_chain_sub_general", "mrx_testing_emptywalk_findall", "mrx_debug_litscan_pieces", "mrx_debug_multiwalk", "mrx_debug_rec_skew", "mrx_testing_comm_shift", "mrx_testing_comm_compact",
     "mrx_debug_set_route", "mrx_testing_set_run", "mrx_debug_filter_form",

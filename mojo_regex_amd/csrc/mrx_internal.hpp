@@ -95,7 +95,6 @@ void* scratch_get(size_t bytes, void* stream);   // nullptr: HIP error
 // next member's work runs after it on the same stream), so that its scratch does not grow with the set size
 struct ScratchMark {
   std::vector<size_t> used;
-  int live = 0;
 };
 ScratchMark scratch_mark(void* stream);
 void scratch_rewind(void* stream, const ScratchMark& m);

@@ -4350,13 +4350,18 @@ namespace {
 // Counts, records, block sums ... live only for one API call.  hipFreeAsync was measured to block
 // the host until the stream reaches it (296 us behind the scan kernel), which serialises host and
 // GPU; so scratch comes from a grow-only arena per (host thread, stream) instead.  Calls on one
-// stream run in order, so the next call may reuse the bytes; the arena is rewound when the last
-// allocation of a call is released and is only ever freed after synchronising its stream.
+// stream run in order, so the next call may reuse the bytes.  Scratch belongs to the call's ScratchScope
+// (mrx_internal.hpp): nothing is freed one by one; the arena is rewound when the outermost scope closes, and
+// inside a call where a phase hands its bytes to the next (scratch_mark() before it, scratch_reuse_from() or
+// scratch_rewind() behind it: stream order makes that safe too).  Its memory is only ever freed after synchronising its stream.
 struct ScratchArena {
   struct Chunk { uint8_t* base; size_t cap, used; };
   std::vector<Chunk> chunks;
-  int live = 0;
   int depth = 0;   // nested ScratchScopes (entry points call each other)
+  bool idle() const {   // nothing handed out
+    for (auto& c : chunks) if (c.used) return false;
+    return true;
+  }
 };
 // keyed by (device, stream): the null stream of two devices must not share an arena
 thread_local std::map<std::pair<int, hipStream_t>, ScratchArena> g_scratch;
@@ -4368,9 +4373,10 @@ static ScratchArena& scratch_arena(hipStream_t s) {
 
 hipError_t scratch_alloc(void** out, size_t bytes, hipStream_t s) {
   ScratchArena& a = scratch_arena(s);
+  if (a.depth == 0) return hipErrorInvalidValue;   // no ScratchScope open: nobody would take the bytes back
   bytes = (bytes + 255) & ~(size_t)255;
   if (bytes == 0) bytes = 256;
-  if (a.live == 0 && a.chunks.size() > 1) {  // grew during the previous call: one chunk from now on
+  if (a.chunks.size() > 1 && a.idle()) {  // grew during the previous call: one chunk from now on
     size_t total = 0;
     hipError_t e = hipStreamSynchronize(s);
     if (e != hipSuccess) return e;
@@ -4385,7 +4391,6 @@ hipError_t scratch_alloc(void** out, size_t bytes, hipStream_t s) {
     if (c.cap - c.used >= bytes) {
       *out = c.base + c.used;
       c.used += bytes;
-      ++a.live;
       return hipSuccess;
     }
   size_t cap = bytes;
@@ -4395,19 +4400,23 @@ hipError_t scratch_alloc(void** out, size_t bytes, hipStream_t s) {
   if (e != hipSuccess) return e;
   a.chunks.push_back({p, cap, bytes});
   *out = p;
-  ++a.live;
   return hipSuccess;
 }
-hipError_t scratch_free(void* p, hipStream_t s) {
-  if (!p) return hipSuccess;
-  ScratchArena& a = scratch_arena(s);
-  if (a.live > 0 && --a.live == 0)
-    for (auto& c : a.chunks) c.used = 0;
-  return hipSuccess;
+// A phase that began with nothing in use (the head of a call) hands its bytes to what follows: the next phase
+// allocates where it lay.  Further inside a call -- something is held at the mark -- the bytes stay until the scope
+// closes, so that what follows lies where it always lay.
+void scratch_reuse_from(hipStream_t s, const mrx::ScratchMark& m) {
+  for (size_t u : m.used) if (u) return;
+  mrx::scratch_rewind(s, m);
 }
 size_t scratch_bytes_reserved() {   // testing: total bytes held by the calling thread's arenas
   size_t t = 0;
   for (auto& kv : g_scratch) for (auto& c : kv.second.chunks) t += c.cap;
+  return t;
+}
+size_t scratch_bytes_in_use() {   // testing: ... and how many of them are handed out and not yet rewound
+  size_t t = 0;
+  for (auto& kv : g_scratch) for (auto& c : kv.second.chunks) t += c.used;
   return t;
 }
 void scratch_release_all() {
@@ -4463,17 +4472,30 @@ int grid_for(int64_t n, int block) {
   const int64_t cap = grid_cap();
   return (int)(g < cap ? g : cap);
 }
+// one lane per text in workgroups of `waves` wavefronts: at least one workgroup, at most what fills the device
+int wave_grid(int64_t n, int waves) { return grid_for((n + 63) / 64, waves); }
+int wstep_grid(int64_t n) { return wave_grid(n, kWsWaves); }
 
-// k_wstep for findall / count: plain route or required-byte route (a bool `use_req_route` in scope)
-// (and a DevPlan `p` or handle `h` whose flags say whether the bitset form runs: `wstep_bits`)
-// (and a bool `wstep_mwalk`: the plan's multi-walk form, k_mwalk, takes the plain route's place)
+// Which form of the stepper family a findall / count call launches (wstep_launch / reqwave_launch).  findall
+// (FindallJob::choose_route, step_scan) and count (run_count_any) fill it by rules of their own.
+struct StepRoute {
+  bool req = false;       // the required-byte route instead of the plain one
+  bool bits = false;      // bitset NFA on the lane-per-text stepper
+  bool lz = false;        // '$' on the LazyDFA search: lane per text only (the cache is the text's)
+  bool empty = false;     // plans with empty matches: count, then emit
+  bool mwalk = false;     // the plan's multi-walk form, k_mwalk, takes the plain route's place
+  int mwalk_k = 0;        // ... its walk slots (DevPlan::mw_k)
+  bool mwalk_pk = false;  // ... in the packed-start form (every text below 64 KiB)
+  bool bm = false;        // stepper behind the right-to-left pass that marks where matches begin (PF_BACKSET)
+  bool bm_big = false;    // ... with its table class indexed (more than 96 states)
+};
 // k_mwalk for a plan of `kw` walk slots; pk: every text is shorter than 64 KiB (the packed-start form, modes that
 // keep start registers)
 std::atomic<int> g_mwalk_pk{1};   // MRX_NO_MWALK_PK=1: never the packed form (A/B, and a parity test compares the two)
 bool mwalk_pk_ok(const Layout& lay, int64_t known_max) {
   static const bool off = getenv("MRX_NO_MWALK_PK") && getenv("MRX_NO_MWALK_PK")[0] == '1';
   if (off || !g_mwalk_pk || lay.vlen) return false;
-  const int64_t m = lay.offsets ? known_max : (lay.lens ? lay.stride : (int64_t)lay.len);
+  const int64_t m = lay.offsets ? known_max : lay.pitch_longest();
   return m >= 0 && m <= 65535;
 }
 template <int MODE, class... Args>
@@ -4511,17 +4533,18 @@ void mwalk_launch(int kw, bool pk, dim3 g, dim3 b, size_t lds_bytes, hipStream_t
   }
 }
 thread_local int64_t t_csr_max_len = -1;   // longest text of the CSR batch req_wave_pays() last looked at (-1: not known)
-#define MRX_WSTEP_LAUNCH(MODE, ...)                                                        \
-  do {                                                                                     \
-    if (wstep_mwalk) mwalk_launch<MODE>(wstep_mwalk_k, wstep_mwalk_pk, __VA_ARGS__);         \
-    else if (wstep_bm && wstep_bm_big) hipLaunchKernelGGL((k_wstep<MODE, 0, 0, 0, 1, 1>), __VA_ARGS__); \
-    else if (wstep_bm) hipLaunchKernelGGL((k_wstep<MODE, 0, 0, 0, 1>), __VA_ARGS__);       \
-    else if (wstep_bits) hipLaunchKernelGGL((k_wstep<MODE, 0, 1>), __VA_ARGS__);           \
-    else if (wstep_empty) hipLaunchKernelGGL((k_wstep<MODE, 0, 0, 1>), __VA_ARGS__);       \
-    else if (use_req_route) hipLaunchKernelGGL((k_wstep<MODE, 1>), __VA_ARGS__);         \
-    else if (wstep_lz) hipLaunchKernelGGL((k_wstep<MODE, 0, 0, 0, 0, 0, 1>), __VA_ARGS__); \
-    else hipLaunchKernelGGL((k_wstep<MODE, 0>), __VA_ARGS__);                              \
-  } while (0)
+// k_wstep / k_mwalk for findall / count
+template <int MODE, class... Args>
+void wstep_launch(const StepRoute& r, dim3 g, dim3 b, size_t lds_bytes, hipStream_t s, Args... args) {
+  if (r.mwalk) mwalk_launch<MODE>(r.mwalk_k, r.mwalk_pk, g, b, lds_bytes, s, args...);
+  else if (r.bm && r.bm_big) hipLaunchKernelGGL((k_wstep<MODE, 0, 0, 0, 1, 1>), g, b, lds_bytes, s, args...);
+  else if (r.bm) hipLaunchKernelGGL((k_wstep<MODE, 0, 0, 0, 1>), g, b, lds_bytes, s, args...);
+  else if (r.bits) hipLaunchKernelGGL((k_wstep<MODE, 0, 1>), g, b, lds_bytes, s, args...);
+  else if (r.empty) hipLaunchKernelGGL((k_wstep<MODE, 0, 0, 1>), g, b, lds_bytes, s, args...);
+  else if (r.req) hipLaunchKernelGGL((k_wstep<MODE, 1>), g, b, lds_bytes, s, args...);
+  else if (r.lz) hipLaunchKernelGGL((k_wstep<MODE, 0, 0, 0, 0, 0, 1>), g, b, lds_bytes, s, args...);
+  else hipLaunchKernelGGL((k_wstep<MODE, 0>), g, b, lds_bytes, s, args...);
+}
 // dynamic LDS of k_wstep for this plan
 size_t wstep_lds(const DevPlan& p, bool mwalk = false, bool bm_big = false) {
   if (mwalk) return mwalk_table_bytes(p);
@@ -4567,7 +4590,7 @@ bool union_pass_for_table_plan(const DevPlan& p, bool search) {
          bscan_dfa_table_bytes(p.nstates, p.ncls) <= 26 * 1024;
 }
 // Bitset NFA, first pass (k_bscan): on return *out is `lay` with every text cut to what the second pass
-// has to look at (mode 0 search, 1 count / findall); *d_limit is scratch the caller frees.
+// has to look at (mode 0 search, 1 count / findall); *d_limit is scratch of the calling scope.
 // Right-to-left pass of a PF_BACKSET plan: on return *out is `lay` with the marks (bm, bm_cnt) attached (scratch of
 // the calling scope).  A CSR batch's byte count is read back once to size the bitmap.
 int backscan_marks(const mrx_handle* h, const Layout& lay, int64_t n, hipStream_t s, Layout* out) {
@@ -4594,10 +4617,7 @@ int backscan_marks(const mrx_handle* h, const Layout& lay, int64_t n, hipStream_
   int32_t* d_cnt = nullptr;
   HIP_TRY(scratch_alloc((void**)&d_bm, sizeof(uint32_t) * (size_t)words, s));
   HIP_TRY(scratch_alloc((void**)&d_cnt, sizeof(int32_t) * (n > 0 ? n : 1), s));
-  const int64_t nw = (n + 63) / 64;
-  int64_t g = (nw + kWsWaves - 1) / kWsWaves;
-  if (g < 1) g = 1;
-  if (g > grid_cap()) g = grid_cap();
+  const int g = wstep_grid(n);
   hipLaunchKernelGGL(k_backscan, dim3((unsigned)g), dim3(64 * kWsWaves), (size_t)p.bk_bytes + 16, s, p, H_BLOB(h), lay, n, d_bm, d_cnt);
   HIP_TRY(hipGetLastError());
   *out = lay;
@@ -4610,10 +4630,7 @@ int bscan_limits(const mrx_handle* h, const Layout& lay, int64_t n, int mode, hi
                  int32_t** d_limit) {
   const DevPlan& p = h->hp.dev;
   HIP_TRY(scratch_alloc((void**)d_limit, sizeof(int32_t) * (n > 0 ? n : 1), s));
-  const int64_t nw = (n + 63) / 64;
-  int64_t g = (nw + kWsWaves - 1) / kWsWaves;
-  if (g < 1) g = 1;
-  if (g > grid_cap()) g = grid_cap();
+  const int g = wstep_grid(n);
   if (!(p.flags & PF_BSTEP))   // a table plan: sets of DFA states
     hipLaunchKernelGGL((k_bscan<1, 1>), dim3((unsigned)g), dim3(64 * kWsWaves), bscan_dfa_table_bytes(p.nstates, p.ncls), s, p,
                        H_BLOB(h), lay, n, mode, *d_limit);
@@ -4643,10 +4660,7 @@ bool bits_fixed_on(const DevPlan& p) {
 int bscan_fixed(const mrx_handle* h, const Layout& lay, int64_t n, int mode, hipStream_t s, int32_t* a, int32_t* b,
                 const int64_t* prefix, int64_t span_cap) {
   const DevPlan& p = h->hp.dev;
-  const int64_t nw = (n + 63) / 64;
-  int64_t g = (nw + kWsWaves - 1) / kWsWaves;
-  if (g < 1) g = 1;
-  if (g > grid_cap()) g = grid_cap();
+  const int g = wstep_grid(n);
   static const int ch = getenv("MRX_BSCAN_CH") ? atoi(getenv("MRX_BSCAN_CH")) : 64;
 #define MRX_BSF(NCH_)                                                                                                       \
   do {                                                                                                                      \
@@ -4668,6 +4682,31 @@ int bscan_fixed(const mrx_handle* h, const Layout& lay, int64_t n, int mode, hip
   return MRX_OK;
 }
 
+// byte count and longest text of a CSR batch: both live on the device (one small kernel, one sync).  At the head of
+// a call the word it reads back through is handed back at once (scratch_reuse_from()).
+int csr_stats(const Layout& lay, int64_t n, hipStream_t s, int64_t* total, int64_t* max_len) {
+  const ScratchMark mark = scratch_mark(s);
+  int32_t* d_max = nullptr;
+  int32_t m = 0;
+  HIP_TRY(scratch_alloc((void**)&d_max, sizeof(int32_t), s));
+  HIP_TRY(hipMemsetAsync(d_max, 0, sizeof(int32_t), s));
+  hipLaunchKernelGGL(k_max_len, dim3(grid_for(n, kBlock * 8)), dim3(kBlock), 0, s, lay.offsets, n, d_max);
+  HIP_TRY(hipMemcpyAsync(&m, d_max, sizeof m, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(total, lay.offsets + n, sizeof *total, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  scratch_reuse_from(s, mark);
+  *max_len = m;
+  return MRX_OK;
+}
+// bytes the batch holds: a CSR batch's count lives on the device (one 8-byte read-back and one synchronisation); at a
+// fixed pitch n texts of `per_text` bytes (the pitch where the rows' span is meant, pitch_longest() for the texts' own bytes)
+int batch_bytes(const Layout& lay, int64_t n, int64_t per_text, hipStream_t s, int64_t* bytes) {
+  *bytes = n * per_text;
+  if (!lay.offsets) return MRX_OK;
+  HIP_TRY(hipMemcpyAsync(bytes, lay.offsets + n, sizeof *bytes, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return MRX_OK;
+}
 // The stepper's routes: one wavefront per text (k_req_wave) when the texts are long or too few to
 // fill the device with one lane each, one lane per text (k_wstep) otherwise.  The average length
 // decides; a CSR batch's byte count lives on the device, so that costs one 8-byte read-back.
@@ -4683,19 +4722,10 @@ int req_wave_pays(const Layout& lay, int64_t n, bool req_route, hipStream_t s, b
   if (n <= 0) return MRX_OK;
   int64_t total = 0, max_len = 0;
   if (lay.offsets) {
-    int32_t* d_max = nullptr;
-    int32_t m = 0;
-    HIP_TRY(scratch_alloc((void**)&d_max, sizeof(int32_t), s));
-    HIP_TRY(hipMemsetAsync(d_max, 0, sizeof(int32_t), s));
-    hipLaunchKernelGGL(k_max_len, dim3(grid_for(n, kBlock * 8)), dim3(kBlock), 0, s, lay.offsets, n, d_max);
-    HIP_TRY(hipMemcpyAsync(&m, d_max, sizeof m, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(&total, lay.offsets + n, sizeof total, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    HIP_TRY(scratch_free(d_max, s));
-    max_len = m;
-    if (!lay.vlen) t_csr_max_len = m;
+    if (int rc = csr_stats(lay, n, s, &total, &max_len)) return rc;
+    if (!lay.vlen) t_csr_max_len = max_len;
   } else {
-    total = n * (lay.lens ? lay.stride : (int64_t)lay.len);
+    total = n * lay.pitch_longest();
   }
   const int64_t avg = total / n;
   // Measured on the reference's benchmark texts (tools/bench_suite.py): with sparse candidates (the
@@ -4720,28 +4750,21 @@ int reqwave_grid(int64_t n) {
   if (g < 1) g = 1;
   return (int)(g < grid_cap() ? g : grid_cap());
 }
-// (a bool `use_req_route` in scope, as for MRX_WSTEP_LAUNCH)
-#define MRX_REQWAVE_LAUNCH(MODE, H, LAY, N, COUNTS, PREFIX, SPANS, CAP, S)                                       \
-  do {                                                                                                           \
-    if (use_req_route)                                                                                           \
-      hipLaunchKernelGGL((k_req_wave<MODE, 1>), dim3(reqwave_grid(N)), dim3(64 * kRqWaves),                      \
-                         reqwave_table_bytes((H)->hp.dev.nstates), S, (H)->hp.dev, H_BLOB(H), LAY, N, COUNTS,  \
-                         PREFIX, SPANS, CAP, (int32_t*)nullptr, (int32_t*)nullptr);                              \
-    else if ((H)->hp.dev.flags & PF_STEP_BIG)                                                                    \
-      hipLaunchKernelGGL((k_req_wave<MODE, 0, 1>), dim3(reqwave_grid(N)), dim3(64 * kRqWaves),                   \
-                         reqwave_big_bytes((H)->hp.dev.nstates, (H)->hp.dev.ncls), S, (H)->hp.dev, H_BLOB(H),  \
-                         LAY, N, COUNTS, PREFIX, SPANS, CAP, (int32_t*)nullptr, (int32_t*)nullptr);              \
-    else                                                                                                         \
-      hipLaunchKernelGGL((k_req_wave<MODE, 0>), dim3(reqwave_grid(N)), dim3(64 * kRqWaves),                      \
-                         reqwave_table_bytes((H)->hp.dev.nstates), S, (H)->hp.dev, H_BLOB(H), LAY, N, COUNTS,  \
-                         PREFIX, SPANS, CAP, (int32_t*)nullptr, (int32_t*)nullptr);                              \
-  } while (0)
-
-int wstep_grid(int64_t n) {
-  const int64_t nw = (n + 63) / 64;
-  int64_t g = (nw + kWsWaves - 1) / kWsWaves;
-  if (g < 1) g = 1;
-  return (int)(g < grid_cap() ? g : grid_cap());
+// k_req_wave for findall / count
+template <int MODE>
+void reqwave_launch(const StepRoute& r, const mrx_handle* h, const Layout& lay, int64_t n, int32_t* counts,
+                    const int64_t* prefix, int32_t* spans, int64_t cap, hipStream_t s) {
+  const DevPlan& p = h->hp.dev;
+  const dim3 g(reqwave_grid(n)), b(64 * kRqWaves);
+  if (r.req)
+    hipLaunchKernelGGL((k_req_wave<MODE, 1>), g, b, reqwave_table_bytes(p.nstates), s, p, H_BLOB(h), lay, n, counts, prefix,
+                       spans, cap, (int32_t*)nullptr, (int32_t*)nullptr);
+  else if (p.flags & PF_STEP_BIG)
+    hipLaunchKernelGGL((k_req_wave<MODE, 0, 1>), g, b, reqwave_big_bytes(p.nstates, p.ncls), s, p, H_BLOB(h), lay, n, counts,
+                       prefix, spans, cap, (int32_t*)nullptr, (int32_t*)nullptr);
+  else
+    hipLaunchKernelGGL((k_req_wave<MODE, 0>), g, b, reqwave_table_bytes(p.nstates), s, p, H_BLOB(h), lay, n, counts, prefix,
+                       spans, cap, (int32_t*)nullptr, (int32_t*)nullptr);
 }
 
 struct ScanTimer {  // HIP events around the dominant scan kernel, on its own stream
@@ -4781,7 +4804,6 @@ int device_scan(const T* d_in, int64_t n, int64_t* d_prefix, int64_t* d_total, h
   hipLaunchKernelGGL(k_scan_add, dim3((unsigned)nblocks), dim3(kScanBlock), 0, s, d_prefix, n,
                      d_bs, d_total);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(scratch_free(d_bs, s));
   return MRX_OK;
 }
 
@@ -4826,9 +4848,7 @@ int bt_prepass(const mrx_handle* h, const Layout& lay, int64_t n, hipStream_t s,
   if ((p.flags & PF_PREFILTER) && h->hp.prefilter_literal != h->hp.nfa_literal) return MRX_OK;
   int2* d_pre = nullptr;
   HIP_TRY(scratch_alloc((void**)&d_pre, sizeof(int2) * n, s));
-  const int64_t nw = (n + 63) / 64;
-  int64_t g = (nw + kWsWaves - 1) / kWsWaves;
-  if (g > grid_cap()) g = grid_cap();
+  const int g = wstep_grid(n);
   // few texts: one lane per text cannot fill the device, and long ones (4549 texts of 59 KB: 71 wavefronts) take
   // as long as one lane needs for its text.  Then the pass runs over 2 KiB pieces instead; their number stays on
   // the device.  (The early exit of the first-occurrence-only form is worth more than that, so only FULL.)
@@ -4850,10 +4870,6 @@ int bt_prepass(const mrx_handle* h, const Layout& lay, int64_t n, hipStream_t s,
     hipLaunchKernelGGL((k_litscan<true, true>), dim3((unsigned)grid_cap()), dim3(64 * kWsWaves), 0, s, H_BLOB(h) + p.off_bt_lit,
                        p.bt_lit_len, H_BLOB(h), lay, n, (int32_t*)nullptr, (int2*)nullptr, d_vfirst, C, d_acc);
     hipLaunchKernelGGL(k_litscan_join, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, s, n, d_acc, d_pre);
-    HIP_TRY(scratch_free(d_cnt, s));
-    HIP_TRY(scratch_free(d_vfirst, s));
-    HIP_TRY(scratch_free(d_acc, s));
-    HIP_TRY(scratch_free(d_tot, s));
   } else if (p.bt_flags & (4 | 8))
     hipLaunchKernelGGL(k_litscan<true>, dim3((unsigned)g), dim3(64 * kWsWaves), 0, s, H_BLOB(h) + p.off_bt_lit, p.bt_lit_len,
                        H_BLOB(h), lay, n, (int32_t*)nullptr, d_pre);
@@ -4911,7 +4927,6 @@ int run_match(const mrx_handle* h, const Layout& lay, int64_t n, int32_t* d_s, i
       hipLaunchKernelGGL((k_wstep<STEP_SEARCH, 0, 1>), dim3(wstep_grid(n)), dim3(64 * kWsWaves), wstep_lds(h->hp.dev), s,
                          h->hp.dev, H_BLOB(h), lay2, n, (int32_t*)nullptr, (const int64_t*)nullptr, (int32_t*)nullptr,
                          (int64_t)0, d_s, d_e);
-      HIP_TRY(scratch_free(d_limit, s));
       g_last_kernel = "k_bstep_search";
     } else
     if (!wave && !big && (mwalk_on(h->hp.dev) || mw_tries_on(h->hp.dev))) {   // several walks in one pass; the few very long texts keep their kernel
@@ -4955,7 +4970,6 @@ int run_match(const mrx_handle* h, const Layout& lay, int64_t n, int32_t* d_s, i
     hipLaunchKernelGGL((k_wstep<STEP_SEARCH, 0>), dim3(wstep_grid(n)), dim3(64 * kWsWaves), wstep_lds(h->hp.dev), s, h->hp.dev,
                        H_BLOB(h), lay2, n, (int32_t*)nullptr, (const int64_t*)nullptr, (int32_t*)nullptr,
                        (int64_t)0, d_s, d_e);
-    if (d_limit) HIP_TRY(scratch_free(d_limit, s));
     g_last_kernel = "k_step_search";
     if (split > 0) {   // the few very long texts of the batch
       hipLaunchKernelGGL((k_req_wave<STEP_SEARCH, 0>), dim3(reqwave_grid(n)), dim3(64 * kRqWaves),
@@ -5030,10 +5044,8 @@ void launch_stream(const mrx_handle* h, const Layout& lay, int64_t n, int32_t* d
                    const int32_t* d_vlen = nullptr, const uint32_t* d_vskip = nullptr, bool rec32 = false,
                    const FusedArgs* fused = nullptr, int fused_grid = 0) {
   const DevPlan& p = h->hp.dev;
-  const int64_t nw = (n + 63) / 64;
-  int64_t g = (nw + kStreamWaves - 1) / kStreamWaves;
-  if (g > grid_cap()) g = grid_cap();
-  if (MODE == ST_FUSED) g = fused_grid;   // one record region per wavefront of this grid
+  // (ST_FUSED: one record region per wavefront of the caller's grid)
+  const int g = MODE == ST_FUSED ? fused_grid : wave_grid(n, kStreamWaves);
   const FusedArgs* fzv = fused;   // device copy (k_fused_init)
   const dim3 grid((unsigned)g), block(64 * kStreamWaves);
   const int kind = MODE == ST_FIRST ? p.fa_kind : p.st_kind;   // automaton form of this mode
@@ -5101,9 +5113,7 @@ void launch_stream_dyn(const mrx_handle* h, const Layout& lay, int64_t n, int32_
                        int32_t* d_s, int32_t* d_e, hipStream_t s, bool rec32) {
   const DevPlan& p = h->hp.dev;
   const int64_t ntasks = (n + kDynTexts - 1) / kDynTexts;
-  int64_t g = (ntasks + kStreamWaves - 1) / kStreamWaves;
-  if (g > grid_cap()) g = grid_cap();
-  const dim3 grid((unsigned)g), block(64 * kStreamWaves);
+  const dim3 grid((unsigned)wave_grid(ntasks * 64, kStreamWaves)), block(64 * kStreamWaves);   // (a wavefront per task)
   const bool table = p.st_kind == 2, wide = p.st_kind == 3;
   const bool pairs = (table || wide) && p.off_stg_pair >= 0 && g_pair_tables;
   const size_t lds = pairs ? (size_t)p.stg_bytes : wide ? 2048 : !table ? 0 : (size_t)p.stg_bytes;
@@ -5166,20 +5176,6 @@ struct Pieces {
   int32_t* back = nullptr;
   Layout lay{};   // the pieces as a batch: offsets = vstart
 };
-// byte count and longest text of a CSR batch: both live on the device (one small kernel, one sync)
-int csr_stats(const Layout& lay, int64_t n, hipStream_t s, int64_t* total, int64_t* max_len) {
-  int32_t* d_max = nullptr;
-  int32_t m = 0;
-  HIP_TRY(scratch_alloc((void**)&d_max, sizeof(int32_t), s));
-  HIP_TRY(hipMemsetAsync(d_max, 0, sizeof(int32_t), s));
-  hipLaunchKernelGGL(k_max_len, dim3(grid_for(n, kBlock * 8)), dim3(kBlock), 0, s, lay.offsets, n, d_max);
-  HIP_TRY(hipMemcpyAsync(&m, d_max, sizeof m, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipMemcpyAsync(total, lay.offsets + n, sizeof *total, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  HIP_TRY(scratch_free(d_max, s));
-  *max_len = m;
-  return MRX_OK;
-}
 // known_total / known_max: csr_stats() of the batch when the caller has them already (< 0: not)
 int pieces_prepare(const mrx_handle* h, const Layout& lay, int64_t n, hipStream_t s, Pieces* pc,
                    int64_t known_total = -1, int64_t known_max = -1, bool disjoint = false, bool mwalk = false) {
@@ -5199,7 +5195,7 @@ int pieces_prepare(const mrx_handle* h, const Layout& lay, int64_t n, hipStream_
   } else if (lay.offsets) {
     if (int rc = csr_stats(lay, n, s, &total, &max_len)) return rc;
   } else {
-    max_len = lay.lens ? lay.stride : (int64_t)lay.len;
+    max_len = lay.pitch_longest();
     total = n * lay.stride;
   }
   int C;
@@ -5230,6 +5226,7 @@ int pieces_prepare(const mrx_handle* h, const Layout& lay, int64_t n, hipStream_
     if (C >= max_len) return MRX_OK;
   }
   // pieces per text -> prefix sums -> how many there are
+  const ScratchMark mark = scratch_mark(s);
   HIP_TRY(scratch_alloc((void**)&pc->vfirst, sizeof(int64_t) * (n + 1), s));
   int64_t nv = 0;
   if (!lay.offsets && !lay.lens) {   // one length: nothing to count, nothing to read back
@@ -5245,11 +5242,9 @@ int pieces_prepare(const mrx_handle* h, const Layout& lay, int64_t n, hipStream_
     if (int rc = device_scan<int32_t>(d_cnt, n, pc->vfirst, d_tot, s)) return rc;
     HIP_TRY(hipMemcpyAsync(&nv, d_tot, sizeof nv, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    HIP_TRY(scratch_free(d_cnt, s));
-    HIP_TRY(scratch_free(d_tot, s));
   }
   if (nv <= n || nv > (int64_t(1) << 24)) {   // nothing to cut after all, or an absurd number of pieces
-    HIP_TRY(scratch_free(pc->vfirst, s));
+    scratch_reuse_from(s, mark);   // count / search go on without pieces, on the bytes the count took
     pc->vfirst = nullptr;
     return MRX_OK;
   }
@@ -5268,17 +5263,6 @@ int pieces_prepare(const mrx_handle* h, const Layout& lay, int64_t n, hipStream_
   pc->lay = csr(lay.data, pc->vstart);
   if (disjoint) pc->lay.vlen = pc->vlen;   // a view: the stepper's kernels read the pieces through Layout::text()
   pc->on = true;
-  return MRX_OK;
-}
-int pieces_release(Pieces* pc, hipStream_t s) {
-  if (!pc->on) return MRX_OK;
-  HIP_TRY(scratch_free(pc->vfirst, s));
-  HIP_TRY(scratch_free(pc->vstart, s));
-  HIP_TRY(scratch_free(pc->vlen, s));
-  HIP_TRY(scratch_free(pc->vskip, s));
-  HIP_TRY(scratch_free(pc->vbase, s));
-  HIP_TRY(scratch_free(pc->back, s));
-  pc->on = false;
   return MRX_OK;
 }
 
@@ -5316,12 +5300,6 @@ int findall_pieces(const mrx_handle* h, const Pieces& pc, int64_t n, int64_t* d_
                      d_total, pc.vbase);
   hipLaunchKernelGGL(k_virt_prefix, dim3(grid_for(n + 1, kBlock)), dim3(kBlock), 0, s, n, pc.vfirst, d_vprefix, d_prefix);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(scratch_free(d_vcounts, s));
-  HIP_TRY(scratch_free(d_recs, s));
-  HIP_TRY(scratch_free(d_nrecs, s));
-  HIP_TRY(scratch_free(d_wbase, s));
-  HIP_TRY(scratch_free(d_vprefix, s));
-  HIP_TRY(scratch_free(d_tsum, s));
   return MRX_OK;
 }
 
@@ -5419,9 +5397,6 @@ static int findall_split(const mrx_handle* h, const Layout& lay, int64_t n, int3
 #undef MRX_DECODE_HALF
   HIP_TRY(hipGetLastError());
   g_last_kernel = "k_stream_findall";
-  HIP_TRY(scratch_free(d_recs, s)); HIP_TRY(scratch_free(d_nrA, s)); HIP_TRY(scratch_free(d_nrB, s));
-  HIP_TRY(scratch_free(d_wbA, s)); HIP_TRY(scratch_free(d_wbB, s)); HIP_TRY(scratch_free(d_tsA, s));
-  HIP_TRY(scratch_free(d_tsB, s)); HIP_TRY(scratch_free(d_totA, s));
   return MRX_OK;
 }
 
@@ -5443,12 +5418,7 @@ static int dense_candidates(const mrx_handle* h, const Layout& lay, int64_t n, h
   *dense = true;
   if (g_long_text_mode == 1) return MRX_OK;
   int64_t bytes = 0;
-  if (lay.offsets) {
-    HIP_TRY(hipMemcpyAsync(&bytes, lay.offsets + n, sizeof bytes, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-  } else {
-    bytes = n * lay.stride;
-  }
+  if (int rc = batch_bytes(lay, n, lay.stride, s, &bytes)) return rc;
   if (bytes > (1 << 20)) bytes = 1 << 20;
   if (bytes <= 0) return MRX_OK;
   unsigned int* d_hits = nullptr;
@@ -5458,7 +5428,6 @@ static int dense_candidates(const mrx_handle* h, const Layout& lay, int64_t n, h
   hipLaunchKernelGGL(k_candidate_density, dim3(256), dim3(kBlock), 0, s, h->hp.dev, H_BLOB(h), lay.data, bytes, d_hits);
   HIP_TRY(hipMemcpyAsync(&hits, d_hits, sizeof hits, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
-  HIP_TRY(scratch_free(d_hits, s));
   *dense = (double)hits >= 0.08 * (double)bytes;
   return MRX_OK;
 }
@@ -5480,12 +5449,7 @@ static int sync_bytes_frequent(const mrx_handle* h, const Layout& lay, int64_t n
   const DevPlan& p = h->hp.dev;
   if (p.st_nsync <= 0 || p.off_st_sync < 0) return MRX_OK;
   int64_t bytes = 0;
-  if (lay.offsets) {
-    HIP_TRY(hipMemcpyAsync(&bytes, lay.offsets + n, sizeof bytes, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-  } else {
-    bytes = n * lay.stride;
-  }
+  if (int rc = batch_bytes(lay, n, lay.stride, s, &bytes)) return rc;
   if (bytes > (1 << 20)) bytes = 1 << 20;
   if (bytes <= 0) return MRX_OK;
   unsigned int* d_hits = nullptr;
@@ -5502,8 +5466,8 @@ static int sync_bytes_frequent(const mrx_handle* h, const Layout& lay, int64_t n
 int run_findall(const mrx_handle* h, const Layout& lay, int64_t n, int64_t* d_prefix, int32_t* d_spans, int64_t span_cap,
                 int64_t* total, void* stream, bool match_next_sequence = false, int64_t known_total = -1, int64_t known_max = -1);
 
-// One findall call.  The members are the state the routes share (the launch macros of this file read the route flags by
-// name); one member function per route -- round 3's run_findall was a single 420-line function steering ~25 flags.
+// One findall call.  The members are the state the routes share; one member function per route -- round 3's
+// run_findall was a single 420-line function steering ~25 flags.
 // Two routes for one plan and batch shape, measured by the handle (mrx_handle::req_tune[key]): the first four eligible calls
 // take route 1, 2, 1, 2, the last two between HIP events on the caller's stream; a later call that finds the last event
 // complete keeps the faster route.  Returns the route this call takes (1 or 2); *slot >= 0 when the call is one of the
@@ -5559,12 +5523,11 @@ struct FindallJob {
   const DevPlan& p;
   int32_t* d_counts = nullptr;
   int64_t* d_total = nullptr;
-  // ---- route (chosen by choose_route(); the launch macros of this file read these by name) ----
-  bool stream_ok = false, use_req_route = false, wstep_bits = false, wstep_lz = false, wstep_empty = false, mw_empty = false, mw_tries = false;
-  bool mwalk_req = false, wstep_mwalk = false;
+  // ---- route (chosen by choose_route() and step_scan()) ----
+  StepRoute rt;                    // the stepper family's form: what wstep_launch / reqwave_launch take
+  bool stream_ok = false, mw_empty = false, mw_tries = false;
+  bool mwalk_req = false;
   DevPlan pk;                      // what the lane kernels are launched with
-  int wstep_mwalk_k = 0;
-  bool wstep_mwalk_pk = false;     // k_mwalk's packed-start form (every text below 64 KiB)
   bool step_ok = false;
   bool bits_fixed = false;         // bitset program whose matches all have one length: the union pass counts and emits by itself
   bool bits_fixed_slots = false;   // ... with the spans in slot rows (one pass)
@@ -5577,12 +5540,9 @@ struct FindallJob {
   int64_t max_text = int64_t(1) << 40;    // longest text of the batch, where known
   bool req_wave = false;           // the stepper's route on the wavefront-per-text kernel
   bool mwalk_two_pass = false;     // multi-walk plan: count pass + emit pass instead of slot rows
-  bool wstep_bm = false;           // stepper behind the right-to-left pass that marks where matches begin (PF_BACKSET)
-  bool wstep_bm_big = false;       // ... with its table class indexed (more than 96 states)
   int step_split = 0;              // > 0: lane kernel for texts below this length AND wavefront kernel for the rest
   Layout lay2;                     // lay + that split
   EvRec* d_recs = nullptr;
-  EvRec* d_recs_alloc = nullptr;   // what d_recs was cut from when it is skewed (mrx_debug_rec_skew)
   int32_t* d_nrecs = nullptr;
   int64_t* d_wbase = nullptr;
   int32_t* d_slots = nullptr;
@@ -5612,34 +5572,34 @@ struct FindallJob {
     stream_ok = !g_force_generic && (p.flags & PF_STREAMABLE) && stream_layout_ok(lay, n);
     // match_next_sequence: the caller (sub) wants the matches that iterating match_next from each
     // match end visits -- the plain walk even on plans whose findall takes the required-byte route
-    use_req_route = (p.flags & PF_STEP_REQ) && !match_next_sequence;
-    wstep_bits = (p.flags & PF_BSTEP) != 0;   // bitset NFA on the lane-per-text stepper
-    wstep_lz = (p.flags & PF_LAZY_END) != 0;  // '$' on the LazyDFA search: lane per text only (the cache is the text's)
+    rt.req = (p.flags & PF_STEP_REQ) && !match_next_sequence;
+    rt.bits = (p.flags & PF_BSTEP) != 0;   // bitset NFA on the lane-per-text stepper
+    rt.lz = (p.flags & PF_LAZY_END) != 0;  // '$' on the LazyDFA search: lane per text only (the cache is the text's)
     // plans with empty matches: count, then emit (nearly every text has more matches than a slot row holds)
     // ... in one pass on k_mwalk when no walk of the plan ever reads beyond its match (PF_MW_EMPTY)
     mw_empty = (p.flags & PF_MW_EMPTY) != 0 && mwalk_enabled() && !match_next_sequence && g_force_generic < 2;
-    wstep_empty = (p.flags & PF_STEP_EMPTY) != 0 && !match_next_sequence && g_force_generic < 2 && !mw_empty;
+    rt.empty = (p.flags & PF_STEP_EMPTY) != 0 && !match_next_sequence && g_force_generic < 2 && !mw_empty;
     // several walks in one pass instead of the restart-per-position loop (plain route; sub's match_next sequence is
     // the same list of matches, but a memchr-prefiltered match_next is not the plain search)
-    mwalk_req = use_req_route && (p.flags & PF_MWALK_REQ) && mwalk_enabled();
+    mwalk_req = rt.req && (p.flags & PF_MWALK_REQ) && mwalk_enabled();
     // ... and plain-route plans outside the multi-walk proofs whose walks stay within seven bytes of their match (PF_MW_TRIES)
-    mw_tries = mw_tries_on(p) && !use_req_route && g_force_generic < 2;
+    mw_tries = mw_tries_on(p) && !rt.req && g_force_generic < 2;
     if (t_in_pieces && t_piece_tries >= 0) mw_tries = mw_tries && t_piece_tries == 1;   // (the pieces follow the call they belong to)
     if (mw_tries && !t_in_pieces && n >= 256 && backset_on(p) && !g_tries_always) {   // (marks + stepper is the other candidate)
       bool use_tries = true;
       tries_route_tuner(&use_tries);
       mw_tries = use_tries;
     }
-    wstep_mwalk = (mwalk_req || (mwalk_on(p) && !use_req_route) || mw_empty || mw_tries) && !wstep_bits && !wstep_empty &&
+    rt.mwalk = (mwalk_req || (mwalk_on(p) && !rt.req) || mw_empty || mw_tries) && !rt.bits && !rt.empty &&
                   !(match_next_sequence && (p.flags & PF_PREFILTER));
     pk = mwalk_req ? mwalk_req_plan(p) : p;
-    wstep_mwalk_k = pk.mw_k;
+    rt.mwalk_k = pk.mw_k;
     step_ok = g_force_generic < 2 &&
-              (wstep_mwalk ||
+              (rt.mwalk ||
                (match_next_sequence ? ((p.flags & PF_STEP_SEARCH) && !(p.flags & PF_PREFILTER))
                                     : (p.flags & (PF_STEPPABLE | PF_STEP_REQ | PF_STEP_EMPTY)) != 0));
     // bitset program whose matches all have one length: the union pass counts and emits by itself (k_bscan modes 2, 3)
-    bits_fixed = step_ok && wstep_bits && bits_fixed_on(p) && !(match_next_sequence && (p.flags & PF_PREFILTER));
+    bits_fixed = step_ok && rt.bits && bits_fixed_on(p) && !(match_next_sequence && (p.flags & PF_PREFILTER));
     lay2 = lay;
     lay_pre = lay;
   }
@@ -5685,7 +5645,7 @@ struct FindallJob {
       rec_row = rec_row_len(lay.lens ? lay.stride : lay.len) + (strided_fast(lay) ? 0 : 1);  // frame: one more group
       nrec = (size_t)rec_row * n;
     }
-    max_text = lay.offsets ? csr_max : (lay.lens ? lay.stride : (int64_t)lay.len);
+    max_text = lay.offsets ? csr_max : lay.pitch_longest();
     rec32 = max_text <= kRec32MaxLen;
     // (a CSR batch of equal-length texts leaves no lane idle: the 64-text wavefronts and their decode are faster)
     dyn = dyn_ok(h, lay, n) && max_text < (int64_t(1) << kDynShift) &&
@@ -5705,7 +5665,7 @@ struct FindallJob {
     int64_t fz_grid = (nw + kStreamWaves - 1) / kStreamWaves;
     if (fz_grid > fused_grid_cap()) fz_grid = fused_grid_cap();
     const size_t fz_nrec = (size_t)(64 * fz_per_text + 64) * (size_t)(fz_grid * kStreamWaves) * 2;   // two regions per wavefront
-    const int64_t batch_bytes = lay.offsets ? csr_total : n * (lay.lens ? lay.stride : (int64_t)lay.len);
+    const int64_t batch_bytes = lay.offsets ? csr_total : n * lay.pitch_longest();
     fused = !dyn && !rows && g_fused && span_cap > 0 && fz_nrec <= 2 * nrec + (size_t(8) << 20) && (g_fused == 2 || batch_bytes >= nw * kFusedMinTaskBytes);
     // texts of at most 1 KiB at a 16-byte aligned pitch, automaton in registers: one launch, no records at all
     // (mrx_stream_bits.hip)
@@ -5766,8 +5726,8 @@ struct FindallJob {
         return rc;
     } else {
     const int64_t skew = g_rec_skew.load(std::memory_order_relaxed);   // (mrx_debug_rec_skew: placement experiments)
-    HIP_TRY(scratch_alloc((void**)&d_recs_alloc, sizeof(EvRec) * nrec + (size_t)skew, s));
-    d_recs = (EvRec*)((uint8_t*)d_recs_alloc + skew);
+    HIP_TRY(scratch_alloc((void**)&d_recs, sizeof(EvRec) * nrec + (size_t)skew, s));
+    d_recs = (EvRec*)((uint8_t*)d_recs + skew);
     HIP_TRY(scratch_alloc((void**)&d_nrecs, sizeof(int32_t) * 2 * nw, s));  // records | matches per wavefront
     HIP_TRY(scratch_alloc((void**)&d_wbase, sizeof(int64_t) * (nw + 1), s));
     ScanTimer tm(s);
@@ -5835,7 +5795,6 @@ struct FindallJob {
                          rec_row, lay.offsets, d_counts, d_wbase, d_tsum, d_prefix, d_spans, span_cap, p.st_fixed_len,
                          d_total);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(scratch_free(d_tsum, s));
     return MRX_OK;
   }
 
@@ -5844,7 +5803,7 @@ struct FindallJob {
   // tables sit in between (tools/r04_tries_cap.py): as for the required-byte routes the handle measures -- the first four
   // eligible calls of a batch shape take the routes alternately, the last two timed; no call waits.
   static uint32_t tries_tune_key(const Layout& lay, int64_t n) {
-    const int64_t bytes_per_text = lay.offsets ? 0 : (lay.lens ? lay.stride : (int64_t)lay.len);
+    const int64_t bytes_per_text = lay.offsets ? 0 : lay.pitch_longest();
     uint32_t lb = 0, nb = 0;
     for (int64_t v = bytes_per_text; v > 1; v >>= 1) ++lb;
     for (int64_t v = n; v > 1; v >>= 1) ++nb;
@@ -5863,7 +5822,7 @@ struct FindallJob {
   // faster route from the first call that finds the last measurement complete.
   int req_route_tuner(bool* pieces) {
     *pieces = false;
-    const int64_t bytes_per_text = lay.offsets ? 0 : (lay.lens ? lay.stride : (int64_t)lay.len);
+    const int64_t bytes_per_text = lay.offsets ? 0 : lay.pitch_longest();
     uint32_t lb = 0, nb = 0;
     for (int64_t v = bytes_per_text; v > 1; v >>= 1) ++lb;
     for (int64_t v = n; v > 1; v >>= 1) ++nb;
@@ -5923,19 +5882,18 @@ struct FindallJob {
   // every other plan, first stage: counts (+ slot rows) on the stepper family / the literal restatement
   int step_scan() {
   bool req_pieces = false;   // required-byte plan: pieces on the multi-walk kernel instead of the wavefront-per-text kernel
-    if (use_req_route && mwalk_req && g_long_text_mode == 0 && !t_in_pieces && p.st_nsync > 0 && span_cap > 0 &&
+    if (rt.req && mwalk_req && g_long_text_mode == 0 && !t_in_pieces && p.st_nsync > 0 && span_cap > 0 &&
         !(p.flags & (PF_STEP_BIG | PF_STREAMABLE)))
       if (int rc = req_route_tuner(&req_pieces)) return rc;
-    if (step_ok && !wstep_bits && !wstep_empty && !t_in_pieces && !(p.flags & PF_STEP_BIG) && p.st_nsync > 0 &&
-        !(p.flags & PF_STREAMABLE) && span_cap > 0 && (!use_req_route || g_long_text_mode == 1 || req_pieces)) {
+    if (step_ok && !rt.bits && !rt.empty && !t_in_pieces && !(p.flags & PF_STEP_BIG) && p.st_nsync > 0 &&
+        !(p.flags & PF_STREAMABLE) && span_cap > 0 && (!rt.req || g_long_text_mode == 1 || req_pieces)) {
       Pieces spc;
-      if (int rc = pieces_prepare(h, lay, n, s, &spc, -1, -1, /*disjoint=*/true, wstep_mwalk)) return rc;
+      if (int rc = pieces_prepare(h, lay, n, s, &spc, -1, -1, /*disjoint=*/true, rt.mwalk)) return rc;
       if (req_pieces && !spc.on) req_tuner_unavailable();   // nothing to cut (texts too short, too many of them): the wavefront kernel it is
-      if (spc.on && !wstep_mwalk) {   // (a multi-walk plan scans every piece once, dense candidates or not)
+      if (spc.on && !rt.mwalk) {   // (a multi-walk plan scans every piece once, dense candidates or not)
         bool dense = true;
         if (int rc = dense_candidates(h, lay, n, s, &dense)) return rc;
-        if (!dense)
-          if (int rc = pieces_release(&spc, s)) return rc;
+        if (!dense) spc.on = false;
       }
       if (spc.on) {
         int64_t* d_vprefix = nullptr;
@@ -5967,40 +5925,38 @@ struct FindallJob {
           *total = tot;
           if (tot > span_cap) rc2 = fail(MRX_E_CAPACITY, "span buffer too small: need " + std::to_string(tot));
         }
-        HIP_TRY(scratch_free(d_vprefix, s));
-        if (int rc3 = pieces_release(&spc, s)) return rc3;
         finished = true;   // the pieces answered the whole call
         finished_rc = rc2;
         return MRX_OK;
       }
     }
-    if (step_ok && !wstep_bits && !wstep_empty && !mw_empty && !mw_tries && !t_in_pieces && !wstep_lz) {
-      if (int rc = req_wave_pays(lay, n, use_req_route, s, &req_wave, (p.flags & PF_STEP_BIG) ? nullptr : &step_split,
-                                 (p.flags & PF_STEP_BIG) != 0, wstep_mwalk, backset_on(p) && !wstep_mwalk))
+    if (step_ok && !rt.bits && !rt.empty && !mw_empty && !mw_tries && !t_in_pieces && !rt.lz) {
+      if (int rc = req_wave_pays(lay, n, rt.req, s, &req_wave, (p.flags & PF_STEP_BIG) ? nullptr : &step_split,
+                                 (p.flags & PF_STEP_BIG) != 0, rt.mwalk, backset_on(p) && !rt.mwalk))
         return rc;
-      wstep_mwalk_pk = wstep_mwalk && mwalk_pk_ok(lay, t_csr_max_len);
+      rt.mwalk_pk = rt.mwalk && mwalk_pk_ok(lay, t_csr_max_len);
     }
     lay2.split = step_split;
-    wstep_bm = step_ok && backset_on(p) && !wstep_mwalk && !wstep_bits && !wstep_empty && !use_req_route && !req_wave &&
+    rt.bm = step_ok && backset_on(p) && !rt.mwalk && !rt.bits && !rt.empty && !rt.req && !req_wave &&
                step_split == 0;
-    wstep_bm_big = wstep_bm && (p.flags & PF_STEP_BIG) != 0;
-    if (wstep_bm) {
+    rt.bm_big = rt.bm && (p.flags & PF_STEP_BIG) != 0;
+    if (rt.bm) {
       const int32_t split_keep = lay2.split;
       if (int rc = backscan_marks(h, lay, n, s, &lay2)) return rc;
       lay2.split = split_keep;
     }
-    if (step_ok && !bits_fixed && !wstep_empty && !wstep_mwalk && !wstep_bm && (wstep_bits || (!req_wave && step_split == 0 && !use_req_route && union_pass_for_table_plan(p, false)))) {
+    if (step_ok && !bits_fixed && !rt.empty && !rt.mwalk && !rt.bm && (rt.bits || (!req_wave && step_split == 0 && !rt.req && union_pass_for_table_plan(p, false)))) {
       // union automaton first: texts in which no walk from any start reaches MATCH are not walked at all
       // (mode 0: a wavefront stops as soon as each of its texts has shown one match end, so on texts full
       // of matches the pass costs next to nothing; cutting tails -- mode 1 -- would scan everything)
       if (int rc = bscan_limits(h, lay, n, 0, s, &lay2, &d_blimit)) return rc;
     }
     // big tables: only the wavefront kernel has their form; many short texts stay on the literal restatement
-    if ((p.flags & PF_STEP_BIG) && !req_wave && !wstep_mwalk && !wstep_bm) step_ok = false;
+    if ((p.flags & PF_STEP_BIG) && !req_wave && !rt.mwalk && !rt.bm) step_ok = false;
     ScanTimer tm(s);
     // multi-walk plans: count, prefix sums, emit -- two one-pass scans whatever the match density (the count pass
     // keeps no start registers and runs at 3 TB/s; slot rows + a second walk for overflowing texts would be three)
-    mwalk_two_pass = wstep_mwalk && !req_wave && step_split == 0;
+    mwalk_two_pass = rt.mwalk && !req_wave && step_split == 0;
     if (mwalk_two_pass && t_in_pieces && t_piece_vbase) {   // every span of this call leaves k_mwalk<STEP_EMIT>
       lay2.vbase = t_piece_vbase;
       t_piece_base_applied = true;
@@ -6011,55 +5967,45 @@ struct FindallJob {
       bits_fixed_slots = p.bs_fixed_len >= 4 && span_cap > 0 && !lay.vlen;
       if (bits_fixed_slots) {
         int64_t bytes = 0;
-        if (lay.offsets) {
-          HIP_TRY(hipMemcpyAsync(&bytes, lay.offsets + n, sizeof bytes, hipMemcpyDeviceToHost, s));
-          HIP_TRY(hipStreamSynchronize(s));
-        } else {
-          bytes = n * (lay.lens ? lay.stride : (int64_t)lay.len);
-        }
+        if (int rc = batch_bytes(lay, n, lay.pitch_longest(), s, &bytes)) return rc;
         lay2.wide_slots = 1;
         HIP_TRY(scratch_alloc((void**)&d_slots, sizeof(int32_t) * 2 * (size_t)(bytes / 4 + 32 * n + 64), s));
       }
       if (int rc = bscan_fixed(h, lay, n, bits_fixed_slots ? 5 : 2, s, d_counts, d_slots, nullptr, 0)) return rc;
-    } else if (step_ok && span_cap > 0 && !wstep_empty && !mwalk_two_pass) {
+    } else if (step_ok && span_cap > 0 && !rt.empty && !mwalk_two_pass) {
       if (req_wave) {
         // long texts: rows of len / 4 + 32 slots (twice the bytes of the batch) -- the second walk
         // is then only for texts with a match every 4 bytes
         int64_t bytes = 0;
-        if (lay.offsets) {
-          HIP_TRY(hipMemcpyAsync(&bytes, lay.offsets + n, sizeof bytes, hipMemcpyDeviceToHost, s));
-          HIP_TRY(hipStreamSynchronize(s));
-        } else {
-          bytes = n * (lay.lens ? lay.stride : (int64_t)lay.len);
-        }
+        if (int rc = batch_bytes(lay, n, lay.pitch_longest(), s, &bytes)) return rc;
         lay2.wide_slots = 1;
         HIP_TRY(scratch_alloc((void**)&d_slots, sizeof(int32_t) * 2 * (size_t)(bytes / 4 + 32 * n + 64), s));
-      } else if (!lay.offsets && step_split == 0 && (lay.lens ? lay.stride : (int64_t)lay.len) >= 2048) {
+      } else if (!lay.offsets && step_split == 0 && lay.pitch_longest() >= 2048) {
         // one lane per text, but texts long enough to hold more than kStepSlots matches as a rule
         // (rows sized as Layout::slot_row sizes them for lay2 -- the bitset first pass gives it per-text lengths)
         lay2.wide_slots = 1;
         HIP_TRY(scratch_alloc((void**)&d_slots,
-                              sizeof(int32_t) * 2 * (size_t)(n * ((lay2.lens ? lay2.stride : (int64_t)lay2.len) / 4 + 32) + 64), s));
+                              sizeof(int32_t) * 2 * (size_t)(n * (lay2.pitch_longest() / 4 + 32) + 64), s));
       } else
       HIP_TRY(scratch_alloc((void**)&d_slots, sizeof(int32_t) * 2 * kStepSlots * (size_t)n, s));
       if (req_wave)
-        MRX_REQWAVE_LAUNCH(STEP_SLOTS, h, lay2, n, d_counts, (const int64_t*)nullptr, d_slots, (int64_t)0, s);
+        reqwave_launch<STEP_SLOTS>(rt, h, lay2, n, d_counts, (const int64_t*)nullptr, d_slots, (int64_t)0, s);
       else
       {
-      MRX_WSTEP_LAUNCH(STEP_SLOTS, dim3(wstep_grid(n)), dim3(64 * kWsWaves), wstep_lds(pk, wstep_mwalk, wstep_bm_big), s, pk,
+      wstep_launch<STEP_SLOTS>(rt, dim3(wstep_grid(n)), dim3(64 * kWsWaves), wstep_lds(pk, rt.mwalk, rt.bm_big), s, pk,
                          H_BLOB(h), lay2, n, d_counts, (const int64_t*)nullptr, d_slots, (int64_t)0,
                          (int32_t*)nullptr, (int32_t*)nullptr);
       if (step_split > 0)
-        MRX_REQWAVE_LAUNCH(STEP_SLOTS, h, lay2, n, d_counts, (const int64_t*)nullptr, d_slots, (int64_t)0, s);
+        reqwave_launch<STEP_SLOTS>(rt, h, lay2, n, d_counts, (const int64_t*)nullptr, d_slots, (int64_t)0, s);
       }
     } else if (step_ok && req_wave)
-      MRX_REQWAVE_LAUNCH(STEP_COUNT, h, lay, n, d_counts, (const int64_t*)nullptr, (int32_t*)nullptr, (int64_t)0, s);
+      reqwave_launch<STEP_COUNT>(rt, h, lay, n, d_counts, (const int64_t*)nullptr, (int32_t*)nullptr, (int64_t)0, s);
     else if (step_ok) {
-      MRX_WSTEP_LAUNCH(STEP_COUNT, dim3(wstep_grid(n)), dim3(64 * kWsWaves), wstep_lds(pk, wstep_mwalk, wstep_bm_big), s, pk,
+      wstep_launch<STEP_COUNT>(rt, dim3(wstep_grid(n)), dim3(64 * kWsWaves), wstep_lds(pk, rt.mwalk, rt.bm_big), s, pk,
                          H_BLOB(h), lay2, n, d_counts, (const int64_t*)nullptr, (int32_t*)nullptr, (int64_t)0,
                          (int32_t*)nullptr, (int32_t*)nullptr);
       if (step_split > 0)
-        MRX_REQWAVE_LAUNCH(STEP_COUNT, h, lay2, n, d_counts, (const int64_t*)nullptr, (int32_t*)nullptr, (int64_t)0, s);
+        reqwave_launch<STEP_COUNT>(rt, h, lay2, n, d_counts, (const int64_t*)nullptr, (int32_t*)nullptr, (int64_t)0, s);
     } else {
       if (p.flags & PF_BT_SEARCH)
         if (int rc = bt_prepass(h, lay, n, s, &lay_pre)) return rc;
@@ -6068,7 +6014,7 @@ struct FindallJob {
       MRX_BT_DISPATCH(bt_kernel_kind(h, plan_uses_backtracker(h)), MRX_L);
   #undef MRX_L
     }
-    g_last_kernel = bits_fixed ? "k_bscan_fixed" : req_wave ? "k_req_wave" : step_ok ? (wstep_mwalk ? (step_split > 0 ? "k_mwalk+k_req_wave" : "k_mwalk") : wstep_bm ? "k_backscan+k_step_count" : wstep_bits ? "k_bstep_count" : wstep_empty ? "k_estep_count" : step_split > 0 ? "k_step_count+k_req_wave" : "k_step_count")
+    g_last_kernel = bits_fixed ? "k_bscan_fixed" : req_wave ? "k_req_wave" : step_ok ? (rt.mwalk ? (step_split > 0 ? "k_mwalk+k_req_wave" : "k_mwalk") : rt.bm ? "k_backscan+k_step_count" : rt.bits ? "k_bstep_count" : rt.empty ? "k_estep_count" : step_split > 0 ? "k_step_count+k_req_wave" : "k_step_count")
                                                       : "k_findall_count";
     HIP_TRY(hipGetLastError());
     tm.stop();
@@ -6085,10 +6031,10 @@ struct FindallJob {
     } else if (step_ok && mwalk_two_pass) {   // second scan, texts that hold a match: spans straight to their CSR place
       Layout lay_e = lay2;
       lay_e.wide_slots = 2;
-      MRX_WSTEP_LAUNCH(STEP_EMIT, dim3(wstep_grid(n)), dim3(64 * kWsWaves), wstep_lds(pk, wstep_mwalk, wstep_bm_big), s, pk, H_BLOB(h),
+      wstep_launch<STEP_EMIT>(rt, dim3(wstep_grid(n)), dim3(64 * kWsWaves), wstep_lds(pk, rt.mwalk, rt.bm_big), s, pk, H_BLOB(h),
                        lay_e, n, d_counts, d_prefix, d_spans, span_cap, (int32_t*)nullptr, (int32_t*)nullptr);
-    } else if (step_ok && wstep_empty) {   // second walk, every text: spans straight to their CSR place
-      MRX_WSTEP_LAUNCH(STEP_EMIT, dim3(wstep_grid(n)), dim3(64 * kWsWaves), wstep_lds(pk, wstep_mwalk, wstep_bm_big), s, pk, H_BLOB(h),
+    } else if (step_ok && rt.empty) {   // second walk, every text: spans straight to their CSR place
+      wstep_launch<STEP_EMIT>(rt, dim3(wstep_grid(n)), dim3(64 * kWsWaves), wstep_lds(pk, rt.mwalk, rt.bm_big), s, pk, H_BLOB(h),
                        lay2, n, (int32_t*)nullptr, d_prefix, d_spans, span_cap, (int32_t*)nullptr, (int32_t*)nullptr);
     } else if (step_ok) {
       if (lay2.wide_slots)
@@ -6099,12 +6045,12 @@ struct FindallJob {
                          d_slots, d_spans, span_cap);
       // wavefronts without an overflowing text leave at once
       if (req_wave)
-        MRX_REQWAVE_LAUNCH(STEP_EMIT, h, lay2, n, d_counts, d_prefix, d_spans, span_cap, s);
+        reqwave_launch<STEP_EMIT>(rt, h, lay2, n, d_counts, d_prefix, d_spans, span_cap, s);
       else {
-      MRX_WSTEP_LAUNCH(STEP_EMIT, dim3(wstep_grid(n)), dim3(64 * kWsWaves), wstep_lds(pk, wstep_mwalk, wstep_bm_big), s, pk, H_BLOB(h),
+      wstep_launch<STEP_EMIT>(rt, dim3(wstep_grid(n)), dim3(64 * kWsWaves), wstep_lds(pk, rt.mwalk, rt.bm_big), s, pk, H_BLOB(h),
                          lay2, n, d_counts, d_prefix, d_spans, span_cap, (int32_t*)nullptr,
                          (int32_t*)nullptr);
-      if (step_split > 0) MRX_REQWAVE_LAUNCH(STEP_EMIT, h, lay2, n, d_counts, d_prefix, d_spans, span_cap, s);
+      if (step_split > 0) reqwave_launch<STEP_EMIT>(rt, h, lay2, n, d_counts, d_prefix, d_spans, span_cap, s);
       }
     } else
   #define MRX_L(B) hipLaunchKernelGGL((k_findall<FA_EMIT, B>), dim3(grid_for(n, kBlock)), dim3(kBlock), lds_for(h), s, p, \
@@ -6161,16 +6107,6 @@ struct FindallJob {
       if (fused_err) return fail(MRX_E_NO_DEVICE, "internal: a wavefront gave up waiting for its predecessors' span counts");
       if (tot > span_cap) rc = fail(MRX_E_CAPACITY, "span buffer too small: need " + std::to_string(tot));
     }  // total == NULL: fully asynchronous; d_counts_prefix[n] holds the total when the stream drains
-    HIP_TRY(scratch_free(d_counts, s));
-    HIP_TRY(scratch_free(d_total, s));
-    if (d_ctrl) { HIP_TRY(scratch_free(d_ctrl, s)); HIP_TRY(scratch_free(d_ctrl, s)); }   // ctrl block and the argument copy
-    if (d_recs_alloc) HIP_TRY(scratch_free(d_recs_alloc, s));
-    else if (d_recs) HIP_TRY(scratch_free(d_recs, s));
-    if (d_nrecs) HIP_TRY(scratch_free(d_nrecs, s));
-    if (d_wbase) HIP_TRY(scratch_free(d_wbase, s));
-    if (d_slots) HIP_TRY(scratch_free(d_slots, s));
-    if (d_blimit) HIP_TRY(scratch_free(d_blimit, s));
-    if (d_rows) HIP_TRY(scratch_free(d_rows, s));
     return rc;
   }
 
@@ -6187,14 +6123,13 @@ struct FindallJob {
     // An event record counts the matches of its text in front of it in 26 bits (kRecBeforeMask), and a
     // text of 2^26 bytes can hold that many (one-byte matches, no synchronising byte to cut at): such
     // texts take the lane-per-text kernels, whose span cursor is 64 bits wide.
-    if (stream_ok && stream_text_too_long(lay.offsets ? csr_max : (lay.lens ? lay.stride : (int64_t)lay.len)))
+    if (stream_ok && stream_text_too_long(lay.offsets ? csr_max : lay.pitch_longest()))
       stream_ok = false;
     if (n > 0 && stream_ok)
       if (int rc = pieces_prepare(h, lay, n, s, &pc, csr_total, csr_max)) return rc;
     by_pieces = pc.on;
     if (pc.on) {
       if (int rc = findall_pieces(h, pc, n, d_prefix, d_spans, span_cap, d_total, s)) return rc;
-      if (int rc = pieces_release(&pc, s)) return rc;
     } else if (n > 0) {
       if (int rc = stream_ok ? stream_scan() : step_scan()) return rc;
       if (finished) return finished_rc;
@@ -6369,9 +6304,10 @@ int sub_from_spans(const mrx_handle* h, const Layout& lay, int64_t n, const std:
     h->sub_matches_per_kib.store(in_bytes >= 1024 ? nm / (in_bytes >> 10) : 0, std::memory_order_relaxed);
     if (nm <= cap) break;
     if (attempt == 1) return fail(MRX_E_NO_DEVICE, "sub: match count changed between two passes");
-    HIP_TRY(scratch_free(d_spans, s));
-    HIP_TRY(scratch_free(d_cum, s));
-    cap = nm;   // more matches than one per eight bytes: once more with room for all of them
+    // more matches than one per eight bytes: once more with room for all of them.  The second attempt's buffers lie
+    // behind the first's, which stay where they are until the call returns (a dense batch sizes its next call's
+    // first attempt by sub_matches_per_kib, so this is paid once).
+    cap = nm;
   }
   if (over) {
     rc = kSubsRetryGeneric;
@@ -6379,15 +6315,6 @@ int sub_from_spans(const mrx_handle* h, const Layout& lay, int64_t n, const std:
     if (total_bytes) *total_bytes = tot;
     if (tot > out_cap) rc = fail(MRX_E_CAPACITY, "output buffer too small: need " + std::to_string(tot));
   }
-  HIP_TRY(scratch_free(d_prefix, s));
-  HIP_TRY(scratch_free(d_spans, s));
-  HIP_TRY(scratch_free(d_rmap, s));
-  HIP_TRY(scratch_free(d_cum, s));
-  HIP_TRY(scratch_free(d_sizes, s));
-  HIP_TRY(scratch_free(d_total, s));
-  HIP_TRY(scratch_free(d_left, s));
-  HIP_TRY(scratch_free(d_go, s));
-  HIP_TRY(scratch_free(d_over, s));
   return rc;
 }
 }  // namespace
@@ -6829,9 +6756,7 @@ int sub_chain_from_spans(const mrx_handle* h, const Layout& lay, int64_t n, cons
     h->sub_matches_per_kib.store(in_bytes >= 1024 ? nm / (in_bytes >> 10) : 0, std::memory_order_relaxed);
     if (nm <= cap) break;
     if (attempt == 1) return fail(MRX_E_NO_DEVICE, "sub: match count changed between two passes");
-    HIP_TRY(scratch_free(d_spans, s));
-    HIP_TRY(scratch_free(d_dcum, s));
-    cap = nm;
+    cap = nm;   // (as in sub_from_spans(): the second attempt's buffers lie behind the first's)
   }
   if (longest > 4096) {
     rc = kSubsRetryGeneric;
@@ -6850,13 +6775,6 @@ int sub_chain_from_spans(const mrx_handle* h, const Layout& lay, int64_t n, cons
       g_last_kernel = "k_subc_emit";
     }
   }
-  HIP_TRY(scratch_free(d_prefix, s));
-  HIP_TRY(scratch_free(d_sizes, s));
-  HIP_TRY(scratch_free(d_total, s));
-  HIP_TRY(scratch_free(d_mask, s));
-  HIP_TRY(scratch_free(d_repl, s));
-  HIP_TRY(scratch_free(d_spans, s));
-  HIP_TRY(scratch_free(d_dcum, s));
   return rc;
 }
 }  // namespace
@@ -6980,13 +6898,8 @@ static int run_search_any(const mrx_handle* h, const Layout& lay, int64_t n, int
     HIP_TRY(scratch_alloc((void**)&vstart, sizeof(int64_t) * (n + 1), s));
     HIP_TRY(scratch_alloc((void**)&vlen, sizeof(int32_t) * n, s));
     HIP_TRY(scratch_alloc((void**)&vskip, sizeof(uint32_t) * n, s));
-    {
-      const int64_t nw = (n + 63) / 64;
-      int64_t g = (nw + kWsWaves - 1) / kWsWaves;
-      if (g > grid_cap()) g = grid_cap();
-      hipLaunchKernelGGL(k_litscan<false>, dim3((unsigned)g), dim3(64 * kWsWaves), 0, s, H_BLOB(h) + p.off_pre, p.pre_len, H_BLOB(h), lay, n,
-                         d_cand, (int2*)nullptr);
-    }
+    hipLaunchKernelGGL(k_litscan<false>, dim3(wstep_grid(n)), dim3(64 * kWsWaves), 0, s, H_BLOB(h) + p.off_pre, p.pre_len, H_BLOB(h), lay, n,
+                       d_cand, (int2*)nullptr);
     hipLaunchKernelGGL(k_view_build, dim3(grid_for(n + 1, kBlock)), dim3(kBlock), 0, s, lay, n, 0, d_cand, vstart, vlen, vskip, 0);
     HIP_TRY(hipGetLastError());
     Layout view{csr(lay.data, vstart)};
@@ -7018,9 +6931,8 @@ static int run_search_any(const mrx_handle* h, const Layout& lay, int64_t n, int
     hipLaunchKernelGGL(k_virt_first, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, s, n, pc.vfirst, d_vs, d_vs + pc.nv,
                        pc.vbase, ds, de);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(scratch_free(d_vs, s));
     g_last_kernel = "k_stream_search_pieces";
-    return pieces_release(&pc, s);
+    return MRX_OK;
   }
   ScanTimer tm(s);
   if (dyn_ok(h, lay, n)) {
@@ -7049,7 +6961,7 @@ static int run_first_any(const mrx_handle* h, const Layout& lay, int64_t n, int3
   hipStream_t s = (hipStream_t)st;
   // a single class run on long texts of a fixed-pitch batch: a wavefront per text (k_first_run)
   if (p.off_fa_run >= 0 && !lay.offsets && !lay.vlen && g_long_text_mode != 2 &&
-      (g_long_text_mode == 1 || g_long_text_mode == 3 || ((lay.lens ? lay.stride : (int64_t)lay.len) >= 2048 && n <= 131072))) {
+      (g_long_text_mode == 1 || g_long_text_mode == 3 || (lay.pitch_longest() >= 2048 && n <= 131072))) {
     ScanTimer tm(s);
     hipLaunchKernelGGL(k_first_run, dim3(grid_for(n * 64, kBlock)), dim3(kBlock), 0, s, p, H_BLOB(h), lay, n, ds, de);
     g_last_kernel = "k_first_run";
@@ -7118,7 +7030,6 @@ static int run_is_match_any(const mrx_handle* h, const Layout& lay, int64_t n, u
       hipLaunchKernelGGL(k_span_to_flag, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, s, n, tmp, f);
       HIP_TRY(hipGetLastError());
     }
-    HIP_TRY(scratch_free(tmp, s));
     return rc;
   }
   return run_match<OP_IS_MATCH>(h, lay, n, nullptr, nullptr, f, st);
@@ -7199,9 +7110,6 @@ static int run_at(int op, const mrx_handle* h, const Layout& lay, int64_t n, int
     hipLaunchKernelGGL(k_view_fix, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, s, lay, n, start, d_starts, rules, ds, de, flag);
     HIP_TRY(hipGetLastError());
   }
-  HIP_TRY(scratch_free(vstart, s));
-  HIP_TRY(scratch_free(vlen, s));
-  HIP_TRY(scratch_free(vskip, s));
   return rc;
 }
 int mrx_match_first_at_dev(const mrx_handle* h, const uint8_t* d, const int64_t* off, int64_t n, int32_t start,
@@ -7261,7 +7169,6 @@ static int run_captures_any(const mrx_handle* h, const Layout& lay, int64_t n, i
                        tmp + n, spans);
     HIP_TRY(hipGetLastError());
   }
-  HIP_TRY(scratch_free(tmp, s));
   return rc;
 }
 int mrx_captures_dev(const mrx_handle* h, const uint8_t* d, const int64_t* off, int64_t n,
@@ -7431,8 +7338,6 @@ static int run_count_any(const mrx_handle* h, const Layout& lay, int64_t n, int3
       launch_stream<ST_COUNT>(h, pc.lay, pc.nv, d_vcounts, nullptr, nullptr, 0, nullptr, nullptr, s, pc.vlen, pc.vskip);
       hipLaunchKernelGGL(k_virt_sum, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, s, n, pc.vfirst, d_vcounts, counts);
       HIP_TRY(hipGetLastError());
-      HIP_TRY(scratch_free(d_vcounts, s));
-      if (int rc = pieces_release(&pc, s)) return rc;
       g_last_kernel = "k_stream_count_pieces";
     } else if (dyn_ok(h, lay, n)) {
       launch_stream_dyn<ST_COUNT>(h, lay, n, counts, nullptr, nullptr, nullptr, nullptr, s, false);
@@ -7442,13 +7347,14 @@ static int run_count_any(const mrx_handle* h, const Layout& lay, int64_t n, int3
     g_last_kernel = "k_stream_count";
     }
   } else {
-    const bool use_req_route = (h->hp.dev.flags & PF_STEP_REQ) != 0;
-    const bool wstep_bits = (h->hp.dev.flags & PF_BSTEP) != 0;
-    const bool wstep_lz = (h->hp.dev.flags & PF_LAZY_END) != 0;
+    StepRoute rt;   // (count never takes k_mwalk's packed-start form: it keeps no start registers)
+    rt.req = (h->hp.dev.flags & PF_STEP_REQ) != 0;
+    rt.bits = (h->hp.dev.flags & PF_BSTEP) != 0;
+    rt.lz = (h->hp.dev.flags & PF_LAZY_END) != 0;
     const bool mw_empty = (h->hp.dev.flags & PF_MW_EMPTY) != 0 && mwalk_enabled() && g_force_generic < 2;
-    const bool wstep_empty = (h->hp.dev.flags & PF_STEP_EMPTY) != 0 && g_force_generic < 2 && !mw_empty;
-    const bool mwalk_req = use_req_route && (h->hp.dev.flags & PF_MWALK_REQ) && mwalk_enabled();
-    bool mw_tries = mw_tries_on(h->hp.dev) && !use_req_route && g_force_generic < 2;
+    rt.empty = (h->hp.dev.flags & PF_STEP_EMPTY) != 0 && g_force_generic < 2 && !mw_empty;
+    const bool mwalk_req = rt.req && (h->hp.dev.flags & PF_MWALK_REQ) && mwalk_enabled();
+    bool mw_tries = mw_tries_on(h->hp.dev) && !rt.req && g_force_generic < 2;
     if (t_in_pieces && t_piece_tries >= 0) mw_tries = mw_tries && t_piece_tries == 1;
     int cnt_slot = -1;
     const uint32_t cnt_key = FindallJob::tries_tune_key(lay, n) | (1u << 29);   // (count's own measurement)
@@ -7458,23 +7364,25 @@ static int run_count_any(const mrx_handle* h, const Layout& lay, int64_t n, int3
       const mrx_handle* h; uint32_t key; int slot; hipStream_t s;
       ~CountTuneEnd() { ab_tuner_end(h, key, slot, s); }
     } cnt_tune_end{h, cnt_key, cnt_slot, s};
-    const bool wstep_mwalk = (mwalk_req || (mwalk_on(h->hp.dev) && !use_req_route) || mw_empty || mw_tries) && !wstep_bits && !wstep_empty;
+    rt.mwalk = (mwalk_req || (mwalk_on(h->hp.dev) && !rt.req) || mw_empty || mw_tries) && !rt.bits && !rt.empty;
     const DevPlan pk = mwalk_req ? mwalk_req_plan(h->hp.dev) : h->hp.dev;
-    const int wstep_mwalk_k = pk.mw_k;
-    const bool wstep_mwalk_pk = false;   // (count keeps no start registers)
+    rt.mwalk_k = pk.mw_k;
     bool req_wave = false;
     int split = 0;
-    if (g_force_generic < 2 && !wstep_bits && !t_in_pieces && (h->hp.dev.flags & (PF_STEPPABLE | PF_STEP_REQ)) &&
+    if (g_force_generic < 2 && !rt.bits && !t_in_pieces && (h->hp.dev.flags & (PF_STEPPABLE | PF_STEP_REQ)) &&
         !(h->hp.dev.flags & (PF_STEP_BIG | PF_STREAMABLE)) && h->hp.dev.st_nsync > 0 &&
-        (!use_req_route || g_long_text_mode == 1)) {
+        (!rt.req || g_long_text_mode == 1)) {
       // long texts: disjoint pieces between synchronising bytes, one lane each (see run_findall)
       Pieces spc;
-      if (int rc = pieces_prepare(h, lay, n, s, &spc, known_total, known_max, /*disjoint=*/true, wstep_mwalk)) return rc;
-      if (spc.on && !wstep_mwalk) {
+      const ScratchMark before_pieces = scratch_mark(s);
+      if (int rc = pieces_prepare(h, lay, n, s, &spc, known_total, known_max, /*disjoint=*/true, rt.mwalk)) return rc;
+      if (spc.on && !rt.mwalk) {
         bool dense = true;
         if (int rc = dense_candidates(h, lay, n, s, &dense)) return rc;
-        if (!dense)
-          if (int rc = pieces_release(&spc, s)) return rc;
+        if (!dense) {   // the wavefront kernel after all: on the pieces' bytes
+          spc.on = false;
+          scratch_reuse_from(s, before_pieces);
+        }
       }
       if (spc.on) {
         int32_t* d_vcounts = nullptr;
@@ -7487,39 +7395,38 @@ static int run_count_any(const mrx_handle* h, const Layout& lay, int64_t n, int3
         if (rc != MRX_OK) return rc;
         hipLaunchKernelGGL(k_virt_sum, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, s, n, spc.vfirst, d_vcounts, counts);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(scratch_free(d_vcounts, s));
-        return pieces_release(&spc, s);
+        return MRX_OK;
       }
     }
-    if (g_force_generic < 2 && !wstep_bits && !wstep_lz && !mw_tries && !t_in_pieces && (h->hp.dev.flags & (PF_STEPPABLE | PF_STEP_REQ)))
-      if (int rc = req_wave_pays(lay, n, use_req_route, s, &req_wave, (h->hp.dev.flags & PF_STEP_BIG) ? nullptr : &split,
-                                 (h->hp.dev.flags & PF_STEP_BIG) != 0, wstep_mwalk, backset_on(h->hp.dev) && !wstep_mwalk))
+    if (g_force_generic < 2 && !rt.bits && !rt.lz && !mw_tries && !t_in_pieces && (h->hp.dev.flags & (PF_STEPPABLE | PF_STEP_REQ)))
+      if (int rc = req_wave_pays(lay, n, rt.req, s, &req_wave, (h->hp.dev.flags & PF_STEP_BIG) ? nullptr : &split,
+                                 (h->hp.dev.flags & PF_STEP_BIG) != 0, rt.mwalk, backset_on(h->hp.dev) && !rt.mwalk))
         return rc;
     Layout lay2 = lay;
     lay2.split = split;
     int32_t* d_blimit = nullptr;
-    const bool wstep_bm = backset_on(h->hp.dev) && !wstep_mwalk && !wstep_bits && !wstep_empty && !use_req_route && !req_wave &&
+    rt.bm = backset_on(h->hp.dev) && !rt.mwalk && !rt.bits && !rt.empty && !rt.req && !req_wave &&
                           split == 0 && (h->hp.dev.flags & PF_STEPPABLE);
-    const bool wstep_bm_big = wstep_bm && (h->hp.dev.flags & PF_STEP_BIG) != 0;
-    if (wstep_bm)
+    rt.bm_big = rt.bm && (h->hp.dev.flags & PF_STEP_BIG) != 0;
+    if (rt.bm)
       if (int rc = backscan_marks(h, lay, n, s, &lay2)) return rc;
-    const bool bits_fixed = wstep_bits && bits_fixed_on(h->hp.dev);
-    if (g_force_generic < 2 && !bits_fixed && !wstep_mwalk && !wstep_bm && (wstep_bits || (!req_wave && split == 0 && !use_req_route && union_pass_for_table_plan(h->hp.dev, false))))
+    const bool bits_fixed = rt.bits && bits_fixed_on(h->hp.dev);
+    if (g_force_generic < 2 && !bits_fixed && !rt.mwalk && !rt.bm && (rt.bits || (!req_wave && split == 0 && !rt.req && union_pass_for_table_plan(h->hp.dev, false))))
       if (int rc = bscan_limits(h, lay, n, 0, s, &lay2, &d_blimit)) return rc;   // union automaton first
-    const bool big_lane = (h->hp.dev.flags & PF_STEP_BIG) && !req_wave && !wstep_mwalk && !wstep_bm;   // -> literal restatement
+    const bool big_lane = (h->hp.dev.flags & PF_STEP_BIG) && !req_wave && !rt.mwalk && !rt.bm;   // -> literal restatement
     if (bits_fixed) {
       if (int rc = bscan_fixed(h, lay, n, 2, s, counts, nullptr, nullptr, 0)) return rc;
       g_last_kernel = "k_bscan_fixed";
     } else if (req_wave) {
-      MRX_REQWAVE_LAUNCH(STEP_COUNT, h, lay, n, counts, (const int64_t*)nullptr, (int32_t*)nullptr, (int64_t)0, s);
+      reqwave_launch<STEP_COUNT>(rt, h, lay, n, counts, (const int64_t*)nullptr, (int32_t*)nullptr, (int64_t)0, s);
       g_last_kernel = "k_req_wave";
-    } else if (g_force_generic < 2 && !big_lane && ((h->hp.dev.flags & (PF_STEPPABLE | PF_STEP_REQ | PF_STEP_EMPTY)) || wstep_mwalk)) {
-      MRX_WSTEP_LAUNCH(STEP_COUNT, dim3(wstep_grid(n)), dim3(64 * kWsWaves), wstep_lds(pk, wstep_mwalk, wstep_bm_big), s, pk,
+    } else if (g_force_generic < 2 && !big_lane && ((h->hp.dev.flags & (PF_STEPPABLE | PF_STEP_REQ | PF_STEP_EMPTY)) || rt.mwalk)) {
+      wstep_launch<STEP_COUNT>(rt, dim3(wstep_grid(n)), dim3(64 * kWsWaves), wstep_lds(pk, rt.mwalk, rt.bm_big), s, pk,
                          H_BLOB(h), lay2, n, counts, (const int64_t*)nullptr, (int32_t*)nullptr, (int64_t)0,
                          (int32_t*)nullptr, (int32_t*)nullptr);
-      g_last_kernel = wstep_mwalk ? "k_mwalk" : wstep_bm ? "k_backscan+k_step_count" : wstep_bits ? "k_bstep_count" : wstep_empty ? "k_estep_count" : "k_step_count";
+      g_last_kernel = rt.mwalk ? "k_mwalk" : rt.bm ? "k_backscan+k_step_count" : rt.bits ? "k_bstep_count" : rt.empty ? "k_estep_count" : "k_step_count";
       if (split > 0) {
-        MRX_REQWAVE_LAUNCH(STEP_COUNT, h, lay2, n, counts, (const int64_t*)nullptr, (int32_t*)nullptr, (int64_t)0, s);
+        reqwave_launch<STEP_COUNT>(rt, h, lay2, n, counts, (const int64_t*)nullptr, (int32_t*)nullptr, (int64_t)0, s);
         g_last_kernel = "k_step_count+k_req_wave";
       }
     } else {
@@ -7620,6 +7527,9 @@ static int sub_any(const mrx_handle* h, const char* repl, size_t repl_len, int64
   if (int rc = check_lds(h)) return rc;
   if (int rc = ensure_device(h)) return rc;
   hipStream_t s = (hipStream_t)st;
+  // a spans route that hands the call back (kSubsRetryGeneric) has enqueued its work; the lane-per-text form below
+  // runs behind it on the same stream and takes over its bytes (not behind mrx_sub_strided_dev's offsets: they stay)
+  const ScratchMark before_spans = scratch_mark(s);
   // \1..\9 on a deterministic chain whose matches are the table walk's: spans of the plain search, groups from the
   // leaves' runs (k_subc_sizes / k_subc_emit); batches with a text or an output beyond the tiles stay the interpreter's
   if (general_groups && h->hp.chain.ok && !g_force_generic && n > 0 && off && count >= 0 &&
@@ -7627,6 +7537,7 @@ static int sub_any(const mrx_handle* h, const char* repl, size_t repl_len, int64
     const int rc = sub_chain_from_spans(h, csr(d, off), n, r, tpl, count, out_off, out, out_cap,
                                         total_bytes, s, known_bytes, known_max);
     if (rc != kSubsRetryGeneric) return rc;
+    scratch_reuse_from(s, before_spans);
   }
   // sub() iterates match_next from the previous match end; on the plain route that is exactly the
   // findall sequence, so the spans of the streaming kernel or of the windowed stepper serve it.
@@ -7662,6 +7573,7 @@ static int sub_any(const mrx_handle* h, const char* repl, size_t repl_len, int64
       const int rc = sub_from_spans(h, csr(d, off), n, rmap, count, out_off, out, out_cap,
                                     total_bytes, s, group_reach, known_bytes, known_max);
       if (rc != kSubsRetryGeneric) return rc;   // else: a group reaches behind its text, the lane-per-text form cuts it
+      scratch_reuse_from(s, before_spans);
     }
   }
   uint8_t* d_repl = nullptr;
@@ -7707,10 +7619,6 @@ static int sub_any(const mrx_handle* h, const char* repl, size_t repl_len, int64
 #undef MRX_L
     HIP_TRY(hipGetLastError());
   }
-  HIP_TRY(scratch_free(d_repl, s));
-  HIP_TRY(scratch_free(d_tpl, s));
-  HIP_TRY(scratch_free(d_sizes, s));
-  HIP_TRY(scratch_free(d_total, s));
   return rc;
 }
 
@@ -7960,15 +7868,9 @@ static int capall_from_spans(const mrx_handle* h, const Layout& lay, int64_t n, 
     h->sub_matches_per_kib.store(in_bytes >= 1024 ? h2[1] / (in_bytes >> 10) : 0, std::memory_order_relaxed);
     if (h2[1] <= cap) break;
     if (attempt == 1) return fail(MRX_E_NO_DEVICE, "captures_all: match count changed between two passes");
-    HIP_TRY(scratch_free(d_spans, s));
-    cap = h2[1];   // more matches than the first guess: once more with room for all of them
+    cap = h2[1];   // more matches than the first guess: once more with room for all of them (behind the first attempt's)
   }
   *total = h2[0];
-  HIP_TRY(scratch_free(d_fprefix, s));
-  HIP_TRY(scratch_free(d_spans, s));
-  HIP_TRY(scratch_free(d_counts, s));
-  HIP_TRY(scratch_free(d_tot2, s));
-  if (d_mask) HIP_TRY(scratch_free(d_mask, s));
   if (h2[0] > match_cap) return fail(MRX_E_CAPACITY, "group rows buffer too small: need " + std::to_string(h2[0]));
   return MRX_OK;
 }
@@ -8055,8 +7957,6 @@ static int captures_all_any(const mrx_handle* h, int64_t count, const Layout& la
   HIP_TRY(hipMemcpyAsync(&tot, d_total, sizeof tot, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
   *total = tot;
-  HIP_TRY(scratch_free(d_counts, s));
-  HIP_TRY(scratch_free(d_total, s));
   if (tot > match_cap) return fail(MRX_E_CAPACITY, "group rows buffer too small: need " + std::to_string(tot));
   return MRX_OK;
 }
@@ -8225,6 +8125,7 @@ void mrx_debug_litscan_pieces(int mode) { g_litscan_pieces = (mode == 0 || mode 
 void mrx_debug_multiwalk(int mode) { g_mwalk_mode = mode == 2 ? 2 : 0; g_mwalk_pk = mode == 3 ? 0 : 1; }
 void mrx_release_scratch(void) { scratch_release_all(); }
 size_t mrx_debug_scratch_bytes(void) { return scratch_bytes_reserved(); }
+size_t mrx_debug_scratch_in_use(void) { return scratch_bytes_in_use(); }
 
 }  // extern "C"
 
@@ -8242,10 +8143,8 @@ void set_last_kernel(const char* name) { g_last_kernel = name; }
 void scratch_scope_enter(void* st) { ++scratch_arena((hipStream_t)st).depth; }
 void scratch_scope_leave(void* st) {
   ScratchArena& a = scratch_arena((hipStream_t)st);
-  if (--a.depth == 0 && a.live != 0) {
-    a.live = 0;
+  if (--a.depth == 0)
     for (auto& c : a.chunks) c.used = 0;
-  }
 }
 void* scratch_get(size_t bytes, void* st) {
   void* p = nullptr;
@@ -8254,13 +8153,11 @@ void* scratch_get(size_t bytes, void* st) {
 ScratchMark scratch_mark(void* st) {
   ScratchArena& a = scratch_arena((hipStream_t)st);
   ScratchMark m;
-  m.live = a.live;
   for (auto& c : a.chunks) m.used.push_back(c.used);
   return m;
 }
 void scratch_rewind(void* st, const ScratchMark& m) {
   ScratchArena& a = scratch_arena((hipStream_t)st);
-  a.live = m.live;
   for (size_t c = 0; c < a.chunks.size(); ++c) a.chunks[c].used = c < m.used.size() ? m.used[c] : 0;
 }
 int batch_bounds(const int64_t* d_offsets, int64_t n, void* st, int64_t* total, int64_t* max_len) {
