@@ -453,7 +453,84 @@ int mrx_set_filter_strided_dev(const mrx_set* s, uint32_t flags, const uint8_t* 
                                int64_t* d_out_offsets, uint8_t* d_out_data, int64_t out_cap, int64_t* d_totals,
                                int64_t* totals, void* stream);
 
+/* ---- extract: the bytes under spans as a new packed batch on the device ----
+ * The primitive, mrx_gather_spans_*, needs no pattern: it takes the spans that findall, split, captures_all or a set's
+ * findall left on the device and copies the bytes they name, piece after piece, into one buffer.
+ *   d_prefix int64[n + 1]             CSR over the texts: text i owns the rows [d_prefix[i], d_prefix[i + 1])
+ *   d_spans int32[rows][row_pairs][2] the rows, 8-byte aligned.  row_pairs = 1 for findall / split / a set's findall,
+ *                                     g + 1 for captures_all; `pair` (0 <= pair < row_pairs) is the pair of each row
+ *                                     that is gathered (captures_all: group j is pair j - 1, the whole match pair g)
+ *   piece_cap                         capacity, in pieces, of d_owner and d_out_offsets
+ * pieces = d_prefix[n], read on the device.  Piece r belongs to the text i with d_prefix[i] <= r < d_prefix[i + 1].
+ * With (s, e) its pair and L the text's length, the piece is text[s' .. e') with s' = min(max(s, 0), L) and
+ * e' = min(max(e, s'), L): a group without an entry, (-1, -1), and a reversed range give an empty piece; a fixed-width
+ * group that reaches behind its text (x(\d)? on "x") is cut at the text's end.  An empty piece adds no byte and its
+ * offset repeats.  Overlapping spans (findall of a self-overlapping exact literal) are each copied in full, so the
+ * output may hold more bytes than the input.  Outputs, all on the device, pieces in row order:
+ *   d_owner int64[piece_cap]            [0, pieces): the text index of each piece
+ *   d_out_offsets int64[piece_cap + 1]  [0, pieces]: the CSR of the output batch; d_out_offsets[pieces] = bytes
+ *   d_out_data uint8[out_cap]           the pieces back to back; any alignment
+ *   d_totals int64[2]                   {pieces, bytes}
+ * Entries of d_owner and d_out_offsets past those are unspecified.  The output is a CSR batch and the input of a
+ * following call as it stands (with bytes and the input's longest text as its known bounds).
+ * No byte of d_out_data at or past bytes, nor at or past out_cap, is ever written, and no element of d_owner at or past
+ * piece_cap, nor of d_out_offsets at or past piece_cap + 1.
+ * Capacity.  pieces > piece_cap: nothing is written to d_out_data, d_owner and d_out_offsets hold nothing of use,
+ * d_totals[0] is the need and d_totals[1] only a lower bound (as *total of mrx_split_dev under a limit; here 0, the
+ * spans are not read).  pieces <= piece_cap and bytes > out_cap: d_owner, d_out_offsets and both totals are complete and
+ * exact, and NO output byte is written.  A call with `totals` returns MRX_E_CAPACITY in either case, totals filled
+ * for a retry (grow the pieces first, then the bytes: two retries at most).
+ * totals (host, int64[2], may be NULL) receives d_totals: the call then reads back once, at its end -- no host
+ * decision sits between its kernels.  With totals == NULL nothing is read back and the call returns without
+ * synchronising: the kernels decide on the device from d_totals, as filter's gather does, and the caller checks
+ * d_totals against its capacities once the stream has drained.
+ * n == 0 or pieces == 0: totals {0, 0}, d_out_offsets = {0}.
+ * MRX_E_ARGUMENT, before anything is enqueued: negative n, piece_cap or out_cap; row_pairs < 1 or pair out of range; a
+ * misaligned d_spans; a bad pitch; a null required pointer (d_offsets, d_prefix, d_out_offsets, d_totals; d_spans and
+ * d_owner when piece_cap > 0; d_out_data when out_cap > 0).
+ * Reads: as filter, a piece's bytes are fetched as the aligned 16-byte words that hold them, so up to 15 bytes in
+ * front of a piece's first byte and behind its last one are read (never used); no word is read for an empty piece.
+ * Scratch: 16 bytes per piece of capacity (piece_cap, not pieces: the sizes are scanned over the host-known
+ * capacity) and the scan's block sums, returned to the arena when the call returns. */
+int mrx_gather_spans_dev(const uint8_t* d_data, const int64_t* d_offsets, int64_t n, const int64_t* d_prefix,
+                         const int32_t* d_spans, int32_t row_pairs, int32_t pair, int64_t piece_cap, int64_t* d_owner,
+                         int64_t* d_out_offsets, uint8_t* d_out_data, int64_t out_cap, int64_t* d_totals, int64_t* totals,
+                         void* stream);
+int mrx_gather_spans_strided_dev(const uint8_t* d_data, int64_t stride, const int32_t* d_lens, int32_t len, int64_t n,
+                                 const int64_t* d_prefix, const int32_t* d_spans, int32_t row_pairs, int32_t pair,
+                                 int64_t piece_cap, int64_t* d_owner, int64_t* d_out_offsets, uint8_t* d_out_data,
+                                 int64_t out_cap, int64_t* d_totals, int64_t* totals, void* stream);
+/* extract: findall's matches as bytes, in one call (re.findall's strings; the reference's Match.get_match_text() per
+ * match).  d_piece_prefix int64[n + 1] receives findall's CSR (d_counts_prefix of mrx_findall_dev); the other outputs
+ * and both capacities are the primitive's, and the pieces are exactly the bytes under mrx_findall_dev's spans, in its
+ * order -- the empty matches of z* and the overlapping occurrences of an exact literal included.  The spans themselves
+ * live in scratch (8 more bytes per piece of capacity: a result that fits has at most piece_cap spans).
+ * mrx_extract_dev on a CSR batch pays findall's one read-back of the batch's bounds before its scan can be enqueued;
+ * the _known and _strided forms with totals == NULL enqueue and return.  Null handle: MRX_E_ARGUMENT.  A pattern whose
+ * findall is refused is refused here, MRX_E_UNSUPPORTED with the same text, before anything is enqueued. */
+int mrx_extract_dev(const mrx_handle* h, const uint8_t* d_data, const int64_t* d_offsets, int64_t n,
+                    int64_t* d_piece_prefix, int64_t* d_owner, int64_t* d_out_offsets, int64_t piece_cap,
+                    uint8_t* d_out_data, int64_t out_cap, int64_t* d_totals, int64_t* totals, void* stream);
+int mrx_extract_known_dev(const mrx_handle* h, const uint8_t* d_data, const int64_t* d_offsets, int64_t n,
+                          int64_t end_offset, int64_t max_text_len, int64_t* d_piece_prefix, int64_t* d_owner,
+                          int64_t* d_out_offsets, int64_t piece_cap, uint8_t* d_out_data, int64_t out_cap,
+                          int64_t* d_totals, int64_t* totals, void* stream);
+int mrx_extract_strided_dev(const mrx_handle* h, const uint8_t* d_data, int64_t stride, const int32_t* d_lens, int32_t len,
+                            int64_t n, int64_t* d_piece_prefix, int64_t* d_owner, int64_t* d_out_offsets,
+                            int64_t piece_cap, uint8_t* d_out_data, int64_t out_cap, int64_t* d_totals, int64_t* totals,
+                            void* stream);
+
 /* ---- host-buffer convenience wrappers (copy in, run, copy out) -------------- */
+/* mrx_gather_spans_dev / mrx_extract_dev on host buffers: owner int64[piece_cap], out_offsets int64[piece_cap + 1],
+ * out_data uint8[out_cap], totals int64[2] = {pieces, bytes} (may be NULL); spans holds prefix[n] rows.  piece_prefix
+ * (extract) is always copied out, owner[0, pieces) and out_offsets[0, pieces] when the pieces fit, out_data only when
+ * the bytes fit too (MRX_E_CAPACITY otherwise). */
+int mrx_gather_spans_batch(const uint8_t* data, const int64_t* offsets, int64_t n, const int64_t* prefix,
+                           const int32_t* spans, int32_t row_pairs, int32_t pair, int64_t piece_cap, int64_t* owner,
+                           int64_t* out_offsets, uint8_t* out_data, int64_t out_cap, int64_t* totals);
+int mrx_extract_batch(const mrx_handle* h, const uint8_t* data, const int64_t* offsets, int64_t n, int64_t* piece_prefix,
+                      int64_t* owner, int64_t* out_offsets, int64_t piece_cap, uint8_t* out_data, int64_t out_cap,
+                      int64_t* totals);
 /* mrx_filter_dev / mrx_set_filter_dev on host buffers: kept_idx int64[n], out_offsets int64[n + 1], out_data
  * uint8[out_cap], totals int64[2] = {kept, bytes} (may be NULL).  kept_idx[0, kept) and out_offsets[0, kept] are
  * copied out, out_data only when all of it fits (MRX_E_CAPACITY otherwise). */

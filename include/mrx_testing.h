@@ -110,6 +110,11 @@ int mrx_testing_set_run(const struct mrx_set* s, int op, const uint8_t* text, in
  * output block, otherwise: profiles/filter.md), 1 = the block form always, 16 = the text form always.  Results are
  * the same. */
 void mrx_debug_filter_form(int form);
+/* Extract (include/mrx.h): the byte mover reports itself as "k_extract_gather" through mrx_last_kernel_name().  Its grid
+ * is sized by out_cap, a wavefront per 1 KiB at least; `workgroups` > 0 caps it (4 wavefronts each), so that a test makes
+ * one wavefront run several rounds of 64 blocks without an output of many megabytes.  0 (default) = no cap.  Results are
+ * the same. */
+void mrx_debug_extract_grid(int workgroups);
 /* Bytes of device memory the calling thread's scratch arenas hold (see mrx_release_scratch). */
 size_t mrx_debug_scratch_bytes(void);
 /* ... and how many of them are handed out and not yet rewound.  Scratch belongs to the call's scope, so between calls

@@ -21,6 +21,9 @@ argument meaning, a *batch* of texts instead of one text:
     (none: k sub() calls in a row)                PatternSet.sub(repls, texts): k patterns' hits, one call
     CompiledRegex.test(text), per text :1091      filter_texts / CompiledRegex.filter / PatternSet.filter:
                                                   the matching texts as a new packed batch
+    Match.get_match_text(), per match             findall_texts / CompiledRegex.extract / split_batch /
+                                                  PatternSet.extract / DeviceBatch.gather_spans: the matched
+                                                  bytes as a new packed batch
 
 All matching runs in the HIP kernels of libmrx_hip.so.  There is no CPU
 fallback: if the library is missing or no GPU is usable, calls raise.
@@ -40,6 +43,7 @@ from .api import (  # noqa: F401
     compile_set,
     filter_texts,
     findall,
+    findall_texts,
     library_path,
     load_library,
     match_first,

@@ -198,6 +198,23 @@ def load_library():
                                                  u8p, C.c_int64, i64p, C.c_void_p, C.c_void_p]),
         "mrx_set_filter_batch": (C.c_int, [H, C.c_uint32, u8p, i64p, C.c_int64, i64p, i64p, u8p, C.c_int64, C.c_void_p]),
         "mrx_debug_filter_form": (None, [C.c_int]),
+        # extract: the batch | (prefix, spans, row_pairs, pair, piece_cap, owner, out_offsets, out_data, out_cap, d_totals,
+        # totals, stream); with a handle (handle) | the batch | (piece_prefix, owner, out_offsets, piece_cap, out_data, ...)
+        "mrx_gather_spans_dev": (C.c_int, [u8p, i64p, C.c_int64, i64p, i32p, C.c_int32, C.c_int32, C.c_int64, i64p, i64p,
+                                           u8p, C.c_int64, i64p, C.c_void_p, C.c_void_p]),
+        "mrx_gather_spans_strided_dev": (C.c_int, [u8p, C.c_int64, i32p, C.c_int32, C.c_int64, i64p, i32p, C.c_int32,
+                                                   C.c_int32, C.c_int64, i64p, i64p, u8p, C.c_int64, i64p, C.c_void_p,
+                                                   C.c_void_p]),
+        "mrx_gather_spans_batch": (C.c_int, [u8p, i64p, C.c_int64, i64p, i32p, C.c_int32, C.c_int32, C.c_int64, i64p, i64p,
+                                             u8p, C.c_int64, C.c_void_p]),
+        "mrx_extract_dev": (C.c_int, [H, u8p, i64p, C.c_int64, i64p, i64p, i64p, C.c_int64, u8p, C.c_int64, i64p,
+                                      C.c_void_p, C.c_void_p]),
+        "mrx_extract_known_dev": (C.c_int, [H, u8p, i64p, C.c_int64, C.c_int64, C.c_int64, i64p, i64p, i64p, C.c_int64, u8p,
+                                            C.c_int64, i64p, C.c_void_p, C.c_void_p]),
+        "mrx_extract_strided_dev": (C.c_int, [H, u8p, C.c_int64, i32p, C.c_int32, C.c_int64, i64p, i64p, i64p, C.c_int64,
+                                              u8p, C.c_int64, i64p, C.c_void_p, C.c_void_p]),
+        "mrx_extract_batch": (C.c_int, [H, u8p, i64p, C.c_int64, i64p, i64p, i64p, C.c_int64, u8p, C.c_int64, C.c_void_p]),
+        "mrx_debug_extract_grid": (None, [C.c_int]),
         "mrx_debug_set_route": (None, [C.c_int]),
         "mrx_testing_set_run": (C.c_int, [H, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_int32)]),
     }
@@ -227,6 +244,8 @@ EXPORTED_SYMBOLS = [
     "mrx_set_findall_batch", "mrx_set_sub_dev", "mrx_set_sub_known_dev", "mrx_set_sub_strided_dev", "mrx_set_sub_batch",
     "mrx_filter_dev", "mrx_filter_known_dev", "mrx_filter_strided_dev", "mrx_filter_batch",
     "mrx_set_filter_dev", "mrx_set_filter_known_dev", "mrx_set_filter_strided_dev", "mrx_set_filter_batch",
+    "mrx_gather_spans_dev", "mrx_gather_spans_strided_dev", "mrx_gather_spans_batch",
+    "mrx_extract_dev", "mrx_extract_known_dev", "mrx_extract_strided_dev", "mrx_extract_batch",
 ]
 TESTING_SYMBOLS = [
     "mrx_timing_reset", "mrx_timing_enable", "mrx_timing_scan_ms", "mrx_last_kernel_name",
@@ -234,7 +253,7 @@ TESTING_SYMBOLS = [
     "mrx_debug_scratch_in_use",
     "mrx_debug_fused_findall", "mrx_debug_stream_bits", "mrx_debug_stream_bits_trace", "mrx_debug_dynamic_texts", "mrx_debug_subs_group",
     "mrx_debug_split_findall", "mrx_debug_dense_rows", "mrx_debug_tries_always", "mrx_debug_chain_sub_general", "mrx_testing_emptywalk_findall", "mrx_debug_litscan_pieces", "mrx_debug_multiwalk", "mrx_debug_rec_skew", "mrx_testing_comm_shift", "mrx_testing_comm_compact",
-    "mrx_debug_set_route", "mrx_testing_set_run", "mrx_debug_filter_form",
+    "mrx_debug_set_route", "mrx_testing_set_run", "mrx_debug_filter_form", "mrx_debug_extract_grid",
 ]
 COMM_SYMBOLS = [
     "mrx_comm_unique_id", "mrx_comm_init", "mrx_comm_free", "mrx_comm_rank", "mrx_comm_size",
@@ -399,6 +418,38 @@ class DeviceBatch:
                                 device=self.data.device)
         raise MrxError("this operation needs a CSR batch (strided batch with padding given)")
 
+    def longest(self) -> Optional[int]:
+        """An upper bound of the longest text where the host knows one (a fixed pitch, known CSR bounds), else None:
+        the known bound that filter's and extract's results carry on."""
+        if self.offsets is not None:
+            return self._max_len
+        return self.stride if self.lens is not None else self.length
+
+    def gather_spans(self, prefix, spans, pair: int = 0, piece_cap: Optional[int] = None, out_cap: Optional[int] = None):
+        """The bytes under spans of this batch's texts as a new packed batch (include/mrx.h, mrx_gather_spans_dev):
+        (pieces DeviceBatch, owner int64[pieces]).  prefix int64[n + 1] is the CSR of the rows over the texts, spans
+        int32[m, 2] (findall, split_dev, a set's findall) or int32[m, g + 1, 2] (captures_all; `pair` picks the pair of
+        each row: group j is pair j - 1, the whole match pair g), both device tensors; m = prefix[n].  A pair is clamped
+        to its text, so an unset group gives an empty piece.  The result is a CSR batch with known bounds where this
+        batch knows its longest text, trimmed as filter's; owner[r] is the text index of piece r.  Without piece_cap /
+        out_cap the call grows them as needed (the input's byte count is no bound: overlapping spans are each copied)."""
+        import torch
+        if spans.dtype != torch.int32 or not spans.is_contiguous() or spans.dim() not in (2, 3) or spans.shape[-1] != 2:
+            raise MrxError("spans must be a contiguous int32[m, 2] or int32[m, g + 1, 2] tensor")
+        if prefix.dtype != torch.int64 or not prefix.is_contiguous() or prefix.numel() != self.n + 1:
+            raise MrxError("prefix must be a contiguous int64[n + 1] tensor")
+        row_pairs = int(spans.shape[1]) if spans.dim() == 3 else 1
+        lib = load_library()
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        return _extract_result(self, _grow_call2(
+            int(spans.shape[0]) if piece_cap is None else int(piece_cap),
+            int(self.data.numel()) if out_cap is None else int(out_cap), self.data.device,
+            lambda pb, pcap, out, ocap, d_totals, totals: self.call(
+                lib, "mrx_gather_spans", (),
+                (_ptr(prefix), _ptr(spans), row_pairs, int(pair), pcap, _ptr(pb[0]), _ptr(pb[1]), _ptr(out), ocap,
+                 _ptr(d_totals), totals, stream)),
+            grow_pieces=piece_cap is None, grow_out=out_cap is None))
+
 
 def _ptr(t) -> int:
     return 0 if t is None else int(t.data_ptr())
@@ -417,6 +468,54 @@ def _grow_call(cap, alloc, call, grow=True, only_larger=False):
             continue
         _check(rc)
         return bufs, int(total.value)
+
+
+def _grow_call2(piece_cap, out_cap, dev, call, grow_pieces=True, grow_out=True):
+    """_grow_call for the two capacities of extract: (owner int64[piece_cap], out_offsets int64[piece_cap + 1]) and
+    out_data uint8[out_cap] on `dev`; rc = call(piece_bufs, piece_cap, out_data, out_cap, d_totals, totals).  On
+    MRX_E_CAPACITY the short capacity grows to the reported need -- first the pieces (the bytes are not known before
+    they fit), then the bytes, so at most two retries -- unless it is the caller's own.  Returns (owner, out_offsets,
+    out_data, piece_cap, out_cap, pieces, bytes)."""
+    import torch
+    d_totals = torch.empty(2, dtype=torch.int64, device=dev)
+    totals = (C.c_int64 * 2)()
+    pb = out = None
+    while True:
+        if pb is None:
+            pb = (torch.empty(max(piece_cap, 1), dtype=torch.int64, device=dev),
+                  torch.empty(piece_cap + 1, dtype=torch.int64, device=dev))
+        if out is None:
+            out = torch.empty(max(out_cap, 1), dtype=torch.uint8, device=dev)
+        rc = call(pb, piece_cap, out, out_cap, d_totals, C.cast(totals, C.c_void_p))
+        if rc == MRX_E_CAPACITY and grow_pieces and int(totals[0]) > piece_cap:
+            piece_cap, pb = int(totals[0]), None
+            continue
+        if rc == MRX_E_CAPACITY and grow_out and int(totals[0]) <= piece_cap and int(totals[1]) > out_cap:
+            out_cap, out = int(totals[1]), None
+            continue
+        _check(rc)
+        return pb[0], pb[1], out, piece_cap, out_cap, int(totals[0]), int(totals[1])
+
+
+def _extract_result(batch: "DeviceBatch", grown):
+    """(pieces DeviceBatch, owner) from _grow_call2's buffers, each trimmed by filter's quarter rule: a result that
+    uses less than a quarter of its buffer is copied out, above that the views are returned as they are."""
+    owner, out_off, out, piece_cap, out_cap, pieces, nbytes = grown
+    trim_p = (lambda t, m: t[:m].clone()) if 4 * pieces < piece_cap else (lambda t, m: t[:m])
+    trim_b = (lambda t, m: t[:m].clone()) if 4 * nbytes < out_cap else (lambda t, m: t[:m])
+    res = DeviceBatch(trim_b(out, nbytes), trim_p(out_off, pieces + 1))
+    longest = batch.longest()
+    if longest is not None:   # known bounds, as filter's result: no piece is longer than its text
+        res._end_offset, res._max_len = nbytes, int(longest)
+    return res, trim_p(owner, pieces)
+
+
+def _piece_lists(pieces: "DeviceBatch", prefix) -> List[List[bytes]]:
+    """Host lists from a pieces batch and the CSR of the pieces over the texts (a device tensor or numpy)."""
+    raw = pieces.data.cpu().numpy().tobytes()
+    off = pieces.offsets.cpu().numpy()
+    prefix = prefix if isinstance(prefix, np.ndarray) else prefix.cpu().numpy()
+    return [[raw[off[r]:off[r + 1]] for r in range(prefix[i], prefix[i + 1])] for i in range(len(prefix) - 1)]
 
 
 MRX_FILTER_INVERT, MRX_FILTER_ALL = 1, 2
@@ -442,7 +541,7 @@ def _filter(lib, stem: str, handle, flags: int, texts):
         _check(batch.call(lib, stem, (handle, flags), (_ptr(out[0]), _ptr(out[1]), _ptr(out[2]), cap, _ptr(out[3]),
                                                        C.cast(totals, C.c_void_p), stream)))
         kept, nbytes = int(totals[0]), int(totals[1])
-        longest = batch._max_len if batch.offsets is not None else (batch.stride if batch.lens is not None else batch.length)
+        longest = batch.longest()
         # The outputs were allocated for the worst case (every text kept).  A result that uses less than a quarter
         # of them is copied out, so that a sparse filter does not pin the input's size for the result's lifetime;
         # above that the views are returned as they are (at most four times the result's own bytes stay allocated).
@@ -628,6 +727,71 @@ class CompiledRegex:
         int64[n + 1], out_data uint8[cap], totals int64[2]) device tensors of the caller; totals = {kept, bytes} once the
         stream has drained.  No byte is written when bytes > cap (check totals[1]); cap = the input's bytes always fits."""
         _filter_async(self._lib, "mrx_filter", self._h, _filter_flags("any", invert), batch, out)
+
+    def extract(self, texts, group: Optional[int] = None, count: int = 0):
+        """The matched bytes themselves (re.findall's strings; include/mrx.h, mrx_extract_dev).  group=None: findall's
+        matches, in its order -- empty matches and the overlapping occurrences of an exact literal included; count must
+        be 0.  group=j, 0 <= j <= num_groups: that group of every captures_all match (at most `count` per text, 0 =
+        all), an unset group as an empty piece; j = 0 is the whole match of that loop, which is not always findall's
+        list: captures_all's matches "are NOT findall's spans where the groups run on the backtracker: it is greedy and
+        the first alternative wins, while findall takes the hybrid engines' leftmost-longest walk ... Exact literals
+        differ too: findall returns overlapping occurrences, this loop does not" (include/mrx.h, mrx_captures_all_dev).
+        A list of texts gives List[List[bytes]]; a DeviceBatch gives (pieces DeviceBatch, prefix int64[n + 1], owner
+        int64[pieces]) on the device: text i's pieces are the texts [prefix[i], prefix[i + 1]) of `pieces`, and owner[r]
+        = i for each of them.  `pieces` carries known bounds as filter's result does.
+        Cost: the piece capacity is findall's default, a match per 8 bytes, and the sizes kernel and the scan run over
+        the capacity, not over the pieces (profiles/extract.md); DeviceBatch.gather_spans on findall's own spans takes
+        an exact capacity."""
+        if not isinstance(texts, DeviceBatch):
+            pieces, prefix, _ = self.extract(DeviceBatch.from_texts([_b(t) for t in texts]), group, count)
+            return _piece_lists(pieces, prefix)
+        if group is None:
+            if count != 0:
+                raise MrxError("count needs a group: findall has no limit")
+            import torch
+            prefix = torch.empty(texts.n + 1, dtype=torch.int64, device=texts.data.device)
+            nbytes = int(texts.data.numel())
+            res = _extract_result(texts, _grow_call2(
+                max(64, nbytes // 8 + texts.n), nbytes, texts.data.device,
+                lambda pb, pcap, out, ocap, d_totals, totals: texts.call(
+                    self._lib, "mrx_extract", (self._h,),
+                    (_ptr(prefix), _ptr(pb[0]), _ptr(pb[1]), pcap, _ptr(out), ocap, _ptr(d_totals), totals,
+                     self._stream_ptr()))))
+            return res[0], prefix, res[1]
+        g = self.num_groups
+        if not 0 <= int(group) <= g:
+            raise MrxError("group must be in [0, %d]" % g)
+        prefix, rows = self._captures_all_dev(texts, count)
+        # rows hold groups 1..g, then group 0
+        pieces, owner = texts.gather_spans(prefix, rows, pair=(int(group) - 1) % (g + 1))
+        return pieces, prefix, owner
+
+    def extract_async(self, batch: "DeviceBatch", out):
+        """Enqueue extract (findall's matches) on the current stream without reading anything back.  out =
+        (piece_prefix int64[n + 1], owner int64[piece_cap], out_offsets int64[piece_cap + 1], out_data uint8[out_cap],
+        totals int64[2]) device tensors of the caller; totals = {pieces, bytes} once the stream has drained.  No byte is
+        written when pieces > piece_cap or bytes > out_cap (check totals against both).  A CSR batch without known bounds
+        still pays findall's one read-back of them."""
+        import torch
+        prefix, owner, out_offsets, out_data, totals = out
+        if prefix.numel() < batch.n + 1 or out_offsets.numel() < owner.numel() + 1 or totals.numel() < 2:
+            raise MrxError("out needs piece_prefix int64[n + 1], owner int64[cap], out_offsets int64[cap + 1], "
+                           "out_data uint8[out_cap], totals int64[2]")
+        for t in (prefix, owner, out_offsets, totals):
+            if t.dtype != torch.int64 or not t.is_contiguous():
+                raise MrxError("piece_prefix, owner, out_offsets and totals must be contiguous int64 tensors")
+        if out_data.dtype != torch.uint8 or not out_data.is_contiguous():
+            raise MrxError("out_data must be a contiguous uint8 tensor")
+        _check(batch.call(self._lib, "mrx_extract", (self._h,),
+                          (_ptr(prefix), _ptr(owner), _ptr(out_offsets), int(owner.numel()), _ptr(out_data),
+                           int(out_data.numel()), _ptr(totals), None, self._stream_ptr())))
+
+    def split_batch(self, batch: "DeviceBatch", maxsplit: int = 0):
+        """regex.split of a device-resident batch as bytes: split_dev's ranges gathered into a new packed batch,
+        (pieces DeviceBatch, piece_prefix int64[n + 1], owner int64[pieces]), shaped as extract's result."""
+        prefix, ranges, total = self.split_dev(batch, maxsplit)
+        pieces, owner = batch.gather_spans(prefix, ranges[:total])
+        return pieces, prefix, owner
 
     def match_all(self, texts):
         """regex.findall per text: (counts_prefix int64[n+1], spans int32[total, 2])."""
@@ -912,6 +1076,22 @@ class PatternSet:
         self._hits_per_byte = total / max(1, int(offsets[-1]))
         return prefix, members[:total], spans[:total]
 
+    def extract(self, texts):
+        """Every member's findall hits as bytes: findall()'s hits, text-major, gathered into a new packed batch
+        (include/mrx.h, mrx_gather_spans_dev).  A DeviceBatch gives (pieces DeviceBatch, text_prefix int64[n + 1],
+        members int32[pieces], owner int64[pieces]) on the device; a list of texts gives a list per text of (member,
+        bytes) tuples."""
+        host = not isinstance(texts, DeviceBatch)
+        batch = DeviceBatch.from_texts([_b(t) for t in texts]) if host else texts
+        prefix, members, spans = self._findall_dev(batch)
+        pieces, owner = batch.gather_spans(prefix, spans)
+        if not host:
+            return pieces, prefix, members, owner
+        members = members.cpu().numpy()
+        prefix = prefix.cpu().numpy()
+        return [[(int(members[prefix[i] + q]), p) for q, p in enumerate(row)]
+                for i, row in enumerate(_piece_lists(pieces, prefix))]
+
     def _default_cap(self, nbytes: int, n: int) -> int:
         """Span capacity without a caller's cap: one hit per 8 bytes, or the density of this set's previous call (+1/8)
         where that was higher, so that a dense rule set does not pay the retry on every call."""
@@ -1061,6 +1241,11 @@ def sub(pattern, repl, texts, count: int = 0) -> List[bytes]:
 def filter_texts(pattern, texts, invert: bool = False):
     """CompiledRegex.filter through the cache (the name leaves the builtin filter alone)."""
     return compile_regex(pattern).filter(texts, invert)
+
+
+def findall_texts(pattern, texts):
+    """CompiledRegex.extract through the cache: findall's matches as bytes (re.findall's strings)."""
+    return compile_regex(pattern).extract(texts)
 
 
 def split(pattern, texts, maxsplit: int = 0) -> List[List[bytes]]:

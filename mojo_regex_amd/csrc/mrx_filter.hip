@@ -39,14 +39,12 @@
 
 #include "../../include/mrx.h"
 #include "../../include/mrx_testing.h"
+#include "mrx_gather_bits.hpp"
 #include "mrx_host_batch.hpp"
 #include "mrx_internal.hpp"
 
 namespace mrx {
 namespace {
-
-typedef unsigned __int128 f_u128;
-typedef uint64_t f_u64x2 __attribute__((ext_vector_type(2)));
 
 constexpr uint32_t kFilterFlags = MRX_FILTER_INVERT | MRX_FILTER_ALL;
 constexpr int kFilterBlock = 256;
@@ -112,38 +110,6 @@ __global__ __launch_bounds__(kFilterBlock) void k_filter_scatter(int64_t n, cons
   }
 }
 
-// bytes p[0 .. 16) as one little-endian value; only the first `need` (1 .. 16) are meaningful, and only the aligned
-// 16-byte words that hold one of them are loaded (p[0 .. need) lies inside a text)
-__device__ __forceinline__ f_u128 filter_window(const uint8_t* p, int need) {
-  const uintptr_t a = (uintptr_t)p;
-  const f_u64x2* w = (const f_u64x2*)(a & ~(uintptr_t)15);
-  const int sh = (int)(a & 15);
-  const f_u64x2 x = w[0];
-  const f_u128 lo = ((f_u128)x.y << 64) | x.x;
-  if (sh == 0) return lo;
-  f_u128 hi = 0;
-  if (sh + need > 16) {
-    const f_u64x2 y = w[1];
-    hi = ((f_u128)y.y << 64) | y.x;
-  }
-  return (lo >> (8 * sh)) | (hi << (128 - 8 * sh));
-}
-__device__ __forceinline__ void filter_store16(uint8_t* aligned, f_u128 v) {
-  f_u64x2 x;
-  x.x = (uint64_t)v;
-  x.y = (uint64_t)(v >> 64);
-  *(f_u64x2*)aligned = x;
-}
-
-// the last r in [a, b) with off[r] <= p (off[a] <= p)
-__device__ __forceinline__ int64_t filter_last_text(const int64_t* __restrict__ off, int64_t a, int64_t b, int64_t p) {
-  while (b - a > 1) {
-    const int64_t mid = (a + b) >> 1;
-    if (off[mid] <= p) a = mid; else b = mid;
-  }
-  return a;
-}
-
 __global__ __launch_bounds__(kFilterBlock) void k_filter_gather(const TextBatch B, const FilterOut O) {
   const int64_t kept = O.totals[0], bytes = O.totals[1];
   if (bytes <= 0 || bytes > O.out_cap) return;
@@ -156,7 +122,7 @@ __global__ __launch_bounds__(kFilterBlock) void k_filter_gather(const TextBatch 
   const int64_t b_begin = w * per, b_end = b_begin + per < nblk ? b_begin + per : nblk;
   if (b_begin >= b_end) return;
   const int64_t p_first = b_begin * 16 - head;
-  int64_t cur = filter_last_text(O.out_off, 0, kept, p_first > 0 ? p_first : 0);
+  int64_t cur = gather_last_le(O.out_off, 0, kept, p_first > 0 ? p_first : 0);
   for (int64_t b0 = b_begin; b0 < b_end; b0 += 64) {
     const int64_t bl = b0 + 63 < b_end ? b0 + 63 : b_end - 1;
     const int64_t pe = bl * 16 - head + 15, pl = pe < bytes ? pe : bytes - 1;   // the round's last byte
@@ -165,30 +131,28 @@ __global__ __launch_bounds__(kFilterBlock) void k_filter_gather(const TextBatch 
       hi += step;
       step <<= 1;
     }
-    hi = filter_last_text(O.out_off, hi, hi + step < kept ? hi + step : kept, pl);
+    hi = gather_last_le(O.out_off, hi, hi + step < kept ? hi + step : kept, pl);
     const int64_t b = b0 + lane;
     if (b <= bl) {
       const int64_t p0 = b * 16 - head;
       int64_t pos = p0 > 0 ? p0 : 0;
       const int64_t endp = p0 + 16 < bytes ? p0 + 16 : bytes;
-      int64_t r = filter_last_text(O.out_off, cur, hi + 1, pos);
-      f_u128 acc = 0;
+      int64_t r = gather_last_le(O.out_off, cur, hi + 1, pos);
+      g_u128 acc = 0;
       while (pos < endp) {   // (out_off[kept] = bytes > pos: r stays below kept)
         const int64_t s = O.out_off[r], e = O.out_off[r + 1];
         if (e > pos) {
           const int take = (int)((e < endp ? e : endp) - pos);
           int32_t L;
           const uint8_t* tp = B.text(O.kept_idx[r], &L);
-          f_u128 v = filter_window(tp + (pos - s), take);
-          if (take < 16) v &= ((f_u128)1 << (8 * take)) - 1;
-          acc |= v << (8 * (int)(pos - p0));
+          acc = gather_place(acc, tp + (pos - s), take, (int)(pos - p0));
           pos += take;
         }
         ++r;
       }
       uint8_t* dst = (uint8_t*)(a0 + (uintptr_t)b * 16);
       if (p0 >= 0 && p0 + 16 <= bytes) {
-        filter_store16(dst, acc);
+        gather_store16(dst, acc);
       } else {   // the first block of an unaligned output, the last block of the output
         for (int q = p0 < 0 ? (int)-p0 : 0; q < (int)(endp - p0); ++q) dst[q] = (uint8_t)(acc >> (8 * q));
       }
@@ -213,7 +177,7 @@ __global__ __launch_bounds__(kFilterBlock) void k_filter_gather_text(const TextB
     const int64_t h = to_boundary < len ? to_boundary : len;   // bytes in front of the row's first aligned block
     const int64_t t0 = h + ((len - h) & ~(int64_t)15);         // ... and from here on behind its last one
     for (int64_t q = sub; q < h; q += G) dst[q] = tp[q];
-    for (int64_t q = h + 16 * (int64_t)sub; q < t0; q += 16 * (int64_t)G) filter_store16(dst + q, filter_window(tp + q, 16));
+    for (int64_t q = h + 16 * (int64_t)sub; q < t0; q += 16 * (int64_t)G) gather_store16(dst + q, gather_window(tp + q, 16));
     for (int64_t q = t0 + sub; q < len; q += G) dst[q] = tp[q];
   }
 }
