@@ -520,6 +520,61 @@ int mrx_extract_strided_dev(const mrx_handle* h, const uint8_t* d_data, int64_t 
                             int64_t piece_cap, uint8_t* d_out_data, int64_t out_cap, int64_t* d_totals, int64_t* totals,
                             void* stream);
 
+/* ---- expand: one templated record per match as a new packed batch on the device ----
+ * Python's [m.expand(t) for m in re.finditer(p, s)], sed -n 's/.../.../p': per match ONE record, the template with each
+ * \j replaced by the bytes of the match's group j -- the bytes mrx_sub_dev puts in place of that match.  It is defined on
+ * the rows of mrx_captures_all_*, with no matcher of its own.
+ * The primitive, mrx_expand_spans_*, needs no pattern: it takes rows that captures_all left on the device.
+ *   d_prefix int64[n + 1]            CSR over the texts: text i owns the rows [d_prefix[i], d_prefix[i + 1])
+ *   d_rows int32[rows][row_pairs][2] the rows, 8-byte aligned: row_pairs = g + 1 pairs each, groups 1..g, then the match
+ *   tpl, tpl_len                     the template, in the one template grammar of the library (mrx_sub_dev's): only \1..\9
+ *                                    are references, every other byte is literal -- \0, \\ and a trailing \ stay as they
+ *                                    are.  Any length and any number of references; an empty template is allowed
+ *   piece_cap                        capacity, in records, of d_owner and d_out_offsets
+ * pieces = d_prefix[n], read on the device; record r belongs to the text i with d_prefix[i] <= r < d_prefix[i + 1].  Its
+ * bytes are the template's with each \j replaced by pair j - 1 of row r clamped to the text as mrx_gather_spans_dev
+ * clamps a pair (s' = min(max(s, 0), L), e' = min(max(e, s'), L)): a group without an entry, (-1, -1), contributes
+ * nothing, a fixed-width group that reaches behind its text is cut, and so does a reference to a group the rows do not
+ * hold (j > row_pairs - 1: nothing).  A template without references gives every match the same record; an empty template
+ * gives empty records, whose offset repeats.  The output may hold more bytes than the input.
+ * Outputs (d_owner, d_out_offsets, d_out_data, d_totals = {pieces, bytes}), both capacity rules (pieces > piece_cap, then
+ * bytes > out_cap), totals == NULL (nothing is read back, the call returns without synchronising) and n == 0 are those
+ * of mrx_gather_spans_dev, word for word; the output is a CSR batch and the input of a following call as it stands (a
+ * record is at most tpl_len + references x the longest text long -- NOT at most the longest text).
+ * MRX_E_ARGUMENT, before anything is written or enqueued: negative n, piece_cap or out_cap; row_pairs < 1; a null tpl
+ * with tpl_len > 0; a misaligned d_rows; a bad pitch; a null required pointer (d_offsets, d_prefix, d_out_offsets,
+ * d_totals; d_rows and d_owner when piece_cap > 0; d_out_data when out_cap > 0).
+ * Reads: as mrx_gather_spans_dev, the aligned 16-byte words that hold a group's bytes are read, so up to 15 bytes in
+ * front of and behind them (never used); no word is read for a group without a byte.  The literals are read the same
+ * way from the call's own padded device copy, never from around `tpl`.
+ * Scratch: 16 bytes per record of capacity, 8 more per distinct referenced group, the parsed template and the scan's
+ * block sums, returned to the arena when the call returns. */
+int mrx_expand_spans_dev(const uint8_t* d_data, const int64_t* d_offsets, int64_t n, const int64_t* d_prefix,
+                         const int32_t* d_rows, int32_t row_pairs, const char* tpl, size_t tpl_len, int64_t piece_cap,
+                         int64_t* d_owner, int64_t* d_out_offsets, uint8_t* d_out_data, int64_t out_cap, int64_t* d_totals,
+                         int64_t* totals, void* stream);
+int mrx_expand_spans_strided_dev(const uint8_t* d_data, int64_t stride, const int32_t* d_lens, int32_t len, int64_t n,
+                                 const int64_t* d_prefix, const int32_t* d_rows, int32_t row_pairs, const char* tpl,
+                                 size_t tpl_len, int64_t piece_cap, int64_t* d_owner, int64_t* d_out_offsets,
+                                 uint8_t* d_out_data, int64_t out_cap, int64_t* d_totals, int64_t* totals, void* stream);
+/* expand with the matcher in front: mrx_captures_all_dev with `count` (at most that many matches per text, 0 = all),
+ * its rows in scratch ((g + 1) * 8 bytes per match of capacity), then the primitive.  d_match_prefix int64[n + 1]
+ * receives captures_all's CSR; match_cap is the capacity, in matches, of d_owner and d_out_offsets (piece_cap above).
+ * The matches are captures_all's, which are not always findall's (see mrx_captures_all_dev).
+ * captures_all returns its total through one stream synchronisation, and this call inherits it: the primitive then runs
+ * over exactly the rows found, not over match_cap.  With totals == NULL nothing more is read back -- a shortage of
+ * out_cap is for the caller to find in d_totals, as for the primitive, while a shortage of match_cap, which the host
+ * knows from captures_all, still returns MRX_E_CAPACITY (d_totals = {matches, 0}, no byte written).
+ * Null handle, negative count or match_cap: MRX_E_ARGUMENT.  A pattern that captures_all refuses is refused here with
+ * the same code and text, before anything is enqueued.  There is no _known form: captures_all has none. */
+int mrx_expand_dev(const mrx_handle* h, const char* tpl, size_t tpl_len, int64_t count, const uint8_t* d_data,
+                   const int64_t* d_offsets, int64_t n, int64_t* d_match_prefix, int64_t* d_owner, int64_t* d_out_offsets,
+                   int64_t match_cap, uint8_t* d_out_data, int64_t out_cap, int64_t* d_totals, int64_t* totals, void* stream);
+int mrx_expand_strided_dev(const mrx_handle* h, const char* tpl, size_t tpl_len, int64_t count, const uint8_t* d_data,
+                           int64_t stride, const int32_t* d_lens, int32_t len, int64_t n, int64_t* d_match_prefix,
+                           int64_t* d_owner, int64_t* d_out_offsets, int64_t match_cap, uint8_t* d_out_data, int64_t out_cap,
+                           int64_t* d_totals, int64_t* totals, void* stream);
+
 /* ---- host-buffer convenience wrappers (copy in, run, copy out) -------------- */
 /* mrx_gather_spans_dev / mrx_extract_dev on host buffers: owner int64[piece_cap], out_offsets int64[piece_cap + 1],
  * out_data uint8[out_cap], totals int64[2] = {pieces, bytes} (may be NULL); spans holds prefix[n] rows.  piece_prefix
@@ -531,6 +586,15 @@ int mrx_gather_spans_batch(const uint8_t* data, const int64_t* offsets, int64_t 
 int mrx_extract_batch(const mrx_handle* h, const uint8_t* data, const int64_t* offsets, int64_t n, int64_t* piece_prefix,
                       int64_t* owner, int64_t* out_offsets, int64_t piece_cap, uint8_t* out_data, int64_t out_cap,
                       int64_t* totals);
+/* mrx_expand_spans_dev / mrx_expand_dev on host buffers, shaped as the two above with the same rules for what is copied
+ * out when: rows holds prefix[n] rows; match_prefix (expand) is always copied out, owner[0, pieces) and
+ * out_offsets[0, pieces] when the records fit, out_data only when the bytes fit too (MRX_E_CAPACITY otherwise). */
+int mrx_expand_spans_batch(const uint8_t* data, const int64_t* offsets, int64_t n, const int64_t* prefix, const int32_t* rows,
+                           int32_t row_pairs, const char* tpl, size_t tpl_len, int64_t piece_cap, int64_t* owner,
+                           int64_t* out_offsets, uint8_t* out_data, int64_t out_cap, int64_t* totals);
+int mrx_expand_batch(const mrx_handle* h, const char* tpl, size_t tpl_len, int64_t count, const uint8_t* data,
+                     const int64_t* offsets, int64_t n, int64_t* match_prefix, int64_t* owner, int64_t* out_offsets,
+                     int64_t match_cap, uint8_t* out_data, int64_t out_cap, int64_t* totals);
 /* mrx_filter_dev / mrx_set_filter_dev on host buffers: kept_idx int64[n], out_offsets int64[n + 1], out_data
  * uint8[out_cap], totals int64[2] = {kept, bytes} (may be NULL).  kept_idx[0, kept) and out_offsets[0, kept] are
  * copied out, out_data only when all of it fits (MRX_E_CAPACITY otherwise). */

@@ -115,6 +115,9 @@ void mrx_debug_filter_form(int form);
  * one wavefront run several rounds of 64 blocks without an output of many megabytes.  0 (default) = no cap.  Results are
  * the same. */
 void mrx_debug_extract_grid(int workgroups);
+/* Expand (include/mrx.h): the byte mover reports itself as "k_expand_gather"; its grid is sized and capped as extract's
+ * (mrx_debug_extract_grid), by a switch of its own.  0 (default) = no cap.  Results are the same. */
+void mrx_debug_expand_grid(int workgroups);
 /* Bytes of device memory the calling thread's scratch arenas hold (see mrx_release_scratch). */
 size_t mrx_debug_scratch_bytes(void);
 /* ... and how many of them are handed out and not yet rewound.  Scratch belongs to the call's scope, so between calls

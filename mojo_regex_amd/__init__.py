@@ -24,6 +24,8 @@ argument meaning, a *batch* of texts instead of one text:
     Match.get_match_text(), per match             findall_texts / CompiledRegex.extract / split_batch /
                                                   PatternSet.extract / DeviceBatch.gather_spans: the matched
                                                   bytes as a new packed batch
+    Match groups into a template, per match       expand / CompiledRegex.expand / DeviceBatch.expand_spans:
+                                                  one templated record per match as a new packed batch
 
 All matching runs in the HIP kernels of libmrx_hip.so.  There is no CPU
 fallback: if the library is missing or no GPU is usable, calls raise.
@@ -41,6 +43,7 @@ from .api import (  # noqa: F401
     clear_regex_cache,
     compile_regex,
     compile_set,
+    expand,
     filter_texts,
     findall,
     findall_texts,

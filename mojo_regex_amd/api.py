@@ -215,6 +215,23 @@ def load_library():
                                               u8p, C.c_int64, i64p, C.c_void_p, C.c_void_p]),
         "mrx_extract_batch": (C.c_int, [H, u8p, i64p, C.c_int64, i64p, i64p, i64p, C.c_int64, u8p, C.c_int64, C.c_void_p]),
         "mrx_debug_extract_grid": (None, [C.c_int]),
+        # expand: the batch | (prefix, rows, row_pairs, tpl, tpl_len, piece_cap, owner, out_offsets, out_data, out_cap,
+        # d_totals, totals, stream); with a handle (handle, tpl, tpl_len, count) | the batch | (match_prefix, owner,
+        # out_offsets, match_cap, out_data, ...)
+        "mrx_expand_spans_dev": (C.c_int, [u8p, i64p, C.c_int64, i64p, i32p, C.c_int32, C.c_char_p, C.c_size_t, C.c_int64,
+                                           i64p, i64p, u8p, C.c_int64, i64p, C.c_void_p, C.c_void_p]),
+        "mrx_expand_spans_strided_dev": (C.c_int, [u8p, C.c_int64, i32p, C.c_int32, C.c_int64, i64p, i32p, C.c_int32,
+                                                   C.c_char_p, C.c_size_t, C.c_int64, i64p, i64p, u8p, C.c_int64, i64p,
+                                                   C.c_void_p, C.c_void_p]),
+        "mrx_expand_spans_batch": (C.c_int, [u8p, i64p, C.c_int64, i64p, i32p, C.c_int32, C.c_char_p, C.c_size_t, C.c_int64,
+                                             i64p, i64p, u8p, C.c_int64, C.c_void_p]),
+        "mrx_expand_dev": (C.c_int, [H, C.c_char_p, C.c_size_t, C.c_int64, u8p, i64p, C.c_int64, i64p, i64p, i64p, C.c_int64,
+                                     u8p, C.c_int64, i64p, C.c_void_p, C.c_void_p]),
+        "mrx_expand_strided_dev": (C.c_int, [H, C.c_char_p, C.c_size_t, C.c_int64, u8p, C.c_int64, i32p, C.c_int32, C.c_int64,
+                                             i64p, i64p, i64p, C.c_int64, u8p, C.c_int64, i64p, C.c_void_p, C.c_void_p]),
+        "mrx_expand_batch": (C.c_int, [H, C.c_char_p, C.c_size_t, C.c_int64, u8p, i64p, C.c_int64, i64p, i64p, i64p,
+                                       C.c_int64, u8p, C.c_int64, C.c_void_p]),
+        "mrx_debug_expand_grid": (None, [C.c_int]),
         "mrx_debug_set_route": (None, [C.c_int]),
         "mrx_testing_set_run": (C.c_int, [H, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_int32)]),
     }
@@ -246,6 +263,8 @@ EXPORTED_SYMBOLS = [
     "mrx_set_filter_dev", "mrx_set_filter_known_dev", "mrx_set_filter_strided_dev", "mrx_set_filter_batch",
     "mrx_gather_spans_dev", "mrx_gather_spans_strided_dev", "mrx_gather_spans_batch",
     "mrx_extract_dev", "mrx_extract_known_dev", "mrx_extract_strided_dev", "mrx_extract_batch",
+    "mrx_expand_spans_dev", "mrx_expand_spans_strided_dev", "mrx_expand_spans_batch",
+    "mrx_expand_dev", "mrx_expand_strided_dev", "mrx_expand_batch",
 ]
 TESTING_SYMBOLS = [
     "mrx_timing_reset", "mrx_timing_enable", "mrx_timing_scan_ms", "mrx_last_kernel_name",
@@ -254,6 +273,7 @@ TESTING_SYMBOLS = [
     "mrx_debug_fused_findall", "mrx_debug_stream_bits", "mrx_debug_stream_bits_trace", "mrx_debug_dynamic_texts", "mrx_debug_subs_group",
     "mrx_debug_split_findall", "mrx_debug_dense_rows", "mrx_debug_tries_always", "mrx_debug_chain_sub_general", "mrx_testing_emptywalk_findall", "mrx_debug_litscan_pieces", "mrx_debug_multiwalk", "mrx_debug_rec_skew", "mrx_testing_comm_shift", "mrx_testing_comm_compact",
     "mrx_debug_set_route", "mrx_testing_set_run", "mrx_debug_filter_form", "mrx_debug_extract_grid",
+    "mrx_debug_expand_grid",
 ]
 COMM_SYMBOLS = [
     "mrx_comm_unique_id", "mrx_comm_init", "mrx_comm_free", "mrx_comm_rank", "mrx_comm_size",
@@ -450,6 +470,34 @@ class DeviceBatch:
                  _ptr(d_totals), totals, stream)),
             grow_pieces=piece_cap is None, grow_out=out_cap is None))
 
+    def expand_spans(self, template, prefix, rows, piece_cap: Optional[int] = None, out_cap: Optional[int] = None):
+        """One record per row of captures_all as a new packed batch (include/mrx.h, mrx_expand_spans_dev): (records
+        DeviceBatch, owner int64[records]).  `template` is sub's template grammar (only \\1..\\9 are references; every
+        other byte is literal); record r is the template with each \\j replaced by group j of row r, clamped to its text
+        as gather_spans clamps a pair -- an unset group and a group the rows do not hold contribute nothing.  prefix
+        int64[n + 1] is the CSR of the rows over the texts and rows int32[m, g + 1, 2] captures_all's rows (groups 1..g,
+        then the match), both device tensors.  Without piece_cap / out_cap the call grows them as needed.  The result
+        is a CSR batch, trimmed as filter's, with known bounds where this batch knows its longest text -- and the bound
+        on a record is len(template) + references x longest, NOT the input's longest text: that is what the result's
+        longest() says."""
+        import torch
+        template = _b(template)
+        if rows.dtype != torch.int32 or not rows.is_contiguous() or rows.dim() != 3 or rows.shape[-1] != 2:
+            raise MrxError("rows must be a contiguous int32[m, g + 1, 2] tensor")
+        if prefix.dtype != torch.int64 or not prefix.is_contiguous() or prefix.numel() != self.n + 1:
+            raise MrxError("prefix must be a contiguous int64[n + 1] tensor")
+        lib = load_library()
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        m = int(rows.shape[0])
+        return _expand_result(self, template, _grow_call2(
+            m if piece_cap is None else int(piece_cap),
+            max(64, int(self.data.numel()) + m * len(template)) if out_cap is None else int(out_cap), self.data.device,
+            lambda pb, pcap, out, ocap, d_totals, totals: self.call(
+                lib, "mrx_expand_spans", (),
+                (_ptr(prefix), _ptr(rows), int(rows.shape[1]), template, len(template), pcap, _ptr(pb[0]), _ptr(pb[1]),
+                 _ptr(out), ocap, _ptr(d_totals), totals, stream)),
+            grow_pieces=piece_cap is None, grow_out=out_cap is None))
+
 
 def _ptr(t) -> int:
     return 0 if t is None else int(t.data_ptr())
@@ -508,6 +556,26 @@ def _extract_result(batch: "DeviceBatch", grown):
     if longest is not None:   # known bounds, as filter's result: no piece is longer than its text
         res._end_offset, res._max_len = nbytes, int(longest)
     return res, trim_p(owner, pieces)
+
+
+def _template_refs(template: bytes) -> int:
+    """The references of a template: the \\1..\\9 of sub's grammar (parse_repl_template scans left to right and passes
+    both bytes of a reference)."""
+    refs, i = 0, 0
+    while i + 1 < len(template):
+        if template[i] == 0x5C and 0x31 <= template[i + 1] <= 0x39:
+            refs, i = refs + 1, i + 2
+        else:
+            i += 1
+    return refs
+
+
+def _expand_result(batch: "DeviceBatch", template: bytes, grown):
+    """_extract_result for expand: a record is at most len(template) + references x the longest text long."""
+    res, owner = _extract_result(batch, grown)
+    if res._max_len is not None:
+        res._max_len = len(template) + _template_refs(template) * res._max_len
+    return res, owner
 
 
 def _piece_lists(pieces: "DeviceBatch", prefix) -> List[List[bytes]]:
@@ -765,6 +833,33 @@ class CompiledRegex:
         # rows hold groups 1..g, then group 0
         pieces, owner = texts.gather_spans(prefix, rows, pair=(int(group) - 1) % (g + 1))
         return pieces, prefix, owner
+
+    def expand(self, template, texts, count: int = 0):
+        """One record per match, built from the match's groups and literal bytes: Python's [m.expand(t) for m in
+        re.finditer(p, s)] (include/mrx.h, mrx_expand_dev).  `template` is sub's template: only \\1..\\9 are references,
+        every other byte is literal; the record of a match is what sub(template, ...) puts in its place -- an unset
+        group and a group the pattern lacks contribute nothing.  The matches are captures_all's (at most `count` per
+        text, 0 = all), which is not always findall's list: captures_all's matches "are NOT findall's spans where the
+        groups run on the backtracker: it is greedy and the first alternative wins, while findall takes the hybrid
+        engines' leftmost-longest walk ... Exact literals differ too: findall returns overlapping occurrences, this loop
+        does not" (include/mrx.h, mrx_captures_all_dev).
+        A list of texts gives List[List[bytes]]; a DeviceBatch gives (records DeviceBatch, prefix int64[n + 1], owner
+        int64[records]) on the device, shaped as extract's result; `records` carries known bounds where the input does,
+        its longest record bounded by len(template) + references x the input's longest text."""
+        template = _b(template)
+        if not isinstance(texts, DeviceBatch):
+            records, prefix, _ = self.expand(template, DeviceBatch.from_texts([_b(t) for t in texts]), count)
+            return _piece_lists(records, prefix)
+        import torch
+        prefix = torch.empty(texts.n + 1, dtype=torch.int64, device=texts.data.device)
+        nbytes = int(texts.data.numel())
+        res = _expand_result(texts, template, _grow_call2(
+            max(64, nbytes // 8 + texts.n), max(64, nbytes), texts.data.device,
+            lambda pb, pcap, out, ocap, d_totals, totals: texts.call(
+                self._lib, "mrx_expand", (self._h, template, len(template), int(count)),
+                (_ptr(prefix), _ptr(pb[0]), _ptr(pb[1]), pcap, _ptr(out), ocap, _ptr(d_totals), totals,
+                 self._stream_ptr()))))
+        return res[0], prefix, res[1]
 
     def extract_async(self, batch: "DeviceBatch", out):
         """Enqueue extract (findall's matches) on the current stream without reading anything back.  out =
@@ -1246,6 +1341,11 @@ def filter_texts(pattern, texts, invert: bool = False):
 def findall_texts(pattern, texts):
     """CompiledRegex.extract through the cache: findall's matches as bytes (re.findall's strings)."""
     return compile_regex(pattern).extract(texts)
+
+
+def expand(pattern, template, texts, count: int = 0):
+    """CompiledRegex.expand through the cache: one templated record per match ([m.expand(t) for m in re.finditer])."""
+    return compile_regex(pattern).expand(template, texts, count)
 
 
 def split(pattern, texts, maxsplit: int = 0) -> List[List[bytes]]:

@@ -66,16 +66,6 @@ struct ExtractOut {
   int64_t out_cap;
 };
 
-// the last q in [a, b) with off[q] <= p (off[a] <= p), by doubling steps from a: cheap when q is close to a
-__device__ __forceinline__ int64_t extract_gallop(const int64_t* __restrict__ off, int64_t a, int64_t b, int64_t p) {
-  int64_t step = 1;
-  while (a + step < b && off[a + step] <= p) {
-    a += step;
-    step <<= 1;
-  }
-  return gather_last_le(off, a, a + step < b ? a + step : b, p);
-}
-
 // Rows that do not all fit get no owner and length 0 (the spans are not read: bytes is then 0, a lower bound).
 __global__ __launch_bounds__(kExtractBlock) void k_extract_sizes(const TextBatch B, int64_t n,
                                                                  const int64_t* __restrict__ prefix,
@@ -120,7 +110,7 @@ __global__ __launch_bounds__(kExtractBlock) void k_extract_gather(const ExtractO
   for (int64_t b0 = b_begin; b0 < b_end; b0 += 64) {
     const int64_t bl = b0 + 63 < b_end ? b0 + 63 : b_end - 1;
     const int64_t pe = bl * 16 - head + 15, pl = pe < bytes ? pe : bytes - 1;   // the round's last byte
-    const int64_t hi = extract_gallop(O.out_off, cur, pieces, pl);
+    const int64_t hi = gather_gallop(O.out_off, cur, pieces, pl);
     const int64_t b = b0 + lane;
     if (b <= bl) {
       const int64_t p0 = b * 16 - head;
@@ -134,7 +124,7 @@ __global__ __launch_bounds__(kExtractBlock) void k_extract_gather(const ExtractO
         acc = gather_place(acc, O.data + O.src[r] + (pos - s), take, (int)(pos - p0));
         pos += take;
         if (pos >= endp) break;
-        r = extract_gallop(O.out_off, r + 1, hi + 1, pos);   // the next piece with a byte: empty ones are stepped over
+        r = gather_gallop(O.out_off, r + 1, hi + 1, pos);   // the next piece with a byte: empty ones are stepped over
       }
       uint8_t* dst = (uint8_t*)(a0 + (uintptr_t)b * 16);
       if (p0 >= 0 && p0 + 16 <= bytes) {
@@ -235,40 +225,6 @@ int extract_run(const mrx_handle* h, const TextBatch& b, BatchForm form, int64_t
   if (int rc = member_findall(h, b, n, d_piece_prefix, spans, a.piece_cap, a.stream, known_total, known_max)) return rc;
   a.d_spans = spans;
   return gather_enqueue(b, n, a);
-}
-
-// host buffers: the batch uploaded, device buffers for the outputs, what is valid copied out
-struct HostOut {
-  int64_t* owner;
-  int64_t* out_offsets;
-  uint8_t* out_data;
-  int64_t* totals;
-};
-struct DevOut {
-  DevBuf<int64_t> ow, oo, dt;
-  DevBuf<uint8_t> od;
-  int alloc(int64_t piece_cap, int64_t out_cap) {
-    if (int rc = ow.alloc((size_t)piece_cap)) return rc;
-    if (int rc = oo.alloc((size_t)piece_cap + 1)) return rc;
-    if (int rc = dt.alloc(2)) return rc;
-    return od.alloc((size_t)out_cap);
-  }
-  // rc: the device call's.  owner and offsets when the pieces fit, the bytes when they fit too
-  int copy_out(int rc, const int64_t tot[2], int64_t piece_cap, const HostOut& o) {
-    if (rc != MRX_OK && rc != MRX_E_CAPACITY) return rc;
-    if (o.totals) { o.totals[0] = tot[0]; o.totals[1] = tot[1]; }
-    if (tot[0] > piece_cap) return rc;
-    if (tot[0] > 0) MRX_HIP_TRY(hipMemcpy(o.owner, ow.p, sizeof(int64_t) * (size_t)tot[0], hipMemcpyDeviceToHost));
-    MRX_HIP_TRY(hipMemcpy(o.out_offsets, oo.p, sizeof(int64_t) * (size_t)(tot[0] + 1), hipMemcpyDeviceToHost));
-    if (rc == MRX_OK && tot[1] > 0) MRX_HIP_TRY(hipMemcpy(o.out_data, od.p, (size_t)tot[1], hipMemcpyDeviceToHost));
-    return rc;
-  }
-};
-int host_out_check(int64_t n, int64_t piece_cap, int64_t out_cap, const int64_t* offsets, const HostOut& o) {
-  if (n < 0 || piece_cap < 0 || out_cap < 0) return internal_fail(MRX_E_ARGUMENT, "n, piece_cap and out_cap must be >= 0");
-  if (!offsets || !o.out_offsets || (piece_cap > 0 && !o.owner) || (out_cap > 0 && !o.out_data))
-    return internal_fail(MRX_E_ARGUMENT, "null argument");
-  return MRX_OK;
 }
 
 }  // namespace

@@ -1,4 +1,4 @@
-// What the output-centric byte movers share (mrx_filter.hip, mrx_extract.hip): a lane owns one 16-byte block of
+// What the output-centric byte movers share (mrx_filter.hip, mrx_extract.hip, mrx_expand.hip): a lane owns one 16-byte block of
 // the output, aligned on the output ADDRESS, finds the piece that holds the block's first byte in the output's CSR and
 // fills the block from that piece's source and the following ones.  Host and device: the block assembly also runs on
 // the CPU against memcpy (tools/extract_block_check.cpp).
@@ -48,6 +48,16 @@ MRX_HD int64_t gather_last_le(const int64_t* __restrict__ off, int64_t a, int64_
     if (off[mid] <= p) a = mid; else b = mid;
   }
   return a;
+}
+
+// the last q in [a, b) with off[q] <= p (off[a] <= p), by doubling steps from a: cheap when q is close to a
+MRX_HD int64_t gather_gallop(const int64_t* __restrict__ off, int64_t a, int64_t b, int64_t p) {
+  int64_t step = 1;
+  while (a + step < b && off[a + step] <= p) {
+    a += step;
+    step <<= 1;
+  }
+  return gather_last_le(off, a, a + step < b ? a + step : b, p);
 }
 
 }  // namespace mrx

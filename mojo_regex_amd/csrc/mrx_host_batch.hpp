@@ -53,4 +53,38 @@ struct DevBuf {
   ~DevBuf() { if (p) (void)hipFree(p); }
   int alloc(size_t count) { MRX_HIP_TRY(hipMalloc((void**)&p, sizeof(T) * (count ? count : 1))); return MRX_OK; }
 };
+// the packed-batch outputs of the extract family (mrx_extract.hip, mrx_expand.hip) on host buffers: device buffers for
+// them, and what is valid copied out
+struct HostOut {
+  int64_t* owner;
+  int64_t* out_offsets;
+  uint8_t* out_data;
+  int64_t* totals;
+};
+struct DevOut {
+  DevBuf<int64_t> ow, oo, dt;
+  DevBuf<uint8_t> od;
+  int alloc(int64_t piece_cap, int64_t out_cap) {
+    if (int rc = ow.alloc((size_t)piece_cap)) return rc;
+    if (int rc = oo.alloc((size_t)piece_cap + 1)) return rc;
+    if (int rc = dt.alloc(2)) return rc;
+    return od.alloc((size_t)out_cap);
+  }
+  // rc: the device call's.  owner and offsets when the pieces fit, the bytes when they fit too
+  int copy_out(int rc, const int64_t tot[2], int64_t piece_cap, const HostOut& o) {
+    if (rc != MRX_OK && rc != MRX_E_CAPACITY) return rc;
+    if (o.totals) { o.totals[0] = tot[0]; o.totals[1] = tot[1]; }
+    if (tot[0] > piece_cap) return rc;
+    if (tot[0] > 0) MRX_HIP_TRY(hipMemcpy(o.owner, ow.p, sizeof(int64_t) * (size_t)tot[0], hipMemcpyDeviceToHost));
+    MRX_HIP_TRY(hipMemcpy(o.out_offsets, oo.p, sizeof(int64_t) * (size_t)(tot[0] + 1), hipMemcpyDeviceToHost));
+    if (rc == MRX_OK && tot[1] > 0) MRX_HIP_TRY(hipMemcpy(o.out_data, od.p, (size_t)tot[1], hipMemcpyDeviceToHost));
+    return rc;
+  }
+};
+inline int host_out_check(int64_t n, int64_t piece_cap, int64_t out_cap, const int64_t* offsets, const HostOut& o) {
+  if (n < 0 || piece_cap < 0 || out_cap < 0) return internal_fail(MRX_E_ARGUMENT, "n, piece_cap and out_cap must be >= 0");
+  if (!offsets || !o.out_offsets || (piece_cap > 0 && !o.owner) || (out_cap > 0 && !o.out_data))
+    return internal_fail(MRX_E_ARGUMENT, "null argument");
+  return MRX_OK;
+}
 }  // namespace mrx

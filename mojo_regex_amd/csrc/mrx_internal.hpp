@@ -75,6 +75,9 @@ bool handle_count_streams(const mrx_handle* h);
 bool handle_search_streams(const mrx_handle* h);
 // why the handle's count / search would be refused before any work is enqueued ("" = it would run)
 std::string handle_refusal(const mrx_handle* h);
+// MRX_OK, or the code with which mrx_captures_all_* refuses this handle's pattern (its text in mrx_last_error()):
+// host work only, so a call that runs captures_all behind its own checks can refuse before it enqueues anything
+int captures_all_refusal(const mrx_handle* h);
 void set_last_kernel(const char* name);
 // per-call scratch of the calling thread on `stream` (see mrx_release_scratch); a set call opens one scope around
 // its own allocations and the single-pattern calls it makes

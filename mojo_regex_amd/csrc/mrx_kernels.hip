@@ -7875,6 +7875,21 @@ static int capall_from_spans(const mrx_handle* h, const Layout& lay, int64_t n, 
   return MRX_OK;
 }
 
+// (mrx_internal.hpp) what captures_all refuses, for the calls that put it in front of their own work (expand)
+int mrx::captures_all_refusal(const mrx_handle* h) {
+  // the groups sub() reads for a template such as "\\1": the general form unless the pattern has the fixed-width one
+  if (h->hp.fixed_total < 0) {
+    if (!h->hp.bt.ok)
+      return fail(MRX_E_UNSUPPORTED,
+                  "sub() with \\1..\\9 on this pattern uses NFAEngine.match_next_with_groups (recursive "
+                  "backtracking matcher, nfa.mojo:500-574); its flat-program form does not cover: " +
+                      (h->hp.bt.why_not.empty() ? std::string("'.*'") : h->hp.bt.why_not));
+  } else if (int rc = check_search_supported(h)) {
+    return rc;
+  }
+  return check_lds(h);
+}
+
 static int captures_all_any(const mrx_handle* h, int64_t count, const Layout& lay_in, int64_t n, int64_t* d_prefix,
                             int32_t* d_groups, int64_t match_cap, int64_t* total, void* st, int64_t known_bytes = -1,
                             int64_t known_max = -1) {
@@ -7887,18 +7902,8 @@ static int captures_all_any(const mrx_handle* h, int64_t count, const Layout& la
   if (match_cap < 0) return fail(MRX_E_ARGUMENT, "negative match_cap");
   if (!d_prefix || (!d_groups && match_cap > 0)) return fail(MRX_E_ARGUMENT, "null output buffer");
   if ((!lay_in.data && n > 0) || (!lay_in.offsets && lay_in.stride <= 0)) return fail(MRX_E_ARGUMENT, "null batch");
-  // the groups sub() reads for a template such as "\\1": the general form unless the pattern has the fixed-width one
+  if (int rc = mrx::captures_all_refusal(h)) return rc;
   const bool general = h->hp.fixed_total < 0;
-  if (general) {
-    if (!h->hp.bt.ok)
-      return fail(MRX_E_UNSUPPORTED,
-                  "sub() with \\1..\\9 on this pattern uses NFAEngine.match_next_with_groups (recursive "
-                  "backtracking matcher, nfa.mojo:500-574); its flat-program form does not cover: " +
-                      (h->hp.bt.why_not.empty() ? std::string("'.*'") : h->hp.bt.why_not));
-  } else if (int rc = check_search_supported(h)) {
-    return rc;
-  }
-  if (int rc = check_lds(h)) return rc;
   if (int rc = ensure_device(h)) return rc;
   hipStream_t s = (hipStream_t)st;
   const int64_t* off = lay_in.offsets;
