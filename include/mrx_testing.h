@@ -84,6 +84,15 @@ void mrx_debug_multiwalk(int mode);
 /* Placement experiments (profiles/r03_scan_forms.md): the streaming findall's record stream begins `bytes` (a multiple
  * of 16) behind the start of its scratch allocation.  Results are the same. */
 void mrx_debug_rec_skew(int64_t bytes);
+/* The three-launch findall of texts of at most 1 KiB at a 16-byte aligned fixed pitch (no offsets, no rows / bits /
+ * fused / dynamic / split / pieces form) writes its event records in 12 bytes instead of 16: {F of the even group, F of
+ * the odd group, start | before << 10 | pair << 20 | lane << 26} (csrc/mrx_rec12.hpp).  0 = never (16-byte records
+ * everywhere), anything else = by that rule (default).  Results are the same.  Environment: MRX_REC12=0. */
+void mrx_debug_rec12(int mode);
+/* The packing of that record's third word on the host, for tests without a GPU: packs the four fields and writes what
+ * the extractors give back to out = {start, pair, lane, before}.  Returns 0, or -1 when a field is out of range
+ * (start 0..1023, pair 0..32, lane 0..63, before 0..1023) or out is NULL. */
+int mrx_testing_rec12_roundtrip(int start, int pair, int lane, int before, int32_t out[4]);
 /* include/mrx_comm.h, padded form of mrx_allgatherv_spans: its two device steps on buffers the caller fills as
  * ncclAllGather would have, so that the multi-rank arithmetic can be checked on one GPU.
  * meta_all: meta_stride int64 words per rank -- 2: {texts, spans}; 4: {texts (-1: that rank's arguments were invalid),

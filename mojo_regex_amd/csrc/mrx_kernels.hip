@@ -32,6 +32,7 @@
 #include "mrx_host_batch.hpp"
 #include "mrx_internal.hpp"
 #include "mrx_lookback.hpp"
+#include "mrx_rec12.hpp"
 
 using namespace mrx;
 
@@ -1981,6 +1982,8 @@ __device__ __forceinline__ void fused_finish(const FusedArgs& fz, const EvRec* _
 // its text), so from there on the walk is the one the whole text's walk takes.  The events of its
 // first vskip[v] & 0x7FFFFFFF bytes belong to the piece before it and are dropped; bit 31 of vskip
 // marks the last piece of a text (the only one that may end a match at the end of the text).
+// REC32 = 2: the 12-byte records of mrx_rec12.hpp, {F even, F odd, meta} at a 12-byte pitch (`recs` is then a dword
+//           stream, `rec_row` = rec12_row_len slots per text).  ST_RECORDS at an aligned fixed pitch only.
 template <int MODE, int CH, int AUTO, int CSR, int VIRT = 0, int REC32 = 0>
 #ifndef MRX_FUSED_WAVES
 #define MRX_FUSED_WAVES 4
@@ -2001,6 +2004,8 @@ __global__ __launch_bounds__(64 * kStreamWaves, (MODE == ST_FUSED ? MRX_FUSED_WA
   constexpr bool ROWS = MODE == ST_ROWS;
   static_assert(!(MODE == ST_FUSED && VIRT), "pieces of long texts keep the three-launch form");
   static_assert(!ROWS || (!CSR && !VIRT && !REC32), "event rows: texts at a fixed aligned pitch");
+  constexpr bool REC12 = REC32 == 2;
+  static_assert(!REC12 || (MODE == ST_RECORDS && !CSR && !VIRT), "12-byte records: the three-launch form at a fixed aligned pitch");
   constexpr int kChunk = CH;
   constexpr int kRowPitch = CH + 16;      // +16: the per-lane 16-byte read-back is bank-conflict free
   constexpr int LPR = CH / 16;            // lanes that cover one text row in a load instruction
@@ -2192,6 +2197,7 @@ __global__ __launch_bounds__(64 * kStreamWaves, (MODE == ST_FUSED ? MRX_FUSED_WA
     EvRec* wave_recs = (MODE == ST_RECORDS)
         ? recs + ((CSR && offsets) ? rec_region_start(offsets[base_text], w) : base_text * rec_row)
         : (MODE == ST_FUSED) ? recs + (((int64_t)blockIdx.x * kStreamWaves + wave) * 2 + half) * fz.rec_cap : nullptr;
+    uint32_t* const wave_recs12 = REC12 ? (uint32_t*)recs + 3 * (base_text * rec_row) : nullptr;   // (rec_row: 12-byte slots)
 
     if (MODE == ST_FIRST) {
       // Probe: most anchored walks end within a few bytes.  Every lane reads the first 16 bytes
@@ -2378,8 +2384,12 @@ __global__ __launch_bounds__(64 * kStreamWaves, (MODE == ST_FUSED ? MRX_FUSED_WA
         if (RECS && REC32) {
           if ((g & 1) == 0) {
             F_even = F;
+            if (REC12) {   // (no frame: gbase is a multiple of 32 here)
+              meta_even = rec12_pack((uint32_t)start, (uint32_t)gbase >> 5, (uint32_t)lane, (uint32_t)cnt);
+            } else {
             sp_even = (uint32_t)start | ((uint32_t)(gbase + kRecPosBias) << 16);
             meta_even = ((uint32_t)lane << 26) | ((uint32_t)cnt & kRecBeforeMask);
+            }
           } else {
             const bool any = ((F_even | F) & 0xAAAAAAAAu) != 0u;
             const uint64_t has = __ballot(any);
@@ -2387,6 +2397,10 @@ __global__ __launch_bounds__(64 * kStreamWaves, (MODE == ST_FUSED ? MRX_FUSED_WA
               if (any) {
                 const int rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(has >> 32),
                                                            __builtin_amdgcn_mbcnt_lo((uint32_t)has, 0));
+                if (REC12) {   // three dwords on a 4-byte aligned address
+                  uint32_t* const d = wave_recs12 + 3 * (wrec + rank);
+                  d[0] = F_even; d[1] = F; d[2] = meta_even;
+                } else
                 *(uint4*)(wave_recs + wrec + rank) = make_uint4(F_even, F, sp_even, meta_even);
               }
               wrec += __builtin_popcountll(has);
@@ -2466,6 +2480,12 @@ __global__ __launch_bounds__(64 * kStreamWaves, (MODE == ST_FUSED ? MRX_FUSED_WA
           EvRec r;
           r.F = 2u; r.start = start; r.pos_base = my_len;  // EMIT at byte 0 of a group placed at len
           r.meta = ((uint32_t)lane << 26) | ((uint32_t)cnt & kRecBeforeMask);
+          if (REC12) {   // the single EMIT bit at byte my_len & 31 of pair my_len >> 5
+            const uint32_t bit = 2u << (2 * (my_len & 15));
+            uint32_t* const d = wave_recs12 + 3 * (wrec + rank);
+            d[0] = (my_len & 16) ? 0u : bit; d[1] = (my_len & 16) ? bit : 0u;
+            d[2] = rec12_pack((uint32_t)start, (uint32_t)my_len >> 5, (uint32_t)lane, (uint32_t)cnt);
+          } else
           if (REC32) *(uint4*)(wave_recs + wrec + rank) = make_uint4(2u, 0u, (uint32_t)start | ((uint32_t)(my_len + kRecPosBias) << 16), r.meta);
           else
           wave_recs[wrec + rank] = r;
@@ -2945,7 +2965,9 @@ constexpr int kScanTile = kScanBlock * kScanItems;
 // (16-bit positions) take 3072 -- config 4's wavefronts hold 2 600 spans and needed two passes over their records
 // (findall 0.505 -> 0.452 ms), config 2 is unchanged, 256-byte texts (config 3) lose 3 % to the lower occupancy and
 // keep 2048.
-template <bool PACK16, bool VBASE = false, bool REC32 = false, bool DYN = false, int TILE = kDecodeTile>
+// REC12 (with REC32): the 12-byte records of mrx_rec12.hpp -- `recs` is a dword stream, `rec_row` counts 12-byte slots, a
+// record arrives as three dwords {F even, F odd, meta}; everything behind the unpacking is the REC32 form's.
+template <bool PACK16, bool VBASE = false, bool REC32 = false, bool DYN = false, int TILE = kDecodeTile, bool REC12 = false>
 __global__ __launch_bounds__(kBlock) void k_decode(int64_t n, const int32_t* __restrict__ wave_nrecs,
                                                    const EvRec* __restrict__ recs, int64_t rec_row,
                                                    const int64_t* __restrict__ offsets,
@@ -2962,6 +2984,7 @@ __global__ __launch_bounds__(kBlock) void k_decode(int64_t n, const int32_t* __r
   // base: spans of the texts in front of this launch's (the second half of a split findall, see findall_split)
   static_assert(!(PACK16 && VBASE), "text-relative positions of a long text do not fit 16 bits");
   static_assert(!(DYN && VBASE), "pieces are not handed out dynamically");
+  static_assert(!REC12 || (REC32 && PACK16 && !VBASE && !DYN), "12-byte records: short texts at a fixed aligned pitch");
   using Slot = typename std::conditional<PACK16, uint32_t, int2>::type;
   __shared__ Slot tile_all[kBlock / 64][TILE];
   __shared__ int dense_upto[kBlock / 64][64];   // dense path: spans of each of the wavefront's texts expanded so far
@@ -3029,6 +3052,7 @@ __global__ __launch_bounds__(kBlock) void k_decode(int64_t n, const int32_t* __r
     const int total_recs = wave_nrecs[w];
     const EvRec* wave_recs = recs + (DYN ? rec_region_dyn(offsets[first], w)
                                          : offsets ? rec_region_start(offsets[first], w) : first * rec_row);
+    const uint32_t* wave_recs12 = REC12 ? (const uint32_t*)recs + 3 * (first * rec_row) : nullptr;
     const int my_vb = (VBASE && i < n) ? vbase[i] : 0;
     if (total_spans > kDecodeDirect) {
       // dense matches: the tile passes would re-read the stream total_spans / kDecodeTile times.  One pass instead.
@@ -3049,8 +3073,13 @@ __global__ __launch_bounds__(kBlock) void k_decode(int64_t n, const int32_t* __r
           const int o = j + u * 64 + lane;
           rr[u].F = 0; rr[u].start = 0; rr[u].pos_base = 0; rr[u].meta = 0;
           if (o < total_recs) {   // last use of the record: non-temporal
+            if (REC12) {   // {F even, F odd, meta}: three dwords on a 4-byte aligned address
+              const uint32_t* q_ = wave_recs12 + 3 * o;
+              rr[u].F = mrx_ldg32(q_); rr[u].start = (int32_t)mrx_ldg32(q_ + 1); rr[u].meta = mrx_ldg32(q_ + 2);
+            } else {
             const uint4 q_ = mrx_ldg((const uint4*)(wave_recs + o));
             rr[u].F = q_.x; rr[u].start = (int32_t)q_.y; rr[u].pos_base = (int32_t)q_.z; rr[u].meta = q_.w;
+            }
           }
         }
         if (kRowCap > 0) {
@@ -3066,11 +3095,11 @@ __global__ __launch_bounds__(kBlock) void k_decode(int64_t n, const int32_t* __r
           const int rel_t = DYN ? rel_lds[r.meta >> kTextShift] : __shfl(my_rel, txt);
           if (VBASE) { const int vb = __shfl(my_vb, (int)(r.meta >> 26)); r.start += vb; r.pos_base += vb; }
           const int done_r = kRowCap > 0 ? __shfl(done_t, txt) : 0;   // spans of my record's text already written
-          int within = (int)(r.meta & kBefore);                       // index of my record's first span within its text
+          int within = REC12 ? rec12_before(r.meta) : (int)(r.meta & kBefore);   // index of my record's first span within its text
           int64_t dst = pre0 + rel_t + within;
           uint32_t Fw = r.F;
-          int pb = REC32 ? (int)((uint32_t)r.pos_base >> 16) - kRecPosBias : r.pos_base;
-          int rstart = REC32 ? (int)((uint32_t)r.pos_base & 0xFFFFu) : r.start;
+          int pb = REC12 ? 32 * rec12_pair(r.meta) : REC32 ? (int)((uint32_t)r.pos_base >> 16) - kRecPosBias : r.pos_base;
+          int rstart = REC12 ? rec12_start(r.meta) : REC32 ? (int)((uint32_t)r.pos_base & 0xFFFFu) : r.start;
 #pragma unroll
           for (int half = 0; half < (REC32 ? 2 : 1); ++half) {
             uint32_t em = Fw & 0xAAAAAAAAu;
@@ -3131,8 +3160,13 @@ __global__ __launch_bounds__(kBlock) void k_decode(int64_t n, const int32_t* __r
           const int o = j + u * 64 + lane;
           rr[u].F = 0; rr[u].start = 0; rr[u].pos_base = 0; rr[u].meta = 0;
           if (o < total_recs) {   // last use of the record: non-temporal
+            if (REC12) {   // {F even, F odd, meta}: three dwords on a 4-byte aligned address
+              const uint32_t* q_ = wave_recs12 + 3 * o;
+              rr[u].F = mrx_ldg32(q_); rr[u].start = (int32_t)mrx_ldg32(q_ + 1); rr[u].meta = mrx_ldg32(q_ + 2);
+            } else {
             const uint4 q_ = mrx_ldg((const uint4*)(wave_recs + o));
             rr[u].F = q_.x; rr[u].start = (int32_t)q_.y; rr[u].pos_base = (int32_t)q_.z; rr[u].meta = q_.w;
+            }
           }
         }
 #pragma unroll
@@ -3140,11 +3174,11 @@ __global__ __launch_bounds__(kBlock) void k_decode(int64_t n, const int32_t* __r
           EvRec r = rr[u];
           const int rel_t = DYN ? rel_lds[r.meta >> kTextShift] : __shfl(my_rel, (int)(r.meta >> 26));
           if (VBASE) { const int vb = __shfl(my_vb, (int)(r.meta >> 26)); r.start += vb; r.pos_base += vb; }
-          int dst = rel_t + (int)(r.meta & kBefore) - tb;
+          int dst = rel_t + (REC12 ? rec12_before(r.meta) : (int)(r.meta & kBefore)) - tb;
           // REC32: {F even, F odd, start | (pos + 16) << 16, meta} -- two event words per record
           uint32_t Fw = r.F;
-          int pb = REC32 ? (int)((uint32_t)r.pos_base >> 16) - kRecPosBias : r.pos_base;
-          int rstart = REC32 ? (int)((uint32_t)r.pos_base & 0xFFFFu) : r.start;
+          int pb = REC12 ? 32 * rec12_pair(r.meta) : REC32 ? (int)((uint32_t)r.pos_base >> 16) - kRecPosBias : r.pos_base;
+          int rstart = REC12 ? rec12_start(r.meta) : REC32 ? (int)((uint32_t)r.pos_base & 0xFFFFu) : r.start;
 #pragma unroll
           for (int half = 0; half < (REC32 ? 2 : 1); ++half) {
             uint32_t em = Fw & 0xAAAAAAAAu;
@@ -5041,8 +5075,10 @@ static bool code_columns_on() {
 template <int MODE>
 void launch_stream(const mrx_handle* h, const Layout& lay, int64_t n, int32_t* d_counts, int32_t* d_nrecs,
                    EvRec* d_recs, int64_t rec_row, int32_t* d_s, int32_t* d_e, hipStream_t s,
-                   const int32_t* d_vlen = nullptr, const uint32_t* d_vskip = nullptr, bool rec32 = false,
+                   const int32_t* d_vlen = nullptr, const uint32_t* d_vskip = nullptr, int rec32 = 0,
                    const FusedArgs* fused = nullptr, int fused_grid = 0) {
+  // rec32: 0 = a record per 16-byte group, 1 = per pair of groups, 2 = per pair in 12 bytes (ST_RECORDS on the aligned
+  // fixed pitch only: d_recs is then the dword stream, rec_row its 12-byte slots per text)
   const DevPlan& p = h->hp.dev;
   // (ST_FUSED: one record region per wavefront of the caller's grid)
   const int g = MODE == ST_FUSED ? fused_grid : wave_grid(n, kStreamWaves);
@@ -5061,6 +5097,9 @@ void launch_stream(const mrx_handle* h, const Layout& lay, int64_t n, int32_t* d
                      d_nrecs, d_recs, rec_row, d_s, d_e, (const int32_t*)nullptr, (const uint32_t*)nullptr, fzv)
 #define MRX_LAUNCH(AUTO, CSR)                                                                     \
   do {                                                                                            \
+    if constexpr (MODE == ST_RECORDS && CSR == 0) {                                               \
+      if (rec32 == 2) { MRX_LAUNCH_R(AUTO, CSR, 2); break; }                                      \
+    }                                                                                             \
     if constexpr (MODE == ST_RECORDS || MODE == ST_FUSED) {                                       \
       if (rec32) MRX_LAUNCH_R(AUTO, CSR, 1); else MRX_LAUNCH_R(AUTO, CSR, 0);                     \
     } else MRX_LAUNCH_R(AUTO, CSR, 0);                                                            \
@@ -5318,6 +5357,9 @@ std::atomic<int> g_split_findall{env_int("MRX_FINDALL_SPLIT", 0)};
 // findall by event rows (ST_ROWS, k_decode_rows): 0 = when the handle's last batch was full of matches, 1 = whenever the
 // batch has the shape, 2 = never (MRX_DENSE_ROWS / mrx_debug_dense_rows)
 std::atomic<int> g_dense_rows{env_int("MRX_DENSE_ROWS", 0)};
+// 12-byte event records (mrx_rec12.hpp) for the three-launch findall of texts of at most 1 KiB at an aligned fixed pitch:
+// 0 = never (16-byte records everywhere), anything else = by that rule (MRX_REC12 / mrx_debug_rec12)
+std::atomic<int> g_rec12{env_int("MRX_REC12", 1)};
 constexpr int64_t kSplitMinTexts = 1 << 18;
 struct SideStream {
   hipStream_t side = nullptr;
@@ -5537,6 +5579,7 @@ struct FindallJob {
   unsigned long long* d_ctrl = nullptr;   // its ticket word, error word and descriptors
   int32_t* d_blimit = nullptr;            // bitset NFA: per-text limits of the first pass
   bool rec32 = false;              // streaming path: one record per two groups (positions fit 16 bits)
+  bool rec12 = false;              // ... in 12 bytes (mrx_rec12.hpp): the plain three launches, aligned fixed pitch, texts <= 1 KiB
   int64_t max_text = int64_t(1) << 40;    // longest text of the batch, where known
   bool req_wave = false;           // the stepper's route on the wavefront-per-text kernel
   bool mwalk_two_pass = false;     // multi-walk plan: count pass + emit pass instead of slot rows
@@ -5726,12 +5769,19 @@ struct FindallJob {
         return rc;
     } else {
     const int64_t skew = g_rec_skew.load(std::memory_order_relaxed);   // (mrx_debug_rec_skew: placement experiments)
-    HIP_TRY(scratch_alloc((void**)&d_recs, sizeof(EvRec) * nrec + (size_t)skew, s));
+    rec12 = g_rec12 != 0 && rec32 && !lay.offsets && strided_fast(lay) && max_text <= kRec12MaxLen;
+    size_t rec_bytes = sizeof(EvRec) * nrec;
+    if (rec12) {   // a wavefront's region: 64 rows of max_text / 32 + 2 slots of 12 bytes (26112 B for 1 KiB texts)
+      rec_row = rec12_row_len(max_text);
+      rec_bytes = (size_t)12 * (size_t)rec_row * (size_t)n;
+    }
+    HIP_TRY(scratch_alloc((void**)&d_recs, rec_bytes + (size_t)skew, s));
     d_recs = (EvRec*)((uint8_t*)d_recs + skew);
     HIP_TRY(scratch_alloc((void**)&d_nrecs, sizeof(int32_t) * 2 * nw, s));  // records | matches per wavefront
     HIP_TRY(scratch_alloc((void**)&d_wbase, sizeof(int64_t) * (nw + 1), s));
     ScanTimer tm(s);
-    launch_stream<ST_RECORDS>(h, lay, n, d_counts, d_nrecs, d_recs, rec_row, nullptr, nullptr, s, nullptr, nullptr, rec32);
+    launch_stream<ST_RECORDS>(h, lay, n, d_counts, d_nrecs, d_recs, rec_row, nullptr, nullptr, s, nullptr, nullptr,
+                              rec12 ? 2 : (int)rec32);
     g_last_kernel = "k_stream_findall";
     HIP_TRY(hipGetLastError());
     tm.stop();
@@ -5778,7 +5828,15 @@ struct FindallJob {
         hipLaunchKernelGGL((k_decode<false, false, false, true>), dg, db, 0, s, n, d_nrecs, d_recs, rec_row, lay.offsets, d_counts,
                            d_wbase, d_tsum, d_prefix, d_spans, span_cap, p.st_fixed_len, d_total);
     } else
-    if (pack16 && rec32 && max_text >= 768)
+    if (rec12 && max_text >= 768)
+      hipLaunchKernelGGL((k_decode<true, false, true, false, 3072, true>), dim3(env_knobs().decode_grid > 0 ? env_knobs().decode_grid : grid_for(n, kBlock) * 2), dim3(kBlock), 0, s, n, d_nrecs, d_recs,
+                         rec_row, lay.offsets, d_counts, d_wbase, d_tsum, d_prefix, d_spans, span_cap, p.st_fixed_len,
+                         d_total, (const int32_t*)nullptr, (const int64_t*)nullptr, env_knobs().decode_reverse);
+    else if (rec12)
+      hipLaunchKernelGGL((k_decode<true, false, true, false, kDecodeTile, true>), dim3(grid_for(n, kBlock) * 2), dim3(kBlock), 0, s, n, d_nrecs, d_recs,
+                         rec_row, lay.offsets, d_counts, d_wbase, d_tsum, d_prefix, d_spans, span_cap, p.st_fixed_len,
+                         d_total);
+    else if (pack16 && rec32 && max_text >= 768)
       hipLaunchKernelGGL((k_decode<true, false, true, false, 3072>), dim3(env_knobs().decode_grid > 0 ? env_knobs().decode_grid : grid_for(n, kBlock) * 2), dim3(kBlock), 0, s, n, d_nrecs, d_recs,
                          rec_row, lay.offsets, d_counts, d_wbase, d_tsum, d_prefix, d_spans, span_cap, p.st_fixed_len,
                          d_total, (const int32_t*)nullptr, (const int64_t*)nullptr, env_knobs().decode_reverse);
@@ -8111,6 +8169,15 @@ const char* mrx_last_kernel_name(void) { return g_last_kernel; }
 void mrx_debug_force_generic(int on) { g_force_generic = on < 0 ? 0 : on > 2 ? 2 : on; }
 void mrx_debug_long_text_kernels(int mode) { g_long_text_mode = mode < 0 ? 0 : mode > 3 ? 0 : mode; }
 void mrx_debug_rec_skew(int64_t bytes) { g_rec_skew = bytes < 0 ? 0 : (bytes & ~int64_t(15)); }
+void mrx_debug_rec12(int mode) { g_rec12 = mode != 0; }
+int mrx_testing_rec12_roundtrip(int start, int pair, int lane, int before, int32_t out[4]) {
+  if (start < 0 || start >= kRec12MaxLen || pair < 0 || pair > kRec12MaxLen / 32 || lane < 0 || lane > 63 || before < 0 ||
+      before >= kRec12MaxLen || !out)
+    return -1;
+  const uint32_t m = rec12_pack((uint32_t)start, (uint32_t)pair, (uint32_t)lane, (uint32_t)before);
+  out[0] = rec12_start(m); out[1] = rec12_pair(m); out[2] = rec12_lane(m); out[3] = rec12_before(m);
+  return 0;
+}
 void mrx_debug_fused_findall(int mode) { g_fused = mode < 0 ? 0 : mode > 2 ? 0 : mode; }
 void mrx_debug_stream_bits(int on) { mrx::stream_bits_set_mode(on); }
 void mrx_debug_stream_bits_trace(int64_t* d_trace) { mrx::stream_bits_set_trace(d_trace); }

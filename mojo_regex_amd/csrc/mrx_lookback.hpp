@@ -21,6 +21,13 @@ __device__ __forceinline__ uint4 mrx_ldg(const uint4* p) {
 #endif
 }
 #define MRX_LDG(P) mrx_ldg(P)
+__device__ __forceinline__ uint32_t mrx_ldg32(const uint32_t* p) {
+#if MRX_NT_LOADS
+  return __builtin_nontemporal_load(p);
+#else
+  return *p;
+#endif
+}
 typedef int mrx_i32x2 __attribute__((ext_vector_type(2)));
 // result spans are written once and not read again by this library
 __device__ __forceinline__ void mrx_stg_span(int32_t* p, int a, int b) {
