@@ -575,6 +575,55 @@ int mrx_expand_strided_dev(const mrx_handle* h, const char* tpl, size_t tpl_len,
                            int64_t* d_owner, int64_t* d_out_offsets, int64_t match_cap, uint8_t* d_out_data, int64_t out_cap,
                            int64_t* d_totals, int64_t* totals, void* stream);
 
+/* ---- distinct: the unique texts of a batch and their counts, grouped on the device ----
+ * sort | uniq -c without the sort; dict.fromkeys(texts) and collections.Counter(texts).  No pattern is involved: the call
+ * takes any batch, typically the pieces that extract left on the device.  Two texts are EQUAL when their lengths and
+ * their bytes are equal (the empty text is a value like any other).  The groups of equal texts are numbered in the
+ * order of their first occurrence.  With n texts and u groups, all on the device:
+ *   d_group_of int64[n]         the group of text i
+ *   d_first int64[n]            [0, u): the lowest index of a text of group g; strictly increasing
+ *   d_counts int64[n]           [0, u): the number of texts in group g; they add up to n
+ *   d_out_offsets int64[n + 1]  [0, u]: the CSR of the values; value g is text d_first[g]; d_out_offsets[u] = bytes
+ *   d_out_data uint8[out_cap]   the values back to back; any alignment
+ *   d_totals int64[2]           {u, bytes}
+ * Entries of d_first, d_counts and d_out_offsets past those are unspecified.  The values are a CSR batch whatever the
+ * input form, and the input of a following call as they stand (with bytes and the input's longest text as known bounds).
+ * The result is a pure function of the input, bit for bit: which lane wins a race inside the kernels decides only
+ * which member of a group stands for it in scratch, never an output.  A hash decides nothing by itself: two texts share
+ * a group only after their bytes have been compared.
+ * No byte of d_out_data at or past bytes, nor at or past out_cap, is ever written, and no element of the n-sized arrays
+ * at or past n (n + 1 for d_out_offsets).
+ * Capacity: u <= n, so arrays of n always fit, and out_cap = the input's byte count always suffices.  When bytes >
+ * out_cap, d_group_of, d_first, d_counts, d_out_offsets and d_totals are still complete and correct, NO value byte is
+ * written, and a call with `totals` returns MRX_E_CAPACITY with totals filled (filter's contract).
+ * totals (host, int64[2], may be NULL) receives d_totals: the call then reads back once, at its end -- no host decision
+ * sits between its kernels.  With totals == NULL nothing is read back and the call returns without synchronising; the
+ * caller checks d_totals[1] against its out_cap once the stream has drained.
+ * The _known form takes a CSR batch's d_offsets[n] and longest text as mrx_filter_known_dev does; they choose between
+ * filter's two byte movers and size nothing.  Upper bounds are fine.
+ * n == 0 gives u = bytes = 0 and d_out_offsets = {0}.  MRX_E_ARGUMENT, before any device call: negative n, out_cap or
+ * known bounds; a bad pitch; a null required pointer (d_offsets, d_out_offsets, d_totals; d_group_of, d_first and
+ * d_counts when n > 0; d_out_data when out_cap > 0); n >= 2^31 (a table slot keeps a text's index in 32 bits).
+ * The table is open addressing at a load of at most one half, probed at most table-size times: a probe that ran out
+ * (it cannot, at that load) is reported as MRX_E_ARGUMENT by a call with `totals`, and as d_totals = {-1, -1} with no
+ * byte written otherwise.
+ * Reads: as filter, a text's bytes are fetched as the aligned 16-byte words that hold them, so up to 15 bytes in front
+ * of a text's first byte and behind its last one are read (never used: they are masked before the hash and the
+ * comparison see them); no word is read for an empty text.
+ * Scratch: 60 bytes per text (hash 8, representative 4, first index and count of a representative 8 + 8, flags and
+ * kept lengths 8 + 8, the two scans 8 + 8), the scans' block sums and the table, 8 bytes times the power of two >= 2 n
+ * (16 to 32 bytes per text), returned to the arena when the call returns. */
+int mrx_distinct_dev(const uint8_t* d_data, const int64_t* d_offsets, int64_t n, int64_t* d_group_of, int64_t* d_first,
+                     int64_t* d_counts, int64_t* d_out_offsets, uint8_t* d_out_data, int64_t out_cap, int64_t* d_totals,
+                     int64_t* totals, void* stream);
+int mrx_distinct_known_dev(const uint8_t* d_data, const int64_t* d_offsets, int64_t n, int64_t end_offset,
+                           int64_t max_text_len, int64_t* d_group_of, int64_t* d_first, int64_t* d_counts,
+                           int64_t* d_out_offsets, uint8_t* d_out_data, int64_t out_cap, int64_t* d_totals,
+                           int64_t* totals, void* stream);
+int mrx_distinct_strided_dev(const uint8_t* d_data, int64_t stride, const int32_t* d_lens, int32_t len, int64_t n,
+                             int64_t* d_group_of, int64_t* d_first, int64_t* d_counts, int64_t* d_out_offsets,
+                             uint8_t* d_out_data, int64_t out_cap, int64_t* d_totals, int64_t* totals, void* stream);
+
 /* ---- host-buffer convenience wrappers (copy in, run, copy out) -------------- */
 /* mrx_gather_spans_dev / mrx_extract_dev on host buffers: owner int64[piece_cap], out_offsets int64[piece_cap + 1],
  * out_data uint8[out_cap], totals int64[2] = {pieces, bytes} (may be NULL); spans holds prefix[n] rows.  piece_prefix
@@ -602,6 +651,11 @@ int mrx_filter_batch(const mrx_handle* h, uint32_t flags, const uint8_t* data, c
                      int64_t* kept_idx, int64_t* out_offsets, uint8_t* out_data, int64_t out_cap, int64_t* totals);
 int mrx_set_filter_batch(const mrx_set* s, uint32_t flags, const uint8_t* data, const int64_t* offsets, int64_t n,
                          int64_t* kept_idx, int64_t* out_offsets, uint8_t* out_data, int64_t out_cap, int64_t* totals);
+/* mrx_distinct_dev on host buffers: group_of, first and counts int64[n], out_offsets int64[n + 1], out_data
+ * uint8[out_cap], totals int64[2] = {u, bytes} (may be NULL).  group_of[0, n), first[0, u), counts[0, u) and
+ * out_offsets[0, u] are copied out, out_data only when all of it fits (MRX_E_CAPACITY otherwise). */
+int mrx_distinct_batch(const uint8_t* data, const int64_t* offsets, int64_t n, int64_t* group_of, int64_t* first,
+                       int64_t* counts, int64_t* out_offsets, uint8_t* out_data, int64_t out_cap, int64_t* totals);
 int mrx_match_first_batch(const mrx_handle* h, const uint8_t* data,
                           const int64_t* offsets, int64_t n, int32_t* start,
                           int32_t* end);

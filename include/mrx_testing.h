@@ -127,6 +127,13 @@ void mrx_debug_extract_grid(int workgroups);
 /* Expand (include/mrx.h): the byte mover reports itself as "k_expand_gather"; its grid is sized and capped as extract's
  * (mrx_debug_extract_grid), by a switch of its own.  0 (default) = no cap.  Results are the same. */
 void mrx_debug_expand_grid(int workgroups);
+/* Distinct (include/mrx.h): `mask` is and-ed onto every text's hash before the table sees it; all ones (default) = the
+ * hash as it is.  0 puts every text into one probe chain with equal tags, so that every decision is a byte comparison
+ * (the probe is then quadratic: keep n small); 3 gives four chains.  Results are the same. */
+void mrx_debug_distinct_hash_mask(uint64_t mask);
+/* Distinct: `workgroups` > 0 caps the grids of its own kernels (4 wavefronts each), so that a test makes one wavefront
+ * run several rounds without a batch of millions of texts.  0 (default) = no cap.  Results are the same. */
+void mrx_debug_distinct_grid(int workgroups);
 /* Bytes of device memory the calling thread's scratch arenas hold (see mrx_release_scratch). */
 size_t mrx_debug_scratch_bytes(void);
 /* ... and how many of them are handed out and not yet rewound.  Scratch belongs to the call's scope, so between calls

@@ -26,6 +26,8 @@ argument meaning, a *batch* of texts instead of one text:
                                                   bytes as a new packed batch
     Match groups into a template, per match       expand / CompiledRegex.expand / DeviceBatch.expand_spans:
                                                   one templated record per match as a new packed batch
+    (none: a Dict[String, Int] on the host)       distinct / value_counts / DeviceBatch.distinct /
+                                                  CompiledRegex.value_counts: the unique texts and their counts
 
 All matching runs in the HIP kernels of libmrx_hip.so.  There is no CPU
 fallback: if the library is missing or no GPU is usable, calls raise.
@@ -43,6 +45,7 @@ from .api import (  # noqa: F401
     clear_regex_cache,
     compile_regex,
     compile_set,
+    distinct,
     expand,
     filter_texts,
     findall,
@@ -54,4 +57,5 @@ from .api import (  # noqa: F401
     search,
     split,
     sub,
+    value_counts,
 )

@@ -234,6 +234,16 @@ def load_library():
         "mrx_expand_batch": (C.c_int, [H, C.c_char_p, C.c_size_t, C.c_int64, u8p, i64p, C.c_int64, i64p, i64p, i64p,
                                        C.c_int64, u8p, C.c_int64, C.c_void_p]),
         "mrx_debug_expand_grid": (None, [C.c_int]),
+        # distinct: the batch | (group_of, first, counts, out_offsets, out_data, out_cap, d_totals, totals, stream)
+        "mrx_distinct_dev": (C.c_int, [u8p, i64p, C.c_int64, i64p, i64p, i64p, i64p, u8p, C.c_int64, i64p, C.c_void_p,
+                                       C.c_void_p]),
+        "mrx_distinct_known_dev": (C.c_int, [u8p, i64p, C.c_int64, C.c_int64, C.c_int64, i64p, i64p, i64p, i64p, u8p,
+                                             C.c_int64, i64p, C.c_void_p, C.c_void_p]),
+        "mrx_distinct_strided_dev": (C.c_int, [u8p, C.c_int64, i32p, C.c_int32, C.c_int64, i64p, i64p, i64p, i64p, u8p,
+                                               C.c_int64, i64p, C.c_void_p, C.c_void_p]),
+        "mrx_distinct_batch": (C.c_int, [u8p, i64p, C.c_int64, i64p, i64p, i64p, i64p, u8p, C.c_int64, C.c_void_p]),
+        "mrx_debug_distinct_hash_mask": (None, [C.c_uint64]),
+        "mrx_debug_distinct_grid": (None, [C.c_int]),
         "mrx_debug_set_route": (None, [C.c_int]),
         "mrx_testing_set_run": (C.c_int, [H, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_int32)]),
     }
@@ -267,6 +277,7 @@ EXPORTED_SYMBOLS = [
     "mrx_extract_dev", "mrx_extract_known_dev", "mrx_extract_strided_dev", "mrx_extract_batch",
     "mrx_expand_spans_dev", "mrx_expand_spans_strided_dev", "mrx_expand_spans_batch",
     "mrx_expand_dev", "mrx_expand_strided_dev", "mrx_expand_batch",
+    "mrx_distinct_dev", "mrx_distinct_known_dev", "mrx_distinct_strided_dev", "mrx_distinct_batch",
 ]
 TESTING_SYMBOLS = [
     "mrx_timing_reset", "mrx_timing_enable", "mrx_timing_scan_ms", "mrx_last_kernel_name",
@@ -275,7 +286,7 @@ TESTING_SYMBOLS = [
     "mrx_debug_fused_findall", "mrx_debug_stream_bits", "mrx_debug_stream_bits_trace", "mrx_debug_dynamic_texts", "mrx_debug_subs_group",
     "mrx_debug_split_findall", "mrx_debug_dense_rows", "mrx_debug_tries_always", "mrx_debug_chain_sub_general", "mrx_testing_emptywalk_findall", "mrx_debug_litscan_pieces", "mrx_debug_multiwalk", "mrx_debug_rec_skew", "mrx_testing_comm_shift", "mrx_testing_comm_compact",
     "mrx_debug_set_route", "mrx_testing_set_run", "mrx_debug_filter_form", "mrx_debug_extract_grid",
-    "mrx_debug_expand_grid",
+    "mrx_debug_expand_grid", "mrx_debug_distinct_hash_mask", "mrx_debug_distinct_grid",
 ]
 # (hooks with a digit in their name, listed apart: the header scan of tests/test_host_tables.py reads [a-z_] names)
 TESTING_SYMBOLS_NUMBERED = ["mrx_debug_rec12", "mrx_testing_rec12_roundtrip"]
@@ -501,6 +512,57 @@ class DeviceBatch:
                 (_ptr(prefix), _ptr(rows), int(rows.shape[1]), template, len(template), pcap, _ptr(pb[0]), _ptr(pb[1]),
                  _ptr(out), ocap, _ptr(d_totals), totals, stream)),
             grow_pieces=piece_cap is None, grow_out=out_cap is None))
+
+    def distinct(self, out_cap: Optional[int] = None):
+        """The unique texts of this batch and how often each occurs (include/mrx.h, mrx_distinct_dev): (values
+        DeviceBatch, counts int64[u], group_of int64[n], first int64[u]), device tensors.  Texts are equal when their
+        lengths and bytes are; the groups are numbered by first occurrence, the order of dict.fromkeys(texts) and of
+        collections.Counter(texts).  Value g is text first[g], counts[g] texts equal it, and group_of[i] is the group
+        of text i.  `values` is a CSR batch, trimmed by filter's quarter rule as counts and first are, with known bounds
+        where this batch knows its longest text.  out_cap defaults to this batch's bytes, which always suffice; a
+        smaller one of the caller's that does not hold the values raises MrxError (MRX_E_CAPACITY)."""
+        import torch
+        dev, n = self.data.device, self.n
+        cap = int(self.data.numel()) if out_cap is None else int(out_cap)
+        group_of = torch.empty(n, dtype=torch.int64, device=dev)
+        first, counts = torch.empty(n, dtype=torch.int64, device=dev), torch.empty(n, dtype=torch.int64, device=dev)
+        out_off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        out = torch.empty(max(cap, 1), dtype=torch.uint8, device=dev)
+        d_totals = torch.empty(2, dtype=torch.int64, device=dev)
+        totals = (C.c_int64 * 2)()
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        _check(self.call(load_library(), "mrx_distinct", (),
+                         (_ptr(group_of), _ptr(first), _ptr(counts), _ptr(out_off), _ptr(out), cap, _ptr(d_totals),
+                          C.cast(totals, C.c_void_p), stream)))
+        u, nbytes = int(totals[0]), int(totals[1])
+        trim_u = (lambda t, m: t[:m].clone()) if 4 * u < n else (lambda t, m: t[:m])
+        trim_b = (lambda t, m: t[:m].clone()) if 4 * nbytes < cap else (lambda t, m: t[:m])
+        values = DeviceBatch(trim_b(out, nbytes), trim_u(out_off, u + 1))
+        longest = self.longest()
+        if longest is not None:   # known bounds, as filter's result: a value is one of the texts
+            values._end_offset, values._max_len = nbytes, int(longest)
+        return values, trim_u(counts, u), group_of, trim_u(first, u)
+
+    def distinct_async(self, out):
+        """Enqueue distinct on the current stream without reading anything back.  out = (group_of int64[n], first
+        int64[n], counts int64[n], out_offsets int64[n + 1], out_data uint8[cap], totals int64[2]) device tensors of the
+        caller; totals = {u, bytes} once the stream has drained.  No byte is written when bytes > cap (check totals[1]);
+        cap = this batch's bytes always fits."""
+        import torch
+        group_of, first, counts, out_offsets, out_data, totals = out
+        if (min(group_of.numel(), first.numel(), counts.numel()) < self.n or out_offsets.numel() < self.n + 1
+                or totals.numel() < 2):
+            raise MrxError("out needs group_of, first and counts int64[n], out_offsets int64[n + 1], out_data uint8[cap], "
+                           "totals int64[2]")
+        for t in (group_of, first, counts, out_offsets, totals):
+            if t.dtype != torch.int64 or not t.is_contiguous():
+                raise MrxError("group_of, first, counts, out_offsets and totals must be contiguous int64 tensors")
+        if out_data.dtype != torch.uint8 or not out_data.is_contiguous():
+            raise MrxError("out_data must be a contiguous uint8 tensor")
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        _check(self.call(load_library(), "mrx_distinct", (),
+                         (_ptr(group_of), _ptr(first), _ptr(counts), _ptr(out_offsets), _ptr(out_data),
+                          int(out_data.numel()), _ptr(totals), None, stream)))
 
 
 def _ptr(t) -> int:
@@ -864,6 +926,21 @@ class CompiledRegex:
                 (_ptr(prefix), _ptr(pb[0]), _ptr(pb[1]), pcap, _ptr(out), ocap, _ptr(d_totals), totals,
                  self._stream_ptr()))))
         return res[0], prefix, res[1]
+
+    def value_counts(self, texts, group: Optional[int] = None, count: int = 0):
+        """Which strings this pattern matched in the batch, and how often each: extract(texts, group, count) followed by
+        distinct over all its pieces (grep -o | sort | uniq -c without the sort).  A DeviceBatch gives (values
+        DeviceBatch, counts int64[u]) on the device, in the order in which the values first occur in extract's pieces;
+        a list of texts gives List[Tuple[bytes, int]] in that order, which equals
+        list(collections.Counter(p for t in texts for p in rx.extract([t], group, count)[0]).items())."""
+        if not isinstance(texts, DeviceBatch):
+            values, counts = self.value_counts(DeviceBatch.from_texts([_b(t) for t in texts]), group, count)
+            raw = values.data.cpu().numpy().tobytes()
+            off = values.offsets.cpu().numpy()
+            return [(raw[off[g]:off[g + 1]], int(c)) for g, c in enumerate(counts.cpu().numpy())]
+        pieces = self.extract(texts, group, count)[0]
+        values, counts, _, _ = pieces.distinct()
+        return values, counts
 
     def extract_async(self, batch: "DeviceBatch", out):
         """Enqueue extract (findall's matches) on the current stream without reading anything back.  out =
@@ -1345,6 +1422,31 @@ def filter_texts(pattern, texts, invert: bool = False):
 def findall_texts(pattern, texts):
     """CompiledRegex.extract through the cache: findall's matches as bytes (re.findall's strings)."""
     return compile_regex(pattern).extract(texts)
+
+
+def distinct(texts):
+    """The unique texts of a list and how often each occurs, through mrx_distinct_batch: (values List[bytes], counts
+    int64[u], group_of int64[n], first int64[u]) as numpy arrays, the values in the order of dict.fromkeys(texts)."""
+    lib = load_library()
+    bs = [_b(t) for t in texts]
+    data, offsets = pack_texts(bs)
+    n, nbytes = len(bs), int(offsets[-1])
+    group_of, first, counts = (np.zeros(max(n, 1), np.int64) for _ in range(3))
+    out_off = np.zeros(n + 1, np.int64)
+    out = np.empty(max(nbytes, 1), np.uint8)
+    totals = (C.c_int64 * 2)()
+    _check(lib.mrx_distinct_batch(data.ctypes.data, offsets.ctypes.data, n, group_of.ctypes.data, first.ctypes.data,
+                                  counts.ctypes.data, out_off.ctypes.data, out.ctypes.data, nbytes,
+                                  C.cast(totals, C.c_void_p)))
+    u = int(totals[0])
+    raw = out[:int(totals[1])].tobytes()
+    return ([raw[out_off[g]:out_off[g + 1]] for g in range(u)], counts[:u].copy(), group_of[:n].copy(),
+            first[:u].copy())
+
+
+def value_counts(pattern, texts, group: Optional[int] = None, count: int = 0):
+    """compile_regex(pattern).value_counts(texts, group, count)."""
+    return compile_regex(pattern).value_counts(texts, group, count)
 
 
 def expand(pattern, template, texts, count: int = 0):

@@ -187,6 +187,13 @@ unsigned filter_grid(int64_t items, int64_t per) {
   return (unsigned)(g < 1 ? 1 : g > (int64_t)kFilterMaxGrid ? (int64_t)kFilterMaxGrid : g);
 }
 
+// the route rule: the text form when the host knows the batch's longest text and it is at most kFilterTextMax
+bool filter_text_form(const TextBatch& b, int64_t known_max) {
+  const int forced = g_filter_form.load(std::memory_order_relaxed);
+  const int64_t longest = b.offsets ? known_max : b.pitch_longest();   // < 0: not known to the host
+  return forced ? forced == 16 : (longest >= 0 && longest <= kFilterTextMax);
+}
+
 struct FilterArgs {
   uint32_t flags;
   int64_t* d_kept_idx;
@@ -217,15 +224,11 @@ int filter_run(const mrx_handle* h, const mrx_set* set, bool is_set, const TextB
                int64_t known_total, int64_t known_max, const FilterArgs& a) {
   if (int rc = filter_check(h, set, is_set, b, form, n, a)) return rc;
   hipStream_t hs = (hipStream_t)a.stream;
-  const int forced = g_filter_form.load(std::memory_order_relaxed);
-  const int64_t longest = b.offsets ? known_max : b.pitch_longest();   // < 0: not known to the host
-  const bool text_form = forced ? forced == 16 : (longest >= 0 && longest <= kFilterTextMax);
-  const char* const name = text_form ? "k_filter_gather_text" : "k_filter_gather";
   if (n == 0) {
     MRX_HIP_TRY(hipMemsetAsync(a.d_out_offsets, 0, sizeof(int64_t), hs));
     MRX_HIP_TRY(hipMemsetAsync(a.d_totals, 0, 2 * sizeof(int64_t), hs));
     if (a.totals) a.totals[0] = a.totals[1] = 0;
-    set_last_kernel(name);
+    set_last_kernel(filter_text_form(b, known_max) ? "k_filter_gather_text" : "k_filter_gather");
     return MRX_OK;
   }
   ScratchScope scope_(a.stream);
@@ -252,15 +255,8 @@ int filter_run(const mrx_handle* h, const mrx_set* set, bool is_set, const TextB
   hipLaunchKernelGGL(k_filter_scatter, dim3(filter_grid(n + 1, kFilterBlock)), blk, 0, hs, n, keep, rank, pos, a.d_kept_idx,
                      a.d_out_offsets);
   MRX_HIP_TRY(hipGetLastError());
-  if (a.out_cap > 0) {   // (nothing fits a capacity of 0, and no empty output has a byte to move)
-    const FilterOut O{a.d_kept_idx, a.d_out_offsets, a.d_totals, a.d_out_data, a.out_cap};
-    if (text_form)
-      hipLaunchKernelGGL(k_filter_gather_text, dim3(filter_grid(n, kFilterBlock / kFilterLanes)), blk, 0, hs, b, O);
-    else   // a wavefront per 64 blocks = 1 KiB of output at least
-      hipLaunchKernelGGL(k_filter_gather, dim3(filter_grid(a.out_cap / 16 + 2, kFilterBlock)), blk, 0, hs, b, O);
-    MRX_HIP_TRY(hipGetLastError());
-  }
-  set_last_kernel(name);
+  if (int rc = filter_gather_kept(b, n, known_max, a.d_kept_idx, a.d_out_offsets, a.d_totals, a.d_out_data, a.out_cap, a.stream))
+    return rc;
   if (!a.totals) return MRX_OK;
   MRX_HIP_TRY(hipMemcpyAsync(a.totals, a.d_totals, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, hs));
   MRX_HIP_TRY(hipStreamSynchronize(hs));
@@ -308,6 +304,24 @@ int filter_batch(const mrx_handle* h, const mrx_set* set, bool is_set, uint32_t 
 }
 
 }  // namespace
+
+int filter_gather_kept(const TextBatch& b, int64_t n, int64_t known_max, const int64_t* d_kept_idx,
+                       const int64_t* d_out_offsets, const int64_t* d_totals, uint8_t* d_out_data, int64_t out_cap,
+                       void* stream) {
+  const bool text_form = filter_text_form(b, known_max);
+  if (out_cap > 0) {   // (nothing fits a capacity of 0, and no empty output has a byte to move)
+    hipStream_t hs = (hipStream_t)stream;
+    const dim3 blk(kFilterBlock);
+    const FilterOut O{d_kept_idx, d_out_offsets, d_totals, d_out_data, out_cap};
+    if (text_form)
+      hipLaunchKernelGGL(k_filter_gather_text, dim3(filter_grid(n, kFilterBlock / kFilterLanes)), blk, 0, hs, b, O);
+    else   // a wavefront per 64 blocks = 1 KiB of output at least
+      hipLaunchKernelGGL(k_filter_gather, dim3(filter_grid(out_cap / 16 + 2, kFilterBlock)), blk, 0, hs, b, O);
+    MRX_HIP_TRY(hipGetLastError());
+  }
+  set_last_kernel(text_form ? "k_filter_gather_text" : "k_filter_gather");
+  return MRX_OK;
+}
 }  // namespace mrx
 
 using namespace mrx;
