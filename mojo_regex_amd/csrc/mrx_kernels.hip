@@ -6909,9 +6909,39 @@ int mrx_num_groups(const mrx_handle* h) {
 }
 const char* mrx_version(void) { return "mrx-hip 0.1 (gfx950)"; }
 
+// captures_all's route for a CSR batch with no text beyond the chain kernel's tile (4096 bytes), from the plan alone:
+// the rows of a deterministic chain from findall's spans (k_capall_chain), the fixed-width windows from findall's spans
+// (k_capall_fixed), or sub_text()'s loop, a lane per text (k_capall_emit).  force_generic: mrx_debug_force_generic's level.
+enum CapallRoute { CAPALL_GENERAL, CAPALL_FIXED, CAPALL_CHAIN };
+static CapallRoute capall_route(const mrx_handle* h, int force_generic) {
+  const HostPlan& hp = h->hp;
+  const uint32_t sfl = hp.dev.flags;
+  const bool general = hp.fixed_total < 0;
+  const ChainGroups& cg = hp.chain;
+  bool chain_ok = general && cg.ok && !force_generic && (sfl & (PF_STREAM_SEARCH | PF_STEP_SEARCH)) &&
+                  hp.why_no_search.empty() && cg.nleaf <= kSubcLeaves && hp.bt.ngroups <= 9;
+  for (int j = 1; chain_ok && j <= hp.bt.ngroups; ++j) chain_ok = cg.gopen[j] >= 0;
+  if (chain_ok) return CAPALL_CHAIN;
+  // (as sub_any's spans route: not with a memchr prefilter, not for exact literals, not for the whole-text shortcut of
+  // "concat" patterns that are not purely groups)
+  const bool spans_ok = !(sfl & PF_EXACT_LITERAL) &&
+                        ((!force_generic && (sfl & PF_STREAM_SEARCH)) ||
+                         (force_generic < 2 && (sfl & PF_STEP_SEARCH) && !(sfl & PF_PREFILTER)));
+  const bool shortcut_differs = hp.fixed_concat && !hp.fixed_pure;
+  if (spans_ok && !general && !shortcut_differs && hp.fixed_total < 0x7FFF) return CAPALL_FIXED;
+  return CAPALL_GENERAL;
+}
+
 size_t mrx_describe(const mrx_handle* h, char* buf, size_t cap) {
   if (!h) return 0;
-  const std::string s = describe_plan(h->hp);
+  std::string s = describe_plan(h->hp);
+  const std::string err = g_err;   // (the refusal's text belongs to the call that is refused, not to describe)
+  const bool refused = mrx::captures_all_refusal(h) != MRX_OK;
+  g_err = err;
+  if (!refused) {   // (no route for a handle that captures_all refuses)
+    const CapallRoute r = capall_route(h, 0);
+    s += std::string("device.capall=") + (r == CAPALL_CHAIN ? "chain" : r == CAPALL_FIXED ? "fixed" : "general") + "\n";
+  }
   if (buf && cap) {
     const size_t k = s.size() < cap - 1 ? s.size() : cap - 1;
     std::memcpy(buf, s.data(), k);
@@ -7966,22 +7996,14 @@ static int captures_all_any(const mrx_handle* h, int64_t count, const Layout& la
   hipStream_t s = (hipStream_t)st;
   const int64_t* off = lay_in.offsets;
   const uint32_t sfl = h->hp.dev.flags;
-  const ChainGroups& cg = h->hp.chain;
-  bool chain_ok = general && cg.ok && !g_force_generic && n > 0 && off && (sfl & (PF_STREAM_SEARCH | PF_STEP_SEARCH)) &&
-                  h->hp.why_no_search.empty() && cg.nleaf <= kSubcLeaves && h->hp.bt.ngroups <= 9;
-  for (int j = 1; chain_ok && j <= h->hp.bt.ngroups; ++j) chain_ok = cg.gopen[j] >= 0;
-  if (chain_ok) {
+  // (the spans routes take CSR batches; a chain batch with a text beyond the tile comes back for route 3)
+  const CapallRoute route = n > 0 && off ? capall_route(h, g_force_generic) : CAPALL_GENERAL;
+  if (route == CAPALL_CHAIN) {
     const int rc = capall_from_spans(h, csr(lay_in.data, off), n, count, true, d_prefix, d_groups,
                                      match_cap, total, s, known_bytes, known_max);
     if (rc != kSubsRetryGeneric) return rc;
   }
-  // (as sub_any's spans route: not with a memchr prefilter, not for exact literals, not for the whole-text shortcut of
-  // "concat" patterns that are not purely groups)
-  const bool spans_ok = !(sfl & PF_EXACT_LITERAL) &&
-                        ((!g_force_generic && (sfl & PF_STREAM_SEARCH)) ||
-                         (g_force_generic < 2 && (sfl & PF_STEP_SEARCH) && !(sfl & PF_PREFILTER)));
-  const bool shortcut_differs = h->hp.fixed_concat && !h->hp.fixed_pure;
-  if (spans_ok && !general && !shortcut_differs && n > 0 && off && h->hp.fixed_total < 0x7FFF)
+  if (route == CAPALL_FIXED)
     return capall_from_spans(h, csr(lay_in.data, off), n, count, false, d_prefix, d_groups, match_cap,
                              total, s, known_bytes, known_max);
   // route 3: sub_text()'s loop, a lane per text

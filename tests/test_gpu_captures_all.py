@@ -17,6 +17,7 @@ import captures_all_expect as E  # noqa: E402
 import layouts as LY  # noqa: E402
 from bench_engine_cases import CASES as BENCH_CASES  # noqa: E402
 from test_gpu_parity import generic_kernels  # noqa: E402
+from capall_gen import KERNEL, route_of  # noqa: E402
 
 FIXED = E.FIXED_PATTERNS
 PATTERNS = [p for p, _ in E.GROUP_PATTERNS] + list(dict.fromkeys(p for p, _ in E.CHAIN_SUBS)) + FIXED
@@ -46,15 +47,23 @@ def _rows_of(prefix, groups, i):
     return [[tuple(int(x) for x in pr) for pr in r] for r in groups[int(prefix[i]):int(prefix[i + 1])]]
 
 
-def _check(pat, texts, count, prefix, groups, g):
+def _check(pat, texts, count, prefix, groups, g, cache=None):
+    """cache: (count, text) -> the oracle's rows (None where its loop does not end), for a second batch of the same texts"""
     prefix = np.asarray(prefix)
     groups = np.asarray(groups)
     assert prefix.shape == (len(texts) + 1,) and groups.shape == (int(prefix[-1]), g + 1, 2)
     checked = 0
     for i, t in enumerate(texts):
-        try:
-            want = E.expected_rows(pat, t, count, g)
-        except O.ReferenceDoesNotTerminate:
+        if cache is not None and (count, t) in cache:
+            want = cache[count, t]
+        else:
+            try:
+                want = E.expected_rows(pat, t, count, g)
+            except O.ReferenceDoesNotTerminate:
+                want = None
+            if cache is not None:
+                cache[count, t] = want
+        if want is None:
             continue
         assert _rows_of(prefix, groups, i) == want, (pat, count, i, t[:80])
         checked += 1
@@ -67,9 +76,16 @@ def test_captures_all_matches_subs_loop(pat):
     rx = M.compile_regex(pat)
     g = rx.num_groups
     texts = _texts(pat)
+    short = [t for t in texts if len(t) <= 4096]   # (without a text beyond the chain kernel's tile: the plan's own route)
+    assert len(short) == len(texts) - 3
+    lib = M.load_library()
+    cache = {}
     for count in (0, 1, 3):
         prefix, groups = rx.captures_all(texts, count)
-        _check(pat, texts, count, prefix, groups, g)
+        _check(pat, texts, count, prefix, groups, g, cache)
+        p2, g2 = rx.captures_all(M.DeviceBatch.from_texts(short), count)
+        assert lib.mrx_last_kernel_name() == KERNEL[route_of(rx.describe())], (pat, lib.mrx_last_kernel_name())
+        _check(pat, short, count, p2.cpu().numpy(), g2.cpu().numpy(), g, cache)
         if count == 0:   # the first row of a text is its captures() row (outside the whole-text shortcut)
             caps = rx.captures(texts)
             orx = O.compile_regex(pat)

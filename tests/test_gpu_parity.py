@@ -920,37 +920,7 @@ def test_sub_with_groups_of_a_chain_from_spans_equals_the_interpreter_and_oracle
     assert lib.mrx_last_kernel_name() == b"k_sub_size"
 
 
-def _random_chain_with_groups(rng):
-    """A random chain of classes and literals with quantifiers, capture groups around runs of its elements (nested now
-    and then), and a replacement template over the groups."""
-    atoms = ["\\w", "\\d", "\\s", "[a-z]", "[a-c]", "[0-9a-f]", "[^ ]", " ", "-", "\\.", "@", "x", "a", ":"]
-    quants = ["", "", "+", "+", "{2}", "{1,3}", "{2,}", "{3,5}"]
-    n = int(rng.integers(1, 7))
-    elems = [atoms[int(rng.integers(len(atoms)))] + quants[int(rng.integers(len(quants)))] for _ in range(n)]
-    opens, closes = [0] * (n + 1), [0] * (n + 1)
-    ngroups = int(rng.integers(1, 4))
-    for _ in range(ngroups):
-        a = int(rng.integers(0, n))
-        b = int(rng.integers(a + 1, n + 1))
-        opens[a] += 1
-        closes[b] += 1
-    # (groups opened at a and closed at b in any order nest or overlap: close the inner ones first by emitting every
-    # close in front of the opens of the same position -- overlapping pairs are then simply another nesting)
-    pat = ""
-    depth = 0
-    for i in range(n):
-        c = min(closes[i], depth)
-        pat += ")" * c
-        depth -= c
-        pat += "(" * opens[i]
-        depth += opens[i]
-        pat += elems[i]
-    pat += ")" * depth
-    refs = [b"\\1", b"\\2", b"\\3", b"\\4", b"<", b">", b"-", b"", b"::", b"x"]
-    repl = b"".join(refs[int(rng.integers(len(refs)))] for _ in range(int(rng.integers(1, 6))))
-    if b"\\" not in repl:
-        repl += b"\\1"
-    return pat.encode(), repl
+from capall_gen import random_chain_with_groups as _random_chain_with_groups  # noqa: E402  (shared with the captures_all route tests)
 
 
 def test_sub_with_groups_on_generated_chains_equals_the_oracle():
