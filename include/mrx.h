@@ -624,6 +624,67 @@ int mrx_distinct_strided_dev(const uint8_t* d_data, int64_t stride, const int32_
                              int64_t* d_group_of, int64_t* d_first, int64_t* d_counts, int64_t* d_out_offsets,
                              uint8_t* d_out_data, int64_t out_cap, int64_t* d_totals, int64_t* totals, void* stream);
 
+/* ---- dictionaries: look up and filter a batch's texts against a value set ----
+ * grep -F -x -f list, isin, vocab.index(token): where distinct answers a question about one batch, a dictionary relates
+ * a batch to a second set of texts.  A dictionary is an immutable handle built once from a batch of m texts, the ENTRIES,
+ * and probed by any number of later batches.  Two texts are EQUAL as for distinct: equal lengths and equal bytes; the
+ * empty text is an entry like any other, and "a" and "a\0" differ.
+ * Lookup: d_index int64[n], on the device; d_index[i] is the LOWEST j with entry j equal to text i, and -1 when there is
+ * none.  Duplicates among the entries are allowed and the lowest index stands for them.  The result is a pure function of
+ * the entries and the text: which lane won a race during the build decides nothing a caller can see.  A hash decides
+ * nothing by itself: an index is reported only after the bytes have been compared.
+ * Build: mrx_dict_build_* copies the entries into device memory that the handle owns (a packed CSR made with filter's byte
+ * movers; plain device memory, not the per-call scratch arena, beside the table, 8 bytes times the power of two >= 2 m, and
+ * 8 bytes an entry of offsets), so the caller's batch may be freed as soon as the build returns.  The build synchronises
+ * the stream twice: once to learn the entries' byte count, which sizes the copy, and once at its end.  Its scratch, 44
+ * bytes an entry and a scan's block sums, goes back to the arena when it returns.  m == 0 is a valid dictionary: every
+ * lookup answers -1.  m >= 2^31: MRX_E_ARGUMENT (a table slot keeps a text's index in 32 bits).  The table is distinct's:
+ * open addressing at a load of at most one half, probed at most table-size times; a build whose probe ran out (it cannot,
+ * at that load) returns MRX_E_ARGUMENT and no handle.  On any error *out is left as it was.
+ * The handle is immutable after the build.  Lookups and filters only read it, so concurrent calls on one handle, from
+ * several threads and on several streams, are safe, as for mrx_handle.  mrx_dict_free(NULL) is a no-op; a handle must not
+ * be freed while a call on it is still running on some stream.  mrx_dict_size is m, mrx_dict_distinct the number of
+ * different entries (both 0 for NULL).
+ * mrx_dict_lookup_* enqueues one kernel and returns: it needs no scratch, reads nothing back and never synchronises.  It
+ * writes exactly d_index[0, n); n == 0 writes nothing.
+ * mrx_dict_filter_*: the contract is mrx_filter_dev's, word for word -- the outputs d_kept_idx, d_out_offsets, d_out_data
+ * and d_totals, both capacity rules (out_cap = the input's byte count always suffices; when bytes > out_cap the indices,
+ * the offsets and d_totals are complete, NO output byte is written, and a call with `totals` returns MRX_E_CAPACITY with
+ * totals filled), totals == NULL (nothing is read back, the call is asynchronous, the gather decides on the device), the
+ * _known bounds (upper bounds are fine; they choose between filter's byte movers) and n == 0 (kept = bytes = 0,
+ * d_out_offsets = {0}) -- with the predicate d_index[i] >= 0: text i is KEPT when it equals some entry.
+ * MRX_FILTER_INVERT keeps the texts that equal no entry.  MRX_FILTER_ALL is ignored, as it is for one pattern; any other
+ * flag bit: MRX_E_ARGUMENT.  d_index int64[n] may be NULL; when given it also receives the lookup result of every input
+ * text, kept or not.  Scratch: filter's 32 bytes per text, and 8 more when d_index is NULL.
+ * MRX_E_ARGUMENT, before any device call: negative n, m or out_cap; negative known bounds; a bad pitch; a null handle; a
+ * null required pointer (d_offsets; out for a build; d_index for a lookup with n > 0; for a filter d_out_offsets,
+ * d_totals, d_kept_idx when n > 0 and d_out_data when out_cap > 0).
+ * Reads: as distinct, a text's bytes are fetched as the aligned 16-byte words that hold them, so up to 15 bytes in front
+ * of a text's first byte and behind its last one are read (never used: they are masked before the hash and the comparison
+ * see them) and no word is read for an empty text.  That holds for the probed batch and, during the build, for the
+ * entries; the handle's copy is padded so that the aligned words around its first and last entry are the handle's own. */
+typedef struct mrx_dict mrx_dict;
+int mrx_dict_build_dev(const uint8_t* d_data, const int64_t* d_offsets, int64_t m, void* stream, mrx_dict** out);
+int mrx_dict_build_strided_dev(const uint8_t* d_data, int64_t stride, const int32_t* d_lens, int32_t len, int64_t m,
+                               void* stream, mrx_dict** out);
+void mrx_dict_free(mrx_dict* d);
+int64_t mrx_dict_size(const mrx_dict* d);
+int64_t mrx_dict_distinct(const mrx_dict* d);
+int mrx_dict_lookup_dev(const mrx_dict* d, const uint8_t* d_data, const int64_t* d_offsets, int64_t n, int64_t* d_index,
+                        void* stream);
+int mrx_dict_lookup_strided_dev(const mrx_dict* d, const uint8_t* d_data, int64_t stride, const int32_t* d_lens, int32_t len,
+                                int64_t n, int64_t* d_index, void* stream);
+int mrx_dict_filter_dev(const mrx_dict* d, uint32_t flags, const uint8_t* d_data, const int64_t* d_offsets, int64_t n,
+                        int64_t* d_index, int64_t* d_kept_idx, int64_t* d_out_offsets, uint8_t* d_out_data, int64_t out_cap,
+                        int64_t* d_totals, int64_t* totals, void* stream);
+int mrx_dict_filter_known_dev(const mrx_dict* d, uint32_t flags, const uint8_t* d_data, const int64_t* d_offsets, int64_t n,
+                              int64_t end_offset, int64_t max_text_len, int64_t* d_index, int64_t* d_kept_idx,
+                              int64_t* d_out_offsets, uint8_t* d_out_data, int64_t out_cap, int64_t* d_totals, int64_t* totals,
+                              void* stream);
+int mrx_dict_filter_strided_dev(const mrx_dict* d, uint32_t flags, const uint8_t* d_data, int64_t stride, const int32_t* d_lens,
+                                int32_t len, int64_t n, int64_t* d_index, int64_t* d_kept_idx, int64_t* d_out_offsets,
+                                uint8_t* d_out_data, int64_t out_cap, int64_t* d_totals, int64_t* totals, void* stream);
+
 /* ---- host-buffer convenience wrappers (copy in, run, copy out) -------------- */
 /* mrx_gather_spans_dev / mrx_extract_dev on host buffers: owner int64[piece_cap], out_offsets int64[piece_cap + 1],
  * out_data uint8[out_cap], totals int64[2] = {pieces, bytes} (may be NULL); spans holds prefix[n] rows.  piece_prefix
@@ -656,6 +717,10 @@ int mrx_set_filter_batch(const mrx_set* s, uint32_t flags, const uint8_t* data, 
  * out_offsets[0, u] are copied out, out_data only when all of it fits (MRX_E_CAPACITY otherwise). */
 int mrx_distinct_batch(const uint8_t* data, const int64_t* offsets, int64_t n, int64_t* group_of, int64_t* first,
                        int64_t* counts, int64_t* out_offsets, uint8_t* out_data, int64_t out_cap, int64_t* totals);
+/* mrx_dict_build_dev and mrx_dict_lookup_dev on host buffers: the entries (dict_data, dict_offsets int64[m + 1]) and the
+ * texts are copied in, a dictionary is built, probed once and freed; index int64[n] receives the result. */
+int mrx_dict_lookup_batch(const uint8_t* dict_data, const int64_t* dict_offsets, int64_t m, const uint8_t* data,
+                          const int64_t* offsets, int64_t n, int64_t* index);
 int mrx_match_first_batch(const mrx_handle* h, const uint8_t* data,
                           const int64_t* offsets, int64_t n, int32_t* start,
                           int32_t* end);

@@ -129,10 +129,14 @@ void mrx_debug_extract_grid(int workgroups);
 void mrx_debug_expand_grid(int workgroups);
 /* Distinct (include/mrx.h): `mask` is and-ed onto every text's hash before the table sees it; all ones (default) = the
  * hash as it is.  0 puts every text into one probe chain with equal tags, so that every decision is a byte comparison
- * (the probe is then quadratic: keep n small); 3 gives four chains.  Results are the same. */
+ * (the probe is then quadratic: keep n small); 3 gives four chains.  Results are the same.
+ * Dictionaries (include/mrx.h) hash as distinct does, so the mask applies to them: the mask in force when
+ * mrx_dict_build_* runs is stored in the handle and used by every lookup and filter on it, whatever the hook says by
+ * then.  Changing the hook later cannot separate a handle from its own table; it takes effect for the next build. */
 void mrx_debug_distinct_hash_mask(uint64_t mask);
 /* Distinct: `workgroups` > 0 caps the grids of its own kernels (4 wavefronts each), so that a test makes one wavefront
- * run several rounds without a batch of millions of texts.  0 (default) = no cap.  Results are the same. */
+ * run several rounds without a batch of millions of texts.  0 (default) = no cap.  Results are the same.  The cap also
+ * holds for a dictionary's build and for its lookup kernel, "k_dict_lookup" in mrx_last_kernel_name(). */
 void mrx_debug_distinct_grid(int workgroups);
 /* Bytes of device memory the calling thread's scratch arenas hold (see mrx_release_scratch). */
 size_t mrx_debug_scratch_bytes(void);

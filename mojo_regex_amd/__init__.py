@@ -28,6 +28,8 @@ argument meaning, a *batch* of texts instead of one text:
                                                   one templated record per match as a new packed batch
     (none: a Dict[String, Int] on the host)       distinct / value_counts / DeviceBatch.distinct /
                                                   CompiledRegex.value_counts: the unique texts and their counts
+    (none: `x in dict` / dict[x] on the host)     Dictionary / build_dictionary / lookup: the index of every
+                                                  text in a fixed set of entries, isin and semi- / anti-join
 
 All matching runs in the HIP kernels of libmrx_hip.so.  There is no CPU
 fallback: if the library is missing or no GPU is usable, calls raise.
@@ -37,10 +39,12 @@ whose name contains '-'.)
 from .api import (  # noqa: F401
     CompiledRegex,
     DeviceBatch,
+    Dictionary,
     MrxError,
     PatternSet,
     RegexSyntaxError,
     UnsupportedPattern,
+    build_dictionary,
     captures_all,
     clear_regex_cache,
     compile_regex,
@@ -52,6 +56,7 @@ from .api import (  # noqa: F401
     findall_texts,
     library_path,
     load_library,
+    lookup,
     match_first,
     pack_texts,
     search,

@@ -244,6 +244,22 @@ def load_library():
         "mrx_distinct_batch": (C.c_int, [u8p, i64p, C.c_int64, i64p, i64p, i64p, i64p, u8p, C.c_int64, C.c_void_p]),
         "mrx_debug_distinct_hash_mask": (None, [C.c_uint64]),
         "mrx_debug_distinct_grid": (None, [C.c_int]),
+        # dictionaries: build: the entries | (stream, out); lookup: handle | the batch | (index, stream); filter:
+        # (handle, flags) | the batch | (index, kept_idx, out_offsets, out_data, out_cap, d_totals, totals, stream)
+        "mrx_dict_build_dev": (C.c_int, [u8p, i64p, C.c_int64, C.c_void_p, C.POINTER(H)]),
+        "mrx_dict_build_strided_dev": (C.c_int, [u8p, C.c_int64, i32p, C.c_int32, C.c_int64, C.c_void_p, C.POINTER(H)]),
+        "mrx_dict_free": (None, [H]),
+        "mrx_dict_size": (C.c_int64, [H]),
+        "mrx_dict_distinct": (C.c_int64, [H]),
+        "mrx_dict_lookup_dev": (C.c_int, [H, u8p, i64p, C.c_int64, i64p, C.c_void_p]),
+        "mrx_dict_lookup_strided_dev": (C.c_int, [H, u8p, C.c_int64, i32p, C.c_int32, C.c_int64, i64p, C.c_void_p]),
+        "mrx_dict_filter_dev": (C.c_int, [H, C.c_uint32, u8p, i64p, C.c_int64, i64p, i64p, i64p, u8p, C.c_int64, i64p,
+                                          C.c_void_p, C.c_void_p]),
+        "mrx_dict_filter_known_dev": (C.c_int, [H, C.c_uint32, u8p, i64p, C.c_int64, C.c_int64, C.c_int64, i64p, i64p, i64p,
+                                                u8p, C.c_int64, i64p, C.c_void_p, C.c_void_p]),
+        "mrx_dict_filter_strided_dev": (C.c_int, [H, C.c_uint32, u8p, C.c_int64, i32p, C.c_int32, C.c_int64, i64p, i64p,
+                                                  i64p, u8p, C.c_int64, i64p, C.c_void_p, C.c_void_p]),
+        "mrx_dict_lookup_batch": (C.c_int, [u8p, i64p, C.c_int64, u8p, i64p, C.c_int64, i64p]),
         "mrx_debug_set_route": (None, [C.c_int]),
         "mrx_testing_set_run": (C.c_int, [H, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_int32)]),
     }
@@ -278,6 +294,9 @@ EXPORTED_SYMBOLS = [
     "mrx_expand_spans_dev", "mrx_expand_spans_strided_dev", "mrx_expand_spans_batch",
     "mrx_expand_dev", "mrx_expand_strided_dev", "mrx_expand_batch",
     "mrx_distinct_dev", "mrx_distinct_known_dev", "mrx_distinct_strided_dev", "mrx_distinct_batch",
+    "mrx_dict_build_dev", "mrx_dict_build_strided_dev", "mrx_dict_free", "mrx_dict_size", "mrx_dict_distinct",
+    "mrx_dict_lookup_dev", "mrx_dict_lookup_strided_dev", "mrx_dict_filter_dev", "mrx_dict_filter_known_dev",
+    "mrx_dict_filter_strided_dev", "mrx_dict_lookup_batch",
 ]
 TESTING_SYMBOLS = [
     "mrx_timing_reset", "mrx_timing_enable", "mrx_timing_scan_ms", "mrx_last_kernel_name",
@@ -661,9 +680,10 @@ def _filter_flags(mode: str = "any", invert: bool = False) -> int:
     return (MRX_FILTER_INVERT if invert else 0) | (MRX_FILTER_ALL if mode == "all" else 0)
 
 
-def _filter(lib, stem: str, handle, flags: int, texts):
-    """filter of one pattern (stem "mrx_filter") or a set ("mrx_set_filter").  The capacity is the input's byte count,
-    which always suffices, so there is no retry."""
+def _filter(lib, stem: str, handle, flags: int, texts, extra=()):
+    """filter of one pattern (stem "mrx_filter"), a set ("mrx_set_filter") or a dictionary ("mrx_dict_filter", a
+    DeviceBatch only; `extra`: its d_index, in front of the outputs).  The capacity is the input's byte count, which
+    always suffices, so there is no retry."""
     if isinstance(texts, DeviceBatch):
         import torch
         batch, dev, n = texts, texts.data.device, texts.n
@@ -672,8 +692,8 @@ def _filter(lib, stem: str, handle, flags: int, texts):
                torch.empty(cap, dtype=torch.uint8, device=dev), torch.empty(2, dtype=torch.int64, device=dev))
         totals = (C.c_int64 * 2)()
         stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        _check(batch.call(lib, stem, (handle, flags), (_ptr(out[0]), _ptr(out[1]), _ptr(out[2]), cap, _ptr(out[3]),
-                                                       C.cast(totals, C.c_void_p), stream)))
+        _check(batch.call(lib, stem, (handle, flags), extra + (_ptr(out[0]), _ptr(out[1]), _ptr(out[2]), cap, _ptr(out[3]),
+                                                               C.cast(totals, C.c_void_p), stream)))
         kept, nbytes = int(totals[0]), int(totals[1])
         longest = batch.longest()
         # The outputs were allocated for the worst case (every text kept).  A result that uses less than a quarter
@@ -699,7 +719,7 @@ def _filter(lib, stem: str, handle, flags: int, texts):
     return [raw[out_off[r]:out_off[r + 1]] for r in range(kept)], idx[:kept].copy()
 
 
-def _filter_async(lib, stem: str, handle, flags: int, batch: "DeviceBatch", out):
+def _filter_async(lib, stem: str, handle, flags: int, batch: "DeviceBatch", out, extra=()):
     import torch
     kept_idx, out_offsets, out_data, totals = out
     if kept_idx.numel() < batch.n or out_offsets.numel() < batch.n + 1 or totals.numel() < 2:
@@ -710,8 +730,87 @@ def _filter_async(lib, stem: str, handle, flags: int, batch: "DeviceBatch", out)
     if out_data.dtype != torch.uint8 or not out_data.is_contiguous():
         raise MrxError("out_data must be a contiguous uint8 tensor")
     stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-    _check(batch.call(lib, stem, (handle, flags), (_ptr(kept_idx), _ptr(out_offsets), _ptr(out_data),
-                                                   int(out_data.numel()), _ptr(totals), None, stream)))
+    _check(batch.call(lib, stem, (handle, flags), extra + (_ptr(kept_idx), _ptr(out_offsets), _ptr(out_data),
+                                                           int(out_data.numel()), _ptr(totals), None, stream)))
+
+
+class Dictionary:
+    """A fixed set of texts, the entries, built once on the device and probed by any number of batches (include/mrx.h,
+    "dictionaries"): grep -F -x -f list, isin, vocab.index(token).  `entries` is a list of texts or a DeviceBatch; the
+    handle keeps its own copy, so the batch may be dropped afterwards.  Texts are equal when their lengths and bytes are;
+    duplicates among the entries are allowed and the lowest index stands for them.  len() is the number of entries."""
+
+    def __init__(self, entries):
+        import torch
+        self._lib = load_library()
+        batch = entries if isinstance(entries, DeviceBatch) else DeviceBatch.from_texts([_b(t) for t in entries])
+        h = C.c_void_p()
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        _check(batch.call(self._lib, (self._lib.mrx_dict_build_dev, self._lib.mrx_dict_build_strided_dev), (),
+                          (stream, C.byref(h))))
+        self._h = h
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None):
+                self._lib.mrx_dict_free(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+    def __len__(self) -> int:
+        return int(self._lib.mrx_dict_size(self._h))
+
+    @property
+    def distinct_count(self) -> int:
+        """How many of the entries are different."""
+        return int(self._lib.mrx_dict_distinct(self._h))
+
+    def lookup_async(self, batch: "DeviceBatch", out):
+        """Enqueue the lookup on the current stream: out int64[n], a device tensor of the caller, receives for every
+        text the lowest index of an entry equal to it, or -1.  Nothing is read back."""
+        import torch
+        if out.dtype != torch.int64 or not out.is_contiguous() or out.numel() < batch.n:
+            raise MrxError("out must be a contiguous int64[n] tensor")
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        _check(batch.call(self._lib, (self._lib.mrx_dict_lookup_dev, self._lib.mrx_dict_lookup_strided_dev), (self._h,),
+                          (_ptr(out), stream)))
+
+    def lookup(self, texts):
+        """For every text the lowest index of an entry equal to it, or -1: np.int64[n] for a list of texts, a device
+        int64 tensor for a DeviceBatch (enqueued on the current stream, nothing read back)."""
+        import torch
+        if isinstance(texts, DeviceBatch):
+            out = torch.empty(texts.n, dtype=torch.int64, device=texts.data.device)
+            self.lookup_async(texts, out)
+            return out
+        batch = DeviceBatch.from_texts([_b(t) for t in texts])
+        return self.lookup(batch).cpu().numpy()
+
+    def isin(self, texts):
+        """bool[n]: is text i an entry?  numpy for a list of texts, a device tensor for a DeviceBatch."""
+        return self.lookup(texts) >= 0
+
+    def filter(self, texts, invert: bool = False):
+        """The texts that are entries (with invert, the others) as a new packed batch, in their order: what
+        CompiledRegex.filter returns, with the same known bounds and the same trimming (include/mrx.h,
+        mrx_dict_filter_dev).  A list of texts gives (kept List[bytes], idx numpy int64[kept]), a DeviceBatch gives
+        (DeviceBatch, idx) with device tensors."""
+        if isinstance(texts, DeviceBatch):
+            return _filter(self._lib, "mrx_dict_filter", self._h, _filter_flags("any", invert), texts, extra=(None,))
+        bs = [_b(t) for t in texts]
+        kept, idx = self.filter(DeviceBatch.from_texts(bs), invert)
+        idx = idx.cpu().numpy()
+        return [bs[int(i)] for i in idx], idx
+
+    def filter_async(self, batch: "DeviceBatch", out, invert: bool = False, index=None):
+        """Enqueue the filter on the current stream without reading anything back: out as CompiledRegex.filter_async's
+        (kept_idx int64[n], out_offsets int64[n + 1], out_data uint8[cap], totals int64[2]).  index int64[n] (optional,
+        a device tensor) also receives the lookup result of every input text."""
+        import torch
+        if index is not None and (index.dtype != torch.int64 or not index.is_contiguous() or index.numel() < batch.n):
+            raise MrxError("index must be a contiguous int64[n] tensor")
+        _filter_async(self._lib, "mrx_dict_filter", self._h, _filter_flags("any", invert), batch, out, extra=(_ptr(index),))
 
 
 class CompiledRegex:
@@ -1442,6 +1541,24 @@ def distinct(texts):
     raw = out[:int(totals[1])].tobytes()
     return ([raw[out_off[g]:out_off[g + 1]] for g in range(u)], counts[:u].copy(), group_of[:n].copy(),
             first[:u].copy())
+
+
+def build_dictionary(entries) -> Dictionary:
+    """Dictionary(entries): a list of texts or a DeviceBatch."""
+    return Dictionary(entries)
+
+
+def lookup(entries, texts):
+    """For every text the lowest index of an entry equal to it, or -1, through mrx_dict_lookup_batch: np.int64[n].
+    One dictionary for one batch; build_dictionary keeps it for many."""
+    lib = load_library()
+    es, bs = [_b(t) for t in entries], [_b(t) for t in texts]
+    edata, eoff = pack_texts(es)
+    data, off = pack_texts(bs)
+    index = np.zeros(max(len(bs), 1), np.int64)
+    _check(lib.mrx_dict_lookup_batch(edata.ctypes.data, eoff.ctypes.data, len(es), data.ctypes.data, off.ctypes.data,
+                                     len(bs), index.ctypes.data))
+    return index[:len(bs)].copy()
 
 
 def value_counts(pattern, texts, group: Optional[int] = None, count: int = 0):

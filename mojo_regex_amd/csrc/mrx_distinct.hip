@@ -252,6 +252,11 @@ __global__ __launch_bounds__(kDistinctBlock) void k_distinct_finish(int64_t n, c
   }
 }
 
+}  // namespace
+
+// ---- shared with dictionaries (mrx_lookup.hip) through mrx_internal.hpp --------------------------------------------
+uint64_t distinct_hash_mask() { return g_distinct_mask.load(std::memory_order_relaxed); }
+
 unsigned distinct_grid(int64_t items, int64_t per) {
   int64_t g = (items + per - 1) / per;
   g = g < 1 ? 1 : g > (int64_t)kDistinctMaxGrid ? (int64_t)kDistinctMaxGrid : g;
@@ -259,6 +264,21 @@ unsigned distinct_grid(int64_t items, int64_t per) {
   if (capped > 0 && g > capped) g = capped;
   return (unsigned)g;
 }
+
+int distinct_groups(const TextBatch& b, int64_t n, uint64_t mask, const DistinctGroups& g, void* stream) {
+  hipStream_t hs = (hipStream_t)stream;
+  const dim3 blk(kDistinctBlock);
+  const dim3 per_text(distinct_grid(n, kDistinctBlock));
+  hipLaunchKernelGGL(k_distinct_hash, per_text, blk, 0, hs, b, n, mask, g.hash);
+  MRX_HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(k_distinct_insert, per_text, blk, 0, hs, b, n, g.hash, g.table, g.slots, g.rep_of, g.err);
+  MRX_HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(k_distinct_first, dim3(distinct_grid(n, kDistinctChunk)), blk, 0, hs, n, g.rep_of, g.first_at, g.count_at);
+  MRX_HIP_TRY(hipGetLastError());
+  return MRX_OK;
+}
+
+namespace {
 
 struct DistinctArgs {
   int64_t* d_group_of;
@@ -314,14 +334,9 @@ int distinct_run(const TextBatch& b, BatchForm form, int64_t n, int64_t known_ma
   MRX_HIP_TRY(hipMemsetAsync(count_at, 0, sizeof(uint64_t) * words, hs));
   MRX_HIP_TRY(hipMemsetAsync(err, 0, sizeof(int32_t), hs));
   const dim3 blk(kDistinctBlock);
-  const uint64_t mask = g_distinct_mask.load(std::memory_order_relaxed);
   const dim3 per_text(distinct_grid(n, kDistinctBlock));
-  hipLaunchKernelGGL(k_distinct_hash, per_text, blk, 0, hs, b, n, mask, hash);
-  MRX_HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(k_distinct_insert, per_text, blk, 0, hs, b, n, hash, table, slots, rep_of, err);
-  MRX_HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(k_distinct_first, dim3(distinct_grid(n, kDistinctChunk)), blk, 0, hs, n, rep_of, first_at, count_at);
-  MRX_HIP_TRY(hipGetLastError());
+  if (int rc = distinct_groups(b, n, distinct_hash_mask(), DistinctGroups{hash, table, slots, rep_of, first_at, count_at, err}, a.stream))
+    return rc;
   hipLaunchKernelGGL(k_distinct_flags, per_text, blk, 0, hs, b, n, rep_of, first_at, klen, keep);
   MRX_HIP_TRY(hipGetLastError());
   if (int rc = exclusive_scan(klen, n, pos, a.d_totals + 1, a.stream)) return rc;

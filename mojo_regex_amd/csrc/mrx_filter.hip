@@ -224,13 +224,8 @@ int filter_run(const mrx_handle* h, const mrx_set* set, bool is_set, const TextB
                int64_t known_total, int64_t known_max, const FilterArgs& a) {
   if (int rc = filter_check(h, set, is_set, b, form, n, a)) return rc;
   hipStream_t hs = (hipStream_t)a.stream;
-  if (n == 0) {
-    MRX_HIP_TRY(hipMemsetAsync(a.d_out_offsets, 0, sizeof(int64_t), hs));
-    MRX_HIP_TRY(hipMemsetAsync(a.d_totals, 0, 2 * sizeof(int64_t), hs));
-    if (a.totals) a.totals[0] = a.totals[1] = 0;
-    set_last_kernel(filter_text_form(b, known_max) ? "k_filter_gather_text" : "k_filter_gather");
-    return MRX_OK;
-  }
+  const FilterDest dest{a.d_kept_idx, a.d_out_offsets, a.d_out_data, a.out_cap, a.d_totals, a.totals, a.stream};
+  if (n == 0) return filter_no_text(b, known_max, dest);
   ScratchScope scope_(a.stream);
   const int k = is_set ? (int)mrx_set_size(set) : 1;
   const int words = (k + 63) / 64;
@@ -250,19 +245,7 @@ int filter_run(const mrx_handle* h, const mrx_set* set, bool is_set, const TextB
   hipLaunchKernelGGL(k_filter_flags, dim3(filter_grid(n, kFilterBlock)), blk, 0, hs, b, n, is_set ? nullptr : (const int32_t*)pred,
                      is_set ? (const uint64_t*)pred : nullptr, k, words, a.flags, klen, keep);
   MRX_HIP_TRY(hipGetLastError());
-  if (int rc = exclusive_scan(klen, n, pos, a.d_totals + 1, a.stream)) return rc;
-  if (int rc = exclusive_scan(keep, n, rank, a.d_totals, a.stream)) return rc;
-  hipLaunchKernelGGL(k_filter_scatter, dim3(filter_grid(n + 1, kFilterBlock)), blk, 0, hs, n, keep, rank, pos, a.d_kept_idx,
-                     a.d_out_offsets);
-  MRX_HIP_TRY(hipGetLastError());
-  if (int rc = filter_gather_kept(b, n, known_max, a.d_kept_idx, a.d_out_offsets, a.d_totals, a.d_out_data, a.out_cap, a.stream))
-    return rc;
-  if (!a.totals) return MRX_OK;
-  MRX_HIP_TRY(hipMemcpyAsync(a.totals, a.d_totals, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, hs));
-  MRX_HIP_TRY(hipStreamSynchronize(hs));
-  if (a.totals[1] > a.out_cap)
-    return internal_fail(MRX_E_CAPACITY, "output buffer too small: need " + std::to_string(a.totals[1]));
-  return MRX_OK;
+  return filter_compact(b, n, known_max, FilterWork{klen, keep, pos, rank}, dest);
 }
 
 int filter_known(const mrx_handle* h, const mrx_set* set, bool is_set, const uint8_t* d_data, const int64_t* d_offsets,
@@ -304,6 +287,32 @@ int filter_batch(const mrx_handle* h, const mrx_set* set, bool is_set, uint32_t 
 }
 
 }  // namespace
+
+int filter_no_text(const TextBatch& b, int64_t known_max, const FilterDest& a) {
+  hipStream_t hs = (hipStream_t)a.stream;
+  MRX_HIP_TRY(hipMemsetAsync(a.d_out_offsets, 0, sizeof(int64_t), hs));
+  MRX_HIP_TRY(hipMemsetAsync(a.d_totals, 0, 2 * sizeof(int64_t), hs));
+  if (a.totals) a.totals[0] = a.totals[1] = 0;
+  set_last_kernel(filter_text_form(b, known_max) ? "k_filter_gather_text" : "k_filter_gather");
+  return MRX_OK;
+}
+
+int filter_compact(const TextBatch& b, int64_t n, int64_t known_max, const FilterWork& w, const FilterDest& a) {
+  hipStream_t hs = (hipStream_t)a.stream;
+  if (int rc = exclusive_scan(w.klen, n, w.pos, a.d_totals + 1, a.stream)) return rc;
+  if (int rc = exclusive_scan(w.keep, n, w.rank, a.d_totals, a.stream)) return rc;
+  hipLaunchKernelGGL(k_filter_scatter, dim3(filter_grid(n + 1, kFilterBlock)), dim3(kFilterBlock), 0, hs, n, w.keep, w.rank, w.pos,
+                     a.d_kept_idx, a.d_out_offsets);
+  MRX_HIP_TRY(hipGetLastError());
+  if (int rc = filter_gather_kept(b, n, known_max, a.d_kept_idx, a.d_out_offsets, a.d_totals, a.d_out_data, a.out_cap, a.stream))
+    return rc;
+  if (!a.totals) return MRX_OK;
+  MRX_HIP_TRY(hipMemcpyAsync(a.totals, a.d_totals, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, hs));
+  MRX_HIP_TRY(hipStreamSynchronize(hs));
+  if (a.totals[1] > a.out_cap)
+    return internal_fail(MRX_E_CAPACITY, "output buffer too small: need " + std::to_string(a.totals[1]));
+  return MRX_OK;
+}
 
 int filter_gather_kept(const TextBatch& b, int64_t n, int64_t known_max, const int64_t* d_kept_idx,
                        const int64_t* d_out_offsets, const int64_t* d_totals, uint8_t* d_out_data, int64_t out_cap,

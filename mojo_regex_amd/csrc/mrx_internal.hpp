@@ -127,6 +127,43 @@ int set_matches(const mrx_set* s, const TextBatch& b, int64_t n, uint64_t* d_bit
 int filter_gather_kept(const TextBatch& b, int64_t n, int64_t known_max, const int64_t* d_kept_idx,
                        const int64_t* d_out_offsets, const int64_t* d_totals, uint8_t* d_out_data, int64_t out_cap,
                        void* stream);
+// mrx_filter.hip: filter from the flags on, for a caller with a predicate of its own (dictionaries): the two scans, the
+// scatter, the gather above and, with a host `totals`, the one read-back and the capacity verdict -- what mrx_filter_*
+// runs behind its own flags kernel.  klen[n] (the kept length, 0 for a dropped text) and keep[n] (1 / 0) were written by
+// work enqueued before; pos[n + 1] and rank[n + 1] are the scans' outputs.  All four are the caller's scratch.
+struct FilterWork {
+  int64_t* klen;
+  int64_t* keep;
+  int64_t* pos;
+  int64_t* rank;
+};
+struct FilterDest {   // the outputs of mrx_filter_dev, as its contract has them
+  int64_t* d_kept_idx;
+  int64_t* d_out_offsets;
+  uint8_t* d_out_data;
+  int64_t out_cap;
+  int64_t* d_totals;
+  int64_t* totals;
+  void* stream;
+};
+int filter_compact(const TextBatch& b, int64_t n, int64_t known_max, const FilterWork& w, const FilterDest& a);
+int filter_no_text(const TextBatch& b, int64_t known_max, const FilterDest& a);   // the n == 0 result
+// mrx_distinct.hip: distinct's first three steps on a checked batch of n >= 1 texts, for a caller that keeps the table
+// (dictionaries): k_distinct_hash, k_distinct_insert and k_distinct_first, launched as distinct launches them.  `table`
+// (`slots` words, a power of two >= 2 n) and count_at[n] are zero, first_at[n] is all ones and *err is 0 when the
+// work runs; hash[n] and rep_of[n] are outputs.  mask: what the hash is and-ed with (distinct_hash_mask()).
+struct DistinctGroups {
+  uint64_t* hash;
+  unsigned long long* table;
+  uint64_t slots;
+  int32_t* rep_of;
+  unsigned long long* first_at;
+  unsigned long long* count_at;
+  int32_t* err;
+};
+int distinct_groups(const TextBatch& b, int64_t n, uint64_t mask, const DistinctGroups& g, void* stream);
+uint64_t distinct_hash_mask();                        // mrx_debug_distinct_hash_mask(): all ones unless a test set it
+unsigned distinct_grid(int64_t items, int64_t per);   // workgroups for `items` at `per` a workgroup, capped by the hook
 // the scan timer of mrx_timing_scan_ms around a launch sequence: begin returns a token for end
 void* scan_timer_begin(void* stream);
 void scan_timer_end(void* token);
