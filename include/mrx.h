@@ -685,6 +685,79 @@ int mrx_dict_filter_strided_dev(const mrx_dict* d, uint32_t flags, const uint8_t
                                 int32_t len, int64_t n, int64_t* d_index, int64_t* d_kept_idx, int64_t* d_out_offsets,
                                 uint8_t* d_out_data, int64_t out_cap, int64_t* d_totals, int64_t* totals, void* stream);
 
+/* ---- sort: the stable ascending order of a batch's texts, and their dense ranks ----
+ * sort, sort -u, the sorted vocabulary: sorted(range(n), key=texts.__getitem__) and numpy.unique(texts,
+ * return_inverse=True).  No pattern is involved: the call takes any batch.  Texts COMPARE as Python's bytes do: bytewise
+ * and unsigned (0x80 sorts above 0x7f), a proper prefix before the longer text ("" < "a" < "a\0" < "a\0\0" < "aa"),
+ * and equal texts keep ascending index order: the sort is stable.  With n texts and u different ones, all on the device:
+ *   d_order int64[n]    d_order[p] is the index of the text at sorted position p
+ *   d_rank int64[n]     (may be NULL) the number of different texts smaller than text i; equal texts share a rank
+ *   d_totals int64[1]   (may be NULL) {u}
+ * The result is a pure function of the input, bit for bit: no hash is involved, every output element is written once,
+ * by the one lane that the key order assigns to it, and no race decides anything.
+ * Exactly [0, n) of each array is written.  n == 0 writes nothing but d_totals = {0}.  To move the texts into that
+ * order, pass d_order to mrx_take_dev.
+ * MRX_E_ARGUMENT, before any device call: negative n or known bounds; a bad pitch; a null required pointer (d_offsets;
+ * d_order when n > 0); n >= 2^31 (a round keeps a text's index in 32 bits).
+ * Rounds and synchronisation: the order is refined 8 bytes of the texts a round.  After round r (r = 0, 1, ...) a
+ * position is final unless its text shares its first 8 (r + 1) bytes with more than 64 others and all of them go on
+ * beyond those bytes (equal texts are final with the word in which they end); a run of at most 64 such texts is
+ * finished at once by comparing them with each other, however long they are.
+ * The call synchronises the stream ONCE PER ROUND (it reads one word: how many positions are left) and returns when
+ * none is left, without a further synchronisation: the outputs are complete once the stream has drained.  A batch takes
+ * at most longest / 8 + 1 rounds (one less when the longest text is a multiple of 8 bytes and known to the host);
+ * typical batches (words, fields, log pieces) take one or two.  The worst case is a
+ * batch in which more than 64 different texts share a long prefix: one round per 8 bytes of it.
+ * The _known form takes a CSR batch's d_offsets[n] and longest text as mrx_filter_known_dev does.  The longest text
+ * spares the radix passes over bytes that no text has, and the round that would only find that texts of that length have
+ * ended (a fixed pitch is such a bound by itself).  An upper bound is
+ * fine; one that is too small gives a wrong order, never an access outside the caller's buffers.
+ * Reads: as distinct, a text's bytes are fetched as the aligned 16-byte words that hold them, so up to 15 bytes in front
+ * of a text's first byte and behind its last one are read (never used: they are masked before a key or a comparison
+ * sees them); no word is read for an empty text.
+ * Scratch: 76 bytes per text (two copies of a round's key and text index, 8 + 8 + 4 each; output positions 4 + 4; group
+ * heads 4; flags, a scan and the distinct-value flags 8 + 8 + 8), 4 KiB per 2048 texts of digit counts and the scans'
+ * block sums, returned to the arena when the call returns. */
+int mrx_sort_dev(const uint8_t* d_data, const int64_t* d_offsets, int64_t n, int64_t* d_order, int64_t* d_rank,
+                 int64_t* d_totals, void* stream);
+int mrx_sort_known_dev(const uint8_t* d_data, const int64_t* d_offsets, int64_t n, int64_t end_offset, int64_t max_text_len,
+                       int64_t* d_order, int64_t* d_rank, int64_t* d_totals, void* stream);
+int mrx_sort_strided_dev(const uint8_t* d_data, int64_t stride, const int32_t* d_lens, int32_t len, int64_t n,
+                         int64_t* d_order, int64_t* d_rank, int64_t* d_totals, void* stream);
+
+/* ---- take: the texts at given indices as a new packed batch ----
+ * texts[index] for an index array: output text j is input text d_index[j].  d_index is int64[k] on the device, in any
+ * order and with repeats, and k may exceed n.  All on the device:
+ *   d_out_offsets int64[k + 1]  the CSR of the output; d_out_offsets[k] = bytes
+ *   d_out_data uint8[out_cap]   the selected texts back to back; any alignment
+ *   d_totals int64[2]           {k, bytes}
+ * The output is a CSR batch whatever the input form, and the input of a following call as it stands (with bytes and the
+ * input's longest text as known bounds).  No byte of d_out_data at or past bytes, nor at or past out_cap, is ever
+ * written, and no element of d_out_offsets past k.
+ * Capacity and totals are filter's: when bytes > out_cap, d_out_offsets and d_totals are still complete and correct, NO
+ * output byte is written, and a call with `totals` returns MRX_E_CAPACITY with totals filled.  totals (host, int64[2],
+ * may be NULL) receives d_totals: the call then reads back once, at its end.  With totals == NULL nothing is read back
+ * and the call returns without synchronising; the caller checks d_totals against its out_cap once the stream has
+ * drained.  Repeats make the input's byte count no bound on bytes.
+ * An index outside [0, n) is found on the device and cannot be refused before the call: it gives d_totals = {-1, -1}
+ * with no output byte written (d_out_offsets is then unspecified), and MRX_E_ARGUMENT from a call with `totals`, as
+ * distinct reports its exhausted probe.
+ * k == 0 gives d_totals = {0, 0} and d_out_offsets = {0}.  MRX_E_ARGUMENT, before any device call: negative n, k, out_cap
+ * or known bounds; a bad pitch; a null required pointer (d_offsets, d_out_offsets, d_totals; d_index when k > 0;
+ * d_out_data when out_cap > 0).
+ * The _known form takes a CSR batch's d_offsets[n] and longest text as mrx_filter_known_dev does; they choose between
+ * filter's two byte movers and size nothing.  Upper bounds are fine.
+ * Reads: as filter.  Scratch: 8 bytes per index and a scan's block sums. */
+int mrx_take_dev(const uint8_t* d_data, const int64_t* d_offsets, int64_t n, const int64_t* d_index, int64_t k,
+                 int64_t* d_out_offsets, uint8_t* d_out_data, int64_t out_cap, int64_t* d_totals, int64_t* totals,
+                 void* stream);
+int mrx_take_known_dev(const uint8_t* d_data, const int64_t* d_offsets, int64_t n, int64_t end_offset, int64_t max_text_len,
+                       const int64_t* d_index, int64_t k, int64_t* d_out_offsets, uint8_t* d_out_data, int64_t out_cap,
+                       int64_t* d_totals, int64_t* totals, void* stream);
+int mrx_take_strided_dev(const uint8_t* d_data, int64_t stride, const int32_t* d_lens, int32_t len, int64_t n,
+                         const int64_t* d_index, int64_t k, int64_t* d_out_offsets, uint8_t* d_out_data, int64_t out_cap,
+                         int64_t* d_totals, int64_t* totals, void* stream);
+
 /* ---- host-buffer convenience wrappers (copy in, run, copy out) -------------- */
 /* mrx_gather_spans_dev / mrx_extract_dev on host buffers: owner int64[piece_cap], out_offsets int64[piece_cap + 1],
  * out_data uint8[out_cap], totals int64[2] = {pieces, bytes} (may be NULL); spans holds prefix[n] rows.  piece_prefix
@@ -717,6 +790,13 @@ int mrx_set_filter_batch(const mrx_set* s, uint32_t flags, const uint8_t* data, 
  * out_offsets[0, u] are copied out, out_data only when all of it fits (MRX_E_CAPACITY otherwise). */
 int mrx_distinct_batch(const uint8_t* data, const int64_t* offsets, int64_t n, int64_t* group_of, int64_t* first,
                        int64_t* counts, int64_t* out_offsets, uint8_t* out_data, int64_t out_cap, int64_t* totals);
+/* mrx_sort_dev on host buffers: order int64[n], rank int64[n] (may be NULL), totals int64[1] = {u} (may be NULL). */
+int mrx_sort_batch(const uint8_t* data, const int64_t* offsets, int64_t n, int64_t* order, int64_t* rank, int64_t* totals);
+/* mrx_take_dev on host buffers: index int64[k], out_offsets int64[k + 1], out_data uint8[out_cap], totals int64[2] =
+ * {k, bytes} (may be NULL; {-1, -1} with MRX_E_ARGUMENT behind an index outside [0, n)).  out_offsets[0, k] is copied
+ * out, out_data only when all of it fits (MRX_E_CAPACITY otherwise). */
+int mrx_take_batch(const uint8_t* data, const int64_t* offsets, int64_t n, const int64_t* index, int64_t k,
+                   int64_t* out_offsets, uint8_t* out_data, int64_t out_cap, int64_t* totals);
 /* mrx_dict_build_dev and mrx_dict_lookup_dev on host buffers: the entries (dict_data, dict_offsets int64[m + 1]) and the
  * texts are copied in, a dictionary is built, probed once and freed; index int64[n] receives the result. */
 int mrx_dict_lookup_batch(const uint8_t* dict_data, const int64_t* dict_offsets, int64_t m, const uint8_t* data,

@@ -138,6 +138,19 @@ void mrx_debug_distinct_hash_mask(uint64_t mask);
  * run several rounds without a batch of millions of texts.  0 (default) = no cap.  Results are the same.  The cap also
  * holds for a dictionary's build and for its lookup kernel, "k_dict_lookup" in mrx_last_kernel_name(). */
 void mrx_debug_distinct_grid(int workgroups);
+/* Sort (include/mrx.h): a group of 2 to `max` positions whose texts agree so far is finished at once by comparing its
+ * members with each other (k_sort_small); larger ones go through another radix round.  64 is the default and the
+ * largest value (a negative or larger argument restores it); 0 sends every group through radix rounds, one per 8 bytes
+ * that its texts share: keep shared prefixes short then.  Results are the same.  Sort reports "k_sort_small" through
+ * mrx_last_kernel_name(), take the byte mover of filter that it ran. */
+void mrx_debug_sort_small(int max);
+/* Sort and take: `workgroups` > 0 caps the grids of their own kernels (4 wavefronts each), so that a test makes one
+ * wavefront run several tiles of a radix pass without a batch of millions of texts.  0 (default) = no cap.  Results
+ * are the same. */
+void mrx_debug_sort_grid(int workgroups);
+/* Sort: the number of 8-byte refinement rounds, each with one synchronisation of the stream, that the calling thread's
+ * last sort call took (0 for a batch without texts, and before any call). */
+int mrx_debug_sort_rounds(void);
 /* Bytes of device memory the calling thread's scratch arenas hold (see mrx_release_scratch). */
 size_t mrx_debug_scratch_bytes(void);
 /* ... and how many of them are handed out and not yet rewound.  Scratch belongs to the call's scope, so between calls

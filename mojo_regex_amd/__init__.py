@@ -30,6 +30,9 @@ argument meaning, a *batch* of texts instead of one text:
                                                   CompiledRegex.value_counts: the unique texts and their counts
     (none: `x in dict` / dict[x] on the host)     Dictionary / build_dictionary / lookup: the index of every
                                                   text in a fixed set of entries, isin and semi- / anti-join
+    (none: sorted(...) on the host)               sort_texts / DeviceBatch.argsort / take / sort, and sort= /
+                                                  top= of value_counts and distinct: the bytewise order of a
+                                                  batch's texts, and the texts at given indices as a new batch
 
 All matching runs in the HIP kernels of libmrx_hip.so.  There is no CPU
 fallback: if the library is missing or no GPU is usable, calls raise.
@@ -60,6 +63,7 @@ from .api import (  # noqa: F401
     match_first,
     pack_texts,
     search,
+    sort_texts,
     split,
     sub,
     value_counts,

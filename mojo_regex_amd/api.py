@@ -260,6 +260,22 @@ def load_library():
         "mrx_dict_filter_strided_dev": (C.c_int, [H, C.c_uint32, u8p, C.c_int64, i32p, C.c_int32, C.c_int64, i64p, i64p,
                                                   i64p, u8p, C.c_int64, i64p, C.c_void_p, C.c_void_p]),
         "mrx_dict_lookup_batch": (C.c_int, [u8p, i64p, C.c_int64, u8p, i64p, C.c_int64, i64p]),
+        # sort: the batch | (order, rank, d_totals, stream); take: the batch | (index, k, out_offsets, out_data, out_cap,
+        # d_totals, totals, stream)
+        "mrx_sort_dev": (C.c_int, [u8p, i64p, C.c_int64, i64p, i64p, i64p, C.c_void_p]),
+        "mrx_sort_known_dev": (C.c_int, [u8p, i64p, C.c_int64, C.c_int64, C.c_int64, i64p, i64p, i64p, C.c_void_p]),
+        "mrx_sort_strided_dev": (C.c_int, [u8p, C.c_int64, i32p, C.c_int32, C.c_int64, i64p, i64p, i64p, C.c_void_p]),
+        "mrx_sort_batch": (C.c_int, [u8p, i64p, C.c_int64, i64p, i64p, C.c_void_p]),
+        "mrx_take_dev": (C.c_int, [u8p, i64p, C.c_int64, i64p, C.c_int64, i64p, u8p, C.c_int64, i64p, C.c_void_p,
+                                   C.c_void_p]),
+        "mrx_take_known_dev": (C.c_int, [u8p, i64p, C.c_int64, C.c_int64, C.c_int64, i64p, C.c_int64, i64p, u8p, C.c_int64,
+                                         i64p, C.c_void_p, C.c_void_p]),
+        "mrx_take_strided_dev": (C.c_int, [u8p, C.c_int64, i32p, C.c_int32, C.c_int64, i64p, C.c_int64, i64p, u8p, C.c_int64,
+                                           i64p, C.c_void_p, C.c_void_p]),
+        "mrx_take_batch": (C.c_int, [u8p, i64p, C.c_int64, i64p, C.c_int64, i64p, u8p, C.c_int64, C.c_void_p]),
+        "mrx_debug_sort_small": (None, [C.c_int]),
+        "mrx_debug_sort_grid": (None, [C.c_int]),
+        "mrx_debug_sort_rounds": (C.c_int, []),
         "mrx_debug_set_route": (None, [C.c_int]),
         "mrx_testing_set_run": (C.c_int, [H, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_int32)]),
     }
@@ -297,6 +313,8 @@ EXPORTED_SYMBOLS = [
     "mrx_dict_build_dev", "mrx_dict_build_strided_dev", "mrx_dict_free", "mrx_dict_size", "mrx_dict_distinct",
     "mrx_dict_lookup_dev", "mrx_dict_lookup_strided_dev", "mrx_dict_filter_dev", "mrx_dict_filter_known_dev",
     "mrx_dict_filter_strided_dev", "mrx_dict_lookup_batch",
+    "mrx_sort_dev", "mrx_sort_known_dev", "mrx_sort_strided_dev", "mrx_sort_batch",
+    "mrx_take_dev", "mrx_take_known_dev", "mrx_take_strided_dev", "mrx_take_batch",
 ]
 TESTING_SYMBOLS = [
     "mrx_timing_reset", "mrx_timing_enable", "mrx_timing_scan_ms", "mrx_last_kernel_name",
@@ -306,6 +324,7 @@ TESTING_SYMBOLS = [
     "mrx_debug_split_findall", "mrx_debug_dense_rows", "mrx_debug_tries_always", "mrx_debug_chain_sub_general", "mrx_testing_emptywalk_findall", "mrx_debug_litscan_pieces", "mrx_debug_multiwalk", "mrx_debug_rec_skew", "mrx_testing_comm_shift", "mrx_testing_comm_compact",
     "mrx_debug_set_route", "mrx_testing_set_run", "mrx_debug_filter_form", "mrx_debug_extract_grid",
     "mrx_debug_expand_grid", "mrx_debug_distinct_hash_mask", "mrx_debug_distinct_grid",
+    "mrx_debug_sort_small", "mrx_debug_sort_grid", "mrx_debug_sort_rounds",
 ]
 # (hooks with a digit in their name, listed apart: the header scan of tests/test_host_tables.py reads [a-z_] names)
 TESTING_SYMBOLS_NUMBERED = ["mrx_debug_rec12", "mrx_testing_rec12_roundtrip"]
@@ -582,6 +601,110 @@ class DeviceBatch:
         _check(self.call(load_library(), "mrx_distinct", (),
                          (_ptr(group_of), _ptr(first), _ptr(counts), _ptr(out_offsets), _ptr(out_data),
                           int(out_data.numel()), _ptr(totals), None, stream)))
+
+    def argsort(self, rank: bool = False):
+        """The stable ascending order of this batch's texts (include/mrx.h, mrx_sort_dev): order int64[n], a device
+        tensor with order[p] the index of the text at sorted position p -- sorted(range(n), key=texts.__getitem__).
+        Texts compare as Python's bytes do: bytewise and unsigned, a proper prefix first, equal texts in index order.
+        With rank=True the result is (order, rank int64[n], distinct_count): rank[i] is the number of different texts
+        smaller than text i, the inverse of numpy.unique(texts, return_inverse=True).  The call synchronises the
+        stream once per 8-byte refinement round (one or two for typical batches)."""
+        import torch
+        dev, n = self.data.device, self.n
+        order = torch.empty(n, dtype=torch.int64, device=dev)
+        ranks = torch.empty(n, dtype=torch.int64, device=dev) if rank else None
+        d_totals = torch.empty(1, dtype=torch.int64, device=dev) if rank else None
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        _check(self.call(load_library(), "mrx_sort", (), (_ptr(order), _ptr(ranks), _ptr(d_totals), stream)))
+        if not rank:
+            return order
+        return order, ranks, int(d_totals.item())
+
+    def _check_index(self, index):
+        import torch
+        if index.dtype != torch.int64 or not index.is_contiguous() or index.dim() != 1 or index.device != self.data.device:
+            raise MrxError("index must be a contiguous int64[k] tensor on the data's device")
+
+    def take(self, index, out_cap: Optional[int] = None):
+        """The texts at `index` (int64[k], a device tensor; any order, repeats allowed, k may exceed n) as a new packed
+        batch (include/mrx.h, mrx_take_dev): text j of the result is text index[j] of this batch.  The result is a CSR
+        DeviceBatch with known bounds: its byte count and, where this batch knows it, this batch's longest text.
+        Without out_cap the output starts at this batch's byte count and grows when repeats need more; an out_cap of
+        the caller's that does not hold the result, and an index outside [0, n), raise MrxError."""
+        import torch
+        self._check_index(index)
+        dev, k = self.data.device, int(index.numel())
+        out_off = torch.empty(k + 1, dtype=torch.int64, device=dev)
+        d_totals = torch.empty(2, dtype=torch.int64, device=dev)
+        totals = (C.c_int64 * 2)()
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        lib = load_library()
+
+        def run(out, cap, total):
+            rc = self.call(lib, "mrx_take", (), (_ptr(index), k, _ptr(out_off), _ptr(out), cap, _ptr(d_totals),
+                                                 C.cast(totals, C.c_void_p), stream))
+            total._obj.value = int(totals[1])
+            return rc
+        out, nbytes = _grow_call(int(self.data.numel()) if out_cap is None else int(out_cap),
+                                 lambda cap: torch.empty(max(cap, 1), dtype=torch.uint8, device=dev), run,
+                                 grow=out_cap is None, only_larger=True)
+        taken = DeviceBatch(out[:nbytes].clone() if 4 * nbytes < out.numel() else out[:nbytes], out_off)
+        longest = self.longest()
+        if longest is not None:   # known bounds, as filter's result: a taken text is one of the texts
+            taken._end_offset, taken._max_len = nbytes, int(longest)
+        return taken
+
+    def take_async(self, index, out):
+        """Enqueue take on the current stream without reading anything back.  out = (out_offsets int64[k + 1], out_data
+        uint8[cap], totals int64[2]) device tensors of the caller; totals = {k, bytes} once the stream has drained, or
+        {-1, -1} when an index lies outside [0, n).  No byte is written when bytes > cap (check totals[1])."""
+        import torch
+        self._check_index(index)
+        out_offsets, out_data, totals = out
+        k = int(index.numel())
+        if out_offsets.numel() < k + 1 or totals.numel() < 2:
+            raise MrxError("out needs out_offsets int64[k + 1], out_data uint8[cap], totals int64[2]")
+        for t in (out_offsets, totals):
+            if t.dtype != torch.int64 or not t.is_contiguous():
+                raise MrxError("out_offsets and totals must be contiguous int64 tensors")
+        if out_data.dtype != torch.uint8 or not out_data.is_contiguous():
+            raise MrxError("out_data must be a contiguous uint8 tensor")
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        _check(self.call(load_library(), "mrx_take", (),
+                         (_ptr(index), k, _ptr(out_offsets), _ptr(out_data), int(out_data.numel()), _ptr(totals), None,
+                          stream)))
+
+    def sort(self):
+        """(sorted_batch, order): this batch's texts in ascending order as a new packed batch -- take(argsort()) -- and
+        the permutation that made it."""
+        order = self.argsort()
+        return self.take(order), order
+
+
+def _sort_counts(values: "DeviceBatch", counts, sort: Optional[str], top: Optional[int]):
+    """The rows (values, counts) of distinct in another order: None = as they are (first occurrence), "value" =
+    ascending by value, "count" = descending by count with ties in first-occurrence order (Counter.most_common);
+    top = k keeps the first k rows of that order."""
+    order = _row_order(values, counts, sort, top)
+    return (values, counts) if order is None else (values.take(order), counts[order])
+
+
+def _row_order(values: "DeviceBatch", counts, sort: Optional[str], top: Optional[int]):
+    """The rows of distinct that _sort_counts keeps, in its order, as an int64 device tensor; None = all, as they are."""
+    import torch
+    if sort not in (None, "value", "count"):
+        raise MrxError("sort must be None, 'value' or 'count'")
+    if top is not None and int(top) < 0:
+        raise MrxError("top must be >= 0")
+    if sort is None and (top is None or int(top) >= values.n):
+        return None
+    if sort == "value":
+        order = values.argsort()
+    elif sort == "count":
+        order = torch.sort(counts, descending=True, stable=True)[1]
+    else:
+        order = torch.arange(values.n, dtype=torch.int64, device=counts.device)
+    return order if top is None else order[:int(top)].contiguous()
 
 
 def _ptr(t) -> int:
@@ -1026,20 +1149,25 @@ class CompiledRegex:
                  self._stream_ptr()))))
         return res[0], prefix, res[1]
 
-    def value_counts(self, texts, group: Optional[int] = None, count: int = 0):
+    def value_counts(self, texts, group: Optional[int] = None, count: int = 0, sort: Optional[str] = None,
+                     top: Optional[int] = None):
         """Which strings this pattern matched in the batch, and how often each: extract(texts, group, count) followed by
         distinct over all its pieces (grep -o | sort | uniq -c without the sort).  A DeviceBatch gives (values
         DeviceBatch, counts int64[u]) on the device, in the order in which the values first occur in extract's pieces;
         a list of texts gives List[Tuple[bytes, int]] in that order, which equals
-        list(collections.Counter(p for t in texts for p in rx.extract([t], group, count)[0]).items())."""
+        list(collections.Counter(p for t in texts for p in rx.extract([t], group, count)[0]).items()).
+        sort="value" orders the rows ascending by value (the sort of sort | uniq -c), sort="count" by descending count
+        with ties in first-occurrence order (Counter.most_common(), sort | uniq -c | sort -rn); top=k keeps the first k
+        rows of the chosen order (most_common(k), head -k).  The rows are reordered on the device: DeviceBatch.argsort
+        or a stable torch.sort of the counts, then DeviceBatch.take."""
         if not isinstance(texts, DeviceBatch):
-            values, counts = self.value_counts(DeviceBatch.from_texts([_b(t) for t in texts]), group, count)
+            values, counts = self.value_counts(DeviceBatch.from_texts([_b(t) for t in texts]), group, count, sort, top)
             raw = values.data.cpu().numpy().tobytes()
             off = values.offsets.cpu().numpy()
             return [(raw[off[g]:off[g + 1]], int(c)) for g, c in enumerate(counts.cpu().numpy())]
         pieces = self.extract(texts, group, count)[0]
         values, counts, _, _ = pieces.distinct()
-        return values, counts
+        return _sort_counts(values, counts, sort, top)
 
     def extract_async(self, batch: "DeviceBatch", out):
         """Enqueue extract (findall's matches) on the current stream without reading anything back.  out =
@@ -1523,11 +1651,25 @@ def findall_texts(pattern, texts):
     return compile_regex(pattern).extract(texts)
 
 
-def distinct(texts):
+def distinct(texts, sort: Optional[str] = None, top: Optional[int] = None):
     """The unique texts of a list and how often each occurs, through mrx_distinct_batch: (values List[bytes], counts
-    int64[u], group_of int64[n], first int64[u]) as numpy arrays, the values in the order of dict.fromkeys(texts)."""
+    int64[u], group_of int64[n], first int64[u]) as numpy arrays, the values in the order of dict.fromkeys(texts).
+    sort="value" / "count" and top=k reorder and cut the rows as CompiledRegex.value_counts does (on the device:
+    DeviceBatch.distinct, argsort and take); group_of then holds the new row of every text, -1 for a text whose value
+    top cut away."""
     lib = load_library()
     bs = [_b(t) for t in texts]
+    if sort is not None or top is not None:
+        import torch
+        values, counts, group_of, first = DeviceBatch.from_texts(bs).distinct()
+        order = _row_order(values, counts, sort, top)
+        if order is not None:
+            new_row = torch.full((values.n,), -1, dtype=torch.int64, device=order.device)
+            new_row[order] = torch.arange(order.numel(), dtype=torch.int64, device=order.device)
+            values, counts, first, group_of = values.take(order), counts[order], first[order], new_row[group_of]
+        raw, off = values.data.cpu().numpy().tobytes(), values.offsets.cpu().numpy()
+        return ([raw[off[g]:off[g + 1]] for g in range(values.n)], counts.cpu().numpy(), group_of.cpu().numpy(),
+                first.cpu().numpy())
     data, offsets = pack_texts(bs)
     n, nbytes = len(bs), int(offsets[-1])
     group_of, first, counts = (np.zeros(max(n, 1), np.int64) for _ in range(3))
@@ -1561,9 +1703,24 @@ def lookup(entries, texts):
     return index[:len(bs)].copy()
 
 
-def value_counts(pattern, texts, group: Optional[int] = None, count: int = 0):
-    """compile_regex(pattern).value_counts(texts, group, count)."""
-    return compile_regex(pattern).value_counts(texts, group, count)
+def value_counts(pattern, texts, group: Optional[int] = None, count: int = 0, sort: Optional[str] = None,
+                 top: Optional[int] = None):
+    """compile_regex(pattern).value_counts(texts, group, count, sort, top)."""
+    return compile_regex(pattern).value_counts(texts, group, count, sort, top)
+
+
+def sort_texts(texts):
+    """sorted(texts) for a list of texts, through mrx_sort_batch: (List[bytes] in ascending order, order int64[n] as a
+    numpy array with order[p] the index of the text at sorted position p).  Texts compare as Python's bytes do and equal
+    texts keep their index order."""
+    lib = load_library()
+    bs = [_b(t) for t in texts]
+    data, offsets = pack_texts(bs)
+    n = len(bs)
+    order = np.zeros(max(n, 1), np.int64)
+    _check(lib.mrx_sort_batch(data.ctypes.data, offsets.ctypes.data, n, order.ctypes.data, None, None))
+    order = order[:n].copy()
+    return [bs[int(i)] for i in order], order
 
 
 def expand(pattern, template, texts, count: int = 0):

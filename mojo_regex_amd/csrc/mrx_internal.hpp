@@ -120,10 +120,12 @@ std::string set_members_refusal(const mrx_set* s);
 int set_matches(const mrx_set* s, const TextBatch& b, int64_t n, uint64_t* d_bits, void* stream, int64_t known_total,
                 int64_t known_max);
 // mrx_filter.hip: the tail of filter's compaction on a checked batch, for a caller that has chosen the kept texts
-// itself (distinct).  d_kept_idx[kept] ascending, d_out_offsets[kept + 1] and d_totals = {kept, bytes} are on the
+// itself (distinct, take).  d_kept_idx[kept], d_out_offsets[kept + 1] and d_totals = {kept, bytes} are on the
 // device, written by work enqueued before; the kept texts' bytes go to d_out_data, by filter's kernels under filter's
-// route rule (known_max: a CSR batch's longest text, < 0 = not known), and nothing is written when bytes > out_cap.
-// n bounds kept.  Enqueues only; reports the kernel's name through mrx_last_kernel_name().
+// route rule (known_max: a CSR batch's longest text, < 0 = not known), and nothing is written when bytes > out_cap
+// or bytes <= 0.  The kernels read d_kept_idx[r] only to find the source of output row r: filter and distinct pass
+// ascending indices, take passes them in any order and with repeats.  n bounds kept (take: n is its k, which may
+// exceed the batch's text count).  Enqueues only; reports the kernel's name through mrx_last_kernel_name().
 int filter_gather_kept(const TextBatch& b, int64_t n, int64_t known_max, const int64_t* d_kept_idx,
                        const int64_t* d_out_offsets, const int64_t* d_totals, uint8_t* d_out_data, int64_t out_cap,
                        void* stream);
