@@ -758,7 +758,67 @@ int mrx_take_strided_dev(const uint8_t* d_data, int64_t stride, const int32_t* d
                          const int64_t* d_index, int64_t k, int64_t* d_out_offsets, uint8_t* d_out_data, int64_t out_cap,
                          int64_t* d_totals, int64_t* totals, void* stream);
 
+/* ---- numbers: pieces parsed to int64 and float64 on the device ----
+ * The step from bytes to numbers: int(piece), int(piece, 16) and float(piece) for every text of a batch, or for the
+ * bytes under every span that findall, split or captures_all left on the device -- read where they lie, inside the
+ * source texts; nothing is gathered in between.  No pattern is involved.
+ * A PIECE is a byte range: a whole text, or a span clamped to its text exactly as mrx_gather_spans_dev clamps a pair.
+ * It is parsed as a whole under one `kind`: it either is a number or it is not, and nothing is searched for inside it.
+ *   MRX_NUM_INT10  [+-]?[0-9]+
+ *   MRX_NUM_INT16  [+-]?(0[xX])?[0-9a-fA-F]+     "0x" with nothing behind it is malformed; the sign applies to the
+ *                                                magnitude, so ffffffffffffffff is out of range, not -1
+ *   MRX_NUM_FLOAT  [+-]?([0-9]+\.?[0-9]*|\.[0-9]+)([eE][+-]?[0-9]+)?
+ * Every kind refuses whatever is outside its grammar: whitespace, underscores, "inf", "nan", NUL bytes and, for the
+ * decimal and the float kind, a 0x prefix.  Any number of leading zeros, any piece length and any number of exponent
+ * digits are allowed.  Each row gets a status byte and an 8-byte value:
+ *   MRX_NUM_OK         parsed; the value is the number (an int64, or the bits of a double for MRX_NUM_FLOAT)
+ *   MRX_NUM_EMPTY      a piece of no bytes, such as an unset group (-1, -1)
+ *   MRX_NUM_MALFORMED  the piece is outside the kind's grammar
+ *   MRX_NUM_RANGE      well-formed, but not answered (below)
+ * A row whose status is not MRX_NUM_OK gets the caller's `fill` word, stored verbatim.
+ * Integers are OK when they lie in [-2^63, 2^63 - 1]: -9223372036854775808 is OK, and -0 is 0.  An overflowing
+ * magnitude saturates to MRX_NUM_RANGE; it never wraps.
+ * Floats are exact or refused, never approximate.  Let d be the integer that all mantissa digits write and q the
+ * exponent minus the number of fraction digits; the factors of ten of d are moved into q.  d = 0 gives +-0.0 whatever
+ * q is, the sign bit kept.  Otherwise the piece is answered when d <= 2^53 and -22 <= q <= 22: the value is
+ * (double)d * 10^q for q >= 0 and (double)d / 10^-q for q < 0 with the sign applied -- both operands are exact, so the
+ * one IEEE operation gives the correctly rounded result, float(piece) bit for bit.  Everything else is MRX_NUM_RANGE:
+ * long mantissas, 1e23, 1e999, 123e-25.  The caller can send those rows elsewhere.
+ *
+ * mrx_parse_*: row i is text i.  d_values int64[n] and d_status uint8[n] are written in [0, n) and nowhere else.
+ * mrx_parse_spans_*: d_prefix, d_spans, row_pairs and pair are those of mrx_gather_spans_dev.  rows = d_prefix[n] is
+ * read on the device and written to d_totals[0]; row r belongs to the text i with d_prefix[i] <= r < d_prefix[i + 1].
+ *   d_values int64[row_cap], d_status uint8[row_cap]   [0, rows)
+ *   d_owner int64[row_cap]   (may be NULL) [0, rows): the text index of each row
+ *   d_totals int64[1]        {rows}
+ * rows > row_cap: nothing but d_totals[0] is written.  totals (host, int64[1], may be NULL) receives d_totals: the call
+ * then reads it back once, at its end, and returns MRX_E_CAPACITY in that case; with totals == NULL it enqueues and
+ * returns.  n == 0 gives rows 0.
+ * MRX_E_ARGUMENT, before anything is enqueued: negative n or row_cap; a kind that is none of the three; row_pairs < 1 or
+ * pair out of range; a misaligned d_spans; a bad pitch; a null required pointer (d_offsets; d_values and d_status when
+ * n > 0, for the spans form when row_cap > 0; d_prefix and d_totals; d_spans when row_cap > 0).
+ * One kernel, a lane per row; no scratch, no atomics.  Reads: a piece's bytes are fetched as the aligned 16-byte words
+ * that hold them, so up to 15 bytes in front of a piece's first byte and behind its last one are read (never used: they
+ * are masked before a byte is classified); no word is read for an empty piece. */
+enum { MRX_NUM_INT10 = 0, MRX_NUM_INT16 = 1, MRX_NUM_FLOAT = 2 };
+enum { MRX_NUM_OK = 0, MRX_NUM_EMPTY = 1, MRX_NUM_MALFORMED = 2, MRX_NUM_RANGE = 3 };
+int mrx_parse_dev(const uint8_t* d_data, const int64_t* d_offsets, int64_t n, int32_t kind, int64_t fill,
+                  int64_t* d_values, uint8_t* d_status, void* stream);
+int mrx_parse_strided_dev(const uint8_t* d_data, int64_t stride, const int32_t* d_lens, int32_t len, int64_t n,
+                          int32_t kind, int64_t fill, int64_t* d_values, uint8_t* d_status, void* stream);
+int mrx_parse_spans_dev(const uint8_t* d_data, const int64_t* d_offsets, int64_t n, const int64_t* d_prefix,
+                        const int32_t* d_spans, int32_t row_pairs, int32_t pair, int32_t kind, int64_t fill,
+                        int64_t row_cap, int64_t* d_values, uint8_t* d_status, int64_t* d_owner, int64_t* d_totals,
+                        int64_t* totals, void* stream);
+int mrx_parse_spans_strided_dev(const uint8_t* d_data, int64_t stride, const int32_t* d_lens, int32_t len, int64_t n,
+                                const int64_t* d_prefix, const int32_t* d_spans, int32_t row_pairs, int32_t pair,
+                                int32_t kind, int64_t fill, int64_t row_cap, int64_t* d_values, uint8_t* d_status,
+                                int64_t* d_owner, int64_t* d_totals, int64_t* totals, void* stream);
+
 /* ---- host-buffer convenience wrappers (copy in, run, copy out) -------------- */
+/* mrx_parse_dev on host buffers: values int64[n], status uint8[n]. */
+int mrx_parse_batch(const uint8_t* data, const int64_t* offsets, int64_t n, int32_t kind, int64_t fill, int64_t* values,
+                    uint8_t* status);
 /* mrx_gather_spans_dev / mrx_extract_dev on host buffers: owner int64[piece_cap], out_offsets int64[piece_cap + 1],
  * out_data uint8[out_cap], totals int64[2] = {pieces, bytes} (may be NULL); spans holds prefix[n] rows.  piece_prefix
  * (extract) is always copied out, owner[0, pieces) and out_offsets[0, pieces] when the pieces fit, out_data only when

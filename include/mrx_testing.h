@@ -151,6 +151,11 @@ void mrx_debug_sort_grid(int workgroups);
 /* Sort: the number of 8-byte refinement rounds, each with one synchronisation of the stream, that the calling thread's
  * last sort call took (0 for a batch without texts, and before any call). */
 int mrx_debug_sort_rounds(void);
+/* Numbers (include/mrx.h): the one kernel reports itself as "k_parse" through mrx_last_kernel_name().  Its grid is a
+ * lane per row, capped as extract's; `workgroups` > 0 caps it further (4 wavefronts each), so that a test makes one
+ * wavefront run several rounds of 64 rows without millions of them.  0 (default) = no cap of its own.  Results are the
+ * same. */
+void mrx_debug_parse_grid(int workgroups);
 /* Bytes of device memory the calling thread's scratch arenas hold (see mrx_release_scratch). */
 size_t mrx_debug_scratch_bytes(void);
 /* ... and how many of them are handed out and not yet rewound.  Scratch belongs to the call's scope, so between calls

@@ -33,6 +33,8 @@ argument meaning, a *batch* of texts instead of one text:
     (none: sorted(...) on the host)               sort_texts / DeviceBatch.argsort / take / sort, and sort= /
                                                   top= of value_counts and distinct: the bytewise order of a
                                                   batch's texts, and the texts at given indices as a new batch
+    (none: int(m.get_match_text()) per match)     numbers / parse_numbers / CompiledRegex.numbers /
+                                                  DeviceBatch.parse / parse_spans: pieces as int64 / float64
 
 All matching runs in the HIP kernels of libmrx_hip.so.  There is no CPU
 fallback: if the library is missing or no GPU is usable, calls raise.
@@ -61,7 +63,9 @@ from .api import (  # noqa: F401
     load_library,
     lookup,
     match_first,
+    numbers,
     pack_texts,
+    parse_numbers,
     search,
     sort_texts,
     split,

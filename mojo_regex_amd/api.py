@@ -276,6 +276,18 @@ def load_library():
         "mrx_debug_sort_small": (None, [C.c_int]),
         "mrx_debug_sort_grid": (None, [C.c_int]),
         "mrx_debug_sort_rounds": (C.c_int, []),
+        # numbers: the batch | (kind, fill, values, status, stream); with spans: the batch | (prefix, spans, row_pairs,
+        # pair, kind, fill, row_cap, values, status, owner, d_totals, totals, stream)
+        "mrx_parse_dev": (C.c_int, [u8p, i64p, C.c_int64, C.c_int32, C.c_int64, i64p, u8p, C.c_void_p]),
+        "mrx_parse_strided_dev": (C.c_int, [u8p, C.c_int64, i32p, C.c_int32, C.c_int64, C.c_int32, C.c_int64, i64p, u8p,
+                                            C.c_void_p]),
+        "mrx_parse_spans_dev": (C.c_int, [u8p, i64p, C.c_int64, i64p, i32p, C.c_int32, C.c_int32, C.c_int32, C.c_int64,
+                                          C.c_int64, i64p, u8p, i64p, i64p, C.c_void_p, C.c_void_p]),
+        "mrx_parse_spans_strided_dev": (C.c_int, [u8p, C.c_int64, i32p, C.c_int32, C.c_int64, i64p, i32p, C.c_int32,
+                                                  C.c_int32, C.c_int32, C.c_int64, C.c_int64, i64p, u8p, i64p, i64p,
+                                                  C.c_void_p, C.c_void_p]),
+        "mrx_parse_batch": (C.c_int, [u8p, i64p, C.c_int64, C.c_int32, C.c_int64, i64p, u8p]),
+        "mrx_debug_parse_grid": (None, [C.c_int]),
         "mrx_debug_set_route": (None, [C.c_int]),
         "mrx_testing_set_run": (C.c_int, [H, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_int32)]),
     }
@@ -315,6 +327,7 @@ EXPORTED_SYMBOLS = [
     "mrx_dict_filter_strided_dev", "mrx_dict_lookup_batch",
     "mrx_sort_dev", "mrx_sort_known_dev", "mrx_sort_strided_dev", "mrx_sort_batch",
     "mrx_take_dev", "mrx_take_known_dev", "mrx_take_strided_dev", "mrx_take_batch",
+    "mrx_parse_dev", "mrx_parse_strided_dev", "mrx_parse_spans_dev", "mrx_parse_spans_strided_dev", "mrx_parse_batch",
 ]
 TESTING_SYMBOLS = [
     "mrx_timing_reset", "mrx_timing_enable", "mrx_timing_scan_ms", "mrx_last_kernel_name",
@@ -324,7 +337,7 @@ TESTING_SYMBOLS = [
     "mrx_debug_split_findall", "mrx_debug_dense_rows", "mrx_debug_tries_always", "mrx_debug_chain_sub_general", "mrx_testing_emptywalk_findall", "mrx_debug_litscan_pieces", "mrx_debug_multiwalk", "mrx_debug_rec_skew", "mrx_testing_comm_shift", "mrx_testing_comm_compact",
     "mrx_debug_set_route", "mrx_testing_set_run", "mrx_debug_filter_form", "mrx_debug_extract_grid",
     "mrx_debug_expand_grid", "mrx_debug_distinct_hash_mask", "mrx_debug_distinct_grid",
-    "mrx_debug_sort_small", "mrx_debug_sort_grid", "mrx_debug_sort_rounds",
+    "mrx_debug_sort_small", "mrx_debug_sort_grid", "mrx_debug_sort_rounds", "mrx_debug_parse_grid",
 ]
 # (hooks with a digit in their name, listed apart: the header scan of tests/test_host_tables.py reads [a-z_] names)
 TESTING_SYMBOLS_NUMBERED = ["mrx_debug_rec12", "mrx_testing_rec12_roundtrip"]
@@ -679,6 +692,78 @@ class DeviceBatch:
         the permutation that made it."""
         order = self.argsort()
         return self.take(order), order
+
+    def parse(self, kind: str = "int", fill=0):
+        """Every text of this batch as a number (include/mrx.h, mrx_parse_dev): (values, status), device tensors.  kind
+        is "int" ([+-]?[0-9]+), "hex" ([+-]?(0[xX])?[0-9a-fA-F]+) or "float" ([+-]?([0-9]+\\.?[0-9]*|\\.[0-9]+)
+        ([eE][+-]?[0-9]+)?); a text is parsed as a whole.  values is int64[n], or float64[n] for "float"; status is
+        uint8[n]: 0 = a number, 1 = an empty text, 2 = outside the grammar, 3 = well-formed but not answered (an integer
+        outside int64; a float that the exact rule does not cover).  Rows that are not numbers hold `fill`.  Enqueues on
+        the current stream and reads nothing back."""
+        import torch
+        k, word = _num_kind(kind), _num_fill(kind, fill)
+        values = torch.empty(self.n, dtype=torch.int64, device=self.data.device)
+        status = torch.empty(self.n, dtype=torch.uint8, device=self.data.device)
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        _check(self.call(load_library(), "mrx_parse", (), (k, word, _ptr(values), _ptr(status), stream)))
+        return (values.view(torch.float64) if kind == "float" else values), status
+
+    def parse_spans(self, prefix, spans, pair: int = 0, kind: str = "int", fill=0):
+        """The bytes under spans of this batch's texts as numbers, read where they lie (include/mrx.h,
+        mrx_parse_spans_dev): (values, status, owner), device tensors with one row per row of `spans`.  prefix, spans
+        and pair are gather_spans' own -- prefix int64[n + 1] the CSR of the rows over the texts, spans int32[m, 2] or
+        int32[m, g + 1, 2] with m = prefix[n] -- and a pair is clamped to its text in the same way, so an unset group is
+        an empty piece (status 1).  kind, fill, values and status are parse's; owner int64[m] is the text index of each
+        row.  The row count is the spans tensor's own: the call enqueues on the current stream and reads nothing back."""
+        import torch
+        if spans.dtype != torch.int32 or not spans.is_contiguous() or spans.dim() not in (2, 3) or spans.shape[-1] != 2:
+            raise MrxError("spans must be a contiguous int32[m, 2] or int32[m, g + 1, 2] tensor")
+        if prefix.dtype != torch.int64 or not prefix.is_contiguous() or prefix.numel() != self.n + 1:
+            raise MrxError("prefix must be a contiguous int64[n + 1] tensor")
+        k, word = _num_kind(kind), _num_fill(kind, fill)
+        row_pairs = int(spans.shape[1]) if spans.dim() == 3 else 1
+        dev, m = self.data.device, int(spans.shape[0])
+        values = torch.empty(m, dtype=torch.int64, device=dev)
+        status = torch.empty(m, dtype=torch.uint8, device=dev)
+        owner = torch.empty(m, dtype=torch.int64, device=dev)
+        d_totals = torch.empty(1, dtype=torch.int64, device=dev)
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        _check(self.call(load_library(), "mrx_parse_spans", (),
+                         (_ptr(prefix), _ptr(spans), row_pairs, int(pair), k, word, m, _ptr(values), _ptr(status),
+                          _ptr(owner), _ptr(d_totals), None, stream)))
+        return (values.view(torch.float64) if kind == "float" else values), status, owner
+
+
+MRX_NUM_INT10, MRX_NUM_INT16, MRX_NUM_FLOAT = range(3)
+MRX_NUM_OK, MRX_NUM_EMPTY, MRX_NUM_MALFORMED, MRX_NUM_RANGE = range(4)
+_NUM_KINDS = {"int": MRX_NUM_INT10, "hex": MRX_NUM_INT16, "float": MRX_NUM_FLOAT}
+
+
+def _num_kind(kind: str) -> int:
+    if kind not in _NUM_KINDS:
+        raise MrxError("kind must be 'int', 'hex' or 'float'")
+    return _NUM_KINDS[kind]
+
+
+def _num_fill(kind: str, fill) -> int:
+    """The 64-bit word stored in a row that is not a number: an int as it is, for "float" the bits of float(fill)."""
+    if kind == "float":
+        return int(np.array([fill], np.float64).view(np.int64)[0])
+    fill = int(fill)
+    if not -(1 << 63) <= fill < (1 << 63):
+        raise MrxError("fill must fit an int64")
+    return fill
+
+
+def _num_lists(kind: str, values, status, prefix=None):
+    """Host lists from values and status (device tensors): the number, or None where the status is not OK; with the
+    CSR of the rows over the texts, one list per text."""
+    conv = float if kind == "float" else int
+    flat = [conv(v) if s == MRX_NUM_OK else None for v, s in zip(values.cpu().numpy().tolist(), status.cpu().numpy().tolist())]
+    if prefix is None:
+        return flat
+    prefix = prefix.cpu().numpy()
+    return [flat[prefix[i]:prefix[i + 1]] for i in range(len(prefix) - 1)]
 
 
 def _sort_counts(values: "DeviceBatch", counts, sort: Optional[str], top: Optional[int]):
@@ -1121,6 +1206,32 @@ class CompiledRegex:
         # rows hold groups 1..g, then group 0
         pieces, owner = texts.gather_spans(prefix, rows, pair=(int(group) - 1) % (g + 1))
         return pieces, prefix, owner
+
+    def numbers(self, texts, kind: str = "int", group: Optional[int] = None, count: int = 0, fill=0):
+        """The matches of this pattern as numbers, without gathering their bytes (include/mrx.h, "numbers"): extract
+        followed by int() or float() on every piece.  group, count and the matches are extract's: group=None parses
+        findall's matches (count must be 0), group=j that group of every captures_all match, an unset group as an empty
+        piece.  kind and fill are DeviceBatch.parse's.  A DeviceBatch gives (values, status, prefix, owner) on the
+        device: text i's rows are [prefix[i], prefix[i + 1]), owner[r] = i for each of them, values int64 (float64 for
+        "float") and status uint8, 0 where the row is a number.  A list of texts gives List[List[Optional[int | float]]],
+        None where the status is not 0."""
+        if not isinstance(texts, DeviceBatch):
+            values, status, prefix, _ = self.numbers(DeviceBatch.from_texts([_b(t) for t in texts]), kind, group, count, fill)
+            return _num_lists(kind, values, status, prefix)
+        _num_kind(kind)
+        if group is None:
+            if count != 0:
+                raise MrxError("count needs a group: findall has no limit")
+            prefix, spans, total = self._dev_findall(texts)
+            rows, pair = spans[:total], 0
+        else:
+            g = self.num_groups
+            if not 0 <= int(group) <= g:
+                raise MrxError("group must be in [0, %d]" % g)
+            prefix, rows = self._captures_all_dev(texts, count)
+            pair = (int(group) - 1) % (g + 1)   # rows hold groups 1..g, then group 0
+        values, status, owner = texts.parse_spans(prefix, rows, pair, kind, fill)
+        return values, status, prefix, owner
 
     def expand(self, template, texts, count: int = 0):
         """One record per match, built from the match's groups and literal bytes: Python's [m.expand(t) for m in
@@ -1707,6 +1818,26 @@ def value_counts(pattern, texts, group: Optional[int] = None, count: int = 0, so
                  top: Optional[int] = None):
     """compile_regex(pattern).value_counts(texts, group, count, sort, top)."""
     return compile_regex(pattern).value_counts(texts, group, count, sort, top)
+
+
+def numbers(pattern, texts, kind: str = "int", group: Optional[int] = None, count: int = 0, fill=0):
+    """compile_regex(pattern).numbers(texts, kind, group, count, fill): the pattern's matches as numbers."""
+    return compile_regex(pattern).numbers(texts, kind, group, count, fill)
+
+
+def parse_numbers(texts, kind: str = "int"):
+    """int(t), int(t, 16) or float(t) for a list of texts, through mrx_parse_batch: List[Optional[int | float]], None
+    where a text is not a number of that kind (include/mrx.h, "numbers": no whitespace, no underscores, no inf or nan)
+    or is not answered (an integer outside int64; a float outside the exact rule)."""
+    lib = load_library()
+    k = _num_kind(kind)
+    bs = [_b(t) for t in texts]
+    data, offsets = pack_texts(bs)
+    n = len(bs)
+    values, status = np.zeros(max(n, 1), np.int64), np.zeros(max(n, 1), np.uint8)
+    _check(lib.mrx_parse_batch(data.ctypes.data, offsets.ctypes.data, n, k, 0, values.ctypes.data, status.ctypes.data))
+    vals = (values.view(np.float64) if kind == "float" else values)[:n].tolist()
+    return [v if s == MRX_NUM_OK else None for v, s in zip(vals, status[:n].tolist())]
 
 
 def sort_texts(texts):
