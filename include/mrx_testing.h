@@ -93,6 +93,23 @@ void mrx_debug_rec12(int mode);
  * the extractors give back to out = {start, pair, lane, before}.  Returns 0, or -1 when a field is out of range
  * (start 0..1023, pair 0..32, lane 0..63, before 0..1023) or out is NULL. */
 int mrx_testing_rec12_roundtrip(int start, int pair, int lane, int before, int32_t out[4]);
+/* k_decode's lean pass (csrc/mrx_decode_bits.hpp): wavefronts of the streaming findall's two-word records (12 or 16
+ * bytes; not the dynamic, split, pieces or fused forms) whose spans fit one LDS tile expand their records without a
+ * per-span bounds test, with the fixed-length form chosen per wavefront, the start as a max and record loads that do
+ * not branch.  0 = the general tile loop everywhere (k_decode<..., false> in a kernel trace), anything else = the lean
+ * pass (k_decode<..., true>; default).  Results are the same.  Environment: MRX_DECODE_LEAN=0. */
+void mrx_debug_decode_lean(int mode);
+/* Which form the last k_decode launch of the streaming findall took: 1 = the lean instantiation, 0 = the general one
+ * (switch off, or a form the lean pass does not cover: dynamic tasks, 32-bit positions, one-word records), -1 = no such
+ * launch yet.  Process-wide, like mrx_last_kernel_name. */
+int mrx_debug_last_decode_lean(void);
+/* That expansion on the host, for tests without a GPU.  Record i of n is {f_even[i], f_odd[i]}, the event words of the
+ * even and the odd group of the pair at text position pb[i]; start[i] = start of the walk alive at the pair's first byte;
+ * fixed_len > 0 = every match is that long.  Writes the record's number of spans (at most 32) to counts[i] and their
+ * (start, end), in text order, to spans[64 i ...] (room for 32 spans a record).  Returns 0, or -1 when n or fixed_len is
+ * negative or an array is NULL. */
+int mrx_testing_decode_expand(int64_t n, const uint32_t* f_even, const uint32_t* f_odd, const int32_t* start, const int32_t* pb,
+                              int fixed_len, int32_t* counts, int32_t* spans);
 /* include/mrx_comm.h, padded form of mrx_allgatherv_spans: its two device steps on buffers the caller fills as
  * ncclAllGather would have, so that the multi-rank arithmetic can be checked on one GPU.
  * meta_all: meta_stride int64 words per rank -- 2: {texts, spans}; 4: {texts (-1: that rank's arguments were invalid),

@@ -138,6 +138,10 @@ def load_library():
         "mrx_debug_rec_skew": (None, [C.c_int64]),
         "mrx_debug_rec12": (None, [C.c_int]),
         "mrx_testing_rec12_roundtrip": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32)]),
+        "mrx_debug_decode_lean": (None, [C.c_int]),
+        "mrx_debug_last_decode_lean": (C.c_int, []),
+        "mrx_testing_decode_expand": (C.c_int, [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                                C.c_void_p, C.c_void_p]),
         "mrx_release_scratch": (None, []),
         "mrx_debug_scratch_bytes": (C.c_size_t, []),
         "mrx_debug_scratch_in_use": (C.c_size_t, []),
@@ -338,6 +342,7 @@ TESTING_SYMBOLS = [
     "mrx_debug_set_route", "mrx_testing_set_run", "mrx_debug_filter_form", "mrx_debug_extract_grid",
     "mrx_debug_expand_grid", "mrx_debug_distinct_hash_mask", "mrx_debug_distinct_grid",
     "mrx_debug_sort_small", "mrx_debug_sort_grid", "mrx_debug_sort_rounds", "mrx_debug_parse_grid",
+    "mrx_debug_decode_lean", "mrx_debug_last_decode_lean", "mrx_testing_decode_expand",
 ]
 # (hooks with a digit in their name, listed apart: the header scan of tests/test_host_tables.py reads [a-z_] names)
 TESTING_SYMBOLS_NUMBERED = ["mrx_debug_rec12", "mrx_testing_rec12_roundtrip"]

@@ -33,6 +33,7 @@
 #include "mrx_internal.hpp"
 #include "mrx_lookback.hpp"
 #include "mrx_rec12.hpp"
+#include "mrx_decode_bits.hpp"
 
 using namespace mrx;
 
@@ -2967,7 +2968,10 @@ constexpr int kScanTile = kScanBlock * kScanItems;
 // keep 2048.
 // REC12 (with REC32): the 12-byte records of mrx_rec12.hpp -- `recs` is a dword stream, `rec_row` counts 12-byte slots, a
 // record arrives as three dwords {F even, F odd, meta}; everything behind the unpacking is the REC32 form's.
-template <bool PACK16, bool VBASE = false, bool REC32 = false, bool DYN = false, int TILE = kDecodeTile, bool REC12 = false>
+// LEAN (PACK16 && REC32, neither VBASE nor DYN): wavefronts whose spans fit one tile take the lean pass (mrx_decode_bits.hpp);
+// the multi-pass and dense paths are the same code either way.  MRX_DECODE_LEAN=0 / mrx_debug_decode_lean(0) launches LEAN = false.
+template <bool PACK16, bool VBASE = false, bool REC32 = false, bool DYN = false, int TILE = kDecodeTile, bool REC12 = false,
+          bool LEAN = false>
 __global__ __launch_bounds__(kBlock) void k_decode(int64_t n, const int32_t* __restrict__ wave_nrecs,
                                                    const EvRec* __restrict__ recs, int64_t rec_row,
                                                    const int64_t* __restrict__ offsets,
@@ -2985,6 +2989,7 @@ __global__ __launch_bounds__(kBlock) void k_decode(int64_t n, const int32_t* __r
   static_assert(!(PACK16 && VBASE), "text-relative positions of a long text do not fit 16 bits");
   static_assert(!(DYN && VBASE), "pieces are not handed out dynamically");
   static_assert(!REC12 || (REC32 && PACK16 && !VBASE && !DYN), "12-byte records: short texts at a fixed aligned pitch");
+  static_assert(!LEAN || (REC32 && PACK16 && !VBASE && !DYN), "lean pass: two-word records, 16-bit positions, static tasks");
   using Slot = typename std::conditional<PACK16, uint32_t, int2>::type;
   __shared__ Slot tile_all[kBlock / 64][TILE];
   __shared__ int dense_upto[kBlock / 64][64];   // dense path: spans of each of the wavefront's texts expanded so far
@@ -3150,6 +3155,57 @@ __global__ __launch_bounds__(kBlock) void k_decode(int64_t n, const int32_t* __r
         }
       }
       continue;
+    }
+    if constexpr (LEAN) {
+      if (total_spans <= kDecodeTile) {   // (wave uniform) one pass: every span of the wavefront has its place in the tile
+        // What differs from the loop below (mrx_decode_bits.hpp): no per-span bounds test -- with tb = 0 and
+        // total_spans <= TILE every index is inside the tile, capacity is checked at the stores --, the fixed-length form
+        // chosen once per wavefront, the start as a max, and record loads that do not branch: a slot behind the
+        // wavefront's last record reads that last record again (same line) and its event words are zeroed.
+        const int nrec = __builtin_amdgcn_readfirstlane(total_recs), nspan = __builtin_amdgcn_readfirstlane(total_spans);
+        const int last_rec = nrec - 1;
+        auto lean_pass = [&](auto fixed_tag) {
+          constexpr bool FIXED = decltype(fixed_tag)::value;
+          for (int j = 0; j < nrec; j += 64 * kDecodeBatch) {
+            uint32_t fe[kDecodeBatch], fo[kDecodeBatch], m2[kDecodeBatch], m3[kDecodeBatch];
+#pragma unroll
+            for (int u = 0; u < kDecodeBatch; ++u) {
+              const int o = j + u * 64 + lane;
+              const int oc = o < last_rec ? o : last_rec;   // (last use of the record: non-temporal)
+              if (REC12) {
+                const uint32_t* q_ = wave_recs12 + 3 * oc;
+                fe[u] = mrx_ldg32(q_); fo[u] = mrx_ldg32(q_ + 1); m3[u] = mrx_ldg32(q_ + 2); m2[u] = 0;
+              } else {
+                const uint4 q_ = mrx_ldg((const uint4*)(wave_recs + oc));
+                fe[u] = q_.x; fo[u] = q_.y; m2[u] = q_.z; m3[u] = q_.w;
+              }
+            }
+#pragma unroll
+            for (int u = 0; u < kDecodeBatch; ++u) {
+              if (j + u * 64 >= nrec) break;   // (wave uniform) the last batch's empty rounds
+              const bool mine = j + u * 64 + lane < nrec;
+              const uint32_t f_even = mine ? fe[u] : 0u, f_odd = mine ? fo[u] : 0u;
+              const uint32_t meta = m3[u];
+              const int rel_t = __shfl(my_rel, (int)(meta >> 26));
+              uint32_t* tp = tile + (rel_t + (REC12 ? rec12_before(meta) : (int)(meta & kBefore)));   // the record's first span
+              const int pb = REC12 ? 32 * rec12_pair(meta) : (int)(m2[u] >> 16) - kRecPosBias;
+              const int rstart = REC12 ? rec12_start(meta) : (int)(m2[u] & 0xFFFFu);
+              auto emit = [&](int st, int end) { *tp++ = ((uint32_t)st << 16) | (uint32_t)end; };
+              decode_expand_record<FIXED>(f_even, f_odd, rstart, pb, fixed_len, emit);
+            }
+          }
+        };
+        if (fixed_len > 0) lean_pass(std::true_type{}); else lean_pass(std::false_type{});
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        for (int k = lane; k < nspan; k += 64) {
+          const int64_t dst = pre0 + k;
+          if (dst < span_cap) { const uint32_t v = tile[k]; mrx_stg_span(spans + 2 * dst, (int)(v >> 16), (int)(v & 0xFFFFu)); }
+        }
+        __builtin_amdgcn_wave_barrier();
+        continue;
+      }
     }
     for (int tb = 0; tb < total_spans; tb += kDecodeTile) {
       for (int j = 0; j < total_recs; j += 64 * kDecodeBatch) {
@@ -5360,6 +5416,10 @@ std::atomic<int> g_dense_rows{env_int("MRX_DENSE_ROWS", 0)};
 // 12-byte event records (mrx_rec12.hpp) for the three-launch findall of texts of at most 1 KiB at an aligned fixed pitch:
 // 0 = never (16-byte records everywhere), anything else = by that rule (MRX_REC12 / mrx_debug_rec12)
 std::atomic<int> g_rec12{env_int("MRX_REC12", 1)};
+// k_decode's lean pass for wavefronts whose spans fit one tile (two-word records, static tasks; mrx_decode_bits.hpp):
+// 0 = the general tile loop everywhere, anything else = the lean pass (MRX_DECODE_LEAN / mrx_debug_decode_lean)
+std::atomic<int> g_decode_lean{env_int("MRX_DECODE_LEAN", 1)};
+std::atomic<int> g_last_decode_lean{-1};   // the last k_decode launch: 1 = LEAN instantiation, 0 = not, -1 = none yet
 constexpr int64_t kSplitMinTexts = 1 << 18;
 struct SideStream {
   hipStream_t side = nullptr;
@@ -5792,6 +5852,7 @@ struct FindallJob {
   // ... and what turns its records into the CSR: prefix sums over the wavefronts' totals, k_decode
   int stream_finish() {
     if (rows) {   // offsets from the scan's counts, then a wavefront per text (k_decode_rows)
+      g_last_decode_lean = 0;
       if (int rc = device_scan<int32_t>(d_counts, n, d_prefix, d_total, s)) return rc;
       // lanes per text by length: a round of 2 G pairs covers 64 G bytes
       const int G = max_text <= 1024 ? 16 : max_text <= 2048 ? 32 : 64;
@@ -5816,6 +5877,7 @@ struct FindallJob {
     hipLaunchKernelGGL(k_scan_local<int32_t>, dim3((unsigned)ntiles), dim3(kScanBlock), 0, s, d_nrecs + nw, nw,
                        d_wbase, d_tsum);
     const bool pack16 = max_text <= 65535;
+    bool decode_lean_ran = false;
     if (dyn) {
       const dim3 dg((unsigned)grid_for(nw * 64, kBlock) * 2), db(kBlock);
       if (pack16 && rec32)
@@ -5827,6 +5889,24 @@ struct FindallJob {
       else
         hipLaunchKernelGGL((k_decode<false, false, false, true>), dg, db, 0, s, n, d_nrecs, d_recs, rec_row, lay.offsets, d_counts,
                            d_wbase, d_tsum, d_prefix, d_spans, span_cap, p.st_fixed_len, d_total);
+    } else
+    if (pack16 && rec32 && g_decode_lean != 0) {
+      // the lean pass (k_decode<..., LEAN = true>): the same four shapes, grids and arguments as the launches below
+      const bool big = max_text >= 768;
+      auto lean = [&](auto tile, auto r12) {
+        hipLaunchKernelGGL((k_decode<true, false, true, false, decltype(tile)::value, decltype(r12)::value, true>),
+                           dim3(big && env_knobs().decode_grid > 0 ? env_knobs().decode_grid : grid_for(n, kBlock) * 2),
+                           dim3(kBlock), 0, s, n, d_nrecs, d_recs, rec_row, lay.offsets, d_counts, d_wbase, d_tsum, d_prefix,
+                           d_spans, span_cap, p.st_fixed_len, d_total, (const int32_t*)nullptr, (const int64_t*)nullptr,
+                           big ? env_knobs().decode_reverse : 0);
+      };
+      using Big = std::integral_constant<int, 3072>;
+      using Small = std::integral_constant<int, kDecodeTile>;
+      if (rec12 && big) lean(Big{}, std::true_type{});
+      else if (rec12) lean(Small{}, std::true_type{});
+      else if (big) lean(Big{}, std::false_type{});
+      else lean(Small{}, std::false_type{});
+      decode_lean_ran = true;
     } else
     if (rec12 && max_text >= 768)
       hipLaunchKernelGGL((k_decode<true, false, true, false, 3072, true>), dim3(env_knobs().decode_grid > 0 ? env_knobs().decode_grid : grid_for(n, kBlock) * 2), dim3(kBlock), 0, s, n, d_nrecs, d_recs,
@@ -5852,6 +5932,7 @@ struct FindallJob {
       hipLaunchKernelGGL(k_decode<false>, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, s, n, d_nrecs, d_recs,
                          rec_row, lay.offsets, d_counts, d_wbase, d_tsum, d_prefix, d_spans, span_cap, p.st_fixed_len,
                          d_total);
+    g_last_decode_lean = decode_lean_ran ? 1 : 0;
     HIP_TRY(hipGetLastError());
     return MRX_OK;
   }
@@ -8192,6 +8273,21 @@ void mrx_debug_force_generic(int on) { g_force_generic = on < 0 ? 0 : on > 2 ? 2
 void mrx_debug_long_text_kernels(int mode) { g_long_text_mode = mode < 0 ? 0 : mode > 3 ? 0 : mode; }
 void mrx_debug_rec_skew(int64_t bytes) { g_rec_skew = bytes < 0 ? 0 : (bytes & ~int64_t(15)); }
 void mrx_debug_rec12(int mode) { g_rec12 = mode != 0; }
+void mrx_debug_decode_lean(int mode) { g_decode_lean = mode != 0; }
+int mrx_debug_last_decode_lean(void) { return g_last_decode_lean; }
+int mrx_testing_decode_expand(int64_t n, const uint32_t* f_even, const uint32_t* f_odd, const int32_t* start, const int32_t* pb,
+                              int fixed_len, int32_t* counts, int32_t* spans) {
+  if (n < 0 || fixed_len < 0 || (n > 0 && (!f_even || !f_odd || !start || !pb || !counts || !spans))) return -1;
+  for (int64_t i = 0; i < n; ++i) {
+    int32_t* out = spans + 64 * i;
+    int cnt = 0;
+    auto emit = [&](int st, int end) { out[2 * cnt] = st; out[2 * cnt + 1] = end; ++cnt; };   // (at most one EMIT per byte)
+    if (fixed_len > 0) decode_expand_record<true>(f_even[i], f_odd[i], start[i], pb[i], fixed_len, emit);
+    else decode_expand_record<false>(f_even[i], f_odd[i], start[i], pb[i], fixed_len, emit);
+    counts[i] = cnt;
+  }
+  return 0;
+}
 int mrx_testing_rec12_roundtrip(int start, int pair, int lane, int before, int32_t out[4]) {
   if (start < 0 || start >= kRec12MaxLen || pair < 0 || pair > kRec12MaxLen / 32 || lane < 0 || lane > 63 || before < 0 ||
       before >= kRec12MaxLen || !out)
