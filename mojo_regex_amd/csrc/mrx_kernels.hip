@@ -2970,6 +2970,20 @@ constexpr int kScanTile = kScanBlock * kScanItems;
 // record arrives as three dwords {F even, F odd, meta}; everything behind the unpacking is the REC32 form's.
 // LEAN (PACK16 && REC32, neither VBASE nor DYN): wavefronts whose spans fit one tile take the lean pass (mrx_decode_bits.hpp);
 // the multi-pass and dense paths are the same code either way.  MRX_DECODE_LEAN=0 / mrx_debug_decode_lean(0) launches LEAN = false.
+template <int G, bool XOR>
+__device__ __forceinline__ int group_scan(int x);   // (DPP inclusive scan, defined with the sub() kernels below)
+
+// Sum over the wavefront of one 64-bit value per lane -- none negative, the total below 2^63 -- as a wave-uniform
+// value: three 32-bit DPP scans (the low word as two 16-bit halves, which 64 lanes cannot overflow, and the high
+// word) whose last lane is read into SGPRs.  No LDS round trip.
+__device__ __forceinline__ int64_t wave_sum64(int64_t v) {
+  const uint32_t lo = (uint32_t)v, hi = (uint32_t)((uint64_t)v >> 32);
+  const uint32_t s0 = (uint32_t)__builtin_amdgcn_readlane(group_scan<64, false>((int)(lo & 0xFFFFu)), 63);
+  const uint32_t s1 = (uint32_t)__builtin_amdgcn_readlane(group_scan<64, false>((int)(lo >> 16)), 63);
+  const uint32_t s2 = (uint32_t)__builtin_amdgcn_readlane(group_scan<64, false>((int)hi), 63);
+  return (int64_t)((uint64_t)s0 + ((uint64_t)s1 << 16) + ((uint64_t)s2 << 32));
+}
+
 template <bool PACK16, bool VBASE = false, bool REC32 = false, bool DYN = false, int TILE = kDecodeTile, bool REC12 = false,
           bool LEAN = false>
 __global__ __launch_bounds__(kBlock) void k_decode(int64_t n, const int32_t* __restrict__ wave_nrecs,
@@ -3003,22 +3017,77 @@ __global__ __launch_bounds__(kBlock) void k_decode(int64_t n, const int32_t* __r
   int* rel_lds = rel_all[DYN ? (threadIdx.x >> 6) : 0];
   const int64_t nw = (n + kTexts - 1) / kTexts;
   const int waves_per_block = blockDim.x >> 6;
-  for (int64_t w0 = (int64_t)blockIdx.x * waves_per_block + (threadIdx.x >> 6); w0 < nw;
+  // the task index is the same in every lane: from SGPRs, so that `w`, `first`, the record base and the loads of
+  // wave_base[w], wave_nrecs[w] and *base are scalar
+  const int wave_in_block = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  for (int64_t w0 = (int64_t)blockIdx.x * waves_per_block + wave_in_block; w0 < nw;
        w0 += (int64_t)gridDim.x * waves_per_block) {
     const int64_t w = reverse ? nw - 1 - w0 : w0;
     const int64_t first = w * kTexts;
     const int64_t i = first + lane;
+    // Everything the task needs is requested here, back to back, before anything is waited for: the three scalars, my
+    // text's count, the sums of the scan tiles in front, and (LEAN) the first batch of records.
+    const int64_t tiles_before = w / kScanTile;
+    const int64_t wbase = wave_base[w];
+    const int total_recs = __builtin_amdgcn_readfirstlane(wave_nrecs[w]);
+    const int64_t base0 = base ? *base : 0;
+    const EvRec* wave_recs = recs + (DYN ? rec_region_dyn(offsets[first], w)
+                                         : offsets ? rec_region_start(offsets[first], w) : first * rec_row);
+    const uint32_t* wave_recs12 = REC12 ? (const uint32_t*)recs + 3 * (first * rec_row) : nullptr;
+    const int my_cnt = (!DYN && i < n) ? counts[i] : 0;
+    int64_t part = lane < tiles_before ? scan_block_sums[lane] : 0;
+    // LEAN: a batch of records, loads that do not branch: a slot behind the wavefront's last record reads that last
+    // record again (same line) and its event words are zeroed where they are used.  No load leaves the wavefront's own
+    // records; a wavefront without a record loads none.
+    uint32_t fe[kDecodeBatch], fo[kDecodeBatch], m2[kDecodeBatch], m3[kDecodeBatch];
+    const int last_rec = total_recs - 1;
+    auto load_batch = [&](int j) {
+#pragma unroll
+      for (int u = 0; u < kDecodeBatch; ++u) {
+        const int o = j + u * 64 + lane;
+        const int oc = o < last_rec ? o : last_rec;   // (last use of the record: non-temporal)
+        if (REC12) {
+          const uint32_t* q_ = wave_recs12 + 3 * oc;
+          fe[u] = mrx_ldg32(q_); fo[u] = mrx_ldg32(q_ + 1); m3[u] = mrx_ldg32(q_ + 2); m2[u] = 0;
+        } else {
+          const uint4 q_ = mrx_ldg((const uint4*)(wave_recs + oc));
+          fe[u] = q_.x; fo[u] = q_.y; m2[u] = q_.z; m3[u] = q_.w;
+        }
+      }
+    };
+    // The batch named as operands, so that the compiler waits for all of it: once behind the header's arithmetic, in
+    // front of every branch, and once behind the lean pass's loop.  A load that some path never reads (a wavefront that
+    // takes another path, the empty rounds of the last batch) otherwise counts as outstanding at the top of the next
+    // task, whose batch takes the same registers, and that batch is held back behind every load and store in flight --
+    // the counts and the previous task's span stores among them.
+    auto retire_batch = [&]() {
+#pragma unroll
+      for (int u = 0; u < kDecodeBatch; ++u) {
+        asm volatile("" ::"v"(fe[u]), "v"(fo[u]), "v"(m3[u]));
+        if (!REC12) asm volatile("" ::"v"(m2[u]));
+      }
+    };
+    if constexpr (LEAN) {
+      if (total_recs > 0) {   // (wave uniform)
+        load_batch(0);
+      } else {   // nothing to read: a wavefront without a record is all header
+#pragma unroll
+        for (int u = 0; u < kDecodeBatch; ++u) fe[u] = fo[u] = m2[u] = m3[u] = 0;
+      }
+    }
     // CSR offsets of my 64 texts: exclusive scan of their counts on top of the wavefront's base
     // wave_base is exclusive within its k_scan_local tile of kScanTile wavefronts; the tiles before
-    // it (at most a few dozen sums) are added here instead of by two more scan launches
-    int64_t pre0 = wave_base[w] + (base ? *base : 0);
-    {
-      const int64_t tiles_before = w / kScanTile;
-      int64_t part = 0;
-      for (int64_t b = lane; b < tiles_before; b += 64) part += scan_block_sums[b];
-      for (int off = 32; off > 0; off >>= 1) part += __shfl_xor(part, off);
-      pre0 += part;
+    // it (at most a few dozen sums: one load per lane) are added here instead of by two more scan launches
+    if (tiles_before > 64) {   // (wave uniform) four independent loads per lane and trip
+      for (int64_t b = 64 + lane; b < tiles_before; b += 256) {
+        const int64_t p0 = scan_block_sums[b];
+        const int64_t p1 = b + 64 < tiles_before ? scan_block_sums[b + 64] : 0;
+        const int64_t p2 = b + 128 < tiles_before ? scan_block_sums[b + 128] : 0;
+        const int64_t p3 = b + 192 < tiles_before ? scan_block_sums[b + 192] : 0;
+        part += (p0 + p1) + (p2 + p3);
+      }
     }
+    const int64_t pre0 = wbase + base0 + wave_sum64(part);
     int my_rel = 0, total_spans = 0;
     if (DYN) {
       __builtin_amdgcn_wave_barrier();
@@ -3037,28 +3106,58 @@ __global__ __launch_bounds__(kBlock) void k_decode(int64_t n, const int32_t* __r
         if (t == n - 1) { prefix[n] = pre0 + carry + incl; *total_out = pre0 + carry + incl; }
         carry += __shfl(incl, 63);
       }
-      total_spans = carry;
+      total_spans = __builtin_amdgcn_readfirstlane(carry);
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
       __builtin_amdgcn_wave_barrier();
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     } else {
-    const int my_cnt = i < n ? counts[i] : 0;
-    int incl = my_cnt;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const int v = __shfl_up(incl, d);
-      if (lane >= d) incl += v;
-    }
+    const int incl = group_scan<64, false>(my_cnt);   // six DPP steps
     my_rel = incl - my_cnt;   // start of my text's spans in the wavefront's range
-    total_spans = __shfl(incl, 63);
+    total_spans = __builtin_amdgcn_readlane(incl, 63);   // an SGPR: the choice of path below is a scalar branch
+    if constexpr (LEAN) retire_batch();   // (in front of the stores, which the same counter counts, and of every branch)
     if (i < n) prefix[i] = pre0 + my_rel;
     if (i == n - 1) { prefix[n] = pre0 + incl; *total_out = pre0 + incl; }
     }
-    const int total_recs = wave_nrecs[w];
-    const EvRec* wave_recs = recs + (DYN ? rec_region_dyn(offsets[first], w)
-                                         : offsets ? rec_region_start(offsets[first], w) : first * rec_row);
-    const uint32_t* wave_recs12 = REC12 ? (const uint32_t*)recs + 3 * (first * rec_row) : nullptr;
     const int my_vb = (VBASE && i < n) ? vbase[i] : 0;
+    if constexpr (LEAN) {
+      if (total_spans <= kDecodeTile) {   // (wave uniform) one pass: every span of the wavefront has its place in the tile
+        // What differs from the loop below (mrx_decode_bits.hpp, DESIGN 3.2): no per-span bounds test -- with tb = 0 and
+        // total_spans <= TILE every index is inside the tile, capacity is checked at the stores --, the fixed-length form
+        // chosen once per wavefront, the start as a max, and the record loads of load_batch above, whose first batch
+        // has been under way since the top of the task.
+        const int nrec = total_recs, nspan = total_spans;
+        auto lean_pass = [&](auto fixed_tag) {
+          constexpr bool FIXED = decltype(fixed_tag)::value;
+          for (int j = 0; j < nrec; j += 64 * kDecodeBatch) {
+            if (j > 0) load_batch(j);   // (wave uniform)
+#pragma unroll
+            for (int u = 0; u < kDecodeBatch; ++u) {
+              if (j + u * 64 >= nrec) break;   // (wave uniform) the last batch's empty rounds
+              const bool mine = j + u * 64 + lane < nrec;
+              const uint32_t f_even = mine ? fe[u] : 0u, f_odd = mine ? fo[u] : 0u;
+              const uint32_t meta = m3[u];
+              const int rel_t = __shfl(my_rel, (int)(meta >> 26));
+              uint32_t* tp = tile + (rel_t + (REC12 ? rec12_before(meta) : (int)(meta & kBefore)));   // the record's first span
+              const int pb = REC12 ? 32 * rec12_pair(meta) : (int)(m2[u] >> 16) - kRecPosBias;
+              const int rstart = REC12 ? rec12_start(meta) : (int)(m2[u] & 0xFFFFu);
+              auto emit = [&](int st, int end) { *tp++ = ((uint32_t)st << 16) | (uint32_t)end; };
+              decode_expand_record<FIXED>(f_even, f_odd, rstart, pb, fixed_len, emit);
+            }
+          }
+        };
+        if (fixed_len > 0) lean_pass(std::true_type{}); else lean_pass(std::false_type{});
+        retire_batch();   // (the last batch's empty rounds, issued with those that were used; in front of the stores)
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        for (int k = lane; k < nspan; k += 64) {
+          const int64_t dst = pre0 + k;
+          if (dst < span_cap) { const uint32_t v = tile[k]; mrx_stg_span(spans + 2 * dst, (int)(v >> 16), (int)(v & 0xFFFFu)); }
+        }
+        __builtin_amdgcn_wave_barrier();
+        continue;
+      }
+    }
     if (total_spans > kDecodeDirect) {
       // dense matches: the tile passes would re-read the stream total_spans / kDecodeTile times.  One pass instead.
       // Round 3: the spans of a batch of records no longer leave as per-lane 8-byte stores scattered over the 64 texts'
@@ -3155,57 +3254,6 @@ __global__ __launch_bounds__(kBlock) void k_decode(int64_t n, const int32_t* __r
         }
       }
       continue;
-    }
-    if constexpr (LEAN) {
-      if (total_spans <= kDecodeTile) {   // (wave uniform) one pass: every span of the wavefront has its place in the tile
-        // What differs from the loop below (mrx_decode_bits.hpp, DESIGN 3.2): no per-span bounds test -- with tb = 0 and
-        // total_spans <= TILE every index is inside the tile, capacity is checked at the stores --, the fixed-length form
-        // chosen once per wavefront, the start as a max, and record loads that do not branch: a slot behind the
-        // wavefront's last record reads that last record again (same line) and its event words are zeroed.
-        const int nrec = __builtin_amdgcn_readfirstlane(total_recs), nspan = __builtin_amdgcn_readfirstlane(total_spans);
-        const int last_rec = nrec - 1;
-        auto lean_pass = [&](auto fixed_tag) {
-          constexpr bool FIXED = decltype(fixed_tag)::value;
-          for (int j = 0; j < nrec; j += 64 * kDecodeBatch) {
-            uint32_t fe[kDecodeBatch], fo[kDecodeBatch], m2[kDecodeBatch], m3[kDecodeBatch];
-#pragma unroll
-            for (int u = 0; u < kDecodeBatch; ++u) {
-              const int o = j + u * 64 + lane;
-              const int oc = o < last_rec ? o : last_rec;   // (last use of the record: non-temporal)
-              if (REC12) {
-                const uint32_t* q_ = wave_recs12 + 3 * oc;
-                fe[u] = mrx_ldg32(q_); fo[u] = mrx_ldg32(q_ + 1); m3[u] = mrx_ldg32(q_ + 2); m2[u] = 0;
-              } else {
-                const uint4 q_ = mrx_ldg((const uint4*)(wave_recs + oc));
-                fe[u] = q_.x; fo[u] = q_.y; m2[u] = q_.z; m3[u] = q_.w;
-              }
-            }
-#pragma unroll
-            for (int u = 0; u < kDecodeBatch; ++u) {
-              if (j + u * 64 >= nrec) break;   // (wave uniform) the last batch's empty rounds
-              const bool mine = j + u * 64 + lane < nrec;
-              const uint32_t f_even = mine ? fe[u] : 0u, f_odd = mine ? fo[u] : 0u;
-              const uint32_t meta = m3[u];
-              const int rel_t = __shfl(my_rel, (int)(meta >> 26));
-              uint32_t* tp = tile + (rel_t + (REC12 ? rec12_before(meta) : (int)(meta & kBefore)));   // the record's first span
-              const int pb = REC12 ? 32 * rec12_pair(meta) : (int)(m2[u] >> 16) - kRecPosBias;
-              const int rstart = REC12 ? rec12_start(meta) : (int)(m2[u] & 0xFFFFu);
-              auto emit = [&](int st, int end) { *tp++ = ((uint32_t)st << 16) | (uint32_t)end; };
-              decode_expand_record<FIXED>(f_even, f_odd, rstart, pb, fixed_len, emit);
-            }
-          }
-        };
-        if (fixed_len > 0) lean_pass(std::true_type{}); else lean_pass(std::false_type{});
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        for (int k = lane; k < nspan; k += 64) {
-          const int64_t dst = pre0 + k;
-          if (dst < span_cap) { const uint32_t v = tile[k]; mrx_stg_span(spans + 2 * dst, (int)(v >> 16), (int)(v & 0xFFFFu)); }
-        }
-        __builtin_amdgcn_wave_barrier();
-        continue;
-      }
     }
     for (int tb = 0; tb < total_spans; tb += kDecodeTile) {
       for (int j = 0; j < total_recs; j += 64 * kDecodeBatch) {
