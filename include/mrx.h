@@ -815,7 +815,74 @@ int mrx_parse_spans_strided_dev(const uint8_t* d_data, int64_t stride, const int
                                 int32_t kind, int64_t fill, int64_t row_cap, int64_t* d_values, uint8_t* d_status,
                                 int64_t* d_owner, int64_t* d_totals, int64_t* totals, void* stream);
 
+/* ---- format: number and text columns written as packed records on the device ----
+ * The step from numbers back to bytes, the inverse of numbers, shaped like expand: one record per row is built from a
+ * template, text columns and number columns, and the records are packed back to back as a new CSR batch, in row order.
+ * The output buffer is the report as it stands, and a batch for the next call (composite keys for distinct, records
+ * for a dictionary).  No pattern is involved.
+ * The TEMPLATE has the one grammar of mrx_sub_dev and mrx_expand_*: \1 .. \9 are references, \j being the cell of
+ * column j (1-based) in the row; every other byte is literal (\0, \\ and a trailing \ stay as they are).  A reference
+ * may repeat; one to a column the call does not have contributes nothing, as expand's to a group the rows lack; an
+ * empty template gives empty records whose offset repeats.
+ * A COLUMN (mrx_column, host memory whose pointers are device pointers) describes the same n rows as every other one:
+ *   MRX_COL_TEXT   the row's text, d_values being the batch's d_data: CSR with d_offsets int64[n + 1], or at a fixed
+ *                  pitch (d_offsets NULL; stride, d_lens, len as every _strided_dev entry point has them); any
+ *                  alignment; an empty text is an empty cell.  arg is not read.
+ *   MRX_COL_INT10  d_values int64[n]: '-' for a negative value, then the decimal magnitude with zeros in front up to at
+ *                  least K = arg digits (0 .. 20; 0 is read as 1): printf's "%.Kd".  INT64_MIN prints all its digits.
+ *   MRX_COL_INT16  d_values int64[n]: '-', then the magnitude in lower-case hex without 0x, padded the same way, so
+ *                  -255 is -ff: the inverse of MRX_NUM_INT16.
+ *   MRX_COL_FIXED  d_values double[n]: fixed notation with P = arg digits (0 .. 9) behind the point, no point for
+ *                  P = 0: printf's "%.Pf".  Correctly rounded from the exact binary value, ties to even (0.5 -> 0,
+ *                  2.5 -> 2, 0.125 at P = 2 -> 0.12); the sign is the sign bit (-0.0 -> -0.000, -0.04 at P = 1 -> -0.0).
+ * A FIXED cell is exact or refused, as a parsed float is: it is answered when N = round_half_even(|v| * 10^P) is below
+ * 10^19, and the cell is then the digits of N, padded to P + 1, with the point put in.  No floating-point operation
+ * decides this: |v| = m * 2^e with m < 2^53 (denormals: e = -1074), m * 10^P is formed in 128 bits and shifted by e,
+ * rounding on the remainder.  Everything else is MRX_NUM_RANGE, NaN and the infinities included.  A number cell has at
+ * most 21 bytes.
+ * d_status uint8[n] (may be NULL) of a number column is what numbers wrote beside the values: a cell whose byte is not
+ * MRX_NUM_OK contributes NOTHING, so a fill word is never printed; nor does a RANGE cell.  It is not read for a text
+ * column.  d_row_status uint8[n] (may be NULL) receives MRX_NUM_OK when every referenced cell of the row was written,
+ * else the status of the lowest-numbered referenced column whose cell was not: its input byte as it is, or
+ * MRX_NUM_RANGE.
+ * Outputs, capacity and totals are take's, word for word:
+ *   d_out_offsets int64[n + 1]  the CSR of the records; d_out_offsets[n] = bytes
+ *   d_out_data uint8[out_cap]   the records back to back; any alignment
+ *   d_totals int64[2]           {n, bytes}
+ * No byte of d_out_data at or past bytes, nor at or past out_cap, is ever written, and no element of d_out_offsets past
+ * n.  When bytes > out_cap, d_out_offsets, d_row_status and d_totals are still complete and correct, NO output byte is
+ * written, and a call with `totals` returns MRX_E_CAPACITY with totals filled.  totals (host, int64[2], may be NULL)
+ * receives d_totals: the call then reads back once, at its end.  With totals == NULL nothing is read back and the call
+ * returns without synchronising.  n == 0 gives d_totals = {0, 0} and d_out_offsets = {0}.  A record is at most tpl_len
+ * plus, per reference, the longest text of a text column or 21 bytes long.
+ * MRX_E_ARGUMENT, before any device call: negative n or out_cap; ncols outside 1 .. 9; a kind that is none of the
+ * four; K outside 0 .. 20 or P outside 0 .. 9; a null tpl with tpl_len > 0; a text column with a bad pitch; a null
+ * required pointer (cols; a column's d_values when n > 0; d_out_offsets; d_totals; d_out_data when out_cap > 0).
+ * Three launches (k_format_sizes, a scan, k_format_gather); no atomics.  Reads: a text cell's bytes are fetched as
+ * mrx_gather_spans_dev fetches a piece's, as the aligned 16-byte words that hold them and none for an empty cell; the
+ * literals come from the call's own padded copy.  Scratch: 8 bytes per row, 12 per row and referenced column, a scan's
+ * block sums and the template, returned to the arena when the call returns. */
+enum { MRX_COL_TEXT = 0, MRX_COL_INT10 = 1, MRX_COL_INT16 = 2, MRX_COL_FIXED = 3 };
+typedef struct mrx_column {
+  int32_t kind, arg;        /* arg: K (INT10, INT16), P (FIXED), not read (TEXT) */
+  const void* d_values;     /* int64[n] / double[n]; TEXT: the batch's d_data */
+  const int64_t* d_offsets; /* TEXT, CSR: int64[n + 1]; else NULL */
+  int64_t stride;           /* TEXT at a fixed pitch ... */
+  const int32_t* d_lens;    /* ... with its lengths int32[n], or NULL and ... */
+  int32_t len, pad_;        /* ... the common length */
+  const uint8_t* d_status;  /* a number column: uint8[n], or NULL */
+} mrx_column;
+int mrx_format_dev(const char* tpl, size_t tpl_len, const mrx_column* cols, int32_t ncols, int64_t n, int64_t* d_out_offsets,
+                   uint8_t* d_out_data, int64_t out_cap, uint8_t* d_row_status, int64_t* d_totals, int64_t* totals,
+                   void* stream);
+
 /* ---- host-buffer convenience wrappers (copy in, run, copy out) -------------- */
+/* mrx_format_dev on host buffers: the columns' pointers are host pointers (a text column's offsets may begin anywhere
+ * and must not decrease); out_offsets int64[n + 1], out_data uint8[out_cap], row_status uint8[n] (may be NULL), totals
+ * int64[2] = {n, bytes} (may be NULL).  out_offsets[0, n] and row_status are copied out, out_data only when all of it
+ * fits (MRX_E_CAPACITY otherwise). */
+int mrx_format_batch(const char* tpl, size_t tpl_len, const mrx_column* cols, int32_t ncols, int64_t n, int64_t* out_offsets,
+                     uint8_t* out_data, int64_t out_cap, uint8_t* row_status, int64_t* totals);
 /* mrx_parse_dev on host buffers: values int64[n], status uint8[n]. */
 int mrx_parse_batch(const uint8_t* data, const int64_t* offsets, int64_t n, int32_t kind, int64_t fill, int64_t* values,
                     uint8_t* status);

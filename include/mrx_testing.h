@@ -173,6 +173,15 @@ int mrx_debug_sort_rounds(void);
  * wavefront run several rounds of 64 rows without millions of them.  0 (default) = no cap of its own.  Results are the
  * same. */
 void mrx_debug_parse_grid(int workgroups);
+/* Format (include/mrx.h): the byte mover reports itself as "k_format_gather"; its grid is sized and capped as expand's
+ * (mrx_debug_expand_grid), and the sizes kernel's, a lane per row, likewise, both by this switch of their own.  0
+ * (default) = no cap.  Results are the same. */
+void mrx_debug_format_grid(int workgroups);
+/* The per-cell formatter of a number column on the CPU, for tests that pin it to Python's % without a GPU: kind and arg
+ * as in mrx_column, value_word the int64 or the bits of the double.  Writes the cell to out and returns its length (at
+ * most 21), or minus the status (-MRX_NUM_RANGE: the cell is not answered; -MRX_NUM_MALFORMED: MRX_COL_TEXT, a kind or
+ * an arg that mrx_format_dev refuses, or a null out). */
+int mrx_testing_format_one(int32_t kind, int32_t arg, int64_t value_word, uint8_t out[32]);
 /* Bytes of device memory the calling thread's scratch arenas hold (see mrx_release_scratch). */
 size_t mrx_debug_scratch_bytes(void);
 /* ... and how many of them are handed out and not yet rewound.  Scratch belongs to the call's scope, so between calls

@@ -35,6 +35,8 @@ argument meaning, a *batch* of texts instead of one text:
                                                   batch's texts, and the texts at given indices as a new batch
     (none: int(m.get_match_text()) per match)     numbers / parse_numbers / CompiledRegex.numbers /
                                                   DeviceBatch.parse / parse_spans: pieces as int64 / float64
+    (none: "%s %d\\n" % row on the host)          format_records / format_numbers / format_records_async:
+                                                  text and number columns as packed records, the report's bytes
 
 All matching runs in the HIP kernels of libmrx_hip.so.  There is no CPU
 fallback: if the library is missing or no GPU is usable, calls raise.
@@ -59,6 +61,9 @@ from .api import (  # noqa: F401
     filter_texts,
     findall,
     findall_texts,
+    format_numbers,
+    format_records,
+    format_records_async,
     library_path,
     load_library,
     lookup,

@@ -292,6 +292,14 @@ def load_library():
                                                   C.c_void_p, C.c_void_p]),
         "mrx_parse_batch": (C.c_int, [u8p, i64p, C.c_int64, C.c_int32, C.c_int64, i64p, u8p]),
         "mrx_debug_parse_grid": (None, [C.c_int]),
+        # format: (tpl, tpl_len, cols, ncols, n, out_offsets, out_data, out_cap, row_status, d_totals, totals, stream); on
+        # host buffers without d_totals and stream
+        "mrx_format_dev": (C.c_int, [C.c_char_p, C.c_size_t, C.c_void_p, C.c_int32, C.c_int64, i64p, u8p, C.c_int64, u8p, i64p,
+                                     C.c_void_p, C.c_void_p]),
+        "mrx_format_batch": (C.c_int, [C.c_char_p, C.c_size_t, C.c_void_p, C.c_int32, C.c_int64, i64p, u8p, C.c_int64, u8p,
+                                       C.c_void_p]),
+        "mrx_debug_format_grid": (None, [C.c_int]),
+        "mrx_testing_format_one": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, C.c_void_p]),
         "mrx_debug_set_route": (None, [C.c_int]),
         "mrx_testing_set_run": (C.c_int, [H, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_int32)]),
     }
@@ -332,6 +340,7 @@ EXPORTED_SYMBOLS = [
     "mrx_sort_dev", "mrx_sort_known_dev", "mrx_sort_strided_dev", "mrx_sort_batch",
     "mrx_take_dev", "mrx_take_known_dev", "mrx_take_strided_dev", "mrx_take_batch",
     "mrx_parse_dev", "mrx_parse_strided_dev", "mrx_parse_spans_dev", "mrx_parse_spans_strided_dev", "mrx_parse_batch",
+    "mrx_format_dev", "mrx_format_batch",
 ]
 TESTING_SYMBOLS = [
     "mrx_timing_reset", "mrx_timing_enable", "mrx_timing_scan_ms", "mrx_last_kernel_name",
@@ -343,6 +352,7 @@ TESTING_SYMBOLS = [
     "mrx_debug_expand_grid", "mrx_debug_distinct_hash_mask", "mrx_debug_distinct_grid",
     "mrx_debug_sort_small", "mrx_debug_sort_grid", "mrx_debug_sort_rounds", "mrx_debug_parse_grid",
     "mrx_debug_decode_lean", "mrx_debug_last_decode_lean", "mrx_testing_decode_expand",
+    "mrx_debug_format_grid", "mrx_testing_format_one",
 ]
 # (hooks with a digit in their name, listed apart: the header scan of tests/test_host_tables.py reads [a-z_] names)
 TESTING_SYMBOLS_NUMBERED = ["mrx_debug_rec12", "mrx_testing_rec12_roundtrip"]
@@ -856,16 +866,22 @@ def _extract_result(batch: "DeviceBatch", grown):
     return res, trim_p(owner, pieces)
 
 
-def _template_refs(template: bytes) -> int:
-    """The references of a template: the \\1..\\9 of sub's grammar (parse_repl_template scans left to right and passes
-    both bytes of a reference)."""
-    refs, i = 0, 0
+def _template_ref_list(template: bytes) -> List[int]:
+    """The references of a template, in order: the j of each \\1..\\9 of sub's grammar (parse_repl_template scans left to
+    right and passes both bytes of a reference)."""
+    refs, i = [], 0
     while i + 1 < len(template):
         if template[i] == 0x5C and 0x31 <= template[i + 1] <= 0x39:
-            refs, i = refs + 1, i + 2
+            refs.append(template[i + 1] - 0x30)
+            i += 2
         else:
             i += 1
     return refs
+
+
+def _template_refs(template: bytes) -> int:
+    """How many references a template has."""
+    return len(_template_ref_list(template))
 
 
 def _expand_result(batch: "DeviceBatch", template: bytes, grown):
@@ -1843,6 +1859,228 @@ def parse_numbers(texts, kind: str = "int"):
     _check(lib.mrx_parse_batch(data.ctypes.data, offsets.ctypes.data, n, k, 0, values.ctypes.data, status.ctypes.data))
     vals = (values.view(np.float64) if kind == "float" else values)[:n].tolist()
     return [v if s == MRX_NUM_OK else None for v, s in zip(vals, status[:n].tolist())]
+
+
+MRX_COL_TEXT, MRX_COL_INT10, MRX_COL_INT16, MRX_COL_FIXED = range(4)
+_FMT_CELL_MAX = 21   # the longest number cell: a sign and 20 digits
+_FMT_BOUND_FIRST = 1 << 26   # a known bound of the output up to here is the first capacity: no retry is ever needed
+_FMT_NUMBER_GUESS = 12       # ... beyond it a number cell is guessed at a sign and 11 digits, and the call may run twice
+
+
+class _Column(C.Structure):
+    """mrx_column of include/mrx.h."""
+    _fields_ = [("kind", C.c_int32), ("arg", C.c_int32), ("d_values", C.c_void_p), ("d_offsets", C.c_void_p),
+                ("stride", C.c_int64), ("d_lens", C.c_void_p), ("len", C.c_int32), ("pad_", C.c_int32),
+                ("d_status", C.c_void_p)]
+
+
+def _fmt_spec(spec) -> Tuple[int, int]:
+    """(kind, arg) of a printf-like spec: "d", ".Kd", "x", ".Kx" (K = 0..20) or ".Pf" (P = 0..9)."""
+    if not isinstance(spec, str) or not spec or spec[-1] not in "dxf":
+        raise MrxError("a column's spec must be 'd', '.Kd', 'x', '.Kx' or '.Pf', not %r" % (spec,))
+    letter, prec = spec[-1], spec[:-1]
+    if prec == "" and letter != "f":
+        return (MRX_COL_INT10 if letter == "d" else MRX_COL_INT16), 0
+    if len(prec) < 2 or len(prec) > 3 or prec[0] != "." or not prec[1:].isdigit() or not prec[1:].isascii():
+        raise MrxError("a column's spec must be 'd', '.Kd', 'x', '.Kx' or '.Pf', not %r" % (spec,))
+    arg = int(prec[1:])
+    if letter == "f":
+        if arg > 9:
+            raise MrxError("the precision P of '.Pf' must be in [0, 9]")
+        return MRX_COL_FIXED, arg
+    if arg > 20:
+        raise MrxError("the digits K of '.K%s' must be in [0, 20]" % letter)
+    return (MRX_COL_INT10 if letter == "d" else MRX_COL_INT16), arg
+
+
+def _fmt_split(col):
+    """(values, spec or None, status or None) of one entry of `columns`: a pair or triple is a tuple whose second
+    element is the spec."""
+    if isinstance(col, tuple) and len(col) in (2, 3) and isinstance(col[1], str):
+        return col[0], col[1], (col[2] if len(col) == 3 else None)
+    return col, None, None
+
+
+def _fmt_device_columns(template: bytes, columns):
+    """The columns of a device call: (mrx_column array, n, device, longest record or None, first capacity, what the
+    array's pointers keep alive).  Every error of a spec, a dtype or a row count is raised here, before any device
+    call."""
+    import torch
+    if not 1 <= len(columns) <= 9:
+        raise MrxError("format takes 1 to 9 columns")
+    arr = (_Column * len(columns))()
+    refs = _template_ref_list(template)
+    keep, n, dev, bounds, sizes = [], None, None, [], []
+    for j, col in enumerate(columns):
+        values, spec, status = _fmt_split(col)
+        c = arr[j]
+        if isinstance(values, DeviceBatch):
+            if spec is not None or status is not None:
+                raise MrxError("a text column takes no spec and no status")
+            rows, where = values.n, values.data.device
+            data = values.data
+            if data.numel() == 0:   # (texts without a byte: the ABI still wants a pointer)
+                data = torch.zeros(16, dtype=torch.uint8, device=where)
+            c.kind, c.arg, c.d_values, c.d_offsets = MRX_COL_TEXT, 0, _ptr(data), _ptr(values.offsets)
+            c.stride, c.d_lens, c.len = values.stride, _ptr(values.lens), values.length
+            keep += [data, values]
+            bounds.append(values.longest())
+            sizes.append(int(values.data.numel()))
+        elif isinstance(values, torch.Tensor):
+            if values.dim() != 1 or not values.is_contiguous():
+                raise MrxError("a number column must be a contiguous one-dimensional tensor")
+            if spec is None:
+                if values.dtype != torch.int64:
+                    raise MrxError("a %s column needs a spec ('.Pf' for float64)" % values.dtype)
+                spec = "d"
+            kind, arg = _fmt_spec(spec)
+            if values.dtype != (torch.float64 if kind == MRX_COL_FIXED else torch.int64):
+                raise MrxError("spec %r does not fit a %s column" % (spec, values.dtype))
+            rows, where = int(values.numel()), values.device
+            if status is not None:
+                if (not isinstance(status, torch.Tensor) or status.dtype != torch.uint8 or not status.is_contiguous()
+                        or status.numel() != rows or status.device != where):
+                    raise MrxError("a column's status must be a contiguous uint8[n] tensor on the values' device")
+            c.kind, c.arg, c.d_values, c.d_status = kind, arg, _ptr(values) if rows else 0, _ptr(status)
+            keep += [values, status]
+            bounds.append(_FMT_CELL_MAX)
+            sizes.append(_FMT_NUMBER_GUESS * rows)
+        else:
+            raise MrxError("a column must be a DeviceBatch, a tensor, (tensor, spec) or (tensor, spec, status)")
+        if n is None:
+            n, dev = rows, where
+        elif rows != n:
+            raise MrxError("columns of different row counts: %d and %d" % (n, rows))
+        elif where != dev:
+            raise MrxError("columns on different devices")
+    used = [j for j in refs if j <= len(columns)]
+    longest = None
+    if all(bounds[j - 1] is not None for j in used):
+        longest = len(template) + sum(int(bounds[j - 1]) for j in used)
+    if longest is not None and n * longest <= _FMT_BOUND_FIRST:
+        first = n * longest
+    else:   # an estimate: every byte of a referenced text column once per reference, 12 bytes a number
+        first = n * len(template) + sum(sizes[j - 1] for j in used)
+    return arr, n, dev, longest, first, keep
+
+
+def _fmt_host_column(values, spec):
+    """One host list as numpy arrays: a list of texts for a text column (bytes; None = an empty text), or (values,
+    spec, status) for a number column, whose None rows carry the status MRX_NUM_EMPTY.  Host work only."""
+    values = list(values)
+    some = next((v for v in values if v is not None), None)
+    if spec is None and (some is None or isinstance(some, (bytes, bytearray, str))):
+        return [b"" if v is None else _b(v) for v in values]
+    if spec is None:
+        if isinstance(some, float):
+            raise MrxError("a float column needs a spec ('.Pf')")
+        spec = "d"
+    kind, _ = _fmt_spec(spec)
+    try:
+        if kind == MRX_COL_FIXED:
+            host = np.array([0.0 if v is None else float(v) for v in values], np.float64)
+        else:
+            if any(v is not None and not isinstance(v, (int, np.integer)) for v in values):
+                raise MrxError("spec %r does not fit a column of %s" % (spec, type(some).__name__))
+            host = np.array([0 if v is None else int(v) for v in values], np.int64)
+    except (OverflowError, TypeError, ValueError) as e:
+        raise MrxError("spec %r does not fit the column: %s" % (spec, e))
+    return host, spec, np.array([MRX_NUM_EMPTY if v is None else MRX_NUM_OK for v in values], np.uint8)
+
+
+def format_records(template, columns, out_cap: Optional[int] = None, status: bool = False):
+    """One record per row from a template, text columns and number columns, packed back to back on the device
+    (include/mrx.h, mrx_format_dev): the inverse of numbers, shaped like expand.  template has sub's grammar -- \\1..\\9
+    name the columns, every other byte is literal; a reference to a column that is not there contributes nothing.
+    A column is a DeviceBatch (the row's text), an int64 tensor (spec "d"), (tensor, spec) or (tensor, spec, status):
+    the cell is b"%<spec>" % value byte for byte, with spec "d" / ".Kd" / "x" / ".Kx" (K = 0..20) for int64 and ".Pf"
+    (P = 0..9) for float64.  A ".Pf" cell is exact or refused: correctly rounded from the binary value, ties to even,
+    where round(|v| * 10^P) is below 10^19; NaN, the infinities and larger values print nothing.  status is the uint8
+    tensor that numbers / parse wrote beside the values: a cell whose byte is not 0 prints nothing.
+    Returns the records as a CSR DeviceBatch with known bounds -- its data tensor is the report as it stands, and the
+    batch feeds distinct, a Dictionary or any other call.  status=True also returns the row status, uint8[n]: 0 where
+    every referenced cell was written, else the status of the lowest-numbered referenced column whose cell was not (its
+    input byte, or 3 for a refused cell).  Without out_cap the output grows to what the records need; an out_cap of the
+    caller's that does not hold them raises MrxError.
+    When every column is a host list -- of bytes, of int, or of float with a spec; None = nothing -- the call uploads
+    them, runs the same kernels and returns List[bytes] (and with status=True the row status as a numpy array)."""
+    import torch
+    template = _b(template)
+    columns = list(columns)
+    host = [not isinstance(_fmt_split(c)[0], (DeviceBatch, torch.Tensor)) for c in columns]
+    if columns and all(host):
+        if not 1 <= len(columns) <= 9:
+            raise MrxError("format takes 1 to 9 columns")
+        staged = [_fmt_host_column(v, spec) for v, spec, _ in map(_fmt_split, columns)]
+        if len({len(c) if isinstance(c, list) else len(c[0]) for c in staged}) != 1:
+            raise MrxError("columns of different row counts")
+        up = lambda a: torch.from_numpy(a).to("cuda")   # noqa: E731
+        res = format_records(template, [DeviceBatch.from_texts(c) if isinstance(c, list) else (up(c[0]), c[1], up(c[2]))
+                                        for c in staged], out_cap, True)
+        raw, off = res[0].data.cpu().numpy().tobytes(), res[0].offsets.cpu().numpy()
+        records = [raw[off[i]:off[i + 1]] for i in range(len(off) - 1)]
+        return (records, res[1].cpu().numpy()) if status else records
+    if any(host):
+        raise MrxError("columns must all be device columns or all be host lists")
+    arr, n, dev, longest, first, keep = _fmt_device_columns(template, columns)
+    out_off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    row_status = torch.empty(n, dtype=torch.uint8, device=dev) if status else None
+    d_totals = torch.empty(2, dtype=torch.int64, device=dev)
+    totals = (C.c_int64 * 2)()
+    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    lib = load_library()
+
+    def run(out, cap, total):
+        rc = lib.mrx_format_dev(template, len(template), C.cast(arr, C.c_void_p), len(columns), n, _ptr(out_off), _ptr(out), cap,
+                                _ptr(row_status), _ptr(d_totals), C.cast(totals, C.c_void_p), stream)
+        total._obj.value = int(totals[1])
+        return rc
+    with torch.cuda.device(dev):
+        out, nbytes = _grow_call(first if out_cap is None else int(out_cap),
+                                 lambda cap: torch.empty(max(cap, 1), dtype=torch.uint8, device=dev), run,
+                                 grow=out_cap is None, only_larger=True)
+    del keep
+    data = out[:nbytes].clone() if 4 * nbytes < out.numel() else out[:nbytes]
+    records = DeviceBatch(data, out_off) if longest is None else DeviceBatch.csr_known(data, out_off, nbytes, longest)
+    return (records, row_status) if status else records
+
+
+def format_numbers(values, spec: str = "d", status=None):
+    """One column under the template \\1, the inverse of parse: every value written as b"%<spec>" % value, as a
+    DeviceBatch for a tensor and as List[bytes] for a host list (None = nothing).  status: the uint8 tensor that parse
+    wrote beside the values; rows whose byte is not 0 become empty texts."""
+    import torch
+    if isinstance(values, torch.Tensor):
+        return format_records(b"\\1", [(values, spec) if status is None else (values, spec, status)])
+    if status is not None:
+        values = [v if s == MRX_NUM_OK else None for v, s in zip(values, status)]
+    return format_records(b"\\1", [(list(values), spec)])
+
+
+def format_records_async(template, columns, out):
+    """Enqueue format_records on the current stream without reading anything back.  columns are device columns; out =
+    (out_offsets int64[n + 1], out_data uint8[cap], totals int64[2]) or, with a fourth entry, (..., row_status
+    uint8[n]), device tensors of the caller; totals = {n, bytes} once the stream has drained.  No byte is written when
+    bytes > cap (check totals[1])."""
+    import torch
+    template = _b(template)
+    arr, n, dev, _, _, keep = _fmt_device_columns(template, list(columns))
+    out_offsets, out_data, totals = out[:3]
+    row_status = out[3] if len(out) > 3 else None
+    if out_offsets.numel() < n + 1 or totals.numel() < 2:
+        raise MrxError("out needs out_offsets int64[n + 1], out_data uint8[cap], totals int64[2]")
+    for t in (out_offsets, totals):
+        if t.dtype != torch.int64 or not t.is_contiguous():
+            raise MrxError("out_offsets and totals must be contiguous int64 tensors")
+    for t in (out_data, row_status):
+        if t is not None and (t.dtype != torch.uint8 or not t.is_contiguous()):
+            raise MrxError("out_data and row_status must be contiguous uint8 tensors")
+    if row_status is not None and row_status.numel() < n:
+        raise MrxError("row_status needs n entries")
+    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    _check(load_library().mrx_format_dev(template, len(template), C.cast(arr, C.c_void_p), len(arr), n, _ptr(out_offsets),
+                                         _ptr(out_data), int(out_data.numel()), _ptr(row_status), _ptr(totals), None, stream))
+    del keep
 
 
 def sort_texts(texts):
