@@ -258,11 +258,7 @@ __global__ __launch_bounds__(kDistinctBlock) void k_distinct_finish(int64_t n, c
 uint64_t distinct_hash_mask() { return g_distinct_mask.load(std::memory_order_relaxed); }
 
 unsigned distinct_grid(int64_t items, int64_t per) {
-  int64_t g = (items + per - 1) / per;
-  g = g < 1 ? 1 : g > (int64_t)kDistinctMaxGrid ? (int64_t)kDistinctMaxGrid : g;
-  const int capped = g_distinct_grid.load(std::memory_order_relaxed);
-  if (capped > 0 && g > capped) g = capped;
-  return (unsigned)g;
+  return grid_for(items, per, kDistinctMaxGrid, g_distinct_grid.load(std::memory_order_relaxed));
 }
 
 int distinct_groups(const TextBatch& b, int64_t n, uint64_t mask, const DistinctGroups& g, void* stream) {
@@ -280,16 +276,9 @@ int distinct_groups(const TextBatch& b, int64_t n, uint64_t mask, const Distinct
 
 namespace {
 
-struct DistinctArgs {
+struct DistinctArgs : PackedDest {   // d_rows: d_first
   int64_t* d_group_of;
-  int64_t* d_first;
   int64_t* d_counts;
-  int64_t* d_out_offsets;
-  uint8_t* d_out_data;
-  int64_t out_cap;
-  int64_t* d_totals;
-  int64_t* totals;
-  void* stream;
 };
 
 // argument errors: nothing has touched the device when one of them returns
@@ -297,7 +286,7 @@ int distinct_check(const TextBatch& b, BatchForm form, int64_t n, const Distinct
   if (n < 0) return internal_fail(MRX_E_ARGUMENT, "n must be >= 0");
   if (a.out_cap < 0) return internal_fail(MRX_E_ARGUMENT, "out_cap must be >= 0");
   if (int rc = check_batch(b, form)) return rc;
-  if (!a.d_out_offsets || !a.d_totals || (n > 0 && (!a.d_group_of || !a.d_first || !a.d_counts)) ||
+  if (!a.d_out_offsets || !a.d_totals || (n > 0 && (!a.d_group_of || !a.d_rows || !a.d_counts)) ||
       (a.out_cap > 0 && !a.d_out_data))
     return internal_fail(MRX_E_ARGUMENT, "null argument");
   if (n >= ((int64_t)1 << 31)) return internal_fail(MRX_E_ARGUMENT, "n must be below 2^31: a table slot keeps a text's index in 32 bits");
@@ -307,12 +296,7 @@ int distinct_check(const TextBatch& b, BatchForm form, int64_t n, const Distinct
 int distinct_run(const TextBatch& b, BatchForm form, int64_t n, int64_t known_max, const DistinctArgs& a) {
   if (int rc = distinct_check(b, form, n, a)) return rc;
   hipStream_t hs = (hipStream_t)a.stream;
-  if (n == 0) {
-    MRX_HIP_TRY(hipMemsetAsync(a.d_out_offsets, 0, sizeof(int64_t), hs));
-    MRX_HIP_TRY(hipMemsetAsync(a.d_totals, 0, 2 * sizeof(int64_t), hs));
-    if (a.totals) a.totals[0] = a.totals[1] = 0;
-    return MRX_OK;
-  }
+  if (n == 0) return packed_empty(a);
   ScratchScope scope_(a.stream);
   uint64_t slots = 2;
   while (slots < 2 * (uint64_t)n) slots <<= 1;
@@ -342,17 +326,11 @@ int distinct_run(const TextBatch& b, BatchForm form, int64_t n, int64_t known_ma
   if (int rc = exclusive_scan(klen, n, pos, a.d_totals + 1, a.stream)) return rc;
   if (int rc = exclusive_scan(keep, n, rank, a.d_totals, a.stream)) return rc;
   hipLaunchKernelGGL(k_distinct_finish, dim3(distinct_grid(n + 1, kDistinctBlock)), blk, 0, hs, n, rep_of, first_at, count_at, rank,
-                     pos, err, DistinctOut{a.d_group_of, a.d_first, a.d_counts, a.d_out_offsets, a.d_totals});
+                     pos, err, DistinctOut{a.d_group_of, a.d_rows, a.d_counts, a.d_out_offsets, a.d_totals});
   MRX_HIP_TRY(hipGetLastError());
-  if (int rc = filter_gather_kept(b, n, known_max, a.d_first, a.d_out_offsets, a.d_totals, a.d_out_data, a.out_cap, a.stream))
+  if (int rc = filter_gather_kept(b, n, known_max, a.d_rows, a.d_out_offsets, a.d_totals, a.d_out_data, a.out_cap, a.stream))
     return rc;
-  if (!a.totals) return MRX_OK;
-  MRX_HIP_TRY(hipMemcpyAsync(a.totals, a.d_totals, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, hs));
-  MRX_HIP_TRY(hipStreamSynchronize(hs));
-  if (a.totals[0] < 0) return internal_fail(MRX_E_ARGUMENT, "distinct: a probe of the table ran out");
-  if (a.totals[1] > a.out_cap)
-    return internal_fail(MRX_E_CAPACITY, "output buffer too small: need " + std::to_string(a.totals[1]));
-  return MRX_OK;
+  return packed_verdict(a, -1, "distinct: a probe of the table ran out");
 }
 
 int distinct_known(const uint8_t* d_data, const int64_t* d_offsets, int64_t n, int64_t end_offset, int64_t max_text_len,
@@ -373,20 +351,20 @@ int mrx_distinct_dev(const uint8_t* d_data, const int64_t* d_offsets, int64_t n,
                      int64_t* d_counts, int64_t* d_out_offsets, uint8_t* d_out_data, int64_t out_cap, int64_t* d_totals,
                      int64_t* totals, void* stream) {
   return distinct_run(csr(d_data, d_offsets), BATCH_CSR, n, -1,
-                      DistinctArgs{d_group_of, d_first, d_counts, d_out_offsets, d_out_data, out_cap, d_totals, totals, stream});
+                      DistinctArgs{{d_first, d_out_offsets, d_out_data, out_cap, d_totals, totals, stream}, d_group_of, d_counts});
 }
 int mrx_distinct_known_dev(const uint8_t* d_data, const int64_t* d_offsets, int64_t n, int64_t end_offset,
                            int64_t max_text_len, int64_t* d_group_of, int64_t* d_first, int64_t* d_counts,
                            int64_t* d_out_offsets, uint8_t* d_out_data, int64_t out_cap, int64_t* d_totals,
                            int64_t* totals, void* stream) {
   return distinct_known(d_data, d_offsets, n, end_offset, max_text_len,
-                        DistinctArgs{d_group_of, d_first, d_counts, d_out_offsets, d_out_data, out_cap, d_totals, totals, stream});
+                        DistinctArgs{{d_first, d_out_offsets, d_out_data, out_cap, d_totals, totals, stream}, d_group_of, d_counts});
 }
 int mrx_distinct_strided_dev(const uint8_t* d_data, int64_t stride, const int32_t* d_lens, int32_t len, int64_t n,
                              int64_t* d_group_of, int64_t* d_first, int64_t* d_counts, int64_t* d_out_offsets,
                              uint8_t* d_out_data, int64_t out_cap, int64_t* d_totals, int64_t* totals, void* stream) {
   return distinct_run(strided(d_data, stride, d_lens, len), BATCH_PITCH, n, -1,
-                      DistinctArgs{d_group_of, d_first, d_counts, d_out_offsets, d_out_data, out_cap, d_totals, totals, stream});
+                      DistinctArgs{{d_first, d_out_offsets, d_out_data, out_cap, d_totals, totals, stream}, d_group_of, d_counts});
 }
 
 // host buffers: argument errors before any device work, as the _dev entry points
@@ -409,7 +387,7 @@ int mrx_distinct_batch(const uint8_t* data, const int64_t* offsets, int64_t n, i
   if (int rc = od.alloc((size_t)out_cap)) return rc;
   int64_t tot[2] = {0, 0};
   const int rc = distinct_known(b.data, b.offsets, n, b.nbytes, b.longest,
-                                DistinctArgs{go.p, fi.p, co.p, oo.p, od.p, out_cap, dt.p, tot, nullptr});
+                                DistinctArgs{{fi.p, oo.p, od.p, out_cap, dt.p, tot, nullptr}, go.p, co.p});
   if (rc != MRX_OK && rc != MRX_E_CAPACITY) return rc;
   if (totals) { totals[0] = tot[0]; totals[1] = tot[1]; }
   if (n > 0) MRX_HIP_TRY(hipMemcpy(group_of, go.p, sizeof(int64_t) * (size_t)n, hipMemcpyDeviceToHost));

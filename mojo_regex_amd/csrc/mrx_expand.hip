@@ -11,11 +11,9 @@
 // mrx_expand_* puts captures_all in front (rows into scratch).  captures_all returns its total through one stream
 // synchronisation, so the primitive then runs over exactly that many rows, not over the capacity.
 //
-// The gather is extract's block form (mrx_extract.hip, mrx_gather_bits.hpp): a lane owns one 16-byte block of the
-// output, aligned on the output address; a wavefront takes a contiguous run of blocks, 64 per round, bisects the output
-// CSR once, gallops per round, and each lane bisects between the round's bounds.  What is new is inside a record: the
-// lane walks the template's segments from the record's start to its own position (expand_seek) and then takes bytes
-// segment by segment, from the text for a group and from the literal buffer for a literal (expand_block,
+// The gather is the block walk of filter and extract (gather_blocks, mrx_gather_bits.hpp).  What is new is inside a
+// record: the lane walks the template's segments from the record's start to its own position (expand_seek) and then
+// takes bytes segment by segment, from the text for a group and from the literal buffer for a literal (expand_block,
 // mrx_expand_bits.hpp).  One form only: work is balanced by output bytes.
 #include <hip/hip_runtime.h>
 
@@ -40,21 +38,14 @@ constexpr unsigned kExpandMaxGrid = 2048;   // 8 workgroups per CU; the kernels 
 
 std::atomic<int> g_expand_grid{0};   // mrx_debug_expand_grid(): workgroups of the gather at most (0 = no cap of its own)
 
-// the rows, the template and where the records go: the arguments behind the batch of mrx_expand_spans_dev
-struct ExpandArgs {
+// where the records go, the rows and the template: the arguments behind the batch of mrx_expand_spans_dev
+struct ExpandArgs : PackedDest {   // d_rows: d_owner
   const int64_t* d_prefix;
-  const int32_t* d_rows;
+  const int32_t* d_groups;   // [rows][row_pairs][2]: the rows of captures_all
   int32_t row_pairs;
   const char* tpl;
   size_t tpl_len;
   int64_t piece_cap;
-  int64_t* d_owner;
-  int64_t* d_out_offsets;
-  uint8_t* d_out_data;
-  int64_t out_cap;
-  int64_t* d_totals;
-  int64_t* totals;
-  void* stream;
 };
 
 // the groups a template names, each once: slot q is pair[q] of a row and is referenced refs[q] times
@@ -150,43 +141,9 @@ __global__ __launch_bounds__(kExpandBlock) void k_expand_sizes(const TextBatch B
 __global__ __launch_bounds__(kExpandBlock, 8) void k_expand_gather(const ExpandOut O) {
   const int64_t pieces = O.totals[0], bytes = O.totals[1];
   if (pieces > O.cap || bytes <= 0 || bytes > O.out_cap) return;
-  const uintptr_t ob = (uintptr_t)O.out, a0 = ob & ~(uintptr_t)15;
-  const int64_t head = (int64_t)(ob - a0);   // output position p lies in block (p + head) / 16
-  const int64_t nblk = (head + bytes + 15) >> 4;
-  const int lane = (int)threadIdx.x & 63;
-  const int64_t nw = (int64_t)gridDim.x * (kExpandBlock / 64), w = (int64_t)blockIdx.x * (kExpandBlock / 64) + ((int)threadIdx.x >> 6);
-  const int64_t per = ((nblk + nw - 1) / nw + 63) & ~(int64_t)63;
-  const int64_t b_begin = w * per, b_end = b_begin + per < nblk ? b_begin + per : nblk;
-  if (b_begin >= b_end) return;
-  const int64_t* __restrict__ off = O.S.out_off;
-  const int64_t p_first = b_begin * 16 - head;
-  int64_t cur = gather_last_le(off, 0, pieces, p_first > 0 ? p_first : 0);
-  for (int64_t b0 = b_begin; b0 < b_end; b0 += 64) {
-    const int64_t bl = b0 + 63 < b_end ? b0 + 63 : b_end - 1;
-    const int64_t pe = bl * 16 - head + 15, pl = pe < bytes ? pe : bytes - 1;   // the round's last byte
-    const int64_t hi = gather_gallop(off, cur, pieces, pl);
-    const int64_t b = b0 + lane;
-    if (b <= bl) {
-      const int64_t p0 = b * 16 - head;
-      const int64_t pos = p0 > 0 ? p0 : 0;
-      const int64_t endp = p0 + 16 < bytes ? p0 + 16 : bytes;
-      // record r holds byte pos (off[pieces] = bytes > pos: r stays below pieces)
-      const int64_t r = gather_last_le(off, cur, hi + 1, pos);
-      const g_u128 acc = expand_block(O.S, r, hi, p0, pos, endp);
-      uint8_t* dst = (uint8_t*)(a0 + (uintptr_t)b * 16);
-      if (p0 >= 0 && p0 + 16 <= bytes) {
-        gather_store16(dst, acc);
-      } else {   // the first block of an unaligned output, the last block of the output
-        for (int q = p0 < 0 ? (int)-p0 : 0; q < (int)(endp - p0); ++q) dst[q] = (uint8_t)(acc >> (8 * q));
-      }
-    }
-    cur = hi;
-  }
-}
-
-unsigned expand_grid(int64_t items, int64_t per) {
-  const int64_t g = (items + per - 1) / per;
-  return (unsigned)(g < 1 ? 1 : g > (int64_t)kExpandMaxGrid ? (int64_t)kExpandMaxGrid : g);
+  gather_blocks<kExpandBlock>(O.out, bytes, O.S.out_off, pieces, [&](int64_t r, int64_t hi, int64_t p0, int64_t pos, int64_t endp) {
+    return expand_block(O.S, r, hi, p0, pos, endp);
+  });
 }
 
 // argument errors: nothing has touched the device when one of them returns.  own_rows: the rows are the call's own
@@ -196,19 +153,16 @@ int expand_check(const TextBatch& b, BatchForm form, int64_t n, const ExpandArgs
   if (a.piece_cap < 0 || a.out_cap < 0) return internal_fail(MRX_E_ARGUMENT, "piece_cap and out_cap must be >= 0");
   if (a.row_pairs < 1) return internal_fail(MRX_E_ARGUMENT, "row_pairs must be >= 1");
   if (!a.tpl && a.tpl_len > 0) return internal_fail(MRX_E_ARGUMENT, "null template of nonzero length");
-  if ((uintptr_t)a.d_rows & 7) return internal_fail(MRX_E_ARGUMENT, "d_rows must be 8-byte aligned");
+  if ((uintptr_t)a.d_groups & 7) return internal_fail(MRX_E_ARGUMENT, "d_rows must be 8-byte aligned");
   if (int rc = check_batch(b, form)) return rc;
-  if (!a.d_prefix || !a.d_out_offsets || !a.d_totals || (a.piece_cap > 0 && (!a.d_owner || (!own_rows && !a.d_rows))) ||
+  if (!a.d_prefix || !a.d_out_offsets || !a.d_totals || (a.piece_cap > 0 && (!a.d_rows || (!own_rows && !a.d_groups))) ||
       (a.out_cap > 0 && !a.d_out_data))
     return internal_fail(MRX_E_ARGUMENT, "null argument");
   return MRX_OK;
 }
 
 int expand_empty(const ExpandArgs& a) {   // n == 0
-  hipStream_t hs = (hipStream_t)a.stream;
-  MRX_HIP_TRY(hipMemsetAsync(a.d_out_offsets, 0, sizeof(int64_t), hs));
-  MRX_HIP_TRY(hipMemsetAsync(a.d_totals, 0, 2 * sizeof(int64_t), hs));
-  if (a.totals) a.totals[0] = a.totals[1] = 0;
+  if (int rc = packed_empty(a)) return rc;
   set_last_kernel("k_expand_gather");
   return MRX_OK;
 }
@@ -228,29 +182,21 @@ int expand_enqueue(const TextBatch& b, int64_t n, const ExpandArgs& a, int64_t c
   if (!plen || !base || !pairs || !d_tpl) return internal_fail(MRX_E_NO_DEVICE, "scratch allocation failed");
   MRX_HIP_TRY(hipMemcpyAsync(d_tpl, t.blob.data(), t.blob.size(), hipMemcpyHostToDevice, hs));
   const dim3 blk(kExpandBlock);
-  hipLaunchKernelGGL(k_expand_sizes, dim3(expand_grid(cap, kExpandBlock)), blk, 0, hs, b, n, a.d_prefix, a.d_rows,
-                     (int)a.row_pairs, t.sl, t.lit_total, cap, a.d_owner, plen, base, pairs, a.d_totals);
+  hipLaunchKernelGGL(k_expand_sizes, dim3(grid_for(cap, kExpandBlock, kExpandMaxGrid)), blk, 0, hs, b, n, a.d_prefix, a.d_groups,
+                     (int)a.row_pairs, t.sl, t.lit_total, cap, a.d_rows, plen, base, pairs, a.d_totals);
   MRX_HIP_TRY(hipGetLastError());
   if (int rc = exclusive_scan(plen, cap, a.d_out_offsets, a.d_totals + 1, a.stream)) return rc;
   if (a.out_cap > 0 && cap > 0 && !t.segs.empty()) {   // (nothing fits a capacity of 0, and no empty output has a byte to move)
     const ExpandOut O{ExpandSrc{b.data, d_tpl + t.lits_at, (const ExpandSeg*)d_tpl, (int32_t)t.segs.size(), t.sl.n, base, pairs,
                                 a.d_out_offsets},
                       a.d_totals, cap, a.d_out_data, a.out_cap};
-    unsigned grid = expand_grid(a.out_cap / 16 + 2, kExpandBlock);   // a wavefront per 64 blocks = 1 KiB of output at least
-    const int capped = g_expand_grid.load(std::memory_order_relaxed);
-    if (capped > 0 && grid > (unsigned)capped) grid = (unsigned)capped;
+    // a wavefront per 64 blocks = 1 KiB of output at least
+    const unsigned grid = grid_for(a.out_cap / 16 + 2, kExpandBlock, kExpandMaxGrid, g_expand_grid.load(std::memory_order_relaxed));
     hipLaunchKernelGGL(k_expand_gather, dim3(grid), blk, 0, hs, O);
     MRX_HIP_TRY(hipGetLastError());
   }
   set_last_kernel("k_expand_gather");
-  if (!a.totals) return MRX_OK;
-  MRX_HIP_TRY(hipMemcpyAsync(a.totals, a.d_totals, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, hs));
-  MRX_HIP_TRY(hipStreamSynchronize(hs));
-  if (a.totals[0] > a.piece_cap)
-    return internal_fail(MRX_E_CAPACITY, "piece buffers too small: need " + std::to_string(a.totals[0]));
-  if (a.totals[1] > a.out_cap)
-    return internal_fail(MRX_E_CAPACITY, "output buffer too small: need " + std::to_string(a.totals[1]));
-  return MRX_OK;
+  return packed_verdict(a, a.piece_cap);
 }
 
 int spans_run(const TextBatch& b, BatchForm form, int64_t n, const ExpandArgs& a) {
@@ -282,7 +228,7 @@ int expand_run(const mrx_handle* h, int64_t count, const TextBatch& b, BatchForm
   int64_t total = 0;
   const int rc = captures_all(rows, &total);
   if (rc != MRX_OK && rc != MRX_E_CAPACITY) return rc;
-  a.d_rows = rows;
+  a.d_groups = rows;
   // rows that do not fit: the kernels run over no row, leave {total, 0} in d_totals and write no byte
   const int rc2 = expand_enqueue(b, n, a, rc == MRX_OK ? total : 0);
   if (rc2 == MRX_OK && rc != MRX_OK)   // (totals == NULL: the host knows this one shortage all the same)
@@ -302,16 +248,16 @@ int mrx_expand_spans_dev(const uint8_t* d_data, const int64_t* d_offsets, int64_
                          int64_t* d_owner, int64_t* d_out_offsets, uint8_t* d_out_data, int64_t out_cap, int64_t* d_totals,
                          int64_t* totals, void* stream) {
   return spans_run(csr(d_data, d_offsets), BATCH_CSR, n,
-                   ExpandArgs{d_prefix, d_rows, row_pairs, tpl, tpl_len, piece_cap, d_owner, d_out_offsets, d_out_data, out_cap,
-                              d_totals, totals, stream});
+                   ExpandArgs{{d_owner, d_out_offsets, d_out_data, out_cap, d_totals, totals, stream}, d_prefix, d_rows, row_pairs,
+                              tpl, tpl_len, piece_cap});
 }
 int mrx_expand_spans_strided_dev(const uint8_t* d_data, int64_t stride, const int32_t* d_lens, int32_t len, int64_t n,
                                  const int64_t* d_prefix, const int32_t* d_rows, int32_t row_pairs, const char* tpl,
                                  size_t tpl_len, int64_t piece_cap, int64_t* d_owner, int64_t* d_out_offsets,
                                  uint8_t* d_out_data, int64_t out_cap, int64_t* d_totals, int64_t* totals, void* stream) {
   return spans_run(strided(d_data, stride, d_lens, len), BATCH_PITCH, n,
-                   ExpandArgs{d_prefix, d_rows, row_pairs, tpl, tpl_len, piece_cap, d_owner, d_out_offsets, d_out_data, out_cap,
-                              d_totals, totals, stream});
+                   ExpandArgs{{d_owner, d_out_offsets, d_out_data, out_cap, d_totals, totals, stream}, d_prefix, d_rows, row_pairs,
+                              tpl, tpl_len, piece_cap});
 }
 int mrx_expand_spans_batch(const uint8_t* data, const int64_t* offsets, int64_t n, const int64_t* prefix, const int32_t* rows,
                            int32_t row_pairs, const char* tpl, size_t tpl_len, int64_t piece_cap, int64_t* owner,
@@ -344,8 +290,8 @@ int mrx_expand_dev(const mrx_handle* h, const char* tpl, size_t tpl_len, int64_t
                    const int64_t* d_offsets, int64_t n, int64_t* d_match_prefix, int64_t* d_owner, int64_t* d_out_offsets,
                    int64_t match_cap, uint8_t* d_out_data, int64_t out_cap, int64_t* d_totals, int64_t* totals, void* stream) {
   return expand_run(h, count, csr(d_data, d_offsets), BATCH_CSR, n, d_match_prefix,
-                    ExpandArgs{nullptr, nullptr, 1, tpl, tpl_len, match_cap, d_owner, d_out_offsets, d_out_data, out_cap,
-                               d_totals, totals, stream},
+                    ExpandArgs{{d_owner, d_out_offsets, d_out_data, out_cap, d_totals, totals, stream}, nullptr, nullptr, 1, tpl,
+                               tpl_len, match_cap},
                     [&](int32_t* rows, int64_t* total) {
                       return mrx_captures_all_dev(h, d_data, d_offsets, n, count, d_match_prefix, rows, match_cap, total, stream);
                     });
@@ -355,8 +301,8 @@ int mrx_expand_strided_dev(const mrx_handle* h, const char* tpl, size_t tpl_len,
                            int64_t* d_owner, int64_t* d_out_offsets, int64_t match_cap, uint8_t* d_out_data, int64_t out_cap,
                            int64_t* d_totals, int64_t* totals, void* stream) {
   return expand_run(h, count, strided(d_data, stride, d_lens, len), BATCH_PITCH, n, d_match_prefix,
-                    ExpandArgs{nullptr, nullptr, 1, tpl, tpl_len, match_cap, d_owner, d_out_offsets, d_out_data, out_cap,
-                               d_totals, totals, stream},
+                    ExpandArgs{{d_owner, d_out_offsets, d_out_data, out_cap, d_totals, totals, stream}, nullptr, nullptr, 1, tpl,
+                               tpl_len, match_cap},
                     [&](int32_t* rows, int64_t* total) {
                       return mrx_captures_all_strided_dev(h, d_data, stride, d_lens, len, n, count, d_match_prefix, rows,
                                                           match_cap, total, stream);

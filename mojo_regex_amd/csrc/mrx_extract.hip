@@ -10,10 +10,8 @@
 // between: the kernels read pieces and bytes from d_totals and write no byte when either capacity is short.  With a
 // host `totals` the call reads d_totals back once, at the end.
 //
-// The gather is filter's block form (mrx_filter.hip, mrx_gather_bits.hpp): a lane owns one 16-byte block of the output,
-// aligned on the output address; a wavefront takes a contiguous run of blocks, 64 per round, bisects the output CSR
-// once for its first block, gallops per round to the piece of the round's last byte, and each lane bisects only
-// between the two.  A piece's source is its position from the sizes kernel, not a text index: a short match shares
+// The gather is the block walk that filter's block form has too (gather_blocks, mrx_gather_bits.hpp) with a fill of its
+// own.  A piece's source is its position from the sizes kernel, not a text index: a short match shares
 // its block with others (a lone [a-z]+\d+ token is about 6 bytes; the headline batch averages 26 bytes a piece, its
 // full-text matches included), each at an address the one before does not predict, so the lane walks the
 // pieces of its block and steps over runs of empty ones by galloping (an empty piece repeats its offset: the last
@@ -40,19 +38,12 @@ constexpr unsigned kExtractMaxGrid = 2048;   // 8 workgroups per CU; the kernels
 
 std::atomic<int> g_extract_grid{0};   // mrx_debug_extract_grid(): workgroups of the gather at most (0 = no cap of its own)
 
-// the rows and where their pieces go: the arguments behind the batch of mrx_gather_spans_dev
-struct SpanArgs {
+// where the pieces go and the rows: the arguments behind the batch of mrx_gather_spans_dev
+struct SpanArgs : PackedDest {   // d_rows: d_owner
   const int64_t* d_prefix;
   const int32_t* d_spans;
   int32_t row_pairs, pair;
   int64_t piece_cap;
-  int64_t* d_owner;
-  int64_t* d_out_offsets;
-  uint8_t* d_out_data;
-  int64_t out_cap;
-  int64_t* d_totals;
-  int64_t* totals;
-  void* stream;
 };
 
 // what the sizes kernel and the scan wrote and the gather reads
@@ -97,49 +88,18 @@ __global__ __launch_bounds__(kExtractBlock) void k_extract_sizes(const TextBatch
 __global__ __launch_bounds__(kExtractBlock) void k_extract_gather(const ExtractOut O) {
   const int64_t pieces = O.totals[0], bytes = O.totals[1];
   if (pieces > O.piece_cap || bytes <= 0 || bytes > O.out_cap) return;
-  const uintptr_t ob = (uintptr_t)O.out, a0 = ob & ~(uintptr_t)15;
-  const int64_t head = (int64_t)(ob - a0);   // output position p lies in block (p + head) / 16
-  const int64_t nblk = (head + bytes + 15) >> 4;
-  const int lane = (int)threadIdx.x & 63;
-  const int64_t nw = (int64_t)gridDim.x * (kExtractBlock / 64), w = (int64_t)blockIdx.x * (kExtractBlock / 64) + ((int)threadIdx.x >> 6);
-  const int64_t per = ((nblk + nw - 1) / nw + 63) & ~(int64_t)63;
-  const int64_t b_begin = w * per, b_end = b_begin + per < nblk ? b_begin + per : nblk;
-  if (b_begin >= b_end) return;
-  const int64_t p_first = b_begin * 16 - head;
-  int64_t cur = gather_last_le(O.out_off, 0, pieces, p_first > 0 ? p_first : 0);
-  for (int64_t b0 = b_begin; b0 < b_end; b0 += 64) {
-    const int64_t bl = b0 + 63 < b_end ? b0 + 63 : b_end - 1;
-    const int64_t pe = bl * 16 - head + 15, pl = pe < bytes ? pe : bytes - 1;   // the round's last byte
-    const int64_t hi = gather_gallop(O.out_off, cur, pieces, pl);
-    const int64_t b = b0 + lane;
-    if (b <= bl) {
-      const int64_t p0 = b * 16 - head;
-      int64_t pos = p0 > 0 ? p0 : 0;
-      const int64_t endp = p0 + 16 < bytes ? p0 + 16 : bytes;
-      int64_t r = gather_last_le(O.out_off, cur, hi + 1, pos);
-      g_u128 acc = 0;
-      while (true) {   // piece r holds byte pos (out_off[pieces] = bytes > pos: r stays below pieces)
-        const int64_t s = O.out_off[r], e = O.out_off[r + 1];
-        const int take = (int)((e < endp ? e : endp) - pos);
-        acc = gather_place(acc, O.data + O.src[r] + (pos - s), take, (int)(pos - p0));
-        pos += take;
-        if (pos >= endp) break;
-        r = gather_gallop(O.out_off, r + 1, hi + 1, pos);   // the next piece with a byte: empty ones are stepped over
-      }
-      uint8_t* dst = (uint8_t*)(a0 + (uintptr_t)b * 16);
-      if (p0 >= 0 && p0 + 16 <= bytes) {
-        gather_store16(dst, acc);
-      } else {   // the first block of an unaligned output, the last block of the output
-        for (int q = p0 < 0 ? (int)-p0 : 0; q < (int)(endp - p0); ++q) dst[q] = (uint8_t)(acc >> (8 * q));
-      }
+  gather_blocks<kExtractBlock>(O.out, bytes, O.out_off, pieces, [&](int64_t r, int64_t hi, int64_t p0, int64_t pos, int64_t endp) {
+    g_u128 acc = 0;
+    while (true) {   // piece r holds byte pos
+      const int64_t s = O.out_off[r], e = O.out_off[r + 1];
+      const int take = (int)((e < endp ? e : endp) - pos);
+      acc = gather_place(acc, O.data + O.src[r] + (pos - s), take, (int)(pos - p0));
+      pos += take;
+      if (pos >= endp) break;
+      r = gather_gallop(O.out_off, r + 1, hi + 1, pos);   // the next piece with a byte: empty ones are stepped over
     }
-    cur = hi;
-  }
-}
-
-unsigned extract_grid(int64_t items, int64_t per) {
-  const int64_t g = (items + per - 1) / per;
-  return (unsigned)(g < 1 ? 1 : g > (int64_t)kExtractMaxGrid ? (int64_t)kExtractMaxGrid : g);
+    return acc;
+  });
 }
 
 // argument errors: nothing has touched the device when one of them returns.  own_spans: the spans are the call's own
@@ -151,17 +111,14 @@ int gather_check(const TextBatch& b, BatchForm form, int64_t n, const SpanArgs& 
   if (a.pair < 0 || a.pair >= a.row_pairs) return internal_fail(MRX_E_ARGUMENT, "pair must be in [0, row_pairs)");
   if ((uintptr_t)a.d_spans & 7) return internal_fail(MRX_E_ARGUMENT, "d_spans must be 8-byte aligned");
   if (int rc = check_batch(b, form)) return rc;
-  if (!a.d_prefix || !a.d_out_offsets || !a.d_totals || (a.piece_cap > 0 && (!a.d_owner || (!own_spans && !a.d_spans))) ||
+  if (!a.d_prefix || !a.d_out_offsets || !a.d_totals || (a.piece_cap > 0 && (!a.d_rows || (!own_spans && !a.d_spans))) ||
       (a.out_cap > 0 && !a.d_out_data))
     return internal_fail(MRX_E_ARGUMENT, "null argument");
   return MRX_OK;
 }
 
 int gather_empty(const SpanArgs& a) {   // n == 0
-  hipStream_t hs = (hipStream_t)a.stream;
-  MRX_HIP_TRY(hipMemsetAsync(a.d_out_offsets, 0, sizeof(int64_t), hs));
-  MRX_HIP_TRY(hipMemsetAsync(a.d_totals, 0, 2 * sizeof(int64_t), hs));
-  if (a.totals) a.totals[0] = a.totals[1] = 0;
+  if (int rc = packed_empty(a)) return rc;
   set_last_kernel("k_extract_gather");
   return MRX_OK;
 }
@@ -175,27 +132,19 @@ int gather_enqueue(const TextBatch& b, int64_t n, const SpanArgs& a) {
   int64_t* src = (int64_t*)scratch_get(sizeof(int64_t) * cap, a.stream);
   if (!plen || !src) return internal_fail(MRX_E_NO_DEVICE, "scratch allocation failed");
   const dim3 blk(kExtractBlock);
-  hipLaunchKernelGGL(k_extract_sizes, dim3(extract_grid(a.piece_cap, kExtractBlock)), blk, 0, hs, b, n, a.d_prefix, a.d_spans,
-                     (int)a.row_pairs, (int)a.pair, a.piece_cap, a.d_owner, plen, src, a.d_totals);
+  hipLaunchKernelGGL(k_extract_sizes, dim3(grid_for(a.piece_cap, kExtractBlock, kExtractMaxGrid)), blk, 0, hs, b, n, a.d_prefix,
+                     a.d_spans, (int)a.row_pairs, (int)a.pair, a.piece_cap, a.d_rows, plen, src, a.d_totals);
   MRX_HIP_TRY(hipGetLastError());
   if (int rc = exclusive_scan(plen, a.piece_cap, a.d_out_offsets, a.d_totals + 1, a.stream)) return rc;
   if (a.out_cap > 0 && a.piece_cap > 0) {   // (nothing fits a capacity of 0, and no empty output has a byte to move)
     const ExtractOut O{b.data, src, a.d_out_offsets, a.d_totals, a.piece_cap, a.d_out_data, a.out_cap};
-    unsigned grid = extract_grid(a.out_cap / 16 + 2, kExtractBlock);   // a wavefront per 64 blocks = 1 KiB of output at least
-    const int capped = g_extract_grid.load(std::memory_order_relaxed);
-    if (capped > 0 && grid > (unsigned)capped) grid = (unsigned)capped;
+    // a wavefront per 64 blocks = 1 KiB of output at least
+    const unsigned grid = grid_for(a.out_cap / 16 + 2, kExtractBlock, kExtractMaxGrid, g_extract_grid.load(std::memory_order_relaxed));
     hipLaunchKernelGGL(k_extract_gather, dim3(grid), blk, 0, hs, O);
     MRX_HIP_TRY(hipGetLastError());
   }
   set_last_kernel("k_extract_gather");
-  if (!a.totals) return MRX_OK;
-  MRX_HIP_TRY(hipMemcpyAsync(a.totals, a.d_totals, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, hs));
-  MRX_HIP_TRY(hipStreamSynchronize(hs));
-  if (a.totals[0] > a.piece_cap)
-    return internal_fail(MRX_E_CAPACITY, "piece buffers too small: need " + std::to_string(a.totals[0]));
-  if (a.totals[1] > a.out_cap)
-    return internal_fail(MRX_E_CAPACITY, "output buffer too small: need " + std::to_string(a.totals[1]));
-  return MRX_OK;
+  return packed_verdict(a, a.piece_cap);
 }
 
 int gather_run(const TextBatch& b, BatchForm form, int64_t n, const SpanArgs& a) {
@@ -239,16 +188,16 @@ int mrx_gather_spans_dev(const uint8_t* d_data, const int64_t* d_offsets, int64_
                          int64_t* d_out_offsets, uint8_t* d_out_data, int64_t out_cap, int64_t* d_totals, int64_t* totals,
                          void* stream) {
   return gather_run(csr(d_data, d_offsets), BATCH_CSR, n,
-                    SpanArgs{d_prefix, d_spans, row_pairs, pair, piece_cap, d_owner, d_out_offsets, d_out_data, out_cap,
-                             d_totals, totals, stream});
+                    SpanArgs{{d_owner, d_out_offsets, d_out_data, out_cap, d_totals, totals, stream}, d_prefix, d_spans,
+                             row_pairs, pair, piece_cap});
 }
 int mrx_gather_spans_strided_dev(const uint8_t* d_data, int64_t stride, const int32_t* d_lens, int32_t len, int64_t n,
                                  const int64_t* d_prefix, const int32_t* d_spans, int32_t row_pairs, int32_t pair,
                                  int64_t piece_cap, int64_t* d_owner, int64_t* d_out_offsets, uint8_t* d_out_data,
                                  int64_t out_cap, int64_t* d_totals, int64_t* totals, void* stream) {
   return gather_run(strided(d_data, stride, d_lens, len), BATCH_PITCH, n,
-                    SpanArgs{d_prefix, d_spans, row_pairs, pair, piece_cap, d_owner, d_out_offsets, d_out_data, out_cap,
-                             d_totals, totals, stream});
+                    SpanArgs{{d_owner, d_out_offsets, d_out_data, out_cap, d_totals, totals, stream}, d_prefix, d_spans,
+                             row_pairs, pair, piece_cap});
 }
 int mrx_gather_spans_batch(const uint8_t* data, const int64_t* offsets, int64_t n, const int64_t* prefix,
                            const int32_t* spans, int32_t row_pairs, int32_t pair, int64_t piece_cap, int64_t* owner,
@@ -281,8 +230,8 @@ int mrx_extract_dev(const mrx_handle* h, const uint8_t* d_data, const int64_t* d
                     int64_t* d_piece_prefix, int64_t* d_owner, int64_t* d_out_offsets, int64_t piece_cap,
                     uint8_t* d_out_data, int64_t out_cap, int64_t* d_totals, int64_t* totals, void* stream) {
   return extract_run(h, csr(d_data, d_offsets), BATCH_CSR, n, -1, -1, d_piece_prefix,
-                     SpanArgs{nullptr, nullptr, 1, 0, piece_cap, d_owner, d_out_offsets, d_out_data, out_cap, d_totals,
-                              totals, stream});
+                     SpanArgs{{d_owner, d_out_offsets, d_out_data, out_cap, d_totals, totals, stream}, nullptr, nullptr, 1,
+                              0, piece_cap});
 }
 int mrx_extract_known_dev(const mrx_handle* h, const uint8_t* d_data, const int64_t* d_offsets, int64_t n,
                           int64_t end_offset, int64_t max_text_len, int64_t* d_piece_prefix, int64_t* d_owner,
@@ -291,16 +240,16 @@ int mrx_extract_known_dev(const mrx_handle* h, const uint8_t* d_data, const int6
   if (end_offset < 0 || max_text_len < 0)
     return internal_fail(MRX_E_ARGUMENT, "end_offset and max_text_len must not be negative");
   return extract_run(h, csr(d_data, d_offsets), BATCH_CSR, n, end_offset, max_text_len, d_piece_prefix,
-                     SpanArgs{nullptr, nullptr, 1, 0, piece_cap, d_owner, d_out_offsets, d_out_data, out_cap, d_totals,
-                              totals, stream});
+                     SpanArgs{{d_owner, d_out_offsets, d_out_data, out_cap, d_totals, totals, stream}, nullptr, nullptr, 1,
+                              0, piece_cap});
 }
 int mrx_extract_strided_dev(const mrx_handle* h, const uint8_t* d_data, int64_t stride, const int32_t* d_lens, int32_t len,
                             int64_t n, int64_t* d_piece_prefix, int64_t* d_owner, int64_t* d_out_offsets,
                             int64_t piece_cap, uint8_t* d_out_data, int64_t out_cap, int64_t* d_totals, int64_t* totals,
                             void* stream) {
   return extract_run(h, strided(d_data, stride, d_lens, len), BATCH_PITCH, n, -1, -1, d_piece_prefix,
-                     SpanArgs{nullptr, nullptr, 1, 0, piece_cap, d_owner, d_out_offsets, d_out_data, out_cap, d_totals,
-                              totals, stream});
+                     SpanArgs{{d_owner, d_out_offsets, d_out_data, out_cap, d_totals, totals, stream}, nullptr, nullptr, 1,
+                              0, piece_cap});
 }
 int mrx_extract_batch(const mrx_handle* h, const uint8_t* data, const int64_t* offsets, int64_t n, int64_t* piece_prefix,
                       int64_t* owner, int64_t* out_offsets, int64_t piece_cap, uint8_t* out_data, int64_t out_cap,

@@ -21,7 +21,8 @@
 // The search for a block's text is what a lane per block would pay log2(kept) dependent loads for.  A wavefront takes
 // one contiguous run of blocks, 64 per round: it bisects all kept texts once for its first block, then per round
 // gallops forward from the last round's text to the text of the round's last byte (uniform, broadcast loads), and
-// each lane bisects only the texts between the two -- none at all inside a long text.
+// each lane bisects only the texts between the two -- none at all inside a long text.  That walk is gather_blocks
+// (mrx_gather_bits.hpp), the one copy that extract, expand and format use too; k_filter_gather adds its block's fill.
 // k_filter_gather_text is the text-centric form for batches of short texts: 16 lanes take one kept text, move the
 // aligned 16-byte blocks that lie inside its output row through the same window and write the row's unaligned head
 // and tail byte by byte.  One text's offsets and index are loaded once for all its blocks, which is why it measured
@@ -113,52 +114,21 @@ __global__ __launch_bounds__(kFilterBlock) void k_filter_scatter(int64_t n, cons
 __global__ __launch_bounds__(kFilterBlock) void k_filter_gather(const TextBatch B, const FilterOut O) {
   const int64_t kept = O.totals[0], bytes = O.totals[1];
   if (bytes <= 0 || bytes > O.out_cap) return;
-  const uintptr_t ob = (uintptr_t)O.out, a0 = ob & ~(uintptr_t)15;
-  const int64_t head = (int64_t)(ob - a0);   // output position p lies in block (p + head) / 16
-  const int64_t nblk = (head + bytes + 15) >> 4;
-  const int lane = (int)threadIdx.x & 63;
-  const int64_t nw = (int64_t)gridDim.x * (kFilterBlock / 64), w = (int64_t)blockIdx.x * (kFilterBlock / 64) + ((int)threadIdx.x >> 6);
-  const int64_t per = ((nblk + nw - 1) / nw + 63) & ~(int64_t)63;
-  const int64_t b_begin = w * per, b_end = b_begin + per < nblk ? b_begin + per : nblk;
-  if (b_begin >= b_end) return;
-  const int64_t p_first = b_begin * 16 - head;
-  int64_t cur = gather_last_le(O.out_off, 0, kept, p_first > 0 ? p_first : 0);
-  for (int64_t b0 = b_begin; b0 < b_end; b0 += 64) {
-    const int64_t bl = b0 + 63 < b_end ? b0 + 63 : b_end - 1;
-    const int64_t pe = bl * 16 - head + 15, pl = pe < bytes ? pe : bytes - 1;   // the round's last byte
-    int64_t hi = cur, step = 1;
-    while (hi + step < kept && O.out_off[hi + step] <= pl) {
-      hi += step;
-      step <<= 1;
-    }
-    hi = gather_last_le(O.out_off, hi, hi + step < kept ? hi + step : kept, pl);
-    const int64_t b = b0 + lane;
-    if (b <= bl) {
-      const int64_t p0 = b * 16 - head;
-      int64_t pos = p0 > 0 ? p0 : 0;
-      const int64_t endp = p0 + 16 < bytes ? p0 + 16 : bytes;
-      int64_t r = gather_last_le(O.out_off, cur, hi + 1, pos);
-      g_u128 acc = 0;
-      while (pos < endp) {   // (out_off[kept] = bytes > pos: r stays below kept)
-        const int64_t s = O.out_off[r], e = O.out_off[r + 1];
-        if (e > pos) {
-          const int take = (int)((e < endp ? e : endp) - pos);
-          int32_t L;
-          const uint8_t* tp = B.text(O.kept_idx[r], &L);
-          acc = gather_place(acc, tp + (pos - s), take, (int)(pos - p0));
-          pos += take;
-        }
-        ++r;
+  gather_blocks<kFilterBlock>(O.out, bytes, O.out_off, kept, [&](int64_t r, int64_t, int64_t p0, int64_t pos, int64_t endp) {
+    g_u128 acc = 0;
+    while (pos < endp) {   // the kept texts of the block one by one: most have a byte
+      const int64_t s = O.out_off[r], e = O.out_off[r + 1];
+      if (e > pos) {
+        const int take = (int)((e < endp ? e : endp) - pos);
+        int32_t L;
+        const uint8_t* tp = B.text(O.kept_idx[r], &L);
+        acc = gather_place(acc, tp + (pos - s), take, (int)(pos - p0));
+        pos += take;
       }
-      uint8_t* dst = (uint8_t*)(a0 + (uintptr_t)b * 16);
-      if (p0 >= 0 && p0 + 16 <= bytes) {
-        gather_store16(dst, acc);
-      } else {   // the first block of an unaligned output, the last block of the output
-        for (int q = p0 < 0 ? (int)-p0 : 0; q < (int)(endp - p0); ++q) dst[q] = (uint8_t)(acc >> (8 * q));
-      }
+      ++r;
     }
-    cur = hi;
-  }
+    return acc;
+  });
 }
 
 __global__ __launch_bounds__(kFilterBlock) void k_filter_gather_text(const TextBatch B, const FilterOut O) {
@@ -182,10 +152,7 @@ __global__ __launch_bounds__(kFilterBlock) void k_filter_gather_text(const TextB
   }
 }
 
-unsigned filter_grid(int64_t items, int64_t per) {
-  const int64_t g = (items + per - 1) / per;
-  return (unsigned)(g < 1 ? 1 : g > (int64_t)kFilterMaxGrid ? (int64_t)kFilterMaxGrid : g);
-}
+unsigned filter_grid(int64_t items, int64_t per) { return grid_for(items, per, kFilterMaxGrid); }
 
 // the route rule: the text form when the host knows the batch's longest text and it is at most kFilterTextMax
 bool filter_text_form(const TextBatch& b, int64_t known_max) {
@@ -194,15 +161,8 @@ bool filter_text_form(const TextBatch& b, int64_t known_max) {
   return forced ? forced == 16 : (longest >= 0 && longest <= kFilterTextMax);
 }
 
-struct FilterArgs {
+struct FilterArgs : PackedDest {   // d_rows: d_kept_idx
   uint32_t flags;
-  int64_t* d_kept_idx;
-  int64_t* d_out_offsets;
-  uint8_t* d_out_data;
-  int64_t out_cap;
-  int64_t* d_totals;
-  int64_t* totals;
-  void* stream;
 };
 
 // argument errors, then refusals: nothing has touched the device when one of them returns
@@ -213,7 +173,7 @@ int filter_check(const mrx_handle* h, const mrx_set* set, bool is_set, const Tex
   if (n < 0) return internal_fail(MRX_E_ARGUMENT, "n must be >= 0");
   if (a.out_cap < 0) return internal_fail(MRX_E_ARGUMENT, "out_cap must be >= 0");
   if (int rc = check_batch(b, form)) return rc;
-  if (!a.d_out_offsets || !a.d_totals || (n > 0 && !a.d_kept_idx) || (a.out_cap > 0 && !a.d_out_data))
+  if (!a.d_out_offsets || !a.d_totals || (n > 0 && !a.d_rows) || (a.out_cap > 0 && !a.d_out_data))
     return internal_fail(MRX_E_ARGUMENT, "null argument");
   const std::string refused = is_set ? set_members_refusal(set) : handle_refusal(h);
   if (!refused.empty()) return internal_fail(MRX_E_UNSUPPORTED, refused);
@@ -224,8 +184,7 @@ int filter_run(const mrx_handle* h, const mrx_set* set, bool is_set, const TextB
                int64_t known_total, int64_t known_max, const FilterArgs& a) {
   if (int rc = filter_check(h, set, is_set, b, form, n, a)) return rc;
   hipStream_t hs = (hipStream_t)a.stream;
-  const FilterDest dest{a.d_kept_idx, a.d_out_offsets, a.d_out_data, a.out_cap, a.d_totals, a.totals, a.stream};
-  if (n == 0) return filter_no_text(b, known_max, dest);
+  if (n == 0) return filter_no_text(b, known_max, a);
   ScratchScope scope_(a.stream);
   const int k = is_set ? (int)mrx_set_size(set) : 1;
   const int words = (k + 63) / 64;
@@ -245,7 +204,7 @@ int filter_run(const mrx_handle* h, const mrx_set* set, bool is_set, const TextB
   hipLaunchKernelGGL(k_filter_flags, dim3(filter_grid(n, kFilterBlock)), blk, 0, hs, b, n, is_set ? nullptr : (const int32_t*)pred,
                      is_set ? (const uint64_t*)pred : nullptr, k, words, a.flags, klen, keep);
   MRX_HIP_TRY(hipGetLastError());
-  return filter_compact(b, n, known_max, FilterWork{klen, keep, pos, rank}, dest);
+  return filter_compact(b, n, known_max, FilterWork{klen, keep, pos, rank}, a);
 }
 
 int filter_known(const mrx_handle* h, const mrx_set* set, bool is_set, const uint8_t* d_data, const int64_t* d_offsets,
@@ -276,7 +235,7 @@ int filter_batch(const mrx_handle* h, const mrx_set* set, bool is_set, uint32_t 
   if (int rc = dt.alloc(2)) return rc;
   if (int rc = od.alloc((size_t)out_cap)) return rc;
   int64_t tot[2] = {0, 0};
-  const FilterArgs a{flags, ki.p, oo.p, od.p, out_cap, dt.p, tot, nullptr};
+  const FilterArgs a{{ki.p, oo.p, od.p, out_cap, dt.p, tot, nullptr}, flags};
   const int rc = filter_known(h, set, is_set, b.data, b.offsets, n, b.nbytes, b.longest, a);
   if (rc != MRX_OK && rc != MRX_E_CAPACITY) return rc;
   if (totals) { totals[0] = tot[0]; totals[1] = tot[1]; }
@@ -288,30 +247,22 @@ int filter_batch(const mrx_handle* h, const mrx_set* set, bool is_set, uint32_t 
 
 }  // namespace
 
-int filter_no_text(const TextBatch& b, int64_t known_max, const FilterDest& a) {
-  hipStream_t hs = (hipStream_t)a.stream;
-  MRX_HIP_TRY(hipMemsetAsync(a.d_out_offsets, 0, sizeof(int64_t), hs));
-  MRX_HIP_TRY(hipMemsetAsync(a.d_totals, 0, 2 * sizeof(int64_t), hs));
-  if (a.totals) a.totals[0] = a.totals[1] = 0;
+int filter_no_text(const TextBatch& b, int64_t known_max, const PackedDest& a) {
+  if (int rc = packed_empty(a)) return rc;
   set_last_kernel(filter_text_form(b, known_max) ? "k_filter_gather_text" : "k_filter_gather");
   return MRX_OK;
 }
 
-int filter_compact(const TextBatch& b, int64_t n, int64_t known_max, const FilterWork& w, const FilterDest& a) {
+int filter_compact(const TextBatch& b, int64_t n, int64_t known_max, const FilterWork& w, const PackedDest& a) {
   hipStream_t hs = (hipStream_t)a.stream;
   if (int rc = exclusive_scan(w.klen, n, w.pos, a.d_totals + 1, a.stream)) return rc;
   if (int rc = exclusive_scan(w.keep, n, w.rank, a.d_totals, a.stream)) return rc;
   hipLaunchKernelGGL(k_filter_scatter, dim3(filter_grid(n + 1, kFilterBlock)), dim3(kFilterBlock), 0, hs, n, w.keep, w.rank, w.pos,
-                     a.d_kept_idx, a.d_out_offsets);
+                     a.d_rows, a.d_out_offsets);
   MRX_HIP_TRY(hipGetLastError());
-  if (int rc = filter_gather_kept(b, n, known_max, a.d_kept_idx, a.d_out_offsets, a.d_totals, a.d_out_data, a.out_cap, a.stream))
+  if (int rc = filter_gather_kept(b, n, known_max, a.d_rows, a.d_out_offsets, a.d_totals, a.d_out_data, a.out_cap, a.stream))
     return rc;
-  if (!a.totals) return MRX_OK;
-  MRX_HIP_TRY(hipMemcpyAsync(a.totals, a.d_totals, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, hs));
-  MRX_HIP_TRY(hipStreamSynchronize(hs));
-  if (a.totals[1] > a.out_cap)
-    return internal_fail(MRX_E_CAPACITY, "output buffer too small: need " + std::to_string(a.totals[1]));
-  return MRX_OK;
+  return packed_verdict(a);
 }
 
 int filter_gather_kept(const TextBatch& b, int64_t n, int64_t known_max, const int64_t* d_kept_idx,
@@ -341,19 +292,19 @@ int mrx_filter_dev(const mrx_handle* h, uint32_t flags, const uint8_t* d_data, c
                    int64_t* d_kept_idx, int64_t* d_out_offsets, uint8_t* d_out_data, int64_t out_cap, int64_t* d_totals,
                    int64_t* totals, void* stream) {
   return filter_run(h, nullptr, false, csr(d_data, d_offsets), BATCH_CSR, n, -1, -1,
-                    FilterArgs{flags, d_kept_idx, d_out_offsets, d_out_data, out_cap, d_totals, totals, stream});
+                    FilterArgs{{d_kept_idx, d_out_offsets, d_out_data, out_cap, d_totals, totals, stream}, flags});
 }
 int mrx_filter_known_dev(const mrx_handle* h, uint32_t flags, const uint8_t* d_data, const int64_t* d_offsets, int64_t n,
                          int64_t end_offset, int64_t max_text_len, int64_t* d_kept_idx, int64_t* d_out_offsets,
                          uint8_t* d_out_data, int64_t out_cap, int64_t* d_totals, int64_t* totals, void* stream) {
   return filter_known(h, nullptr, false, d_data, d_offsets, n, end_offset, max_text_len,
-                      FilterArgs{flags, d_kept_idx, d_out_offsets, d_out_data, out_cap, d_totals, totals, stream});
+                      FilterArgs{{d_kept_idx, d_out_offsets, d_out_data, out_cap, d_totals, totals, stream}, flags});
 }
 int mrx_filter_strided_dev(const mrx_handle* h, uint32_t flags, const uint8_t* d_data, int64_t stride,
                            const int32_t* d_lens, int32_t len, int64_t n, int64_t* d_kept_idx, int64_t* d_out_offsets,
                            uint8_t* d_out_data, int64_t out_cap, int64_t* d_totals, int64_t* totals, void* stream) {
   return filter_run(h, nullptr, false, strided(d_data, stride, d_lens, len), BATCH_PITCH, n, -1, -1,
-                    FilterArgs{flags, d_kept_idx, d_out_offsets, d_out_data, out_cap, d_totals, totals, stream});
+                    FilterArgs{{d_kept_idx, d_out_offsets, d_out_data, out_cap, d_totals, totals, stream}, flags});
 }
 int mrx_filter_batch(const mrx_handle* h, uint32_t flags, const uint8_t* data, const int64_t* offsets, int64_t n,
                      int64_t* kept_idx, int64_t* out_offsets, uint8_t* out_data, int64_t out_cap, int64_t* totals) {
@@ -364,20 +315,20 @@ int mrx_set_filter_dev(const mrx_set* s, uint32_t flags, const uint8_t* d_data, 
                        int64_t* d_kept_idx, int64_t* d_out_offsets, uint8_t* d_out_data, int64_t out_cap,
                        int64_t* d_totals, int64_t* totals, void* stream) {
   return filter_run(nullptr, s, true, csr(d_data, d_offsets), BATCH_CSR, n, -1, -1,
-                    FilterArgs{flags, d_kept_idx, d_out_offsets, d_out_data, out_cap, d_totals, totals, stream});
+                    FilterArgs{{d_kept_idx, d_out_offsets, d_out_data, out_cap, d_totals, totals, stream}, flags});
 }
 int mrx_set_filter_known_dev(const mrx_set* s, uint32_t flags, const uint8_t* d_data, const int64_t* d_offsets, int64_t n,
                              int64_t end_offset, int64_t max_text_len, int64_t* d_kept_idx, int64_t* d_out_offsets,
                              uint8_t* d_out_data, int64_t out_cap, int64_t* d_totals, int64_t* totals, void* stream) {
   return filter_known(nullptr, s, true, d_data, d_offsets, n, end_offset, max_text_len,
-                      FilterArgs{flags, d_kept_idx, d_out_offsets, d_out_data, out_cap, d_totals, totals, stream});
+                      FilterArgs{{d_kept_idx, d_out_offsets, d_out_data, out_cap, d_totals, totals, stream}, flags});
 }
 int mrx_set_filter_strided_dev(const mrx_set* s, uint32_t flags, const uint8_t* d_data, int64_t stride,
                                const int32_t* d_lens, int32_t len, int64_t n, int64_t* d_kept_idx,
                                int64_t* d_out_offsets, uint8_t* d_out_data, int64_t out_cap, int64_t* d_totals,
                                int64_t* totals, void* stream) {
   return filter_run(nullptr, s, true, strided(d_data, stride, d_lens, len), BATCH_PITCH, n, -1, -1,
-                    FilterArgs{flags, d_kept_idx, d_out_offsets, d_out_data, out_cap, d_totals, totals, stream});
+                    FilterArgs{{d_kept_idx, d_out_offsets, d_out_data, out_cap, d_totals, totals, stream}, flags});
 }
 int mrx_set_filter_batch(const mrx_set* s, uint32_t flags, const uint8_t* data, const int64_t* offsets, int64_t n,
                          int64_t* kept_idx, int64_t* out_offsets, uint8_t* out_data, int64_t out_cap, int64_t* totals) {

@@ -9,11 +9,9 @@
 //                    scaling of a FIXED cell done here, once), the record's length and the row's status
 //   exclusive_scan   of the lengths, straight into d_out_offsets; sum -> d_totals[1]
 //   k_format_gather  the bytes
-// The gather is k_expand_gather's block form (mrx_expand.hip): a lane owns one 16-byte block of the output, aligned on
-// the output address; a wavefront takes a contiguous run of blocks, 64 per round, bisects the output CSR once, gallops
-// per round, and each lane bisects between the round's bounds and then walks the record's segments (format_block).  A
-// literal and a text cell go through gather_place; a number cell is rendered in registers and placed by the same mask
-// and shift (format_place).  No atomics, no LDS.
+// The gather is the block walk of the other byte movers (gather_blocks, mrx_gather_bits.hpp); its fill walks the
+// record's segments as k_expand_gather's does (format_block).  A literal and a text cell go through gather_place; a
+// number cell is rendered in registers and placed by the same mask and shift (format_place).  No atomics, no LDS.
 #include <hip/hip_runtime.h>
 
 #include <atomic>
@@ -46,19 +44,13 @@ struct FormatCol {
   int32_t kind, arg, refs, pad_;
 };
 
-struct FormatArgs {
+struct FormatArgs : PackedDest {   // d_rows: none
   const char* tpl;
   size_t tpl_len;
   const mrx_column* cols;
   int32_t ncols;
   int64_t n;
-  int64_t* d_out_offsets;
-  uint8_t* d_out_data;
-  int64_t out_cap;
   uint8_t* d_row_status;
-  int64_t* d_totals;
-  int64_t* totals;
-  void* stream;
 };
 
 TextBatch column_text(const mrx_column& c) {
@@ -159,45 +151,13 @@ __global__ __launch_bounds__(kFormatBlock) void k_format_sizes(const FormatCol* 
 __global__ __launch_bounds__(kFormatBlock) void k_format_gather(const FormatOut O) {
   const int64_t rows = O.S.rows, bytes = O.totals[1];
   if (bytes <= 0 || bytes > O.out_cap) return;
-  const uintptr_t ob = (uintptr_t)O.out, a0 = ob & ~(uintptr_t)15;
-  const int64_t head = (int64_t)(ob - a0);   // output position p lies in block (p + head) / 16
-  const int64_t nblk = (head + bytes + 15) >> 4;
-  const int lane = (int)threadIdx.x & 63;
-  const int64_t nw = (int64_t)gridDim.x * (kFormatBlock / 64), w = (int64_t)blockIdx.x * (kFormatBlock / 64) + ((int)threadIdx.x >> 6);
-  const int64_t per = ((nblk + nw - 1) / nw + 63) & ~(int64_t)63;
-  const int64_t b_begin = w * per, b_end = b_begin + per < nblk ? b_begin + per : nblk;
-  if (b_begin >= b_end) return;
-  const int64_t* __restrict__ off = O.S.out_off;
-  const int64_t p_first = b_begin * 16 - head;
-  int64_t cur = gather_last_le(off, 0, rows, p_first > 0 ? p_first : 0);
-  for (int64_t b0 = b_begin; b0 < b_end; b0 += 64) {
-    const int64_t bl = b0 + 63 < b_end ? b0 + 63 : b_end - 1;
-    const int64_t pe = bl * 16 - head + 15, pl = pe < bytes ? pe : bytes - 1;   // the round's last byte
-    const int64_t hi = gather_gallop(off, cur, rows, pl);
-    const int64_t b = b0 + lane;
-    if (b <= bl) {
-      const int64_t p0 = b * 16 - head;
-      const int64_t pos = p0 > 0 ? p0 : 0;
-      const int64_t endp = p0 + 16 < bytes ? p0 + 16 : bytes;
-      // record r holds byte pos (off[rows] = bytes > pos: r stays below rows)
-      const int64_t r = gather_last_le(off, cur, hi + 1, pos);
-      const g_u128 acc = format_block(O.S, r, hi, p0, pos, endp);
-      uint8_t* dst = (uint8_t*)(a0 + (uintptr_t)b * 16);
-      if (p0 >= 0 && p0 + 16 <= bytes) {
-        gather_store16(dst, acc);
-      } else {   // the first block of an unaligned output, the last block of the output
-        for (int q = p0 < 0 ? (int)-p0 : 0; q < (int)(endp - p0); ++q) dst[q] = (uint8_t)(acc >> (8 * q));
-      }
-    }
-    cur = hi;
-  }
+  gather_blocks<kFormatBlock>(O.out, bytes, O.S.out_off, rows, [&](int64_t r, int64_t hi, int64_t p0, int64_t pos, int64_t endp) {
+    return format_block(O.S, r, hi, p0, pos, endp);
+  });
 }
 
 unsigned format_grid(int64_t items, int64_t per) {
-  int64_t g = (items + per - 1) / per;
-  g = g < 1 ? 1 : g > (int64_t)kFormatMaxGrid ? (int64_t)kFormatMaxGrid : g;
-  const int capped = g_format_grid.load(std::memory_order_relaxed);
-  return (unsigned)(capped > 0 && g > capped ? capped : g);
+  return grid_for(items, per, kFormatMaxGrid, g_format_grid.load(std::memory_order_relaxed));
 }
 
 // what every entry point refuses about a column whatever memory its pointers mean
@@ -238,9 +198,7 @@ int format_run(const FormatArgs& a) {
   if (int rc = format_check(a)) return rc;
   hipStream_t hs = (hipStream_t)a.stream;
   if (a.n == 0) {
-    MRX_HIP_TRY(hipMemsetAsync(a.d_out_offsets, 0, sizeof(int64_t), hs));
-    MRX_HIP_TRY(hipMemsetAsync(a.d_totals, 0, 2 * sizeof(int64_t), hs));
-    if (a.totals) a.totals[0] = a.totals[1] = 0;
+    if (int rc = packed_empty(a)) return rc;
     set_last_kernel("k_format_gather");
     return MRX_OK;
   }
@@ -268,12 +226,7 @@ int format_run(const FormatArgs& a) {
     MRX_HIP_TRY(hipGetLastError());
   }
   set_last_kernel("k_format_gather");
-  if (!a.totals) return MRX_OK;
-  MRX_HIP_TRY(hipMemcpyAsync(a.totals, a.d_totals, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, hs));
-  MRX_HIP_TRY(hipStreamSynchronize(hs));
-  if (a.totals[1] > a.out_cap)
-    return internal_fail(MRX_E_CAPACITY, "output buffer too small: need " + std::to_string(a.totals[1]));
-  return MRX_OK;
+  return packed_verdict(a);
 }
 
 // a host column's buffers on the device
@@ -294,15 +247,16 @@ extern "C" {
 int mrx_format_dev(const char* tpl, size_t tpl_len, const mrx_column* cols, int32_t ncols, int64_t n, int64_t* d_out_offsets,
                    uint8_t* d_out_data, int64_t out_cap, uint8_t* d_row_status, int64_t* d_totals, int64_t* totals,
                    void* stream) {
-  return format_run(FormatArgs{tpl, tpl_len, cols, ncols, n, d_out_offsets, d_out_data, out_cap, d_row_status, d_totals, totals, stream});
+  return format_run(FormatArgs{{nullptr, d_out_offsets, d_out_data, out_cap, d_totals, totals, stream}, tpl, tpl_len, cols, ncols, n,
+                               d_row_status});
 }
 
 // host buffers: argument errors before any device work, as the _dev entry point
 int mrx_format_batch(const char* tpl, size_t tpl_len, const mrx_column* cols, int32_t ncols, int64_t n, int64_t* out_offsets,
                      uint8_t* out_data, int64_t out_cap, uint8_t* row_status, int64_t* totals) {
   int64_t fake_totals[2];   // (the device call wants one; this wrapper allocates its own)
-  if (int rc = format_check(FormatArgs{tpl, tpl_len, cols, ncols, n, out_offsets, out_data, out_cap, row_status, fake_totals,
-                                       nullptr, nullptr}))
+  if (int rc = format_check(FormatArgs{{nullptr, out_offsets, out_data, out_cap, fake_totals, nullptr, nullptr}, tpl, tpl_len, cols,
+                                       ncols, n, row_status}))
     return rc;
   std::vector<std::unique_ptr<DevColumn>> held;
   std::vector<mrx_column> dcols(cols, cols + ncols);
@@ -349,8 +303,8 @@ int mrx_format_batch(const char* tpl, size_t tpl_len, const mrx_column* cols, in
   if (int rc = od.alloc((size_t)out_cap)) return rc;
   if (int rc = rs.alloc((size_t)n)) return rc;
   int64_t tot[2] = {0, 0};
-  const int rc = format_run(FormatArgs{tpl, tpl_len, dcols.data(), ncols, n, oo.p, od.p, out_cap, row_status ? rs.p : nullptr, dt.p,
-                                       tot, nullptr});
+  const int rc = format_run(FormatArgs{{nullptr, oo.p, od.p, out_cap, dt.p, tot, nullptr}, tpl, tpl_len, dcols.data(), ncols, n,
+                                       row_status ? rs.p : nullptr});
   if (rc != MRX_OK && rc != MRX_E_CAPACITY) return rc;
   if (totals) { totals[0] = tot[0]; totals[1] = tot[1]; }
   MRX_HIP_TRY(hipMemcpy(out_offsets, oo.p, sizeof(int64_t) * (size_t)(n + 1), hipMemcpyDeviceToHost));

@@ -1,7 +1,9 @@
-// What the output-centric byte movers share (mrx_filter.hip, mrx_extract.hip, mrx_expand.hip): a lane owns one 16-byte block of
-// the output, aligned on the output ADDRESS, finds the piece that holds the block's first byte in the output's CSR and
-// fills the block from that piece's source and the following ones.  Host and device: the block assembly also runs on
-// the CPU against memcpy (tools/extract_block_check.cpp).
+// What the output-centric byte movers share (mrx_filter.hip, mrx_extract.hip, mrx_expand.hip, mrx_format.hip): a lane owns
+// one 16-byte block of the output, aligned on the output ADDRESS, finds the row that holds the block's first byte in the
+// output's CSR and fills the block from that row's source and the following ones.  The block assembly (window, place,
+// store, the two searches) is host and device code: it also runs on the CPU against memcpy (tools/extract_block_check.cpp,
+// expand_block_check.cpp, format_check.cpp, each with a sequential loop over the blocks of its own).  The walk that gives
+// every lane its block, gather_blocks at the end of this file, is device code and the only copy of it.
 #pragma once
 #include <cstdint>
 
@@ -59,5 +61,49 @@ MRX_HD int64_t gather_gallop(const int64_t* __restrict__ off, int64_t a, int64_t
   }
   return gather_last_le(off, a, a + step < b ? a + step : b, p);
 }
+
+#if defined(__HIPCC__)
+// The block walk of a gather kernel launched with workgroups of kBlock lanes: out[0, bytes) (bytes > 0) is cut into
+// 16-byte blocks aligned on out's address, and off[rows + 1] is its CSR (off[rows] = bytes).  A wavefront takes one
+// contiguous run of blocks, 64 per round: it bisects all rows once for its first block, then per round gallops forward
+// from the last round's row to the row of the round's last byte (uniform, broadcast loads), and each lane bisects only
+// the rows between the two.  fill(r, hi, p0, pos, endp) returns the lane's block: bytes [pos, endp) of the output, byte
+// p of it at block position p - p0 (p0 <= pos < endp <= p0 + 16); row r holds byte pos and row hi the round's last
+// byte (off[rows] = bytes > pos: r stays below rows).  A block inside the output goes out as one aligned 16-byte store;
+// only the first block (an unaligned out) and the last one (the end of the output) are written byte by byte, so nothing
+// outside [0, bytes) is touched.
+template <int kBlock, class Fill>
+__device__ __forceinline__ void gather_blocks(uint8_t* out, int64_t bytes, const int64_t* off, int64_t rows, const Fill& fill) {
+  const uintptr_t ob = (uintptr_t)out, a0 = ob & ~(uintptr_t)15;
+  const int64_t head = (int64_t)(ob - a0);   // output position p lies in block (p + head) / 16
+  const int64_t nblk = (head + bytes + 15) >> 4;
+  const int lane = (int)threadIdx.x & 63;
+  const int64_t nw = (int64_t)gridDim.x * (kBlock / 64), w = (int64_t)blockIdx.x * (kBlock / 64) + ((int)threadIdx.x >> 6);
+  const int64_t per = ((nblk + nw - 1) / nw + 63) & ~(int64_t)63;
+  const int64_t b_begin = w * per, b_end = b_begin + per < nblk ? b_begin + per : nblk;
+  if (b_begin >= b_end) return;
+  const int64_t p_first = b_begin * 16 - head;
+  int64_t cur = gather_last_le(off, 0, rows, p_first > 0 ? p_first : 0);
+  for (int64_t b0 = b_begin; b0 < b_end; b0 += 64) {
+    const int64_t bl = b0 + 63 < b_end ? b0 + 63 : b_end - 1;
+    const int64_t pe = bl * 16 - head + 15, pl = pe < bytes ? pe : bytes - 1;   // the round's last byte
+    const int64_t hi = gather_gallop(off, cur, rows, pl);
+    const int64_t b = b0 + lane;
+    if (b <= bl) {
+      const int64_t p0 = b * 16 - head;
+      const int64_t pos = p0 > 0 ? p0 : 0;
+      const int64_t endp = p0 + 16 < bytes ? p0 + 16 : bytes;
+      const g_u128 acc = fill(gather_last_le(off, cur, hi + 1, pos), hi, p0, pos, endp);
+      uint8_t* dst = (uint8_t*)(a0 + (uintptr_t)b * 16);
+      if (p0 >= 0 && p0 + 16 <= bytes) {
+        gather_store16(dst, acc);
+      } else {   // the first block of an unaligned output, the last block of the output
+        for (int q = p0 < 0 ? (int)-p0 : 0; q < (int)(endp - p0); ++q) dst[q] = (uint8_t)(acc >> (8 * q));
+      }
+    }
+    cur = hi;
+  }
+}
+#endif
 
 }  // namespace mrx

@@ -1,5 +1,7 @@
-// Host-buffer staging of the mrx_*_batch wrappers (mrx_kernels.hip, mrx_set.hip): a CSR batch copied to the device
-// with offsets made relative to its first byte, and device buffers for the outputs, all freed on every way out.
+// Host code that the entry points share.  The packed-output tail of the byte movers: the n == 0 result, the read-back
+// of {rows, bytes} with the capacity verdict, and the workgroup count.  Host-buffer staging of the mrx_*_batch wrappers
+// (mrx_kernels.hip, mrx_set.hip): a CSR batch copied to the device with offsets made relative to its first byte, and
+// device buffers for the outputs, all freed on every way out.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -19,6 +21,40 @@
   } while (0)
 
 namespace mrx {
+// ---- the packed-output tail of the byte movers (PackedDest, mrx_internal.hpp) --------------------------------------
+// The n == 0 result: an output CSR of no row and {0, 0} on both sides.  (The kernel's name is the caller's to report.)
+inline int packed_empty(const PackedDest& d) {
+  hipStream_t hs = (hipStream_t)d.stream;
+  MRX_HIP_TRY(hipMemsetAsync(d.d_out_offsets, 0, sizeof(int64_t), hs));
+  MRX_HIP_TRY(hipMemsetAsync(d.d_totals, 0, 2 * sizeof(int64_t), hs));
+  if (d.totals) d.totals[0] = d.totals[1] = 0;
+  return MRX_OK;
+}
+// Behind the gather.  Without a host `totals` the call has only enqueued; with one, d_totals = {rows, bytes} is read
+// back once and turned into the verdict.  piece_cap: the capacity in rows of an operation that has one (extract,
+// expand), else < 0.  failed: the message of an operation whose kernels report a failure of their own as rows < 0 (take,
+// distinct), else nullptr.
+inline int packed_verdict(const PackedDest& d, int64_t piece_cap = -1, const char* failed = nullptr) {
+  if (!d.totals) return MRX_OK;
+  hipStream_t hs = (hipStream_t)d.stream;
+  MRX_HIP_TRY(hipMemcpyAsync(d.totals, d.d_totals, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, hs));
+  MRX_HIP_TRY(hipStreamSynchronize(hs));
+  if (failed && d.totals[0] < 0) return internal_fail(MRX_E_ARGUMENT, failed);
+  if (piece_cap >= 0 && d.totals[0] > piece_cap)
+    return internal_fail(MRX_E_CAPACITY, "piece buffers too small: need " + std::to_string(d.totals[0]));
+  if (d.totals[1] > d.out_cap)
+    return internal_fail(MRX_E_CAPACITY, "output buffer too small: need " + std::to_string(d.totals[1]));
+  return MRX_OK;
+}
+// workgroups for `items` at `per` a workgroup: at least one, at most max_grid, and at most `cap` where a test has set
+// one (mrx_debug_*_grid; 0 = none)
+inline unsigned grid_for(int64_t items, int64_t per, unsigned max_grid, int cap = 0) {
+  int64_t g = (items + per - 1) / per;
+  g = g < 1 ? 1 : g > (int64_t)max_grid ? (int64_t)max_grid : g;
+  return (unsigned)(cap > 0 && g > cap ? cap : g);
+}
+
+// ---- host-buffer staging -------------------------------------------------------------------------------------------
 struct DevBatch {
   uint8_t* data = nullptr;
   int64_t* offsets = nullptr;

@@ -139,17 +139,22 @@ struct FilterWork {
   int64_t* pos;
   int64_t* rank;
 };
-struct FilterDest {   // the outputs of mrx_filter_dev, as its contract has them
-  int64_t* d_kept_idx;
-  int64_t* d_out_offsets;
+// Where a byte mover leaves its packed CSR batch, as the contracts of include/mrx.h have it: the one destination of
+// filter, extract, expand, format, take, distinct and the dictionaries' filter.  The argument structs of those calls
+// begin with it; what it ends in on the host (the n == 0 result, the read-back and the capacity verdict) is in
+// mrx_host_batch.hpp.
+struct PackedDest {
+  int64_t* d_rows;          // an index per output row: filter's kept_idx, extract's and expand's owner, distinct's first
+                            // (format and take have none: nullptr)
+  int64_t* d_out_offsets;   // [rows + 1]
   uint8_t* d_out_data;
   int64_t out_cap;
-  int64_t* d_totals;
-  int64_t* totals;
+  int64_t* d_totals;        // {rows, bytes} on the device
+  int64_t* totals;          // ... and on the host, or nullptr: the call only enqueues
   void* stream;
 };
-int filter_compact(const TextBatch& b, int64_t n, int64_t known_max, const FilterWork& w, const FilterDest& a);
-int filter_no_text(const TextBatch& b, int64_t known_max, const FilterDest& a);   // the n == 0 result
+int filter_compact(const TextBatch& b, int64_t n, int64_t known_max, const FilterWork& w, const PackedDest& a);
+int filter_no_text(const TextBatch& b, int64_t known_max, const PackedDest& a);   // the n == 0 result, and the kernel's name
 // mrx_distinct.hip: distinct's first three steps on a checked batch of n >= 1 texts, for a caller that keeps the table
 // (dictionaries): k_distinct_hash, k_distinct_insert and k_distinct_first, launched as distinct launches them.  `table`
 // (`slots` words, a power of two >= 2 n) and count_at[n] are zero, first_at[n] is all ones and *err is 0 when the

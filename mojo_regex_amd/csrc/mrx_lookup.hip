@@ -249,17 +249,17 @@ int dict_lookup(const mrx_dict* d, const TextBatch& b, BatchForm form, int64_t n
 struct DictFilterArgs {
   uint32_t flags;
   int64_t* d_index;
-  FilterDest dest;
+  PackedDest dest;
 };
 
 int dict_filter(const mrx_dict* d, const TextBatch& b, BatchForm form, int64_t n, int64_t known_max, const DictFilterArgs& a) {
-  const FilterDest& o = a.dest;
+  const PackedDest& o = a.dest;
   if (!d) return internal_fail(MRX_E_ARGUMENT, "null dictionary");
   if (a.flags & ~kDictFilterFlags) return internal_fail(MRX_E_ARGUMENT, "unknown flag bits");
   if (n < 0) return internal_fail(MRX_E_ARGUMENT, "n must be >= 0");
   if (o.out_cap < 0) return internal_fail(MRX_E_ARGUMENT, "out_cap must be >= 0");
   if (int rc = check_batch(b, form)) return rc;
-  if (!o.d_out_offsets || !o.d_totals || (n > 0 && !o.d_kept_idx) || (o.out_cap > 0 && !o.d_out_data))
+  if (!o.d_out_offsets || !o.d_totals || (n > 0 && !o.d_rows) || (o.out_cap > 0 && !o.d_out_data))
     return internal_fail(MRX_E_ARGUMENT, "null argument");
   if (n == 0) return filter_no_text(b, known_max, o);
   ScratchScope scope_(o.stream);

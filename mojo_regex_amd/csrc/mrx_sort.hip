@@ -250,11 +250,7 @@ __global__ void k_take_totals(int64_t k, const int32_t* __restrict__ err, int64_
 }
 
 unsigned sort_grid(int64_t items, int64_t per) {
-  int64_t g = (items + per - 1) / per;
-  g = g < 1 ? 1 : g > (int64_t)kSortMaxGrid ? (int64_t)kSortMaxGrid : g;
-  const int capped = g_sort_grid.load(std::memory_order_relaxed);
-  if (capped > 0 && g > capped) g = capped;
-  return (unsigned)g;
+  return grid_for(items, per, kSortMaxGrid, g_sort_grid.load(std::memory_order_relaxed));
 }
 
 // argument errors: nothing has touched the device when one of them returns
@@ -356,15 +352,9 @@ int sort_run(const TextBatch& b, BatchForm form, int64_t n, int64_t known_max, i
   return MRX_OK;
 }
 
-struct TakeArgs {
+struct TakeArgs : PackedDest {   // d_rows: none (the caller's d_index is what a row came from)
   const int64_t* d_index;
   int64_t k;
-  int64_t* d_out_offsets;
-  uint8_t* d_out_data;
-  int64_t out_cap;
-  int64_t* d_totals;
-  int64_t* totals;
-  void* stream;
 };
 
 // argument errors: nothing has touched the device when one of them returns
@@ -380,8 +370,7 @@ int take_check(const TextBatch& b, BatchForm form, int64_t n, const TakeArgs& a)
 int take_run(const TextBatch& b, BatchForm form, int64_t n, int64_t known_max, const TakeArgs& a) {
   if (int rc = take_check(b, form, n, a)) return rc;
   hipStream_t hs = (hipStream_t)a.stream;
-  if (a.k == 0)
-    return filter_no_text(b, known_max, FilterDest{nullptr, a.d_out_offsets, a.d_out_data, a.out_cap, a.d_totals, a.totals, a.stream});
+  if (a.k == 0) return filter_no_text(b, known_max, a);
   ScratchScope scope_(a.stream);
   int64_t* klen = (int64_t*)scratch_get(sizeof(int64_t) * (size_t)a.k, a.stream);
   int32_t* err = (int32_t*)scratch_get(sizeof(int32_t), a.stream);
@@ -394,13 +383,7 @@ int take_run(const TextBatch& b, BatchForm form, int64_t n, int64_t known_max, c
   MRX_HIP_TRY(hipGetLastError());
   if (int rc = filter_gather_kept(b, a.k, known_max, a.d_index, a.d_out_offsets, a.d_totals, a.d_out_data, a.out_cap, a.stream))
     return rc;
-  if (!a.totals) return MRX_OK;
-  MRX_HIP_TRY(hipMemcpyAsync(a.totals, a.d_totals, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, hs));
-  MRX_HIP_TRY(hipStreamSynchronize(hs));
-  if (a.totals[0] < 0) return internal_fail(MRX_E_ARGUMENT, "take: an index is outside [0, n)");
-  if (a.totals[1] > a.out_cap)
-    return internal_fail(MRX_E_CAPACITY, "output buffer too small: need " + std::to_string(a.totals[1]));
-  return MRX_OK;
+  return packed_verdict(a, -1, "take: an index is outside [0, n)");
 }
 
 int known_check(int64_t end_offset, int64_t max_text_len) {
@@ -434,20 +417,20 @@ int mrx_sort_strided_dev(const uint8_t* d_data, int64_t stride, const int32_t* d
 int mrx_take_dev(const uint8_t* d_data, const int64_t* d_offsets, int64_t n, const int64_t* d_index, int64_t k,
                  int64_t* d_out_offsets, uint8_t* d_out_data, int64_t out_cap, int64_t* d_totals, int64_t* totals,
                  void* stream) {
-  return take_run(csr(d_data, d_offsets), BATCH_CSR, n, -1, TakeArgs{d_index, k, d_out_offsets, d_out_data, out_cap, d_totals, totals, stream});
+  return take_run(csr(d_data, d_offsets), BATCH_CSR, n, -1, TakeArgs{{nullptr, d_out_offsets, d_out_data, out_cap, d_totals, totals, stream}, d_index, k});
 }
 int mrx_take_known_dev(const uint8_t* d_data, const int64_t* d_offsets, int64_t n, int64_t end_offset, int64_t max_text_len,
                        const int64_t* d_index, int64_t k, int64_t* d_out_offsets, uint8_t* d_out_data, int64_t out_cap,
                        int64_t* d_totals, int64_t* totals, void* stream) {
   if (int rc = known_check(end_offset, max_text_len)) return rc;
   return take_run(csr(d_data, d_offsets), BATCH_CSR, n, max_text_len,
-                  TakeArgs{d_index, k, d_out_offsets, d_out_data, out_cap, d_totals, totals, stream});
+                  TakeArgs{{nullptr, d_out_offsets, d_out_data, out_cap, d_totals, totals, stream}, d_index, k});
 }
 int mrx_take_strided_dev(const uint8_t* d_data, int64_t stride, const int32_t* d_lens, int32_t len, int64_t n,
                          const int64_t* d_index, int64_t k, int64_t* d_out_offsets, uint8_t* d_out_data, int64_t out_cap,
                          int64_t* d_totals, int64_t* totals, void* stream) {
   return take_run(strided(d_data, stride, d_lens, len), BATCH_PITCH, n, -1,
-                  TakeArgs{d_index, k, d_out_offsets, d_out_data, out_cap, d_totals, totals, stream});
+                  TakeArgs{{nullptr, d_out_offsets, d_out_data, out_cap, d_totals, totals, stream}, d_index, k});
 }
 
 // host buffers: argument errors before any device work, as the _dev entry points
@@ -486,7 +469,7 @@ int mrx_take_batch(const uint8_t* data, const int64_t* offsets, int64_t n, const
   if (int rc = od.alloc((size_t)out_cap)) return rc;
   if (k > 0) MRX_HIP_TRY(hipMemcpy(ix.p, index, sizeof(int64_t) * (size_t)k, hipMemcpyHostToDevice));
   int64_t tot[2] = {0, 0};
-  const int rc = take_run(csr(b.data, b.offsets), BATCH_CSR, n, b.longest, TakeArgs{ix.p, k, oo.p, od.p, out_cap, dt.p, tot, nullptr});
+  const int rc = take_run(csr(b.data, b.offsets), BATCH_CSR, n, b.longest, TakeArgs{{nullptr, oo.p, od.p, out_cap, dt.p, tot, nullptr}, ix.p, k});
   if (totals && (rc == MRX_OK || rc == MRX_E_CAPACITY || tot[0] < 0)) { totals[0] = tot[0]; totals[1] = tot[1]; }
   if (rc != MRX_OK && rc != MRX_E_CAPACITY) return rc;
   MRX_HIP_TRY(hipMemcpy(out_offsets, oo.p, sizeof(int64_t) * (size_t)(k + 1), hipMemcpyDeviceToHost));

@@ -299,6 +299,45 @@ def test_both_forms_give_the_same_bytes_on_short_and_long_texts(each_form):
         assert lib.mrx_last_kernel_name() == each_form
 
 
+def test_block_form_carries_its_texts_over_three_rounds_of_a_wavefront():
+    """At its full grid (2048 workgroups of 4 wavefronts) k_filter_gather gives a wavefront one round of 64 blocks up to
+    2048 x 4 x 64 x 16 B = 8 MiB of kept bytes.  Between 16 and 24 MiB make it three, so that the texts a round ended
+    with (cur, hi) are where the next one begins.  The predicate is one literal byte that the generator plants, inverted
+    so that empty texts are kept too: the expected output is a numpy selection, no oracle call per text."""
+    import torch
+    lib = M.load_library()
+    rng = np.random.default_rng(20261020)
+    n = 170_000
+    lens = rng.integers(0, 301, size=n)
+    lens[rng.random(n) < 0.05] = 0
+    off = np.zeros(n + 1, dtype=np.int64)
+    off[1:] = np.cumsum(lens)
+    al = np.frombuffer(b"abcxyz0189 -", dtype=np.uint8)
+    data = al[rng.integers(0, len(al), size=int(off[-1]))]
+    drop = (rng.random(n) < 0.25) & (lens > 0)
+    data[off[:-1][drop] + (rng.random(int(drop.sum())) * lens[drop]).astype(np.int64)] = ord("Q")
+    keep = ~drop
+    widx = np.nonzero(keep)[0]
+    woff = np.concatenate([[0], np.cumsum(lens[keep])])
+    wdata = data[np.repeat(keep, lens)]
+    nbytes = len(wdata)
+    assert (16 << 20) < nbytes <= (24 << 20) and np.any(lens[keep] == 0) and np.any(lens[keep] == 300)
+    batch = M.DeviceBatch(torch.from_numpy(data).cuda(), torch.from_numpy(off).cuda())
+    skew, cap = 7, len(data)
+    buf = torch.full((skew + cap + 64,), 0xA5, dtype=torch.uint8, device="cuda")
+    lib.mrx_debug_filter_form(1)
+    try:
+        rc, idx, got_off, dt, ht = _raw_call(M.compile_regex(b"Q"), batch, buf[skew:], cap, flags=M.api.MRX_FILTER_INVERT)
+        assert lib.mrx_last_kernel_name() == b"k_filter_gather"
+    finally:
+        lib.mrx_debug_filter_form(0)
+    assert rc == M.api.MRX_OK and dt == [len(widx), nbytes] and ht == dt
+    got = _np(buf)
+    assert np.all(got[:skew] == 0xA5) and np.all(got[skew + nbytes:] == 0xA5)
+    assert np.array_equal(got[skew:skew + nbytes], wdata)
+    assert np.array_equal(idx[:len(widx)], widx) and np.array_equal(got_off[:len(widx) + 1], woff)
+
+
 def test_host_list_wrappers():
     texts = LY.make_texts(b"\\d+", 150, n_long=2) + CANNOT + [b""]
     kept, idx = M.compile_regex(b"\\d+").filter(texts)

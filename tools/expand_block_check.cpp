@@ -30,7 +30,9 @@ using namespace mrx;
 
 namespace {
 
-// out[0 .. bytes) as nw wavefronts of k_expand_gather assemble it, lane after lane
+// out[0 .. bytes) as nw wavefronts of k_expand_gather assemble it, lane after lane: a sequential loop of this file's own
+// with the arithmetic of the device's one walk (gather_blocks in mrx_gather_bits.hpp, device code: it takes its wavefront
+// and lane from the launch) around the same fill, expand_block
 void gather_records(const ExpandSrc& S, int64_t pieces, int64_t bytes, uint8_t* out, int64_t nw) {
   if (bytes <= 0) return;
   const uintptr_t ob = (uintptr_t)out, a0 = ob & ~(uintptr_t)15;

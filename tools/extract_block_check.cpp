@@ -25,8 +25,10 @@ namespace {
 
 struct Piece { int64_t src, len; };
 
-// the blocks of out[0 .. bytes) as the kernel's lanes assemble them, one after the other
-void gather_blocks(const uint8_t* data, const std::vector<Piece>& pieces, const std::vector<int64_t>& off, uint8_t* out,
+// the blocks of out[0 .. bytes) as the kernel's lanes assemble them, one after the other: a sequential loop of this
+// file's own around the same block assembly (the device's one walk, gather_blocks in mrx_gather_bits.hpp, is device code:
+// it takes its wavefront and lane from the launch)
+void blocks_in_turn(const uint8_t* data, const std::vector<Piece>& pieces, const std::vector<int64_t>& off, uint8_t* out,
                    int64_t bytes) {
   const int64_t n = (int64_t)pieces.size();
   const uintptr_t ob = (uintptr_t)out, a0 = ob & ~(uintptr_t)15;
@@ -80,7 +82,7 @@ int main() {
       uint8_t* buf = (uint8_t*)aligned_alloc(16, out_bytes);
       memset(buf, 0xA5, out_bytes);
       uint8_t* out = buf + 16 + skew;
-      gather_blocks(src, pieces, off, out, bytes);
+      blocks_in_turn(src, pieces, off, out, bytes);
       if (memcmp(out, want.data(), (size_t)bytes) != 0) {
         printf("FAIL: bytes differ (text shift %d, output skew %d)\n", shift, skew);
         return 1;

@@ -178,7 +178,9 @@ int check_cells(std::mt19937_64& rng) {
   return 0;
 }
 
-// out[0 .. bytes) as nw wavefronts of k_format_gather assemble it, lane after lane
+// out[0 .. bytes) as nw wavefronts of k_format_gather assemble it, lane after lane: a sequential loop of this file's own
+// with the arithmetic of the device's one walk (gather_blocks in mrx_gather_bits.hpp, device code: it takes its wavefront
+// and lane from the launch) around the same fill, format_block
 void gather_records(const FormatSrc& S, int64_t bytes, uint8_t* out, int64_t nw) {
   if (bytes <= 0) return;
   const uintptr_t ob = (uintptr_t)out, a0 = ob & ~(uintptr_t)15;
