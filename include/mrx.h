@@ -876,7 +876,100 @@ int mrx_format_dev(const char* tpl, size_t tpl_len, const mrx_column* cols, int3
                    uint8_t* d_out_data, int64_t out_cap, uint8_t* d_row_status, int64_t* d_totals, int64_t* totals,
                    void* stream);
 
+/* ---- keywords: find thousands of literals in one pass ----
+ * grep -F -f list and grep -v -F -f list, keyword tagging, the search for 10^4 indicators in every log line: which of a
+ * long list of literals occur INSIDE each text.  (A dictionary answers the whole-text form, grep -F -x -f list; a pattern
+ * set has at most 256 members and runs every member's own call.)  A keyword set is an immutable handle built once from m
+ * ENTRIES (byte strings) and probed by any number of batches.  One Aho-Corasick automaton over all entries, one pass
+ * over the texts: the cost of a call does not depend on m, only the size of the table does.  No reference semantics are
+ * involved; the contract is this one.
+ * A HIT: entry j OCCURS in text t at [s, e) when t[s:e] == entry j.  Every occurrence counts, overlapping and nested ones
+ * included: `a`, `aa`, `aaa`, `aaaa` have 18 hits in `aaaaaa`, as the overlapping findall of an exact literal.
+ * Entries that are equal share the LOWEST index among them and an occurrence is reported once, under that index.  An empty
+ * entry (it would occur everywhere) is MRX_E_ARGUMENT with a message that names its index.  m == 0 is valid: nothing
+ * occurs.  m >= 2^31: MRX_E_ARGUMENT.
+ * MRX_KW_IGNORE_CASE (build flag): ASCII A-Z are folded onto a-z in the entries and in the texts; nothing else is folded
+ * and spans are unchanged.  Entries that are equal after folding are duplicates.  Any other flag bit: MRX_E_ARGUMENT.
+ * Build: on the host -- a trie, failure links in breadth-first order, completed to a dense table of 4-byte words over
+ * byte classes (every byte that occurs in no entry shares one class, whose column goes to the root; with
+ * MRX_KW_IGNORE_CASE upper and lower case share a class), states numbered shallowest first.  mrx_kw_build takes host
+ * entries (entry j = data[offsets[j], offsets[j + 1])); mrx_kw_build_dev takes a CSR batch on the device, copies it to the
+ * host and synchronises the stream for that.  Both upload the automaton into device memory that the handle owns (plain
+ * device memory, not the scratch arena) and synchronise once more at the end, so the entries may go when the build
+ * returns.  A table (states x classes x 4 bytes) above 1 GiB is MRX_E_UNSUPPORTED with a message that gives states and
+ * classes: a stated limit, never an approximation.  On any error *out is left as it was.  The handle is immutable; calls
+ * on it from several threads and streams are safe; mrx_kw_free(NULL) is a no-op.  mrx_kw_size is m, mrx_kw_distinct the
+ * number of different entries (0 for NULL); mrx_kw_describe writes "keywords: m=.. distinct=.. states=.. classes=..
+ * lmax=.. table_bytes=.. ignore_case=.." (returns the bytes needed excluding NUL, writes at most cap).
+ * Operations, over the text-batch layout of the single-pattern _dev entry points and with their argument rules:
+ *   contains  d_flag uint8[n]: 1 when any entry occurs in text i
+ *   count     d_count int64[n]: the number of hits in text i
+ *   findall   d_text_prefix int64[n + 1], d_entries int32[total], d_spans int32[total][2] (8-byte aligned, text-relative):
+ *             text i's hits are [d_text_prefix[i], d_text_prefix[i + 1]), in ascending (end, start) order -- at one end
+ *             position the longest entry comes first.  The capacity rule is mrx_set_findall_dev's: total > span_cap is
+ *             MRX_E_CAPACITY with *total and d_text_prefix valid, and nothing is written at or beyond span_cap (retry with
+ *             *total).  total may be NULL.  n == 0 gives d_text_prefix = {0}.
+ *   filter    mrx_filter_dev's contract word for word (outputs, both capacity rules, totals == NULL, the _known bounds,
+ *             n == 0), as mrx_dict_filter_dev has it, with the predicate `contains`: text i is KEPT when some entry occurs
+ *             in it; MRX_FILTER_INVERT keeps the texts in which no entry occurs; MRX_FILTER_ALL is ignored; any other flag
+ *             bit is MRX_E_ARGUMENT.
+ * How: every text is cut into pieces of P bytes; a piece walks from the root, beginning Lmax - 1 bytes (the longest
+ * entry's length less one) in front of its first byte but never in front of the text, and reports exactly the hits
+ * whose last byte lies in it.  Pieces are independent, so one decomposition serves every batch shape, a few texts of many
+ * MiB included.  k_kw_count writes one hit count per piece; ONE exclusive scan of those gives count, contains and
+ * d_text_prefix (differences and values at the texts' first pieces); k_kw_emit walks the pieces that have hits again and
+ * writes them at scan[piece].  No memory atomics: every result is a pure function of entries and texts, whichever lane
+ * ran first.  P: 8 x (Lmax - 1) rounded up to 16, 1024 at least; halved (down to 2 x (Lmax - 1), 64 at least) while the
+ * batch has fewer than 2^18 pieces.
+ * Synchronisation: contains, count and a filter with totals == NULL enqueue and return; findall synchronises once, for
+ * the total.  A CSR batch without known bounds adds one synchronisation for its byte count; the _known forms (findall,
+ * filter) spare it, and upper bounds are fine.
+ * Reads: a text's bytes are fetched as the aligned 16-byte words that hold them, so up to 15 bytes in front of a text's
+ * first byte and behind its last one are read and never used: no byte outside [0, len) of a text reaches a state or a
+ * hit, the last bytes of the previous text of a packed CSR batch included.  No word is read for an empty text.
+ * Scratch: 16 bytes per piece and a scan's block sums; a CSR batch 16 bytes per text more; filter's 32 bytes per text.
+ * MRX_E_ARGUMENT, before any device call: negative n, m, span_cap or out_cap; negative known bounds; a bad pitch; a null
+ * handle; unknown flag bits; a null required pointer (offsets, out; d_offsets; the output of contains / count when
+ * n > 0; d_text_prefix; d_entries and d_spans when n > 0 and span_cap > 0; filter's as mrx_filter_dev); d_spans not 8-byte
+ * aligned. */
+enum { MRX_KW_IGNORE_CASE = 1 };
+typedef struct mrx_kw mrx_kw;
+int mrx_kw_build(const uint8_t* data, const int64_t* offsets, int64_t m, uint32_t flags, void* stream, mrx_kw** out);
+int mrx_kw_build_dev(const uint8_t* d_data, const int64_t* d_offsets, int64_t m, uint32_t flags, void* stream, mrx_kw** out);
+void mrx_kw_free(mrx_kw* k);
+int64_t mrx_kw_size(const mrx_kw* k);
+int64_t mrx_kw_distinct(const mrx_kw* k);
+size_t mrx_kw_describe(const mrx_kw* k, char* buf, size_t cap);
+int mrx_kw_contains_dev(const mrx_kw* k, const uint8_t* d_data, const int64_t* d_offsets, int64_t n, uint8_t* d_flag,
+                        void* stream);
+int mrx_kw_contains_strided_dev(const mrx_kw* k, const uint8_t* d_data, int64_t stride, const int32_t* d_lens, int32_t len,
+                                int64_t n, uint8_t* d_flag, void* stream);
+int mrx_kw_count_dev(const mrx_kw* k, const uint8_t* d_data, const int64_t* d_offsets, int64_t n, int64_t* d_count,
+                     void* stream);
+int mrx_kw_count_strided_dev(const mrx_kw* k, const uint8_t* d_data, int64_t stride, const int32_t* d_lens, int32_t len,
+                             int64_t n, int64_t* d_count, void* stream);
+int mrx_kw_findall_dev(const mrx_kw* k, const uint8_t* d_data, const int64_t* d_offsets, int64_t n, int64_t* d_text_prefix,
+                       int32_t* d_entries, int32_t* d_spans, int64_t span_cap, int64_t* total, void* stream);
+int mrx_kw_findall_known_dev(const mrx_kw* k, const uint8_t* d_data, const int64_t* d_offsets, int64_t n,
+                             int64_t end_offset, int64_t max_text_len, int64_t* d_text_prefix, int32_t* d_entries,
+                             int32_t* d_spans, int64_t span_cap, int64_t* total, void* stream);
+int mrx_kw_findall_strided_dev(const mrx_kw* k, const uint8_t* d_data, int64_t stride, const int32_t* d_lens, int32_t len,
+                               int64_t n, int64_t* d_text_prefix, int32_t* d_entries, int32_t* d_spans, int64_t span_cap,
+                               int64_t* total, void* stream);
+int mrx_kw_filter_dev(const mrx_kw* k, uint32_t flags, const uint8_t* d_data, const int64_t* d_offsets, int64_t n,
+                      int64_t* d_kept_idx, int64_t* d_out_offsets, uint8_t* d_out_data, int64_t out_cap, int64_t* d_totals,
+                      int64_t* totals, void* stream);
+int mrx_kw_filter_known_dev(const mrx_kw* k, uint32_t flags, const uint8_t* d_data, const int64_t* d_offsets, int64_t n,
+                            int64_t end_offset, int64_t max_text_len, int64_t* d_kept_idx, int64_t* d_out_offsets,
+                            uint8_t* d_out_data, int64_t out_cap, int64_t* d_totals, int64_t* totals, void* stream);
+int mrx_kw_filter_strided_dev(const mrx_kw* k, uint32_t flags, const uint8_t* d_data, int64_t stride, const int32_t* d_lens,
+                              int32_t len, int64_t n, int64_t* d_kept_idx, int64_t* d_out_offsets, uint8_t* d_out_data,
+                              int64_t out_cap, int64_t* d_totals, int64_t* totals, void* stream);
+
 /* ---- host-buffer convenience wrappers (copy in, run, copy out) -------------- */
+/* mrx_kw_findall_dev on host buffers: text_prefix is always copied out, entries and spans only when all hits fit */
+int mrx_kw_findall_batch(const mrx_kw* k, const uint8_t* data, const int64_t* offsets, int64_t n, int64_t* text_prefix,
+                         int32_t* entries, int32_t* spans, int64_t span_cap, int64_t* total);
 /* mrx_format_dev on host buffers: the columns' pointers are host pointers (a text column's offsets may begin anywhere
  * and must not decrease); out_offsets int64[n + 1], out_data uint8[out_cap], row_status uint8[n] (may be NULL), totals
  * int64[2] = {n, bytes} (may be NULL).  out_offsets[0, n] and row_status are copied out, out_data only when all of it

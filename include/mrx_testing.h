@@ -182,6 +182,22 @@ void mrx_debug_format_grid(int workgroups);
  * most 21), or minus the status (-MRX_NUM_RANGE: the cell is not answered; -MRX_NUM_MALFORMED: MRX_COL_TEXT, a kind or
  * an arg that mrx_format_dev refuses, or a null out). */
 int mrx_testing_format_one(int32_t kind, int32_t arg, int64_t value_word, uint8_t out[32]);
+/* Keywords (include/mrx.h): the piece size P of every later call is `bytes` (> 0; 16 and 32 cut short test texts into
+ * several pieces with entries longer than two of them); 0 (default) = the rule that the contract states.  The pass
+ * reports itself as "k_kw_count" or "k_kw_emit" through mrx_last_kernel_name().  Results are the same. */
+void mrx_debug_kw_piece(int64_t bytes);
+/* Keywords: 0 = every row of the table is read from global memory, anything else (default) = the rows of the shallowest
+ * states, as many as fit 32 KiB, are kept in LDS beside the class map.  Results are the same. */
+void mrx_debug_kw_tier(int on);
+/* Keywords on the CPU, for tests without a GPU: the automaton is built from the entries (entry j = entry_data[
+ * entry_offsets[j], entry_offsets[j + 1]), flags as mrx_kw_build) and the walk of the kernels runs over the same pieces
+ * (the pinned size, else the rule), one after the other, on the texts data[offsets[i], offsets[i + 1]).  Outputs as
+ * mrx_kw_findall_batch: text_prefix int64[n + 1], entries int32[span_cap], spans int32[span_cap][2], *total (may be
+ * NULL).  describe (may be NULL) receives at most describe_cap bytes of what mrx_kw_describe would print.  Returns
+ * MRX_OK, MRX_E_CAPACITY (the prefix and *total are valid) or the build's error. */
+int mrx_debug_kw_host_findall(const uint8_t* entry_data, const int64_t* entry_offsets, int64_t m, uint32_t flags,
+                              const uint8_t* data, const int64_t* offsets, int64_t n, int64_t* text_prefix, int32_t* entries,
+                              int32_t* spans, int64_t span_cap, int64_t* total, char* describe, size_t describe_cap);
 /* Bytes of device memory the calling thread's scratch arenas hold (see mrx_release_scratch). */
 size_t mrx_debug_scratch_bytes(void);
 /* ... and how many of them are handed out and not yet rewound.  Scratch belongs to the call's scope, so between calls

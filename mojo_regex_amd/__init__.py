@@ -37,6 +37,8 @@ argument meaning, a *batch* of texts instead of one text:
                                                   DeviceBatch.parse / parse_spans: pieces as int64 / float64
     (none: "%s %d\\n" % row on the host)          format_records / format_numbers / format_records_async:
                                                   text and number columns as packed records, the report's bytes
+    (none: one alternation of literals per call)  Keywords / build_keywords / keywords_filter: which of
+                                                  thousands of literals occur inside each text, one pass
 
 All matching runs in the HIP kernels of libmrx_hip.so.  There is no CPU
 fallback: if the library is missing or no GPU is usable, calls raise.
@@ -47,11 +49,13 @@ from .api import (  # noqa: F401
     CompiledRegex,
     DeviceBatch,
     Dictionary,
+    Keywords,
     MrxError,
     PatternSet,
     RegexSyntaxError,
     UnsupportedPattern,
     build_dictionary,
+    build_keywords,
     captures_all,
     clear_regex_cache,
     compile_regex,
@@ -64,6 +68,7 @@ from .api import (  # noqa: F401
     format_numbers,
     format_records,
     format_records_async,
+    keywords_filter,
     library_path,
     load_library,
     lookup,

@@ -300,6 +300,35 @@ def load_library():
                                        C.c_void_p]),
         "mrx_debug_format_grid": (None, [C.c_int]),
         "mrx_testing_format_one": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, C.c_void_p]),
+        # keywords: the handle | the batch | (flag / count, stream); findall: ... | (text_prefix, entries, spans, span_cap,
+        # total, stream); filter as mrx_filter
+        "mrx_kw_build": (C.c_int, [u8p, i64p, C.c_int64, C.c_uint32, C.c_void_p, C.POINTER(H)]),
+        "mrx_kw_build_dev": (C.c_int, [u8p, i64p, C.c_int64, C.c_uint32, C.c_void_p, C.POINTER(H)]),
+        "mrx_kw_free": (None, [H]),
+        "mrx_kw_size": (C.c_int64, [H]),
+        "mrx_kw_distinct": (C.c_int64, [H]),
+        "mrx_kw_describe": (C.c_size_t, [H, C.c_char_p, C.c_size_t]),
+        "mrx_kw_contains_dev": (C.c_int, [H, u8p, i64p, C.c_int64, u8p, C.c_void_p]),
+        "mrx_kw_contains_strided_dev": (C.c_int, [H, u8p, C.c_int64, i32p, C.c_int32, C.c_int64, u8p, C.c_void_p]),
+        "mrx_kw_count_dev": (C.c_int, [H, u8p, i64p, C.c_int64, i64p, C.c_void_p]),
+        "mrx_kw_count_strided_dev": (C.c_int, [H, u8p, C.c_int64, i32p, C.c_int32, C.c_int64, i64p, C.c_void_p]),
+        "mrx_kw_findall_dev": (C.c_int, [H, u8p, i64p, C.c_int64, i64p, i32p, i32p, C.c_int64, C.POINTER(C.c_int64),
+                                         C.c_void_p]),
+        "mrx_kw_findall_known_dev": (C.c_int, [H, u8p, i64p, C.c_int64, C.c_int64, C.c_int64, i64p, i32p, i32p, C.c_int64,
+                                               C.POINTER(C.c_int64), C.c_void_p]),
+        "mrx_kw_findall_strided_dev": (C.c_int, [H, u8p, C.c_int64, i32p, C.c_int32, C.c_int64, i64p, i32p, i32p, C.c_int64,
+                                                 C.POINTER(C.c_int64), C.c_void_p]),
+        "mrx_kw_filter_dev": (C.c_int, [H, C.c_uint32, u8p, i64p, C.c_int64, i64p, i64p, u8p, C.c_int64, i64p, C.c_void_p,
+                                        C.c_void_p]),
+        "mrx_kw_filter_known_dev": (C.c_int, [H, C.c_uint32, u8p, i64p, C.c_int64, C.c_int64, C.c_int64, i64p, i64p, u8p,
+                                              C.c_int64, i64p, C.c_void_p, C.c_void_p]),
+        "mrx_kw_filter_strided_dev": (C.c_int, [H, C.c_uint32, u8p, C.c_int64, i32p, C.c_int32, C.c_int64, i64p, i64p, u8p,
+                                                C.c_int64, i64p, C.c_void_p, C.c_void_p]),
+        "mrx_kw_findall_batch": (C.c_int, [H, u8p, i64p, C.c_int64, i64p, i32p, i32p, C.c_int64, C.POINTER(C.c_int64)]),
+        "mrx_debug_kw_piece": (None, [C.c_int64]),
+        "mrx_debug_kw_tier": (None, [C.c_int]),
+        "mrx_debug_kw_host_findall": (C.c_int, [u8p, i64p, C.c_int64, C.c_uint32, u8p, i64p, C.c_int64, i64p, i32p, i32p,
+                                                C.c_int64, C.POINTER(C.c_int64), C.c_char_p, C.c_size_t]),
         "mrx_debug_set_route": (None, [C.c_int]),
         "mrx_testing_set_run": (C.c_int, [H, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_int32)]),
     }
@@ -341,6 +370,10 @@ EXPORTED_SYMBOLS = [
     "mrx_take_dev", "mrx_take_known_dev", "mrx_take_strided_dev", "mrx_take_batch",
     "mrx_parse_dev", "mrx_parse_strided_dev", "mrx_parse_spans_dev", "mrx_parse_spans_strided_dev", "mrx_parse_batch",
     "mrx_format_dev", "mrx_format_batch",
+    "mrx_kw_build", "mrx_kw_build_dev", "mrx_kw_free", "mrx_kw_size", "mrx_kw_distinct", "mrx_kw_describe",
+    "mrx_kw_contains_dev", "mrx_kw_contains_strided_dev", "mrx_kw_count_dev", "mrx_kw_count_strided_dev",
+    "mrx_kw_findall_dev", "mrx_kw_findall_known_dev", "mrx_kw_findall_strided_dev", "mrx_kw_filter_dev",
+    "mrx_kw_filter_known_dev", "mrx_kw_filter_strided_dev", "mrx_kw_findall_batch",
 ]
 TESTING_SYMBOLS = [
     "mrx_timing_reset", "mrx_timing_enable", "mrx_timing_scan_ms", "mrx_last_kernel_name",
@@ -353,6 +386,7 @@ TESTING_SYMBOLS = [
     "mrx_debug_sort_small", "mrx_debug_sort_grid", "mrx_debug_sort_rounds", "mrx_debug_parse_grid",
     "mrx_debug_decode_lean", "mrx_debug_last_decode_lean", "mrx_testing_decode_expand",
     "mrx_debug_format_grid", "mrx_testing_format_one",
+    "mrx_debug_kw_piece", "mrx_debug_kw_tier", "mrx_debug_kw_host_findall",
 ]
 # (hooks with a digit in their name, listed apart: the header scan of tests/test_host_tables.py reads [a-z_] names)
 TESTING_SYMBOLS_NUMBERED = ["mrx_debug_rec12", "mrx_testing_rec12_roundtrip"]
@@ -1040,6 +1074,140 @@ class Dictionary:
         if index is not None and (index.dtype != torch.int64 or not index.is_contiguous() or index.numel() < batch.n):
             raise MrxError("index must be a contiguous int64[n] tensor")
         _filter_async(self._lib, "mrx_dict_filter", self._h, _filter_flags("any", invert), batch, out, extra=(_ptr(index),))
+
+
+MRX_KW_IGNORE_CASE = 1
+
+
+class Keywords:
+    """A fixed list of literals, the entries, searched for INSIDE every text in one pass (include/mrx.h, "keywords"):
+    grep -F -f list, keyword tagging.  `entries` is a list of byte strings or a DeviceBatch; the handle keeps its own
+    automaton, so the entries may be dropped afterwards.  Every occurrence is a hit, overlapping and nested ones
+    included; equal entries share the lowest index among them; an empty entry is refused.  With ignore_case ASCII A-Z
+    are folded onto a-z in the entries and in the texts.  len() is the number of entries."""
+
+    def __init__(self, entries, ignore_case: bool = False):
+        self._lib = load_library()
+        flags = MRX_KW_IGNORE_CASE if ignore_case else 0
+        h = C.c_void_p()
+        if isinstance(entries, DeviceBatch) and entries.offsets is not None:
+            import torch
+            stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+            _check(self._lib.mrx_kw_build_dev(_ptr(entries.data), _ptr(entries.offsets), entries.n, flags, stream,
+                                              C.byref(h)))
+        else:
+            if isinstance(entries, DeviceBatch):   # a fixed pitch: the build runs on the host anyway
+                rows = entries.data.cpu().numpy().reshape(entries.n, entries.stride)
+                lens = entries.lens.cpu().numpy() if entries.lens is not None else [entries.length] * entries.n
+                entries = [rows[j, :int(lens[j])].tobytes() for j in range(entries.n)]
+            data, offsets = pack_texts(entries)
+            _check(self._lib.mrx_kw_build(data.ctypes.data, offsets.ctypes.data, len(offsets) - 1, flags, None,
+                                          C.byref(h)))
+        self._h = h
+        self._hits_per_byte = 0.0
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None):
+                self._lib.mrx_kw_free(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+    def __len__(self) -> int:
+        return int(self._lib.mrx_kw_size(self._h))
+
+    @property
+    def distinct_count(self) -> int:
+        """How many of the entries are different (after folding, with ignore_case)."""
+        return int(self._lib.mrx_kw_distinct(self._h))
+
+    def describe(self) -> str:
+        """m, distinct entries, states, byte classes, the longest entry and the table's bytes."""
+        need = self._lib.mrx_kw_describe(self._h, None, 0)
+        buf = C.create_string_buffer(need + 1)
+        self._lib.mrx_kw_describe(self._h, buf, need + 1)
+        return buf.value.decode("utf-8", "replace")
+
+    def _per_text(self, op: str, dtype, texts):
+        import torch
+        host = not isinstance(texts, DeviceBatch)
+        batch = DeviceBatch.from_texts([_b(t) for t in texts]) if host else texts
+        out = torch.empty(batch.n, dtype=dtype, device=batch.data.device)
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        _check(batch.call(self._lib, (getattr(self._lib, op + "_dev"), getattr(self._lib, op + "_strided_dev")),
+                          (self._h,), (_ptr(out), stream)))
+        return out.cpu().numpy() if host else out
+
+    def contains(self, texts):
+        """bool[n]: does any entry occur in text i?  numpy for a list of texts, a device tensor for a DeviceBatch
+        (enqueued on the current stream, nothing read back)."""
+        import torch
+        return self._per_text("mrx_kw_contains", torch.uint8, texts) != 0
+
+    def count(self, texts):
+        """int64[n]: the number of hits in text i; numpy for a list of texts, a device tensor for a DeviceBatch."""
+        import torch
+        return self._per_text("mrx_kw_count", torch.int64, texts)
+
+    def _default_cap(self, nbytes: int, n: int) -> int:
+        """Span capacity without a caller's cap: one hit per 8 bytes, or the density of the previous call (+1/8)."""
+        return max(64, nbytes // 8 + n, int(nbytes * self._hits_per_byte * 1.125) + n + 64)
+
+    def findall(self, texts, span_cap: Optional[int] = None):
+        """Every hit of every entry, text-major (include/mrx.h, mrx_kw_findall_dev): (text_prefix int64[n+1], entries
+        int32[total], spans int32[total, 2]).  Text i's hits are [text_prefix[i], text_prefix[i+1]) in ascending (end,
+        start) order.  A list of bytes gives numpy arrays, a DeviceBatch device tensors.  Without span_cap the call
+        retries once with the total it needs."""
+        if isinstance(texts, DeviceBatch):
+            import torch
+            batch, dev, n = texts, texts.data.device, texts.n
+            stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+            prefix = torch.empty(n + 1, dtype=torch.int64, device=dev)
+            nbytes = int(batch.data.numel())
+            (ents, spans), total = _grow_call(
+                int(span_cap) if span_cap is not None else self._default_cap(nbytes, n),
+                lambda cap: (torch.empty(max(cap, 1), dtype=torch.int32, device=dev),
+                             torch.empty((max(cap, 1), 2), dtype=torch.int32, device=dev)),
+                lambda es, cap, total: batch.call(self._lib, "mrx_kw_findall", (self._h,),
+                                                  (_ptr(prefix), _ptr(es[0]), _ptr(es[1]), cap, total, stream)),
+                grow=span_cap is None, only_larger=True)
+        else:
+            data, offsets = pack_texts(texts)
+            n, nbytes = len(offsets) - 1, int(offsets[-1])
+            prefix = np.zeros(n + 1, np.int64)
+            (ents, spans), total = _grow_call(
+                int(span_cap) if span_cap is not None else self._default_cap(nbytes, n),
+                lambda cap: (np.empty(max(cap, 1), np.int32), np.empty((max(cap, 1), 2), np.int32)),
+                lambda es, cap, total: self._lib.mrx_kw_findall_batch(self._h, data.ctypes.data, offsets.ctypes.data, n,
+                                                                      prefix.ctypes.data, es[0].ctypes.data,
+                                                                      es[1].ctypes.data, cap, total),
+                grow=span_cap is None, only_larger=True)
+        self._hits_per_byte = total / max(1, nbytes)
+        return prefix, ents[:total], spans[:total]
+
+    def findall_lists(self, texts) -> List[List[Tuple[int, int, int]]]:
+        """findall() as a list per text of (entry, start, end) tuples."""
+        prefix, ents, spans = self.findall(texts)
+        if not isinstance(prefix, np.ndarray):
+            prefix, ents, spans = prefix.cpu().numpy(), ents.cpu().numpy(), spans.cpu().numpy()
+        return [[(int(ents[q]), int(spans[q, 0]), int(spans[q, 1])) for q in range(prefix[i], prefix[i + 1])]
+                for i in range(len(prefix) - 1)]
+
+    def filter(self, texts, invert: bool = False):
+        """The texts in which some entry occurs (with invert, the others) as a new packed batch, in their order: what
+        CompiledRegex.filter returns (include/mrx.h, mrx_kw_filter_dev).  A list of texts gives (kept List[bytes], idx
+        numpy int64[kept]), a DeviceBatch gives (DeviceBatch, idx) with device tensors."""
+        if isinstance(texts, DeviceBatch):
+            return _filter(self._lib, "mrx_kw_filter", self._h, _filter_flags("any", invert), texts)
+        bs = [_b(t) for t in texts]
+        kept, idx = self.filter(DeviceBatch.from_texts(bs), invert)
+        idx = idx.cpu().numpy()
+        return [bs[int(i)] for i in idx], idx
+
+    def filter_async(self, batch: "DeviceBatch", out, invert: bool = False):
+        """filter() enqueued on the current stream without a read-back, as CompiledRegex.filter_async."""
+        _filter_async(self._lib, "mrx_kw_filter", self._h, _filter_flags("any", invert), batch, out)
 
 
 class CompiledRegex:
@@ -1820,6 +1988,17 @@ def distinct(texts, sort: Optional[str] = None, top: Optional[int] = None):
 def build_dictionary(entries) -> Dictionary:
     """Dictionary(entries): a list of texts or a DeviceBatch."""
     return Dictionary(entries)
+
+
+def build_keywords(entries, ignore_case: bool = False) -> Keywords:
+    """Keywords(entries, ignore_case): a list of byte strings or a DeviceBatch."""
+    return Keywords(entries, ignore_case)
+
+
+def keywords_filter(entries, texts, invert: bool = False):
+    """The texts in which some entry occurs (with invert, the others): one keyword set for one batch;
+    build_keywords keeps it for many."""
+    return Keywords(entries).filter(texts, invert)
 
 
 def lookup(entries, texts):
