@@ -4614,8 +4614,9 @@ int grid_for(int64_t n, int block) {
 int wave_grid(int64_t n, int waves) { return grid_for((n + 63) / 64, waves); }
 int wstep_grid(int64_t n) { return wave_grid(n, kWsWaves); }
 
-// Which form of the stepper family a findall / count call launches (wstep_launch / reqwave_launch).  findall
-// (FindallJob::choose_route, step_scan) and count (run_count_any) fill it by rules of their own.
+// Which form of the stepper family a findall / count call launches (wstep_launch / reqwave_launch).  Filled in one
+// place for both, FindallJob::choose_route and step_scan (count is the job's counts-only mode); where the two differ,
+// the condition names the mode ("count and findall: the kept differences").
 struct StepRoute {
   bool req = false;       // the required-byte route instead of the plain one
   bool bits = false;      // bitset NFA on the lane-per-text stepper
@@ -4909,7 +4910,7 @@ struct ScanTimer {  // HIP events around the dominant scan kernel, on its own st
   hipEvent_t a = nullptr, b = nullptr;
   hipStream_t s;
   bool on;
-  explicit ScanTimer(hipStream_t st) : s(st), on(g_timing) {
+  explicit ScanTimer(hipStream_t st, bool enable = true) : s(st), on(g_timing && enable) {
     if (on) { (void)hipEventCreate(&a); (void)hipEventCreate(&b); (void)hipEventRecord(a, s); }
   }
   void stop() {
@@ -5615,15 +5616,17 @@ static int sync_bytes_frequent(const mrx_handle* h, const Layout& lay, int64_t n
 
 int run_findall(const mrx_handle* h, const Layout& lay, int64_t n, int64_t* d_prefix, int32_t* d_spans, int64_t span_cap,
                 int64_t* total, void* stream, bool match_next_sequence = false, int64_t known_total = -1, int64_t known_max = -1);
+int run_count_any(const mrx_handle* h, const Layout& lay, int64_t n, int32_t* counts, void* st, int64_t known_total = -1,
+                  int64_t known_max = -1);
 
-// One findall call.  The members are the state the routes share; one member function per route -- round 3's
-// run_findall was a single 420-line function steering ~25 flags.
 // Two routes for one plan and batch shape, measured by the handle (mrx_handle::req_tune[key]): the first four eligible calls
 // take route 1, 2, 1, 2, the last two between HIP events on the caller's stream; a later call that finds the last event
 // complete keeps the faster route.  Returns the route this call takes (1 or 2); *slot >= 0 when the call is one of the
 // four (ab_tuner_end records its closing event once the call's work is enqueued).  No call waits; a stream under graph
-// capture is left alone (route 1).
-static int ab_tuner_begin(const mrx_handle* h, uint32_t key, hipStream_t s, const char* what, int* slot) {
+// capture is left alone (route 1).  The one tuner of this file: the pending-tries walk (findall, count) and the
+// required-byte routes on long texts use it, each under its key (route_tune_key) and with its words (TuneLabels).
+struct TuneLabels { const char *what, *route1, *route2, *pick1, *pick2; };   // MRX_TUNE_VERBOSE's line
+static int ab_tuner_begin(const mrx_handle* h, uint32_t key, hipStream_t s, const TuneLabels& lb, int* slot) {
   *slot = -1;
   hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
   if (hipStreamIsCapturing(s, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) return 1;
@@ -5636,8 +5639,8 @@ static int ab_tuner_begin(const mrx_handle* h, uint32_t key, hipStream_t s, cons
         hipEventElapsedTime(&t.ms_pieces, t.ev[3][0], t.ev[3][1]) != hipSuccess) { t.choice = 1; return 1; }
     t.choice = t.ms_pieces < t.ms_wave ? 2 : 1;
     static const bool verbose = getenv("MRX_TUNE_VERBOSE") != nullptr;
-    if (verbose) fprintf(stderr, "mrx: %s of '%s' (key %08x): pending tries %.3f ms, marks + stepper %.3f ms -> %s\n", what,
-                         h->hp.pattern.c_str(), key, t.ms_wave, t.ms_pieces, t.choice == 2 ? "marks" : "tries");
+    if (verbose) fprintf(stderr, "mrx: %s of '%s' (key %08x): %s %.3f ms, %s %.3f ms -> %s\n", lb.what, h->hp.pattern.c_str(), key,
+                         lb.route1, t.ms_wave, lb.route2, t.ms_pieces, t.choice == 2 ? lb.pick2 : lb.pick1);
     return t.choice;
   }
   if (!t.ev[3][1]) {
@@ -5658,7 +5661,59 @@ static void ab_tuner_end(const mrx_handle* h, uint32_t key, int slot, hipStream_
   mrx_handle::ReqTune& t = h->req_tune[key];
   if (t.ev[slot][1]) (void)hipEventRecord(t.ev[slot][1], s);
 }
+// The measured call's closing event, on every way out of the call: close() where the call's work is enqueued (before
+// the total is read back), the destructor for the returns in between.
+struct TuneEnd {
+  const mrx_handle* h;
+  hipStream_t s;
+  uint32_t key = 0;
+  int slot = -1;
+  TuneEnd(const mrx_handle* h_, hipStream_t s_) : h(h_), s(s_) {}
+  TuneEnd(const TuneEnd&) = delete;
+  TuneEnd& operator=(const TuneEnd&) = delete;
+  void close() { ab_tuner_end(h, key, slot, s); slot = -1; }
+  ~TuneEnd() { close(); }
+};
+// A tuner's key: the batch shape (CSR or the pitch's longest text, the text count, both as powers of two) and the device;
+// kind: 0 the required-byte routes, bit 30 the pending-tries walk against marks + stepper, with bit 29 count's own measurement
+static uint32_t route_tune_key(const Layout& lay, int64_t n, uint32_t kind) {
+  const int64_t bytes_per_text = lay.offsets ? 0 : lay.pitch_longest();
+  uint32_t lb = 0, nb = 0;
+  for (int64_t v = bytes_per_text; v > 1; v >>= 1) ++lb;
+  for (int64_t v = n; v > 1; v >>= 1) ++nb;
+  return kind | (lay.offsets ? 1u << 31 : 0u) | ((uint32_t)(t_dev & 63) << 16) | (lb << 8) | nb;
+}
 
+// the total behind a findall (one stream synchronisation when the caller asked for it; total == NULL: fully
+// asynchronous); d_err: the one-launch forms' error word, read back with it
+static int read_back_total(const int64_t* d_tot, int64_t span_cap, int64_t* total, hipStream_t s,
+                           const unsigned long long* d_err = nullptr) {
+  if (!total) return MRX_OK;
+  int64_t tot = 0;
+  unsigned long long err = 0;
+  HIP_TRY(hipMemcpyAsync(&tot, d_tot, sizeof tot, hipMemcpyDeviceToHost, s));
+  if (d_err) HIP_TRY(hipMemcpyAsync(&err, d_err, sizeof err, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  *total = tot;
+  if (err) return fail(MRX_E_NO_DEVICE, "internal: a wavefront gave up waiting for its predecessors' span counts");
+  if (tot > span_cap) return fail(MRX_E_CAPACITY, "span buffer too small: need " + std::to_string(tot));
+  return MRX_OK;
+}
+
+// '^'-anchored DFA plan: the anchored automaton's run from byte 0 is the whole answer -- 0 or 1 per text into counts;
+// *d_se: the runs' starts [n] and ends [n] (scratch of the calling scope)
+static int anchored_counts(const mrx_handle* h, const Layout& lay, int64_t n, hipStream_t s, int32_t* counts, int32_t** d_se) {
+  HIP_TRY(scratch_alloc((void**)d_se, sizeof(int32_t) * 2 * n, s));
+  ScanTimer tm(s);
+  launch_stream<ST_FIRST>(h, lay, n, nullptr, nullptr, nullptr, 0, *d_se, *d_se + n, s, lay.vlen, lay.vskip);
+  HIP_TRY(hipGetLastError());
+  tm.stop();
+  hipLaunchKernelGGL(k_first_to_counts, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, s, n, *d_se, counts);
+  return MRX_OK;
+}
+
+// One findall call -- or, counts-only, the stepper family's share of one count call.  The members are the state the
+// routes share; one member function per route -- round 3's run_findall was a single 420-line function steering ~25 flags.
 struct FindallJob {
   const mrx_handle* h;
   const Layout& lay;
@@ -5671,6 +5726,9 @@ struct FindallJob {
   bool match_next_sequence;
   int64_t known_total, known_max;
   const DevPlan& p;
+  // count: the stepper family's first stage and nothing behind it -- d_counts is the caller's buffer; no d_total, no
+  // prefix sums, no spans, no read-back (count())
+  const bool counts_only;
   int32_t* d_counts = nullptr;
   int64_t* d_total = nullptr;
   // ---- route (chosen by choose_route() and step_scan()) ----
@@ -5707,14 +5765,18 @@ struct FindallJob {
   bool rows = false, rows_shape = false;
   uint2* d_rows = nullptr;
   int64_t row_pairs = 0;
-  // required-byte plan on long texts: the route being timed for the handle's tuner (0: none), and when the call began
-  int tune_route = 0, tune_slot = 0;
-  uint32_t tune_key = 0;
+  TuneEnd tune;                    // the route a handle's tuner is timing on this call, if any
 
   FindallJob(const mrx_handle* h_, const Layout& lay_, int64_t n_, int64_t* d_prefix_, int32_t* d_spans_, int64_t span_cap_,
              int64_t* total_, hipStream_t s_, bool mns, int64_t kt, int64_t km)
       : h(h_), lay(lay_), n(n_), d_prefix(d_prefix_), d_spans(d_spans_), span_cap(span_cap_), total(total_), s(s_),
-        match_next_sequence(mns), known_total(kt), known_max(km), p(h_->hp.dev), pk(h_->hp.dev), lay2(lay_), lay_pre(lay_) {}
+        match_next_sequence(mns), known_total(kt), known_max(km), p(h_->hp.dev), counts_only(false), pk(h_->hp.dev), lay2(lay_),
+        lay_pre(lay_), tune(h_, s_) {}
+  // counts-only mode
+  FindallJob(const mrx_handle* h_, const Layout& lay_, int64_t n_, int32_t* counts, hipStream_t s_, int64_t kt, int64_t km)
+      : h(h_), lay(lay_), n(n_), d_prefix(nullptr), d_spans(nullptr), span_cap(0), total(nullptr), s(s_),
+        match_next_sequence(false), known_total(kt), known_max(km), p(h_->hp.dev), counts_only(true), d_counts(counts),
+        pk(h_->hp.dev), lay2(lay_), lay_pre(lay_), tune(h_, s_) {}
 
   // Which kernels serve this call.  Streamable plans: the streaming scan (records -> prefix sums -> decode, or one of
   // its one-launch forms); everything else: the stepper family (multi-walk table, backward marks, bitset union pass,
@@ -5736,11 +5798,8 @@ struct FindallJob {
     // ... and plain-route plans outside the multi-walk proofs whose walks stay within seven bytes of their match (PF_MW_TRIES)
     mw_tries = mw_tries_on(p) && !rt.req && g_force_generic < 2;
     if (t_in_pieces && t_piece_tries >= 0) mw_tries = mw_tries && t_piece_tries == 1;   // (the pieces follow the call they belong to)
-    if (mw_tries && !t_in_pieces && n >= 256 && backset_on(p) && !g_tries_always) {   // (marks + stepper is the other candidate)
-      bool use_tries = true;
-      tries_route_tuner(&use_tries);
-      mw_tries = use_tries;
-    }
+    if (mw_tries && !t_in_pieces && n >= 256 && backset_on(p) && !g_tries_always)   // (marks + stepper is the other candidate)
+      mw_tries = tries_route_tuner();
     rt.mwalk = (mwalk_req || (mwalk_on(p) && !rt.req) || mw_empty || mw_tries) && !rt.bits && !rt.empty &&
                   !(match_next_sequence && (p.flags & PF_PREFILTER));
     pk = mwalk_req ? mwalk_req_plan(p) : p;
@@ -5757,30 +5816,15 @@ struct FindallJob {
 
   // '^'-anchored DFA plan: the anchored automaton's run from byte 0 is the whole answer
   int anchored() {
-  int32_t* d_se = nullptr;
-    HIP_TRY(scratch_alloc((void**)&d_se, sizeof(int32_t) * 2 * n, s));
-    {
-      ScanTimer tm(s);
-      launch_stream<ST_FIRST>(h, lay, n, nullptr, nullptr, nullptr, 0, d_se, d_se + n, s, lay.vlen, lay.vskip);
-      HIP_TRY(hipGetLastError());
-      tm.stop();
-    }
-    hipLaunchKernelGGL(k_first_to_counts, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, s, n, d_se, d_counts);
+    int32_t* d_se = nullptr;
+    if (int rc = anchored_counts(h, lay, n, s, d_counts, &d_se)) return rc;
     if (int rc = device_scan<int32_t>(d_counts, n, d_prefix, d_total, s)) return rc;
     if (span_cap > 0)
       hipLaunchKernelGGL(k_first_to_spans, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, s, n, d_se, d_se + n, d_prefix, d_spans,
                          span_cap);
     HIP_TRY(hipGetLastError());
     g_last_kernel = "k_stream_first_findall";
-    int rc = MRX_OK;
-    if (total) {
-      int64_t tot = 0;
-      HIP_TRY(hipMemcpyAsync(&tot, d_total, sizeof tot, hipMemcpyDeviceToHost, s));
-      HIP_TRY(hipStreamSynchronize(s));
-      *total = tot;
-      if (tot > span_cap) rc = fail(MRX_E_CAPACITY, "span buffer too small: need " + std::to_string(tot));
-    }
-    return rc;
+    return read_back_total(d_total, span_cap, total, s);
   }
 
   // streamable plan: the scan (records, or one of the one-launch forms)
@@ -5897,6 +5941,15 @@ struct FindallJob {
     return MRX_OK;
   }
 
+  // k_decode in one of its forms (VBASE is findall_pieces' business), always with the same arguments; the trailing
+  // three are the kernel's defaults but for `reverse`
+  template <bool PACK16, bool REC32 = false, bool DYN = false, int TILE = kDecodeTile, bool REC12 = false, bool LEAN = false>
+  void decode_launch(unsigned grid, const int64_t* d_tsum, int reverse = 0) {
+    hipLaunchKernelGGL((k_decode<PACK16, false, REC32, DYN, TILE, REC12, LEAN>), dim3(grid), dim3(kBlock), 0, s, n, d_nrecs,
+                       d_recs, rec_row, lay.offsets, d_counts, d_wbase, d_tsum, d_prefix, d_spans, span_cap, p.st_fixed_len,
+                       d_total, (const int32_t*)nullptr, (const int64_t*)nullptr, reverse);
+  }
+
   // ... and what turns its records into the CSR: prefix sums over the wavefronts' totals, k_decode
   int stream_finish() {
     if (rows) {   // offsets from the scan's counts, then a wavefront per text (k_decode_rows)
@@ -5925,62 +5978,29 @@ struct FindallJob {
     hipLaunchKernelGGL(k_scan_local<int32_t>, dim3((unsigned)ntiles), dim3(kScanBlock), 0, s, d_nrecs + nw, nw,
                        d_wbase, d_tsum);
     const bool pack16 = max_text <= 65535;
-    bool decode_lean_ran = false;
+    // one k_decode per record form; texts of 768 bytes and more take the 3072-span tile, and only they the grid and
+    // reverse knobs (MRX_DECODE_GRID, MRX_DECODE_REVERSE)
+    const bool big = max_text >= 768, lean = pack16 && rec32 && g_decode_lean != 0;
+    const unsigned g2 = (unsigned)grid_for(n, kBlock) * 2;
+    const unsigned gbig = env_knobs().decode_grid > 0 ? (unsigned)env_knobs().decode_grid : g2;
+    const int rev = env_knobs().decode_reverse;
     if (dyn) {
-      const dim3 dg((unsigned)grid_for(nw * 64, kBlock) * 2), db(kBlock);
-      if (pack16 && rec32)
-        hipLaunchKernelGGL((k_decode<true, false, true, true, MRX_DYN_DECODE_TILE>), dg, db, 0, s, n, d_nrecs, d_recs, rec_row, lay.offsets, d_counts,
-                           d_wbase, d_tsum, d_prefix, d_spans, span_cap, p.st_fixed_len, d_total);
-      else if (pack16)
-        hipLaunchKernelGGL((k_decode<true, false, false, true>), dg, db, 0, s, n, d_nrecs, d_recs, rec_row, lay.offsets, d_counts,
-                           d_wbase, d_tsum, d_prefix, d_spans, span_cap, p.st_fixed_len, d_total);
-      else
-        hipLaunchKernelGGL((k_decode<false, false, false, true>), dg, db, 0, s, n, d_nrecs, d_recs, rec_row, lay.offsets, d_counts,
-                           d_wbase, d_tsum, d_prefix, d_spans, span_cap, p.st_fixed_len, d_total);
-    } else
-    if (pack16 && rec32 && g_decode_lean != 0) {
-      // the lean pass (k_decode<..., LEAN = true>): the same four shapes, grids and arguments as the launches below
-      const bool big = max_text >= 768;
-      auto lean = [&](auto tile, auto r12) {
-        hipLaunchKernelGGL((k_decode<true, false, true, false, decltype(tile)::value, decltype(r12)::value, true>),
-                           dim3(big && env_knobs().decode_grid > 0 ? env_knobs().decode_grid : grid_for(n, kBlock) * 2),
-                           dim3(kBlock), 0, s, n, d_nrecs, d_recs, rec_row, lay.offsets, d_counts, d_wbase, d_tsum, d_prefix,
-                           d_spans, span_cap, p.st_fixed_len, d_total, (const int32_t*)nullptr, (const int64_t*)nullptr,
-                           big ? env_knobs().decode_reverse : 0);
-      };
-      using Big = std::integral_constant<int, 3072>;
-      using Small = std::integral_constant<int, kDecodeTile>;
-      if (rec12 && big) lean(Big{}, std::true_type{});
-      else if (rec12) lean(Small{}, std::true_type{});
-      else if (big) lean(Big{}, std::false_type{});
-      else lean(Small{}, std::false_type{});
-      decode_lean_ran = true;
-    } else
-    if (rec12 && max_text >= 768)
-      hipLaunchKernelGGL((k_decode<true, false, true, false, 3072, true>), dim3(env_knobs().decode_grid > 0 ? env_knobs().decode_grid : grid_for(n, kBlock) * 2), dim3(kBlock), 0, s, n, d_nrecs, d_recs,
-                         rec_row, lay.offsets, d_counts, d_wbase, d_tsum, d_prefix, d_spans, span_cap, p.st_fixed_len,
-                         d_total, (const int32_t*)nullptr, (const int64_t*)nullptr, env_knobs().decode_reverse);
-    else if (rec12)
-      hipLaunchKernelGGL((k_decode<true, false, true, false, kDecodeTile, true>), dim3(grid_for(n, kBlock) * 2), dim3(kBlock), 0, s, n, d_nrecs, d_recs,
-                         rec_row, lay.offsets, d_counts, d_wbase, d_tsum, d_prefix, d_spans, span_cap, p.st_fixed_len,
-                         d_total);
-    else if (pack16 && rec32 && max_text >= 768)
-      hipLaunchKernelGGL((k_decode<true, false, true, false, 3072>), dim3(env_knobs().decode_grid > 0 ? env_knobs().decode_grid : grid_for(n, kBlock) * 2), dim3(kBlock), 0, s, n, d_nrecs, d_recs,
-                         rec_row, lay.offsets, d_counts, d_wbase, d_tsum, d_prefix, d_spans, span_cap, p.st_fixed_len,
-                         d_total, (const int32_t*)nullptr, (const int64_t*)nullptr, env_knobs().decode_reverse);
-    else if (pack16 && rec32)
-      hipLaunchKernelGGL((k_decode<true, false, true>), dim3(grid_for(n, kBlock) * 2), dim3(kBlock), 0, s, n, d_nrecs, d_recs,
-                         rec_row, lay.offsets, d_counts, d_wbase, d_tsum, d_prefix, d_spans, span_cap, p.st_fixed_len,
-                         d_total);
-    else if (pack16)
-      hipLaunchKernelGGL(k_decode<true>, dim3(grid_for(n, kBlock) * 2), dim3(kBlock), 0, s, n, d_nrecs, d_recs,
-                         rec_row, lay.offsets, d_counts, d_wbase, d_tsum, d_prefix, d_spans, span_cap, p.st_fixed_len,
-                         d_total);
-    else
-      hipLaunchKernelGGL(k_decode<false>, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, s, n, d_nrecs, d_recs,
-                         rec_row, lay.offsets, d_counts, d_wbase, d_tsum, d_prefix, d_spans, span_cap, p.st_fixed_len,
-                         d_total);
-    g_last_decode_lean = decode_lean_ran ? 1 : 0;
+      const unsigned gd = (unsigned)grid_for(nw * 64, kBlock) * 2;
+      if (pack16 && rec32) decode_launch<true, true, true, MRX_DYN_DECODE_TILE>(gd, d_tsum);
+      else if (pack16) decode_launch<true, false, true>(gd, d_tsum);
+      else decode_launch<false, false, true>(gd, d_tsum);
+    } else if (lean) {   // the lean pass (k_decode<..., LEAN = true>): the same four shapes, grids and arguments as the four below
+      if (rec12 && big) decode_launch<true, true, false, 3072, true, true>(gbig, d_tsum, rev);
+      else if (rec12) decode_launch<true, true, false, kDecodeTile, true, true>(g2, d_tsum);
+      else if (big) decode_launch<true, true, false, 3072, false, true>(gbig, d_tsum, rev);
+      else decode_launch<true, true, false, kDecodeTile, false, true>(g2, d_tsum);
+    } else if (rec12 && big) decode_launch<true, true, false, 3072, true>(gbig, d_tsum, rev);
+    else if (rec12) decode_launch<true, true, false, kDecodeTile, true>(g2, d_tsum);
+    else if (pack16 && rec32 && big) decode_launch<true, true, false, 3072>(gbig, d_tsum, rev);
+    else if (pack16 && rec32) decode_launch<true, true>(g2, d_tsum);
+    else if (pack16) decode_launch<true>(g2, d_tsum);
+    else decode_launch<false>((unsigned)grid_for(n, kBlock), d_tsum);
+    g_last_decode_lean = !dyn && lean ? 1 : 0;
     HIP_TRY(hipGetLastError());
     return MRX_OK;
   }
@@ -5988,142 +6008,131 @@ struct FindallJob {
   // ---- PF_MW_TRIES plan: the pending-tries walk or round 3's marks + stepper?  (mrx_handle::req_tune, kind bit 30) ----
   // The one-pass walk wins where matches are found (3-10 x), marks alone are faster where nothing matches, and bigger
   // tables sit in between (tools/r04_tries_cap.py): as for the required-byte routes the handle measures -- the first four
-  // eligible calls of a batch shape take the routes alternately, the last two timed; no call waits.
-  static uint32_t tries_tune_key(const Layout& lay, int64_t n) {
-    const int64_t bytes_per_text = lay.offsets ? 0 : lay.pitch_longest();
-    uint32_t lb = 0, nb = 0;
-    for (int64_t v = bytes_per_text; v > 1; v >>= 1) ++lb;
-    for (int64_t v = n; v > 1; v >>= 1) ++nb;
-    return (1u << 30) | (lay.offsets ? 1u << 31 : 0u) | ((uint32_t)(t_dev & 63) << 16) | (lb << 8) | nb;
-  }
-  void tries_route_tuner(bool* use_tries) {
-    int slot = -1;
-    const uint32_t key = tries_tune_key(lay, n);
-    *use_tries = ab_tuner_begin(h, key, s, "findall", &slot) == 1;
-    if (slot >= 0) { tune_key = key; tune_slot = slot; tune_route = *use_tries ? 1 : 2; }
+  // eligible calls of a batch shape take the routes alternately, the last two timed; no call waits.  count measures for
+  // itself (bit 29).  Returns whether this call takes the tries.
+  bool tries_route_tuner() {
+    tune.key = route_tune_key(lay, n, (1u << 30) | (counts_only ? 1u << 29 : 0u));
+    return ab_tuner_begin(h, tune.key, s, {counts_only ? "count" : "findall", "pending tries", "marks + stepper", "tries", "marks"},
+                          &tune.slot) == 1;
   }
 
   // ---- required-byte plan on long texts: which route?  (mrx_handle::req_tune) ----
   // First call of a batch shape: are the plan's synchronising bytes frequent in the text at all (one small kernel, one
-  // 4-byte read-back; else: the wavefront kernel, for good).  Then four measured calls (mrx_handle::ReqTune), and the
-  // faster route from the first call that finds the last measurement complete.
+  // 4-byte read-back; else: the wavefront kernel, for good).  Then ab_tuner_begin's four measured calls, and the faster
+  // route from the first call that finds the last measurement complete.
   int req_route_tuner(bool* pieces) {
     *pieces = false;
-    const int64_t bytes_per_text = lay.offsets ? 0 : lay.pitch_longest();
-    uint32_t lb = 0, nb = 0;
-    for (int64_t v = bytes_per_text; v > 1; v >>= 1) ++lb;
-    for (int64_t v = n; v > 1; v >>= 1) ++nb;
-    tune_key = (lay.offsets ? 1u << 31 : 0u) | ((uint32_t)(t_dev & 63) << 16) | (lb << 8) | nb;
+    tune.key = route_tune_key(lay, n, 0);
     bool probe = false;
-    {
+    {   // (an entry that has a measured call has been probed)
       std::lock_guard<std::mutex> lk(h->tune_mu);
-      mrx_handle::ReqTune& t = h->req_tune[tune_key];
-      if (t.choice) { *pieces = t.choice == 2; return MRX_OK; }
-      if (t.issued == 4) {   // all four are enqueued: through?
-        if (hipEventQuery(t.ev[3][1]) != hipSuccess) return MRX_OK;   // not yet: the default route, unmeasured
-        if (hipEventElapsedTime(&t.ms_wave, t.ev[2][0], t.ev[2][1]) != hipSuccess ||
-            hipEventElapsedTime(&t.ms_pieces, t.ev[3][0], t.ev[3][1]) != hipSuccess) { t.choice = 1; return MRX_OK; }
-        t.choice = t.ms_pieces < t.ms_wave ? 2 : 1;
-        static const bool verbose = getenv("MRX_TUNE_VERBOSE") != nullptr;
-        if (verbose) fprintf(stderr, "mrx: required-byte route of '%s' (key %08x): wavefront %.3f ms, pieces %.3f ms -> %s\n",
-                             h->hp.pattern.c_str(), tune_key, t.ms_wave, t.ms_pieces, t.choice == 2 ? "pieces" : "wavefront");
-        *pieces = t.choice == 2;
-        return MRX_OK;
-      }
+      mrx_handle::ReqTune& t = h->req_tune[tune.key];
+      if (t.choice) { *pieces = t.choice == 2; return MRX_OK; }   // the steady state: one look
       probe = !t.probed;
       t.probed = true;
     }
     if (probe) {
       bool freq = false;
       if (int rc = sync_bytes_frequent(h, lay, n, s, &freq)) return rc;
-      std::lock_guard<std::mutex> lk(h->tune_mu);
-      mrx_handle::ReqTune& t = h->req_tune[tune_key];
-      if (!freq) { t.choice = 1; return MRX_OK; }
-      t.dev = t_dev;
-      for (auto& pr : t.ev)
-        for (auto& e : pr)
-          if (hipEventCreate(&e) != hipSuccess) { t.choice = 1; return MRX_OK; }
+      if (!freq) { req_tuner_unavailable(); return MRX_OK; }
     }
-    std::lock_guard<std::mutex> lk(h->tune_mu);
-    mrx_handle::ReqTune& t = h->req_tune[tune_key];
-    if (t.choice || t.issued >= 4 || !t.ev[3][1]) return MRX_OK;   // (another thread got here first, or is still probing)
-    tune_slot = t.issued++;
-    tune_route = (tune_slot & 1) ? 2 : 1;
-    *pieces = tune_route == 2;
-    HIP_TRY(hipEventRecord(t.ev[tune_slot][0], s));
+    *pieces = ab_tuner_begin(h, tune.key, s, {"required-byte route", "wavefront", "pieces", "wavefront", "pieces"}, &tune.slot) == 2;
     return MRX_OK;
   }
-  void req_tuner_unavailable() {   // nothing to cut: the wavefront kernel it is
+  void req_tuner_unavailable() {   // nothing to cut: the wavefront kernel it is, and this call is not a measurement
     std::lock_guard<std::mutex> lk(h->tune_mu);
-    h->req_tune[tune_key].choice = 1;
-    tune_route = 0;
+    h->req_tune[tune.key].choice = 1;
+    tune.slot = -1;
   }
-  void req_tuner_report() {   // the call's work is enqueued: close the measurement
-    if (!tune_route) return;
-    std::lock_guard<std::mutex> lk(h->tune_mu);
-    mrx_handle::ReqTune& t = h->req_tune[tune_key];
-    if (t.ev[tune_slot][1]) (void)hipEventRecord(t.ev[tune_slot][1], s);
-    tune_route = 0;
+
+  // The stepper's pieces as a batch of their own (t_in_pieces): findall over them, then the texts' entries of the
+  // per-piece prefix sums and the pieces' bases on the spans; the name tells (..._pieces)
+  int findall_pieces_step(const Pieces& spc) {
+    int64_t* d_vprefix = nullptr;
+    HIP_TRY(scratch_alloc((void**)&d_vprefix, sizeof(int64_t) * (spc.nv + 1), s));
+    t_in_pieces = true;
+    t_piece_vbase = spc.vbase;
+    t_piece_base_applied = false;
+    t_piece_tries = (p.flags & PF_MW_TRIES) ? (mw_tries ? 1 : 0) : -1;
+    const int rc = run_findall(h, spc.lay, spc.nv, d_vprefix, d_spans, span_cap, nullptr, s, match_next_sequence);
+    t_in_pieces = false;
+    t_piece_vbase = nullptr;
+    t_piece_tries = -1;
+    if (rc != MRX_OK) return rc;
+    const std::string inner = g_last_kernel;
+    hipLaunchKernelGGL(k_virt_prefix, dim3(grid_for(n + 1, kBlock)), dim3(kBlock), 0, s, n, spc.vfirst, d_vprefix, d_prefix);
+    if (!t_piece_base_applied)
+      hipLaunchKernelGGL(k_virt_add_base, dim3(grid_cap()), dim3(kBlock), 0, s, spc.nv, d_vprefix, spc.vbase,
+                         d_spans, span_cap);
+    HIP_TRY(hipGetLastError());
+    static thread_local std::string piece_name;
+    piece_name = inner + "_pieces";
+    g_last_kernel = piece_name.c_str();
+    tune.close();
+    return read_back_total(d_vprefix + spc.nv, span_cap, total, s);
+  }
+  // ... count over them, then each text's sum; the name stays the inner call's
+  int count_pieces(const Pieces& spc) {
+    int32_t* d_vcounts = nullptr;
+    HIP_TRY(scratch_alloc((void**)&d_vcounts, sizeof(int32_t) * spc.nv, s));
+    t_in_pieces = true;
+    t_piece_tries = (p.flags & PF_MW_TRIES) ? (mw_tries ? 1 : 0) : -1;
+    const int rc = run_count_any(h, spc.lay, spc.nv, d_vcounts, s);
+    t_in_pieces = false;
+    t_piece_tries = -1;
+    if (rc != MRX_OK) return rc;
+    hipLaunchKernelGGL(k_virt_sum, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, s, n, spc.vfirst, d_vcounts, d_counts);
+    HIP_TRY(hipGetLastError());
+    return MRX_OK;
   }
 
   // every other plan, first stage: counts (+ slot rows) on the stepper family / the literal restatement
   int step_scan() {
-  bool req_pieces = false;   // required-byte plan: pieces on the multi-walk kernel instead of the wavefront-per-text kernel
+    bool req_pieces = false;   // required-byte plan: pieces on the multi-walk kernel instead of the wavefront-per-text kernel
     if (rt.req && mwalk_req && g_long_text_mode == 0 && !t_in_pieces && p.st_nsync > 0 && span_cap > 0 &&
         !(p.flags & (PF_STEP_BIG | PF_STREAMABLE)))
       if (int rc = req_route_tuner(&req_pieces)) return rc;
-    if (step_ok && !rt.bits && !rt.empty && !t_in_pieces && !(p.flags & PF_STEP_BIG) && p.st_nsync > 0 &&
-        !(p.flags & PF_STREAMABLE) && span_cap > 0 && (!rt.req || g_long_text_mode == 1 || req_pieces)) {
+    // "A plan of the lane kernels": findall asks step_ok, count the plan's flags.  The two agree on every plan of the
+    // tests' corpus (tests/test_step_flag_families_host.py) but not by the planner's text: mrx_plan.cpp sets PF_MWALK
+    // and PF_MW_TRIES under conditions that do not name those of PF_STEPPABLE / PF_STEP_REQ (table size, anchors), and
+    // for such a plan rt.mwalk alone makes step_ok.  So both wordings stay, here and for the wavefront kernel below.
+    const bool flags_ok = g_force_generic < 2 && (p.flags & (PF_STEPPABLE | PF_STEP_REQ)) != 0;
+    // long texts: disjoint pieces between synchronising bytes, one lane each.  findall cuts when spans are wanted and
+    // may follow the required-byte tuner into the pieces; count cuts on its own rule only
+    if ((counts_only ? flags_ok : step_ok && !rt.empty && span_cap > 0) && !rt.bits && !t_in_pieces &&
+        !(p.flags & (PF_STEP_BIG | PF_STREAMABLE)) && p.st_nsync > 0 && (!rt.req || g_long_text_mode == 1 || req_pieces)) {
       Pieces spc;
-      if (int rc = pieces_prepare(h, lay, n, s, &spc, -1, -1, /*disjoint=*/true, rt.mwalk)) return rc;
-      if (req_pieces && !spc.on) req_tuner_unavailable();   // nothing to cut (texts too short, too many of them): the wavefront kernel it is
+      ScratchMark before_pieces;
+      if (counts_only) before_pieces = scratch_mark(s);
+      // (count hands on the batch's statistics when its caller has them: pattern sets)
+      if (int rc = pieces_prepare(h, lay, n, s, &spc, counts_only ? known_total : -1, counts_only ? known_max : -1,
+                                  /*disjoint=*/true, rt.mwalk))
+        return rc;
+      if (req_pieces && !spc.on) req_tuner_unavailable();   // nothing to cut (texts too short, too many of them)
       if (spc.on && !rt.mwalk) {   // (a multi-walk plan scans every piece once, dense candidates or not)
         bool dense = true;
         if (int rc = dense_candidates(h, lay, n, s, &dense)) return rc;
-        if (!dense) spc.on = false;
+        if (!dense) {   // the lane / wavefront kernels after all; count: on the pieces' bytes (findall keeps them)
+          spc.on = false;
+          if (counts_only) scratch_reuse_from(s, before_pieces);
+        }
       }
       if (spc.on) {
-        int64_t* d_vprefix = nullptr;
-        HIP_TRY(scratch_alloc((void**)&d_vprefix, sizeof(int64_t) * (spc.nv + 1), s));
-        t_in_pieces = true;
-        t_piece_vbase = spc.vbase;
-        t_piece_base_applied = false;
-        t_piece_tries = (p.flags & PF_MW_TRIES) ? (mw_tries ? 1 : 0) : -1;
-        const int rc = run_findall(h, spc.lay, spc.nv, d_vprefix, d_spans, span_cap, nullptr, s, match_next_sequence);
-        t_in_pieces = false;
-        t_piece_vbase = nullptr;
-        t_piece_tries = -1;
-        if (rc != MRX_OK) return rc;
-        const std::string inner = g_last_kernel;
-        hipLaunchKernelGGL(k_virt_prefix, dim3(grid_for(n + 1, kBlock)), dim3(kBlock), 0, s, n, spc.vfirst, d_vprefix, d_prefix);
-        if (!t_piece_base_applied)
-          hipLaunchKernelGGL(k_virt_add_base, dim3(grid_cap()), dim3(kBlock), 0, s, spc.nv, d_vprefix, spc.vbase,
-                             d_spans, span_cap);
-        HIP_TRY(hipGetLastError());
-        static thread_local std::string piece_name;
-        piece_name = inner + "_pieces";
-        g_last_kernel = piece_name.c_str();
-        req_tuner_report();
-        int rc2 = MRX_OK;
-        if (total) {
-          int64_t tot = 0;
-          HIP_TRY(hipMemcpyAsync(&tot, d_vprefix + spc.nv, sizeof tot, hipMemcpyDeviceToHost, s));
-          HIP_TRY(hipStreamSynchronize(s));
-          *total = tot;
-          if (tot > span_cap) rc2 = fail(MRX_E_CAPACITY, "span buffer too small: need " + std::to_string(tot));
-        }
-        finished = true;   // the pieces answered the whole call
-        finished_rc = rc2;
-        return MRX_OK;
+        finished = true;   // the pieces answer the whole call
+        return counts_only ? count_pieces(spc) : findall_pieces_step(spc);
       }
     }
-    if (step_ok && !rt.bits && !rt.empty && !mw_empty && !mw_tries && !t_in_pieces && !rt.lz) {
+    // one wavefront per text, or a split between the two kernels?  (the two wordings: see above)
+    if ((counts_only ? flags_ok : step_ok && !rt.empty && !mw_empty) && !rt.bits && !mw_tries && !t_in_pieces && !rt.lz) {
       if (int rc = req_wave_pays(lay, n, rt.req, s, &req_wave, (p.flags & PF_STEP_BIG) ? nullptr : &step_split,
                                  (p.flags & PF_STEP_BIG) != 0, rt.mwalk, backset_on(p) && !rt.mwalk))
         return rc;
-      rt.mwalk_pk = rt.mwalk && mwalk_pk_ok(lay, t_csr_max_len);
+      // (count never takes k_mwalk's packed-start form: it keeps no start registers)
+      rt.mwalk_pk = !counts_only && rt.mwalk && mwalk_pk_ok(lay, t_csr_max_len);
     }
     lay2.split = step_split;
+    // (counts-only: step_ok here is PF_STEPPABLE -- without rt.mwalk, rt.req and rt.empty nothing else makes it, and
+    // backset_on() means g_force_generic == 0)
     rt.bm = step_ok && backset_on(p) && !rt.mwalk && !rt.bits && !rt.empty && !rt.req && !req_wave &&
                step_split == 0;
     rt.bm_big = rt.bm && (p.flags & PF_STEP_BIG) != 0;
@@ -6132,6 +6141,8 @@ struct FindallJob {
       if (int rc = backscan_marks(h, lay, n, s, &lay2)) return rc;
       lay2.split = split_keep;
     }
+    // (rt.bits and the union pass both mean PF_STEPPABLE -- mrx_plan.cpp sets PF_BSTEP only together with it --, which
+    // excludes PF_START_ACCEPTING and with it PF_STEP_EMPTY: step_ok && !rt.empty says g_force_generic < 2 here)
     if (step_ok && !bits_fixed && !rt.empty && !rt.mwalk && !rt.bm && (rt.bits || (!req_wave && step_split == 0 && !rt.req && union_pass_for_table_plan(p, false)))) {
       // union automaton first: texts in which no walk from any start reaches MATCH are not walked at all
       // (mode 0: a wavefront stops as soon as each of its texts has shown one match end, so on texts full
@@ -6140,7 +6151,7 @@ struct FindallJob {
     }
     // big tables: only the wavefront kernel has their form; many short texts stay on the literal restatement
     if ((p.flags & PF_STEP_BIG) && !req_wave && !rt.mwalk && !rt.bm) step_ok = false;
-    ScanTimer tm(s);
+    ScanTimer tm(s, !counts_only);   // (count times the whole call: run_count_any)
     // multi-walk plans: count, prefix sums, emit -- two one-pass scans whatever the match density (the count pass
     // keeps no start registers and runs at 3 TB/s; slot rows + a second walk for overflowing texts would be three)
     mwalk_two_pass = rt.mwalk && !req_wave && step_split == 0;
@@ -6201,7 +6212,7 @@ struct FindallJob {
       MRX_BT_DISPATCH(bt_kernel_kind(h, plan_uses_backtracker(h)), MRX_L);
   #undef MRX_L
     }
-    g_last_kernel = bits_fixed ? "k_bscan_fixed" : req_wave ? "k_req_wave" : step_ok ? (rt.mwalk ? (step_split > 0 ? "k_mwalk+k_req_wave" : "k_mwalk") : rt.bm ? "k_backscan+k_step_count" : rt.bits ? "k_bstep_count" : rt.empty ? "k_estep_count" : step_split > 0 ? "k_step_count+k_req_wave" : "k_step_count")
+    g_last_kernel = bits_fixed ? "k_bscan_fixed" : req_wave ? "k_req_wave" : step_ok ? (rt.mwalk ? (step_split > 0 ? (counts_only ? "k_step_count+k_req_wave" : "k_mwalk+k_req_wave") : "k_mwalk") : rt.bm ? "k_backscan+k_step_count" : rt.bits ? "k_bstep_count" : rt.empty ? "k_estep_count" : step_split > 0 ? "k_step_count+k_req_wave" : "k_step_count")
                                                       : "k_findall_count";
     HIP_TRY(hipGetLastError());
     tm.stop();
@@ -6281,20 +6292,16 @@ struct FindallJob {
   }
 
   int read_total() {
-    req_tuner_report();
+    tune.close();   // the call's work is enqueued
     dense_probe_send();
-  int rc = MRX_OK;
-    if (total) {
-      int64_t tot = 0;
-      unsigned long long fused_err = 0;
-      HIP_TRY(hipMemcpyAsync(&tot, d_total, sizeof tot, hipMemcpyDeviceToHost, s));
-      if (d_ctrl) HIP_TRY(hipMemcpyAsync(&fused_err, d_ctrl + 1, sizeof fused_err, hipMemcpyDeviceToHost, s));
-      HIP_TRY(hipStreamSynchronize(s));
-      *total = tot;
-      if (fused_err) return fail(MRX_E_NO_DEVICE, "internal: a wavefront gave up waiting for its predecessors' span counts");
-      if (tot > span_cap) rc = fail(MRX_E_CAPACITY, "span buffer too small: need " + std::to_string(tot));
-    }  // total == NULL: fully asynchronous; d_counts_prefix[n] holds the total when the stream drains
-    return rc;
+    // total == NULL: fully asynchronous; d_counts_prefix[n] holds the total when the stream drains
+    return read_back_total(d_total, span_cap, total, s, d_ctrl ? d_ctrl + 1 : nullptr);
+  }
+
+  // count of a plan that does not stream (n > 0): the first stage is the whole call
+  int count() {
+    choose_route();
+    return step_scan();
   }
 
   int run() {
@@ -6319,7 +6326,7 @@ struct FindallJob {
       if (int rc = findall_pieces(h, pc, n, d_prefix, d_spans, span_cap, d_total, s)) return rc;
     } else if (n > 0) {
       if (int rc = stream_ok ? stream_scan() : step_scan()) return rc;
-      if (finished) return finished_rc;
+      if (finished) return MRX_OK;
     }
     if (by_pieces || fused || split_done) {
       // done over the pieces above / by the one launch / in two halves (findall_split)
@@ -6333,7 +6340,6 @@ struct FindallJob {
       if (int rc = step_finish()) return rc;
     return read_total();
   }
-  int finished_rc = MRX_OK;
 };
 
 int run_findall(const mrx_handle* h, const Layout& lay, int64_t n, int64_t* d_prefix, int32_t* d_spans, int64_t span_cap,
@@ -6347,6 +6353,55 @@ int run_findall(const mrx_handle* h, const Layout& lay, int64_t n, int64_t* d_pr
   if (int rc = ensure_device(h)) return rc;
   FindallJob job(h, lay, n, d_prefix, d_spans, span_cap, total, (hipStream_t)stream, match_next_sequence, known_total, known_max);
   return job.run();
+}
+
+// count for any layout: the anchored automaton, the streaming scan, or the stepper family through FindallJob's
+// counts-only mode.  known_total / known_max: csr_stats() of a CSR batch when the caller has them already (< 0: not;
+// pattern-set findall)
+int run_count_any(const mrx_handle* h, const Layout& lay, int64_t n, int32_t* counts, void* st, int64_t known_total,
+                  int64_t known_max) {
+  ScratchScope scratch_scope_((hipStream_t)st);
+  if (!h) return fail(MRX_E_ARGUMENT, "null handle");
+  if (int rc = check_search_supported(h)) return rc;
+  if (int rc = check_lds(h)) return rc;
+  if (int rc = ensure_device(h)) return rc;
+  if (n <= 0) return MRX_OK;
+  hipStream_t s = (hipStream_t)st;
+  if (anchored_at_zero(h) && stream_layout_ok(lay, n)) {
+    int32_t* d_se = nullptr;
+    if (int rc = anchored_counts(h, lay, n, s, counts, &d_se)) return rc;
+    HIP_TRY(hipGetLastError());
+    g_last_kernel = "k_stream_first_count";
+    return MRX_OK;
+  }
+  ScanTimer tm(s);
+  if (!g_force_generic && (h->hp.dev.flags & PF_STREAMABLE) && stream_layout_ok(lay, n)) {
+    Pieces pc;
+    if (int rc = pieces_prepare(h, lay, n, s, &pc, known_total, known_max)) return rc;
+    if (pc.on) {   // long texts: count per piece, then add up each text's pieces
+      int32_t* d_vcounts = nullptr;
+      HIP_TRY(scratch_alloc((void**)&d_vcounts, sizeof(int32_t) * pc.nv, s));
+      launch_stream<ST_COUNT>(h, pc.lay, pc.nv, d_vcounts, nullptr, nullptr, 0, nullptr, nullptr, s, pc.vlen, pc.vskip);
+      hipLaunchKernelGGL(k_virt_sum, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, s, n, pc.vfirst, d_vcounts, counts);
+      HIP_TRY(hipGetLastError());
+      g_last_kernel = "k_stream_count_pieces";
+    } else if (dyn_ok(h, lay, n)) {
+      launch_stream_dyn<ST_COUNT>(h, lay, n, counts, nullptr, nullptr, nullptr, nullptr, s, false);
+      g_last_kernel = "k_stream_count_dyn";
+    } else {
+    launch_stream<ST_COUNT>(h, lay, n, counts, nullptr, nullptr, 0, nullptr, nullptr, s);
+    g_last_kernel = "k_stream_count";
+    }
+    HIP_TRY(hipGetLastError());
+    tm.stop();
+    return MRX_OK;
+  }
+  FindallJob job(h, lay, n, counts, s, known_total, known_max);   // (its tuner measurement closes when the call returns)
+  if (int rc = job.count()) return rc;
+  if (job.finished) return MRX_OK;   // (the pieces: each inner call was timed)
+  HIP_TRY(hipGetLastError());
+  tm.stop();
+  return MRX_OK;
 }
 
 }  // namespace
@@ -7523,144 +7578,6 @@ int mrx_split_strided_dev(const mrx_handle* h, const uint8_t* d, int64_t stride,
   return run_split(h, b, n, maxsplit, d_piece_prefix, d_pieces, piece_cap, total, st);
 }
 
-// known_total / known_max: csr_stats() of a CSR batch when the caller has them already (< 0: not; pattern-set findall)
-static int run_count_any(const mrx_handle* h, const Layout& lay, int64_t n, int32_t* counts, void* st,
-                         int64_t known_total = -1, int64_t known_max = -1) {
-  ScratchScope scratch_scope_((hipStream_t)st);
-  if (!h) return fail(MRX_E_ARGUMENT, "null handle");
-  if (int rc = check_search_supported(h)) return rc;
-  if (int rc = check_lds(h)) return rc;
-  if (int rc = ensure_device(h)) return rc;
-  if (n <= 0) return MRX_OK;
-  hipStream_t s = (hipStream_t)st;
-  if (anchored_at_zero(h) && stream_layout_ok(lay, n)) {
-    int32_t* d_se = nullptr;
-    HIP_TRY(scratch_alloc((void**)&d_se, sizeof(int32_t) * 2 * n, s));
-    ScanTimer tm(s);
-    launch_stream<ST_FIRST>(h, lay, n, nullptr, nullptr, nullptr, 0, d_se, d_se + n, s, lay.vlen, lay.vskip);
-    HIP_TRY(hipGetLastError());
-    tm.stop();
-    hipLaunchKernelGGL(k_first_to_counts, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, s, n, d_se, counts);
-    HIP_TRY(hipGetLastError());
-    g_last_kernel = "k_stream_first_count";
-    return MRX_OK;
-  }
-  ScanTimer tm(s);
-  if (!g_force_generic && (h->hp.dev.flags & PF_STREAMABLE) && stream_layout_ok(lay, n)) {
-    Pieces pc;
-    if (int rc = pieces_prepare(h, lay, n, s, &pc, known_total, known_max)) return rc;
-    if (pc.on) {   // long texts: count per piece, then add up each text's pieces
-      int32_t* d_vcounts = nullptr;
-      HIP_TRY(scratch_alloc((void**)&d_vcounts, sizeof(int32_t) * pc.nv, s));
-      launch_stream<ST_COUNT>(h, pc.lay, pc.nv, d_vcounts, nullptr, nullptr, 0, nullptr, nullptr, s, pc.vlen, pc.vskip);
-      hipLaunchKernelGGL(k_virt_sum, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, s, n, pc.vfirst, d_vcounts, counts);
-      HIP_TRY(hipGetLastError());
-      g_last_kernel = "k_stream_count_pieces";
-    } else if (dyn_ok(h, lay, n)) {
-      launch_stream_dyn<ST_COUNT>(h, lay, n, counts, nullptr, nullptr, nullptr, nullptr, s, false);
-      g_last_kernel = "k_stream_count_dyn";
-    } else {
-    launch_stream<ST_COUNT>(h, lay, n, counts, nullptr, nullptr, 0, nullptr, nullptr, s);
-    g_last_kernel = "k_stream_count";
-    }
-  } else {
-    StepRoute rt;   // (count never takes k_mwalk's packed-start form: it keeps no start registers)
-    rt.req = (h->hp.dev.flags & PF_STEP_REQ) != 0;
-    rt.bits = (h->hp.dev.flags & PF_BSTEP) != 0;
-    rt.lz = (h->hp.dev.flags & PF_LAZY_END) != 0;
-    const bool mw_empty = (h->hp.dev.flags & PF_MW_EMPTY) != 0 && mwalk_enabled() && g_force_generic < 2;
-    rt.empty = (h->hp.dev.flags & PF_STEP_EMPTY) != 0 && g_force_generic < 2 && !mw_empty;
-    const bool mwalk_req = rt.req && (h->hp.dev.flags & PF_MWALK_REQ) && mwalk_enabled();
-    bool mw_tries = mw_tries_on(h->hp.dev) && !rt.req && g_force_generic < 2;
-    if (t_in_pieces && t_piece_tries >= 0) mw_tries = mw_tries && t_piece_tries == 1;
-    int cnt_slot = -1;
-    const uint32_t cnt_key = FindallJob::tries_tune_key(lay, n) | (1u << 29);   // (count's own measurement)
-    if (mw_tries && !t_in_pieces && n >= 256 && backset_on(h->hp.dev) && !g_tries_always)
-      mw_tries = ab_tuner_begin(h, cnt_key, s, "count", &cnt_slot) == 1;
-    struct CountTuneEnd {   // (closes the measurement on every way out of this call)
-      const mrx_handle* h; uint32_t key; int slot; hipStream_t s;
-      ~CountTuneEnd() { ab_tuner_end(h, key, slot, s); }
-    } cnt_tune_end{h, cnt_key, cnt_slot, s};
-    rt.mwalk = (mwalk_req || (mwalk_on(h->hp.dev) && !rt.req) || mw_empty || mw_tries) && !rt.bits && !rt.empty;
-    const DevPlan pk = mwalk_req ? mwalk_req_plan(h->hp.dev) : h->hp.dev;
-    rt.mwalk_k = pk.mw_k;
-    bool req_wave = false;
-    int split = 0;
-    if (g_force_generic < 2 && !rt.bits && !t_in_pieces && (h->hp.dev.flags & (PF_STEPPABLE | PF_STEP_REQ)) &&
-        !(h->hp.dev.flags & (PF_STEP_BIG | PF_STREAMABLE)) && h->hp.dev.st_nsync > 0 &&
-        (!rt.req || g_long_text_mode == 1)) {
-      // long texts: disjoint pieces between synchronising bytes, one lane each (see run_findall)
-      Pieces spc;
-      const ScratchMark before_pieces = scratch_mark(s);
-      if (int rc = pieces_prepare(h, lay, n, s, &spc, known_total, known_max, /*disjoint=*/true, rt.mwalk)) return rc;
-      if (spc.on && !rt.mwalk) {
-        bool dense = true;
-        if (int rc = dense_candidates(h, lay, n, s, &dense)) return rc;
-        if (!dense) {   // the wavefront kernel after all: on the pieces' bytes
-          spc.on = false;
-          scratch_reuse_from(s, before_pieces);
-        }
-      }
-      if (spc.on) {
-        int32_t* d_vcounts = nullptr;
-        HIP_TRY(scratch_alloc((void**)&d_vcounts, sizeof(int32_t) * spc.nv, s));
-        t_in_pieces = true;
-        t_piece_tries = (h->hp.dev.flags & PF_MW_TRIES) ? (mw_tries ? 1 : 0) : -1;
-        const int rc = run_count_any(h, spc.lay, spc.nv, d_vcounts, st);
-        t_in_pieces = false;
-        t_piece_tries = -1;
-        if (rc != MRX_OK) return rc;
-        hipLaunchKernelGGL(k_virt_sum, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, s, n, spc.vfirst, d_vcounts, counts);
-        HIP_TRY(hipGetLastError());
-        return MRX_OK;
-      }
-    }
-    if (g_force_generic < 2 && !rt.bits && !rt.lz && !mw_tries && !t_in_pieces && (h->hp.dev.flags & (PF_STEPPABLE | PF_STEP_REQ)))
-      if (int rc = req_wave_pays(lay, n, rt.req, s, &req_wave, (h->hp.dev.flags & PF_STEP_BIG) ? nullptr : &split,
-                                 (h->hp.dev.flags & PF_STEP_BIG) != 0, rt.mwalk, backset_on(h->hp.dev) && !rt.mwalk))
-        return rc;
-    Layout lay2 = lay;
-    lay2.split = split;
-    int32_t* d_blimit = nullptr;
-    rt.bm = backset_on(h->hp.dev) && !rt.mwalk && !rt.bits && !rt.empty && !rt.req && !req_wave &&
-                          split == 0 && (h->hp.dev.flags & PF_STEPPABLE);
-    rt.bm_big = rt.bm && (h->hp.dev.flags & PF_STEP_BIG) != 0;
-    if (rt.bm)
-      if (int rc = backscan_marks(h, lay, n, s, &lay2)) return rc;
-    const bool bits_fixed = rt.bits && bits_fixed_on(h->hp.dev);
-    if (g_force_generic < 2 && !bits_fixed && !rt.mwalk && !rt.bm && (rt.bits || (!req_wave && split == 0 && !rt.req && union_pass_for_table_plan(h->hp.dev, false))))
-      if (int rc = bscan_limits(h, lay, n, 0, s, &lay2, &d_blimit)) return rc;   // union automaton first
-    const bool big_lane = (h->hp.dev.flags & PF_STEP_BIG) && !req_wave && !rt.mwalk && !rt.bm;   // -> literal restatement
-    if (bits_fixed) {
-      if (int rc = bscan_fixed(h, lay, n, 2, s, counts, nullptr, nullptr, 0)) return rc;
-      g_last_kernel = "k_bscan_fixed";
-    } else if (req_wave) {
-      reqwave_launch<STEP_COUNT>(rt, h, lay, n, counts, (const int64_t*)nullptr, (int32_t*)nullptr, (int64_t)0, s);
-      g_last_kernel = "k_req_wave";
-    } else if (g_force_generic < 2 && !big_lane && ((h->hp.dev.flags & (PF_STEPPABLE | PF_STEP_REQ | PF_STEP_EMPTY)) || rt.mwalk)) {
-      wstep_launch<STEP_COUNT>(rt, dim3(wstep_grid(n)), dim3(64 * kWsWaves), wstep_lds(pk, rt.mwalk, rt.bm_big), s, pk,
-                         H_BLOB(h), lay2, n, counts, (const int64_t*)nullptr, (int32_t*)nullptr, (int64_t)0,
-                         (int32_t*)nullptr, (int32_t*)nullptr);
-      g_last_kernel = rt.mwalk ? "k_mwalk" : rt.bm ? "k_backscan+k_step_count" : rt.bits ? "k_bstep_count" : rt.empty ? "k_estep_count" : "k_step_count";
-      if (split > 0) {
-        reqwave_launch<STEP_COUNT>(rt, h, lay2, n, counts, (const int64_t*)nullptr, (int32_t*)nullptr, (int64_t)0, s);
-        g_last_kernel = "k_step_count+k_req_wave";
-      }
-    } else {
-      Layout layp = lay;
-      if (h->hp.dev.flags & PF_BT_SEARCH)
-        if (int rc = bt_prepass(h, lay, n, s, &layp)) return rc;
-#define MRX_L(B) hipLaunchKernelGGL((k_findall<FA_COUNT, B>), dim3(grid_for(n, kBlock)), dim3(kBlock), lds_for(h), s, \
-                                   h->hp.dev, H_BLOB(h), layp, n, counts, (const int64_t*)nullptr, (int32_t*)nullptr, (int64_t)0)
-      MRX_BT_DISPATCH(bt_kernel_kind(h, plan_uses_backtracker(h)), MRX_L);
-#undef MRX_L
-      g_last_kernel = "k_findall_count";
-    }
-  }
-  HIP_TRY(hipGetLastError());
-  tm.stop();
-  return MRX_OK;
-}
 int mrx_count_dev(const mrx_handle* h, const uint8_t* d, const int64_t* off, int64_t n,
                   int32_t* counts, void* st) {
   const TextBatch b = csr(d, off);
