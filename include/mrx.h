@@ -966,7 +966,77 @@ int mrx_kw_filter_strided_dev(const mrx_kw* k, uint32_t flags, const uint8_t* d_
                               int32_t len, int64_t n, int64_t* d_kept_idx, int64_t* d_out_offsets, uint8_t* d_out_data,
                               int64_t out_cap, int64_t* d_totals, int64_t* totals, void* stream);
 
+/* ---- lines: a batch's texts cut at one separator byte, as a new packed batch on the device ----
+ * The first step of a pipeline over a file: a buffer's bytes (one text, or the texts of a batch) become the batch of lines
+ * that every other call takes.  No pattern and no automaton: with `sep` one byte, lines(t) is t.split(sep) with the last
+ * piece dropped when it is empty.
+ *   b""  -> []        b"\n" -> [b""]        b"a" -> [b"a"]        b"a\nb" and b"a\nb\n" -> [b"a", b"b"]
+ *   b"\n\na" -> [b"", b"", b"a"]
+ * Every separator ends a line, and an unterminated, non-empty tail is a line too: a text's line count is its separator
+ * count, plus one if it is not empty and its last byte is no separator.  A line never crosses a text boundary, and bytes
+ * outside a text never make or change a line.  flags:
+ *   MRX_LINES_KEEPENDS      every terminated line keeps its separator (splitlines(keepends=True) restricted to sep)
+ *   MRX_LINES_CRLF          needs sep == '\n' and no MRX_LINES_KEEPENDS: one '\r' directly in front of a dropped '\n' of
+ *                           the same text is dropped with it.  A '\r' anywhere else stays, a text's last byte included.
+ *   MRX_LINES_DROP_PARTIAL  every text's unterminated tail is left out (reading a file in chunks)
+ * Outputs, all on the device, lines in text order:
+ *   d_line_prefix int64[n + 1]          CSR over the texts: text i owns the lines [d_line_prefix[i], d_line_prefix[i + 1]);
+ *                                       right for empty texts too, wherever they stand
+ *   d_owner int64[piece_cap]            [0, lines): the text index of each line
+ *   d_out_offsets int64[piece_cap + 1]  [0, lines]: the CSR of the output batch; d_out_offsets[lines] = bytes
+ *   d_out_data uint8[out_cap]           the lines back to back; any alignment
+ *   d_totals int64[4]                   {lines, bytes, longest line, tail}
+ * tail is the byte count of the LAST text's unterminated tail, whatever the flags say (0 when it ends in a separator or
+ * n == 0): a caller that reads a file in chunks carries buf[len - tail, len) into the next one.  The longest line counts
+ * the separator under MRX_LINES_KEEPENDS.  The output is a CSR batch and the input of a following call as it stands, with
+ * bytes and the longest line as its known bounds -- both exact.  Entries of d_owner and d_out_offsets past the lines are
+ * unspecified.  No byte of d_out_data at or past bytes, nor at or past out_cap, is ever written, and no element of
+ * d_owner at or past piece_cap, nor of d_out_offsets at or past piece_cap + 1.
+ * Capacity.  lines > piece_cap: nothing is written to d_out_data, d_owner and d_out_offsets hold nothing of use;
+ * d_line_prefix, d_totals[0] (the need), d_totals[1] and d_totals[3] are exact, d_totals[2] is 0.  lines <= piece_cap and
+ * bytes > out_cap: d_line_prefix, d_owner, d_out_offsets and all four totals are complete and exact, and NO output byte is
+ * written (out_cap == 0 with MRX_LINES_KEEPENDS on one text is how a caller gets the offsets of the lines inside its
+ * own buffer, which the output would only repeat).  A call with `totals` returns MRX_E_CAPACITY in either case, totals
+ * filled for a retry (grow the lines first, then the bytes: two retries at most).
+ * totals (host, int64[4], may be NULL) receives d_totals: the call then reads back once, at its end -- no host decision
+ * sits between its kernels.  With totals == NULL the call returns without synchronising behind its kernels: they decide
+ * on the device from d_totals, and the caller checks d_totals against its capacities once the stream has drained.
+ * n == 0 or no line: totals {0, 0, 0, tail}, d_out_offsets = {0}.
+ * MRX_E_ARGUMENT, before anything is enqueued: an unknown flag; MRX_LINES_CRLF with another separator than '\n' or with
+ * MRX_LINES_KEEPENDS; negative n, piece_cap, out_cap, end_offset or max_text_len; a bad pitch; a null required pointer (d_offsets, d_line_prefix,
+ * d_out_offsets, d_totals; d_owner when piece_cap > 0; d_out_data when out_cap > 0).
+ * Sizes: every position is 64-bit.  The CSR form serves a text of 2^31 bytes and more; the strided form keeps its int32
+ * length.
+ * Reads: as filter and extract, the aligned 16-byte words that hold a text's bytes, so up to 15 bytes in front of a
+ * text's first byte and behind its last one are read (never used); no word is read for an empty text.
+ * Scratch: 40 bytes per piece of the input (a text is cut into pieces of 4 KiB; an empty text has none), up to 48 per
+ * text, and the scans' block sums: nothing is sized by a capacity.  It is returned to the arena when the call returns.  The CSR
+ * form reads d_offsets[0] and d_offsets[n] back (one synchronisation, before its first kernel) to size it; the strided
+ * form sizes it from its arguments and mrx_lines_known_dev from end_offset, the batch's byte count d_offsets[n] -
+ * d_offsets[0] or an upper bound of it (max_text_len is not used), and neither reads anything: with totals == NULL they
+ * enqueue and return.  end_offset must not be too small, and d_offsets must not decrease anywhere: the kernels index the
+ * scratch with the real offsets.
+ * The result is the same bit for bit on every run: no atomics, and no wavefront waits for another. */
+enum { MRX_LINES_KEEPENDS = 1, MRX_LINES_CRLF = 2, MRX_LINES_DROP_PARTIAL = 4 };
+int mrx_lines_dev(uint32_t flags, uint8_t sep, const uint8_t* d_data, const int64_t* d_offsets, int64_t n,
+                  int64_t* d_line_prefix, int64_t* d_owner, int64_t* d_out_offsets, int64_t piece_cap, uint8_t* d_out_data,
+                  int64_t out_cap, int64_t* d_totals, int64_t* totals, void* stream);
+int mrx_lines_known_dev(uint32_t flags, uint8_t sep, const uint8_t* d_data, const int64_t* d_offsets, int64_t n,
+                        int64_t end_offset, int64_t max_text_len, int64_t* d_line_prefix, int64_t* d_owner,
+                        int64_t* d_out_offsets, int64_t piece_cap, uint8_t* d_out_data, int64_t out_cap, int64_t* d_totals,
+                        int64_t* totals, void* stream);
+int mrx_lines_strided_dev(uint32_t flags, uint8_t sep, const uint8_t* d_data, int64_t stride, const int32_t* d_lens,
+                          int32_t len, int64_t n, int64_t* d_line_prefix, int64_t* d_owner, int64_t* d_out_offsets,
+                          int64_t piece_cap, uint8_t* d_out_data, int64_t out_cap, int64_t* d_totals, int64_t* totals,
+                          void* stream);
+
 /* ---- host-buffer convenience wrappers (copy in, run, copy out) -------------- */
+/* mrx_lines_dev on host buffers: line_prefix int64[n + 1], owner int64[piece_cap], out_offsets int64[piece_cap + 1],
+ * out_data uint8[out_cap], totals int64[4] (may be NULL).  line_prefix is always copied out, owner[0, lines) and
+ * out_offsets[0, lines] when the lines fit, out_data only when the bytes fit too (MRX_E_CAPACITY otherwise). */
+int mrx_lines_batch(uint32_t flags, uint8_t sep, const uint8_t* data, const int64_t* offsets, int64_t n,
+                    int64_t* line_prefix, int64_t* owner, int64_t* out_offsets, int64_t piece_cap, uint8_t* out_data,
+                    int64_t out_cap, int64_t* totals);
 /* mrx_kw_findall_dev on host buffers: text_prefix is always copied out, entries and spans only when all hits fit */
 int mrx_kw_findall_batch(const mrx_kw* k, const uint8_t* data, const int64_t* offsets, int64_t n, int64_t* text_prefix,
                          int32_t* entries, int32_t* spans, int64_t span_cap, int64_t* total);

@@ -198,6 +198,20 @@ void mrx_debug_kw_tier(int on);
 int mrx_debug_kw_host_findall(const uint8_t* entry_data, const int64_t* entry_offsets, int64_t m, uint32_t flags,
                               const uint8_t* data, const int64_t* offsets, int64_t n, int64_t* text_prefix, int32_t* entries,
                               int32_t* spans, int64_t span_cap, int64_t* total, char* describe, size_t describe_cap);
+/* Lines (include/mrx.h): bytes > 0 pins the piece size P of every later call (rounded up to a multiple of 1024, a
+ * wavefront's round), 0 restores the default, a negative value changes nothing.  Returns the P in force: tests place
+ * their separators by it.  The pass reports itself as "k_lines_emit" through mrx_last_kernel_name().  Results are the
+ * same. */
+int64_t mrx_debug_lines_piece(int64_t bytes);
+/* How often mrx_lines_* has synchronised with the device on this process so far: the CSR form's read-back of its two
+ * offsets and every read-back of the totals. */
+int64_t mrx_debug_lines_syncs(void);
+/* Lines on the CPU, for tests without a GPU: the block walk of the kernels over the same pieces (the pinned size, else
+ * the default), one after the other, on the texts data[offsets[i], offsets[i + 1]).  Arguments, outputs, capacity rules
+ * and return codes as mrx_lines_batch. */
+int mrx_debug_lines_host(uint32_t flags, uint8_t sep, const uint8_t* data, const int64_t* offsets, int64_t n,
+                         int64_t* line_prefix, int64_t* owner, int64_t* out_offsets, int64_t piece_cap, uint8_t* out_data,
+                         int64_t out_cap, int64_t* totals);
 /* Bytes of device memory the calling thread's scratch arenas hold (see mrx_release_scratch). */
 size_t mrx_debug_scratch_bytes(void);
 /* ... and how many of them are handed out and not yet rewound.  Scratch belongs to the call's scope, so between calls

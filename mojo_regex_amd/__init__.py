@@ -39,6 +39,8 @@ argument meaning, a *batch* of texts instead of one text:
                                                   text and number columns as packed records, the report's bytes
     (none: one alternation of literals per call)  Keywords / build_keywords / keywords_filter: which of
                                                   thousands of literals occur inside each text, one pass
+    (none: text.split("\\n") on the host)         lines_of / DeviceBatch.from_lines / lines / lines_async: a
+                                                  buffer's bytes as the packed batch of its lines
 
 All matching runs in the HIP kernels of libmrx_hip.so.  There is no CPU
 fallback: if the library is missing or no GPU is usable, calls raise.
@@ -70,6 +72,7 @@ from .api import (  # noqa: F401
     format_records_async,
     keywords_filter,
     library_path,
+    lines_of,
     load_library,
     lookup,
     match_first,

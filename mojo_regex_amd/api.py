@@ -329,6 +329,18 @@ def load_library():
         "mrx_debug_kw_tier": (None, [C.c_int]),
         "mrx_debug_kw_host_findall": (C.c_int, [u8p, i64p, C.c_int64, C.c_uint32, u8p, i64p, C.c_int64, i64p, i32p, i32p,
                                                 C.c_int64, C.POINTER(C.c_int64), C.c_char_p, C.c_size_t]),
+        "mrx_lines_dev": (C.c_int, [C.c_uint32, C.c_uint8, u8p, i64p, C.c_int64, i64p, i64p, i64p, C.c_int64, u8p, C.c_int64,
+                                    i64p, C.c_void_p, C.c_void_p]),
+        "mrx_lines_known_dev": (C.c_int, [C.c_uint32, C.c_uint8, u8p, i64p, C.c_int64, C.c_int64, C.c_int64, i64p, i64p, i64p,
+                                          C.c_int64, u8p, C.c_int64, i64p, C.c_void_p, C.c_void_p]),
+        "mrx_lines_strided_dev": (C.c_int, [C.c_uint32, C.c_uint8, u8p, C.c_int64, i32p, C.c_int32, C.c_int64, i64p, i64p,
+                                            i64p, C.c_int64, u8p, C.c_int64, i64p, C.c_void_p, C.c_void_p]),
+        "mrx_lines_batch": (C.c_int, [C.c_uint32, C.c_uint8, u8p, i64p, C.c_int64, i64p, i64p, i64p, C.c_int64, u8p,
+                                      C.c_int64, C.c_void_p]),
+        "mrx_debug_lines_piece": (C.c_int64, [C.c_int64]),
+        "mrx_debug_lines_syncs": (C.c_int64, []),
+        "mrx_debug_lines_host": (C.c_int, [C.c_uint32, C.c_uint8, u8p, i64p, C.c_int64, i64p, i64p, i64p, C.c_int64, u8p,
+                                           C.c_int64, C.c_void_p]),
         "mrx_debug_set_route": (None, [C.c_int]),
         "mrx_testing_set_run": (C.c_int, [H, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_int32)]),
     }
@@ -374,6 +386,7 @@ EXPORTED_SYMBOLS = [
     "mrx_kw_contains_dev", "mrx_kw_contains_strided_dev", "mrx_kw_count_dev", "mrx_kw_count_strided_dev",
     "mrx_kw_findall_dev", "mrx_kw_findall_known_dev", "mrx_kw_findall_strided_dev", "mrx_kw_filter_dev",
     "mrx_kw_filter_known_dev", "mrx_kw_filter_strided_dev", "mrx_kw_findall_batch",
+    "mrx_lines_dev", "mrx_lines_known_dev", "mrx_lines_strided_dev", "mrx_lines_batch",
 ]
 TESTING_SYMBOLS = [
     "mrx_timing_reset", "mrx_timing_enable", "mrx_timing_scan_ms", "mrx_last_kernel_name",
@@ -387,6 +400,7 @@ TESTING_SYMBOLS = [
     "mrx_debug_decode_lean", "mrx_debug_last_decode_lean", "mrx_testing_decode_expand",
     "mrx_debug_format_grid", "mrx_testing_format_one",
     "mrx_debug_kw_piece", "mrx_debug_kw_tier", "mrx_debug_kw_host_findall",
+    "mrx_debug_lines_piece", "mrx_debug_lines_syncs", "mrx_debug_lines_host",
 ]
 # (hooks with a digit in their name, listed apart: the header scan of tests/test_host_tables.py reads [a-z_] names)
 TESTING_SYMBOLS_NUMBERED = ["mrx_debug_rec12", "mrx_testing_rec12_roundtrip"]
@@ -442,6 +456,8 @@ class DeviceBatch:
         # them ("neither may be too small"), so a stale or hand-set value would be an out-of-bounds write, not an error
         self._end_offset: Optional[int] = None
         self._max_len: Optional[int] = None
+        # from_lines only: the byte count of the source buffer's unterminated tail (include/mrx.h, "lines")
+        self.tail: Optional[int] = None
         if offsets is not None:
             if offsets.dtype != torch.int64 or not offsets.is_contiguous() or offsets.device != data.device:
                 raise MrxError("offsets must be a contiguous int64 tensor on the data's device")
@@ -559,6 +575,107 @@ class DeviceBatch:
         if self.offsets is not None:
             return self._max_len
         return self.stride if self.lens is not None else self.length
+
+    def lines(self, sep=b"\n", keepends: bool = False, crlf: bool = False, partial: bool = True,
+              piece_cap: Optional[int] = None, out_cap: Optional[int] = None):
+        """This batch's texts cut at the byte `sep` into a new packed batch (include/mrx.h, mrx_lines_dev): (lines
+        DeviceBatch, prefix int64[n + 1], owner int64[lines]), shaped as extract's result.  The lines of a text are
+        text.split(sep) with the last piece dropped when it is empty: every separator ends a line, an unterminated
+        tail is a line too, and no line crosses a text boundary.  keepends leaves every terminated line its separator;
+        crlf (sep b"\\n" only, not with keepends) also drops one b"\\r" directly in front of a dropped b"\\n";
+        partial=False leaves every text's unterminated tail out.  `lines.tail` is the byte count of the last text's
+        unterminated tail, whatever `partial` says.  Without piece_cap / out_cap the call grows them as extract does
+        (the default holds a line per 32 bytes; more lines cost one more pass).  `lines` is a CSR batch with known
+        bounds, both exact: its bytes and its longest line, so findall on it reads nothing back and routes by the real
+        line length.  A CSR input without known bounds pays one read-back of its first and last offset; one with them
+        and a strided one do not."""
+        return self._lines_call(_lines_flags(sep, keepends, crlf, partial), piece_cap, out_cap, True)
+
+    def _lines_call(self, flags_sep, piece_cap: Optional[int], out_cap: Optional[int], move: bool):
+        """lines() with extract's grow-and-retry over the four totals of mrx_lines_*: first the lines, then the bytes,
+        each unless it is the caller's own.  move=False (from_lines with keepends: one text, whose lines with their
+        separators are its own bytes) asks for the offsets alone with an output capacity of 0, takes the capacity code
+        that the missing bytes give for success, and returns the input's data under the new offsets."""
+        import torch
+        dev, nbytes = self.data.device, int(self.data.numel())
+        prefix = torch.empty(self.n + 1, dtype=torch.int64, device=dev)
+        d_totals = torch.empty(4, dtype=torch.int64, device=dev)
+        totals = (C.c_int64 * 4)()
+        lib = load_library()
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        pcap = nbytes // 32 + self.n + 64 if piece_cap is None else int(piece_cap)
+        ocap = 0 if not move else nbytes if out_cap is None else int(out_cap)
+        pb = out = None
+        while True:
+            if pb is None:
+                pb = (torch.empty(max(pcap, 1), dtype=torch.int64, device=dev), torch.empty(pcap + 1, dtype=torch.int64, device=dev))
+            if out is None and ocap > 0:
+                out = torch.empty(ocap, dtype=torch.uint8, device=dev)
+            rc = self.call(lib, "mrx_lines", flags_sep,
+                           (_ptr(prefix), _ptr(pb[0]), _ptr(pb[1]), pcap, _ptr(out), ocap, _ptr(d_totals),
+                            C.cast(totals, C.c_void_p), stream))
+            nlines, nb = int(totals[0]), int(totals[1])
+            if rc == MRX_E_CAPACITY and piece_cap is None and nlines > pcap:
+                pcap, pb = nlines, None
+                continue
+            if rc == MRX_E_CAPACITY and nlines <= pcap and nb > ocap:
+                if not move:
+                    break
+                if out_cap is None:
+                    ocap, out = nb, None
+                    continue
+            _check(rc)
+            break
+        trim_p = (lambda t, m: t[:m].clone()) if 4 * nlines < pcap else (lambda t, m: t[:m])
+        trim_b = (lambda t, m: t[:m].clone()) if 4 * nb < ocap else (lambda t, m: t[:m])
+        if not move:
+            data = self.data
+        else:
+            data = trim_b(out, nb) if out is not None else torch.empty(0, dtype=torch.uint8, device=dev)
+        res = DeviceBatch(data, trim_p(pb[1], nlines + 1))
+        res._end_offset, res._max_len, res.tail = nb, int(totals[2]), int(totals[3])
+        return res, prefix, trim_p(pb[0], nlines)
+
+    @classmethod
+    def from_lines(cls, data, sep=b"\n", keepends: bool = False, crlf: bool = False, partial: bool = True,
+                   piece_cap: Optional[int] = None, out_cap: Optional[int] = None):
+        """The lines of one buffer on the device (a file's bytes as a contiguous uint8 tensor) as a batch: lines() of
+        the batch whose one text is the buffer, with `.tail` set for reading in chunks -- with partial=False carry
+        data[len - tail:] in front of the next chunk.  Below 2^31 bytes the buffer is taken as a strided batch of one
+        text (nothing is uploaded and nothing read back before the kernels), at and above that as a CSR batch of two
+        offsets.  With keepends=True no byte moves: the result's `data` is the caller's tensor and only the offsets are
+        computed."""
+        import torch
+        if data.dtype != torch.uint8 or data.dim() != 1 or not data.is_contiguous():
+            raise MrxError("from_lines needs a contiguous one-dimensional uint8 tensor")
+        nbytes = int(data.numel())
+        if 0 < nbytes < (1 << 31):
+            src = cls.strided(data, nbytes, length=nbytes)
+        else:
+            src = cls(data, torch.tensor([0, nbytes], dtype=torch.int64, device=data.device))
+        return src._lines_call(_lines_flags(sep, keepends, crlf, partial), piece_cap, out_cap, not keepends)[0]
+
+    def lines_async(self, out, sep=b"\n", keepends: bool = False, crlf: bool = False, partial: bool = True):
+        """Enqueue lines() on the current stream without reading its result back.  out = (line_prefix int64[n + 1],
+        owner int64[piece_cap], out_offsets int64[piece_cap + 1], out_data uint8[out_cap], totals int64[4]) device
+        tensors of the caller; totals = {lines, bytes, longest line, tail} once the stream has drained.  No byte is
+        written when lines > piece_cap or bytes > out_cap (check totals against both).  A CSR batch without known
+        bounds still pays the read-back of its first and last offset before the first kernel."""
+        import torch
+        flags, sep_byte = _lines_flags(sep, keepends, crlf, partial)
+        prefix, owner, out_offsets, out_data, totals = out
+        if prefix.numel() < self.n + 1 or out_offsets.numel() < owner.numel() + 1 or totals.numel() < 4:
+            raise MrxError("out needs line_prefix int64[n + 1], owner int64[cap], out_offsets int64[cap + 1], "
+                           "out_data uint8[out_cap], totals int64[4]")
+        for t in (prefix, owner, out_offsets, totals):
+            if t.dtype != torch.int64 or not t.is_contiguous():
+                raise MrxError("line_prefix, owner, out_offsets and totals must be contiguous int64 tensors")
+        if out_data.dtype != torch.uint8 or not out_data.is_contiguous():
+            raise MrxError("out_data must be a contiguous uint8 tensor")
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        _check(self.call(load_library(), "mrx_lines", (flags, sep_byte),
+                         (_ptr(prefix), _ptr(owner), _ptr(out_offsets), int(owner.numel()), _ptr(out_data),
+                          int(out_data.numel()), _ptr(totals), None, stream)))
 
     def gather_spans(self, prefix, spans, pair: int = 0, piece_cap: Optional[int] = None, out_cap: Optional[int] = None):
         """The bytes under spans of this batch's texts as a new packed batch (include/mrx.h, mrx_gather_spans_dev):
@@ -935,6 +1052,16 @@ def _piece_lists(pieces: "DeviceBatch", prefix) -> List[List[bytes]]:
 
 
 MRX_FILTER_INVERT, MRX_FILTER_ALL = 1, 2
+MRX_LINES_KEEPENDS, MRX_LINES_CRLF, MRX_LINES_DROP_PARTIAL = 1, 2, 4
+
+
+def _lines_flags(sep, keepends: bool, crlf: bool, partial: bool) -> Tuple[int, int]:
+    """(flags, separator byte) of mrx_lines_*; which combinations are refused is the C side's to say."""
+    sep = _b(sep)
+    if len(sep) != 1:
+        raise MrxError("sep must be a single byte: compile_regex(sep).split_batch cuts at longer separators")
+    return ((MRX_LINES_KEEPENDS if keepends else 0) | (MRX_LINES_CRLF if crlf else 0) |
+            (0 if partial else MRX_LINES_DROP_PARTIAL)), sep[0]
 
 
 def _filter_flags(mode: str = "any", invert: bool = False) -> int:
@@ -1983,6 +2110,16 @@ def distinct(texts, sort: Optional[str] = None, top: Optional[int] = None):
     raw = out[:int(totals[1])].tobytes()
     return ([raw[out_off[g]:out_off[g + 1]] for g in range(u)], counts[:u].copy(), group_of[:n].copy(),
             first[:u].copy())
+
+
+def lines_of(texts, sep=b"\n", keepends: bool = False, crlf: bool = False, partial: bool = True):
+    """The lines of host texts (DeviceBatch.lines): a list of texts gives List[List[bytes]], one bytes object its
+    List[bytes]."""
+    single = isinstance(texts, (bytes, bytearray, memoryview, str))
+    batch = DeviceBatch.from_texts([_b(texts)] if single else [_b(t) for t in texts])
+    pieces, prefix, _ = batch.lines(sep, keepends, crlf, partial)
+    out = _piece_lists(pieces, prefix)
+    return out[0] if single else out
 
 
 def build_dictionary(entries) -> Dictionary:

@@ -23,21 +23,22 @@
 namespace mrx {
 // ---- the packed-output tail of the byte movers (PackedDest, mrx_internal.hpp) --------------------------------------
 // The n == 0 result: an output CSR of no row and {0, 0} on both sides.  (The kernel's name is the caller's to report.)
-inline int packed_empty(const PackedDest& d) {
+// ntotals: the entries of the totals, {rows, bytes} first (lines has four).
+inline int packed_empty(const PackedDest& d, int ntotals = 2) {
   hipStream_t hs = (hipStream_t)d.stream;
   MRX_HIP_TRY(hipMemsetAsync(d.d_out_offsets, 0, sizeof(int64_t), hs));
-  MRX_HIP_TRY(hipMemsetAsync(d.d_totals, 0, 2 * sizeof(int64_t), hs));
-  if (d.totals) d.totals[0] = d.totals[1] = 0;
+  MRX_HIP_TRY(hipMemsetAsync(d.d_totals, 0, ntotals * sizeof(int64_t), hs));
+  if (d.totals) std::fill(d.totals, d.totals + ntotals, (int64_t)0);
   return MRX_OK;
 }
 // Behind the gather.  Without a host `totals` the call has only enqueued; with one, d_totals = {rows, bytes} is read
 // back once and turned into the verdict.  piece_cap: the capacity in rows of an operation that has one (extract,
 // expand), else < 0.  failed: the message of an operation whose kernels report a failure of their own as rows < 0 (take,
-// distinct), else nullptr.
-inline int packed_verdict(const PackedDest& d, int64_t piece_cap = -1, const char* failed = nullptr) {
+// distinct), else nullptr.  ntotals: the entries of the totals that are read back (lines: four).
+inline int packed_verdict(const PackedDest& d, int64_t piece_cap = -1, const char* failed = nullptr, int ntotals = 2) {
   if (!d.totals) return MRX_OK;
   hipStream_t hs = (hipStream_t)d.stream;
-  MRX_HIP_TRY(hipMemcpyAsync(d.totals, d.d_totals, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, hs));
+  MRX_HIP_TRY(hipMemcpyAsync(d.totals, d.d_totals, ntotals * sizeof(int64_t), hipMemcpyDeviceToHost, hs));
   MRX_HIP_TRY(hipStreamSynchronize(hs));
   if (failed && d.totals[0] < 0) return internal_fail(MRX_E_ARGUMENT, failed);
   if (piece_cap >= 0 && d.totals[0] > piece_cap)
