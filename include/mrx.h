@@ -1030,7 +1030,67 @@ int mrx_lines_strided_dev(uint32_t flags, uint8_t sep, const uint8_t* d_data, in
                           int64_t piece_cap, uint8_t* d_out_data, int64_t out_cap, int64_t* d_totals, int64_t* totals,
                           void* stream);
 
+/* ---- fields: the columns of every text as span rows on the device ----
+ * What cut -d, -f2,5, awk '{print $1, $NF}' and line.split()[3] do first: for every text of a batch, the byte ranges of
+ * f requested columns, one fixed-width row per text.  No pattern and no automaton.  Two modes define a text's parts:
+ *   delimiter mode   (delim one byte d) parts = t.split(d): every delimiter separates and empty fields exist; the
+ *                    field count is nf = count(d) + 1.  The empty text has one empty field, (0, 0): awk says NF = 0
+ *                    there, this call follows Python.
+ *   whitespace mode  (MRX_FIELDS_WHITESPACE, delim ignored) parts = t.split() of Python bytes: whitespace is exactly the
+ *                    six bytes 0x09 .. 0x0D and 0x20; runs separate, leading and trailing runs make no field, and a
+ *                    text without any other byte has nf = 0.
+ * columns (host, int32[f], 1 <= f <= MRX_FIELDS_MAX_COLUMNS) may repeat and stand in any order: c > 0 names
+ * parts[c - 1], as cut and awk count; c < 0 names parts[nf + c], so -1 is $NF; 0 is refused.
+ *   MRX_FIELDS_REST  every column must be positive.  With cmax the largest column the parts are t.split(d, cmax - 1)
+ *                    (or t.split(None, cmax - 1)): column cmax, if it exists, runs to the end of the text -- a log line's
+ *                    message -- and nf is min(nf, cmax).
+ * Pair j of text i's row is (start, end) of that part, relative to the text's first byte; a part that does not exist
+ * gives (-1, -1), which mrx_gather_spans_* turns into an empty piece, mrx_parse_spans_* into MRX_NUM_EMPTY, and which
+ * contributes nothing to mrx_expand_spans_*.  (mrx_expand_spans_* takes a row's last pair for the whole match, which no
+ * reference names: \j is pair j - 1 for j < row_pairs.  A caller that expands all of its columns asks for one more.)
+ *   text          call                               row                                      nf
+ *   b""           ",", {1, -1}                       (0,0) (0,0)                              1
+ *   b""           whitespace, {1, -1}                (-1,-1) (-1,-1)                          0
+ *   b" a  b c "   whitespace, {1, 2, 3, -1}          (1,2) (4,5) (6,7) (6,7)                  3
+ *   b" a  b c "   whitespace, rest, {2}              (4,8)                                    2
+ *   b"a,b,,c"     ",", {3, 4, 5, -4, -5}             (4,4) (5,6) (-1,-1) (0,1) (-1,-1)        4
+ *   b"a,b,,c"     ",", rest, {2}                     (2,6)                                    2
+ * Outputs, all on the device:
+ *   d_rows int32[n][f][2]   8-byte aligned: a captures_all row block with one row per text (row_pairs = f)
+ *   d_nf int32[n]           (may be NULL) the field counts
+ *   d_prefix int64[n + 1]   (may be NULL) the values 0 .. n: the identity CSR of the rows over the texts that
+ *                           mrx_gather_spans_*, mrx_parse_spans_* and mrx_expand_spans_* ask for
+ * No totals, no capacity and no scratch, and no synchronisation on any form: the call enqueues and returns.  n == 0
+ * enqueues nothing (and writes nothing, d_prefix[0] included).  Spans are int32 (texts of up to 2 GiB - 1).  Bytes outside
+ * a text never make or change a field.
+ * Reads: as filter, the aligned 16-byte words that hold a text's bytes, so up to 15 bytes in front of a text's first
+ * byte and behind its last one are read (never used: they are masked before a byte is compared); no word is read for an
+ * empty text.  Under MRX_FIELDS_REST, and when d_nf is NULL and no column is negative, a text is read only up to the end
+ * of its largest column; the results do not differ.  Negative columns read a text twice.
+ * The _known form takes a CSR batch's d_offsets[n] and longest text as mrx_filter_known_dev does; here they only choose
+ * the route (the lanes that share a text, from the mean length end_offset / n; the strided form takes the pitch or the
+ * common length).  They size nothing, so a wrong bound costs time, never memory.
+ * One kernel, a group of 1 to 64 lanes per text.  Fields are a per-line operation: a text longer than the group's
+ * 16 bytes per lane takes more rounds of the same group, so one text of many MiB is answered correctly and slowly.
+ * The result is the same bit for bit on every run: no atomics, and no wavefront waits for another.
+ * MRX_E_ARGUMENT, before anything is enqueued: an unknown flag; f < 1 or f > MRX_FIELDS_MAX_COLUMNS; a column 0;
+ * MRX_FIELDS_REST with a negative column; negative n, end_offset or max_text_len; a bad pitch; a null d_rows, d_offsets
+ * or columns; a d_rows that is not 8-byte aligned. */
+enum { MRX_FIELDS_WHITESPACE = 1, MRX_FIELDS_REST = 2 };
+#define MRX_FIELDS_MAX_COLUMNS 32
+int mrx_fields_dev(uint32_t flags, uint8_t delim, const int32_t* columns, int32_t f, const uint8_t* d_data,
+                   const int64_t* d_offsets, int64_t n, int32_t* d_rows, int32_t* d_nf, int64_t* d_prefix, void* stream);
+int mrx_fields_known_dev(uint32_t flags, uint8_t delim, const int32_t* columns, int32_t f, const uint8_t* d_data,
+                         const int64_t* d_offsets, int64_t n, int64_t end_offset, int64_t max_text_len, int32_t* d_rows,
+                         int32_t* d_nf, int64_t* d_prefix, void* stream);
+int mrx_fields_strided_dev(uint32_t flags, uint8_t delim, const int32_t* columns, int32_t f, const uint8_t* d_data,
+                           int64_t stride, const int32_t* d_lens, int32_t len, int64_t n, int32_t* d_rows, int32_t* d_nf,
+                           int64_t* d_prefix, void* stream);
+
 /* ---- host-buffer convenience wrappers (copy in, run, copy out) -------------- */
+/* mrx_fields_dev on host buffers: rows int32[n][f][2], nf int32[n] (may be NULL), prefix int64[n + 1] (may be NULL). */
+int mrx_fields_batch(uint32_t flags, uint8_t delim, const int32_t* columns, int32_t f, const uint8_t* data,
+                     const int64_t* offsets, int64_t n, int32_t* rows, int32_t* nf, int64_t* prefix);
 /* mrx_lines_dev on host buffers: line_prefix int64[n + 1], owner int64[piece_cap], out_offsets int64[piece_cap + 1],
  * out_data uint8[out_cap], totals int64[4] (may be NULL).  line_prefix is always copied out, owner[0, lines) and
  * out_offsets[0, lines] when the lines fit, out_data only when the bytes fit too (MRX_E_CAPACITY otherwise). */

@@ -212,6 +212,19 @@ int64_t mrx_debug_lines_syncs(void);
 int mrx_debug_lines_host(uint32_t flags, uint8_t sep, const uint8_t* data, const int64_t* offsets, int64_t n,
                          int64_t* line_prefix, int64_t* owner, int64_t* out_offsets, int64_t piece_cap, uint8_t* out_data,
                          int64_t out_cap, int64_t* totals);
+/* Fields (include/mrx.h): `lanes`, a power of two from 1 to 64, pins G, the lanes that share a text, for every later
+ * call; 0 restores the rule (the mean text length where the call knows it); any other value changes nothing.  Returns
+ * the pin in force (0 = the rule).  The kernel reports itself as "k_fields" through mrx_last_kernel_name().  Results are
+ * the same. */
+int mrx_debug_fields_group(int lanes);
+/* Fields: `workgroups` > 0 caps the grid, so that a test makes one wavefront run many rounds of texts without millions
+ * of them, as mrx_debug_parse_grid does.  0 (default) = no cap of its own.  Results are the same. */
+void mrx_debug_fields_grid(int workgroups);
+/* Fields on the CPU, for tests without a GPU: the walk of the kernel over the same groups and rounds (the pinned G, else
+ * the rule from the mean length), one text after the other, on the texts data[offsets[i], offsets[i + 1]).  Arguments,
+ * outputs and return codes as mrx_fields_batch. */
+int mrx_debug_fields_host(uint32_t flags, uint8_t delim, const int32_t* columns, int32_t f, const uint8_t* data,
+                          const int64_t* offsets, int64_t n, int32_t* rows, int32_t* nf, int64_t* prefix);
 /* Bytes of device memory the calling thread's scratch arenas hold (see mrx_release_scratch). */
 size_t mrx_debug_scratch_bytes(void);
 /* ... and how many of them are handed out and not yet rewound.  Scratch belongs to the call's scope, so between calls

@@ -41,6 +41,8 @@ argument meaning, a *batch* of texts instead of one text:
                                                   thousands of literals occur inside each text, one pass
     (none: text.split("\\n") on the host)         lines_of / DeviceBatch.from_lines / lines / lines_async: a
                                                   buffer's bytes as the packed batch of its lines
+    (none: text.split()[k] on the host)           fields_of / DeviceBatch.fields / fields_async / cut: the
+                                                  columns of every text as span rows, no pattern involved
 
 All matching runs in the HIP kernels of libmrx_hip.so.  There is no CPU
 fallback: if the library is missing or no GPU is usable, calls raise.
@@ -64,6 +66,7 @@ from .api import (  # noqa: F401
     compile_set,
     distinct,
     expand,
+    fields_of,
     filter_texts,
     findall,
     findall_texts,

@@ -341,6 +341,17 @@ def load_library():
         "mrx_debug_lines_syncs": (C.c_int64, []),
         "mrx_debug_lines_host": (C.c_int, [C.c_uint32, C.c_uint8, u8p, i64p, C.c_int64, i64p, i64p, i64p, C.c_int64, u8p,
                                            C.c_int64, C.c_void_p]),
+        "mrx_fields_dev": (C.c_int, [C.c_uint32, C.c_uint8, i32p, C.c_int32, u8p, i64p, C.c_int64, i32p, i32p, i64p,
+                                     C.c_void_p]),
+        "mrx_fields_known_dev": (C.c_int, [C.c_uint32, C.c_uint8, i32p, C.c_int32, u8p, i64p, C.c_int64, C.c_int64,
+                                           C.c_int64, i32p, i32p, i64p, C.c_void_p]),
+        "mrx_fields_strided_dev": (C.c_int, [C.c_uint32, C.c_uint8, i32p, C.c_int32, u8p, C.c_int64, i32p, C.c_int32,
+                                             C.c_int64, i32p, i32p, i64p, C.c_void_p]),
+        "mrx_fields_batch": (C.c_int, [C.c_uint32, C.c_uint8, i32p, C.c_int32, u8p, i64p, C.c_int64, i32p, i32p, i64p]),
+        "mrx_debug_fields_group": (C.c_int, [C.c_int]),
+        "mrx_debug_fields_grid": (None, [C.c_int]),
+        "mrx_debug_fields_host": (C.c_int, [C.c_uint32, C.c_uint8, i32p, C.c_int32, u8p, i64p, C.c_int64, i32p, i32p,
+                                            i64p]),
         "mrx_debug_set_route": (None, [C.c_int]),
         "mrx_testing_set_run": (C.c_int, [H, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_int32)]),
     }
@@ -387,6 +398,7 @@ EXPORTED_SYMBOLS = [
     "mrx_kw_findall_dev", "mrx_kw_findall_known_dev", "mrx_kw_findall_strided_dev", "mrx_kw_filter_dev",
     "mrx_kw_filter_known_dev", "mrx_kw_filter_strided_dev", "mrx_kw_findall_batch",
     "mrx_lines_dev", "mrx_lines_known_dev", "mrx_lines_strided_dev", "mrx_lines_batch",
+    "mrx_fields_dev", "mrx_fields_known_dev", "mrx_fields_strided_dev", "mrx_fields_batch",
 ]
 TESTING_SYMBOLS = [
     "mrx_timing_reset", "mrx_timing_enable", "mrx_timing_scan_ms", "mrx_last_kernel_name",
@@ -401,6 +413,7 @@ TESTING_SYMBOLS = [
     "mrx_debug_format_grid", "mrx_testing_format_one",
     "mrx_debug_kw_piece", "mrx_debug_kw_tier", "mrx_debug_kw_host_findall",
     "mrx_debug_lines_piece", "mrx_debug_lines_syncs", "mrx_debug_lines_host",
+    "mrx_debug_fields_group", "mrx_debug_fields_grid", "mrx_debug_fields_host",
 ]
 # (hooks with a digit in their name, listed apart: the header scan of tests/test_host_tables.py reads [a-z_] names)
 TESTING_SYMBOLS_NUMBERED = ["mrx_debug_rec12", "mrx_testing_rec12_roundtrip"]
@@ -676,6 +689,57 @@ class DeviceBatch:
         _check(self.call(load_library(), "mrx_lines", (flags, sep_byte),
                          (_ptr(prefix), _ptr(owner), _ptr(out_offsets), int(owner.numel()), _ptr(out_data),
                           int(out_data.numel()), _ptr(totals), None, stream)))
+
+    def fields(self, columns, delim=None, rest: bool = False, counts: bool = True):
+        """The columns of every text as span rows (include/mrx.h, mrx_fields_dev): (prefix int64[n + 1], rows
+        int32[n, f, 2], nf int32[n]), device tensors.  delim=None is whitespace mode, bytes.split() of every text; delim
+        one byte is t.split(delim).  columns count from 1 as cut and awk do, or from -1 at the end ($NF); rest=True
+        makes the largest column run to the end of the text.  rows[i, j] is (start, end) of column columns[j] in text i,
+        (-1, -1) where the text has no such part; nf[i] is the field count (None with counts=False, which lets the
+        kernel stop reading a text behind its largest column).  prefix is the identity CSR 0 .. n: prefix and rows go
+        to gather_spans(pair=j), parse_spans(pair=j) and expand_spans as they stand.  A batch with known bounds passes
+        them on.  The call enqueues on the current stream and reads nothing back."""
+        import torch
+        dev, f = self.data.device, len(columns)
+        rows = torch.empty((self.n, f, 2), dtype=torch.int32, device=dev)
+        nf = torch.empty(self.n, dtype=torch.int32, device=dev) if counts else None
+        # n == 0 enqueues nothing: the one entry of the prefix is the host's to write
+        prefix = torch.empty(self.n + 1, dtype=torch.int64, device=dev) if self.n else torch.zeros(1, dtype=torch.int64, device=dev)
+        self.fields_async((prefix, rows, nf), columns, delim, rest)
+        return prefix, rows, nf
+
+    def fields_async(self, out, columns, delim=None, rest: bool = False):
+        """fields() on the caller's tensors out = (prefix int64[n + 1] or None, rows int32[n, f, 2], nf int32[n] or
+        None): enqueues on the current stream and returns.  Nothing is written for a batch without texts."""
+        import torch
+        flags, delim_byte, cols = _fields_args(columns, delim, rest)
+        prefix, rows, nf = out
+        if rows is None or rows.dtype != torch.int32 or not rows.is_contiguous() or rows.numel() < self.n * len(cols) * 2:
+            raise MrxError("rows must be a contiguous int32[n, f, 2] tensor")
+        if nf is not None and (nf.dtype != torch.int32 or not nf.is_contiguous() or nf.numel() < self.n):
+            raise MrxError("nf must be a contiguous int32[n] tensor")
+        if prefix is not None and (prefix.dtype != torch.int64 or not prefix.is_contiguous() or prefix.numel() < self.n + 1):
+            raise MrxError("prefix must be a contiguous int64[n + 1] tensor")
+        if self.n == 0:   # nothing is enqueued, but the columns are still the C side's to refuse (no rows: no address)
+            rows = torch.empty(2, dtype=torch.int32, device=self.data.device)
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        _check(self.call(load_library(), "mrx_fields", (flags, delim_byte, cols.ctypes.data, len(cols)),
+                         (_ptr(rows), _ptr(nf), _ptr(prefix), stream)))
+
+    def cut(self, columns, delim=None, out_delim=None, end=b"\n"):
+        """cut -d<delim> -f<columns>, or awk '{print $a, $b}' with delim=None: one record per text, the named columns
+        joined by out_delim (default: delim, or one space in whitespace mode) and closed by `end`, as a new packed
+        batch: (records DeviceBatch, owner int64[n]).  This is fields() followed by expand_spans() with the template
+        \\1<out_delim>\\2...<end>, so a column that a text does not have contributes nothing, and at most 9 columns
+        can be named: expand's templates know \\1 .. \\9 only."""
+        if len(columns) > 9:
+            raise MrxError("cut takes at most 9 columns: it runs expand_spans, whose templates know \\1 .. \\9 only "
+                           "(fields() itself takes %d)" % MRX_FIELDS_MAX_COLUMNS)
+        sep = _b(out_delim) if out_delim is not None else (_b(delim) if delim is not None else b" ")
+        template = sep.join(b"\\" + str(j + 1).encode() for j in range(len(columns))) + _b(end)
+        # expand takes a row's last pair for the whole match, which no reference names: one more pair stands there
+        prefix, rows, _ = self.fields(list(columns) + [1], delim, counts=False)
+        return self.expand_spans(template, prefix, rows)
 
     def gather_spans(self, prefix, spans, pair: int = 0, piece_cap: Optional[int] = None, out_cap: Optional[int] = None):
         """The bytes under spans of this batch's texts as a new packed batch (include/mrx.h, mrx_gather_spans_dev):
@@ -1062,6 +1126,27 @@ def _lines_flags(sep, keepends: bool, crlf: bool, partial: bool) -> Tuple[int, i
         raise MrxError("sep must be a single byte: compile_regex(sep).split_batch cuts at longer separators")
     return ((MRX_LINES_KEEPENDS if keepends else 0) | (MRX_LINES_CRLF if crlf else 0) |
             (0 if partial else MRX_LINES_DROP_PARTIAL)), sep[0]
+
+
+MRX_FIELDS_WHITESPACE, MRX_FIELDS_REST = 1, 2
+MRX_FIELDS_MAX_COLUMNS = 32
+
+
+def _fields_args(columns, delim, rest: bool):
+    """(flags, delimiter byte, columns as int32 array) of mrx_fields_*; which columns are refused is the C side's to say."""
+    flags = MRX_FIELDS_REST if rest else 0
+    if delim is None:
+        flags, delim_byte = flags | MRX_FIELDS_WHITESPACE, 0
+    else:
+        delim = _b(delim)
+        if len(delim) != 1:
+            raise MrxError("delim must be a single byte (or None for whitespace): compile_regex(delim).split_dev cuts "
+                           "at longer delimiters")
+        delim_byte = delim[0]
+    cols = [int(c) for c in columns]
+    if any(not -(1 << 31) <= c < (1 << 31) for c in cols):
+        raise MrxError("a column must fit an int32")
+    return flags, delim_byte, np.array(cols, dtype=np.int32)
 
 
 def _filter_flags(mode: str = "any", invert: bool = False) -> int:
@@ -2120,6 +2205,18 @@ def lines_of(texts, sep=b"\n", keepends: bool = False, crlf: bool = False, parti
     pieces, prefix, _ = batch.lines(sep, keepends, crlf, partial)
     out = _piece_lists(pieces, prefix)
     return out[0] if single else out
+
+
+def fields_of(texts, columns, delim=None, rest: bool = False):
+    """The columns of host texts (DeviceBatch.fields): List[List[Optional[bytes]]], one list per text with the bytes of
+    every requested column, None for a part that the text does not have."""
+    bs = [_b(t) for t in texts]
+    _fields_args(columns, delim, rest)
+    if not bs:
+        return []
+    _, rows, _ = DeviceBatch.from_texts(bs).fields(columns, delim, rest, counts=False)
+    rows = rows.cpu().numpy()
+    return [[None if s < 0 else t[s:e] for s, e in rows[i].tolist()] for i, t in enumerate(bs)]
 
 
 def build_dictionary(entries) -> Dictionary:
