@@ -1087,7 +1087,111 @@ int mrx_fields_strided_dev(uint32_t flags, uint8_t delim, const int32_t* columns
                            int64_t stride, const int32_t* d_lens, int32_t len, int64_t n, int32_t* d_rows, int32_t* d_nf,
                            int64_t* d_prefix, void* stream);
 
+/* ---- translate: bytes.translate and tr -s for every text, as a new batch on the device ----
+ * The step that normalises bytes: tr A-Z a-z, tr -d '\r"', tr '\t' ' ', tr -s ' ', sed y/../../.  No pattern and no
+ * automaton.  For every text t of the batch:
+ *   1. u = t.translate(table, delete): the bytes of the delete set are dropped, the others go through `table`
+ *   2. with a squeeze set, byte k > 0 of u is dropped when u[k] is in the set and u[k] == u[k - 1] (tr -s on the mapped
+ *      bytes).  A run never reaches across a text boundary, and a text's first byte is always kept.
+ * table (host, uint8[256]) may be NULL, the identity.  delete_set and squeeze_set (host, 32-byte bitmaps: byte c is a
+ * member when bit c & 7 of byte c >> 3 is set) may be NULL, empty.  Both with a member in one call is refused: the byte
+ * in front of a squeezed one would be the last SURVIVING byte, any distance back; two calls do it.  All three empty is
+ * a copy.
+ *   text            call                                       result
+ *   b"GET /A b"     table = bytes.lower's                      b"get /a b"
+ *   b"a\r\n"        delete {\r}                                b"a\n"
+ *   b"a  b   c"     squeeze {' '}                              b"a b c"
+ *   b"a\t b"        table \t -> ' ', squeeze {' '}             b"a b"         (the run exists only behind the map)
+ *   b"aab"          squeeze {' '}                              b"aab"         (a run of a byte outside the set stays)
+ * Same-length form (delete and squeeze empty): the output has the input's layout, so no offsets are written:
+ *   CSR          byte p of d_data, d_offsets[0] <= p < d_offsets[n], goes to byte p of d_out_data: the result is the batch
+ *                (d_out_data, d_offsets).  out_cap must be at least d_offsets[n].
+ *   fixed pitch  the rows' region, bytes [0, (n - 1) * stride + (d_lens ? stride : len)) of both buffers: the result is
+ *                the batch (d_out_data, stride, d_lens, len).  Both buffers hold that region; out_cap must be at least
+ *                its size.
+ * The texts of a CSR batch are contiguous, so the region is exactly the texts; the bytes of a fixed-pitch region outside
+ * the texts (row padding) are unspecified in the output.  Nothing outside the region is written.  d_out_offsets,
+ * d_totals and totals may be NULL and are not touched; known bounds of the input are those of the output.  One kernel,
+ * a lane per aligned 16-byte block of the output region, no scratch, nothing scanned.  MRX_E_CAPACITY, before anything is
+ * enqueued, when the region does not fit out_cap; mrx_translate_known_dev tells from end_offset, which must then be at
+ * least d_offsets[n] (the kernel compares d_offsets[n] itself and writes nothing when it does not fit).
+ * Packed form (a delete or a squeeze set): the output is a packed CSR batch:
+ *   d_out_offsets int64[n + 1]   the CSR of the output; d_out_offsets[n] = bytes
+ *   d_out_data uint8[out_cap]    the texts back to back; any alignment
+ *   d_totals int64[2]            {bytes, longest text}, both exact: the known bounds of the output
+ * The input's byte count is always capacity enough.  bytes > out_cap: d_out_offsets and d_totals are complete and exact
+ * and NO output byte is written; a call with `totals` returns MRX_E_CAPACITY.  totals (host, int64[2], may be NULL)
+ * receives d_totals: the call then reads back once, at its end.  With totals == NULL the call only enqueues.  n == 0:
+ * totals {0, 0}, d_out_offsets = {0}.  No byte of d_out_data at or past bytes, nor at or past out_cap, is ever written.
+ * Input and output must not overlap, in either form.
+ * MRX_E_ARGUMENT, before anything is enqueued: delete and squeeze together; negative n, out_cap, end_offset or
+ * max_text_len; a bad pitch; a null required pointer (d_offsets; d_out_data when out_cap > 0; in the packed form
+ * d_out_offsets and d_totals).
+ * Sizes: every position is 64-bit; the CSR form serves a text of 2^31 bytes and more, the strided form keeps its int32
+ * length.  Empty texts are served wherever they stand.
+ * Reads: the aligned 16-byte words that hold a text's bytes (same-length form: the region's), so up to 15 bytes in front
+ * and behind are read and never used: they are masked before a byte is looked up.
+ * Scratch (packed form): 16 bytes per piece of the input (a text is cut into pieces of 4 KiB; an empty text has none),
+ * 16 per text of a CSR batch, and the scan's block sums; returned to the arena when the call returns.  mrx_translate_dev
+ * reads d_offsets[0] and d_offsets[n] back (one synchronisation, before its first kernel); the strided form and
+ * mrx_translate_known_dev (end_offset: d_offsets[n] - d_offsets[0] or an upper bound, max_text_len is not used) read
+ * nothing.  end_offset must not be too small, and d_offsets must not decrease anywhere.
+ * Lookup: one table of 256 entries (the mapped byte and the sets' flags) in LDS, filled once per workgroup.
+ * The result is the same bit for bit on every run: no atomics, and no wavefront waits for another. */
+int mrx_translate_dev(const uint8_t* table, const uint8_t* delete_set, const uint8_t* squeeze_set, const uint8_t* d_data,
+                      const int64_t* d_offsets, int64_t n, uint8_t* d_out_data, int64_t out_cap, int64_t* d_out_offsets,
+                      int64_t* d_totals, int64_t* totals, void* stream);
+int mrx_translate_known_dev(const uint8_t* table, const uint8_t* delete_set, const uint8_t* squeeze_set,
+                            const uint8_t* d_data, const int64_t* d_offsets, int64_t n, int64_t end_offset,
+                            int64_t max_text_len, uint8_t* d_out_data, int64_t out_cap, int64_t* d_out_offsets,
+                            int64_t* d_totals, int64_t* totals, void* stream);
+int mrx_translate_strided_dev(const uint8_t* table, const uint8_t* delete_set, const uint8_t* squeeze_set,
+                              const uint8_t* d_data, int64_t stride, const int32_t* d_lens, int32_t len, int64_t n,
+                              uint8_t* d_out_data, int64_t out_cap, int64_t* d_out_offsets, int64_t* d_totals,
+                              int64_t* totals, void* stream);
+
+/* ---- strip: bytes.strip of every text as span rows on the device ----
+ * For every text of L bytes one pair (start, end), relative to the text's first byte, in the shape of fields' rows with
+ * f = 1.  set (host, 32-byte bitmap as above) holds the bytes to strip; NULL is the six whitespace bytes of
+ * bytes.strip(): 0x09 .. 0x0D and 0x20, the ones fields splits at.
+ *   start  the number of leading bytes in the set under MRX_STRIP_LEFT, else 0
+ *   end    L minus the trailing bytes in the set counted inside [start, L) under MRX_STRIP_RIGHT, else L
+ * A text of set bytes alone gives (L, L) with MRX_STRIP_LEFT and (0, 0) with MRX_STRIP_RIGHT alone.
+ *   text        flags           row            text        flags    row
+ *   b"  42 "    left | right    (2, 4)         b"   "      left     (3, 3)
+ *   b"  42 "    left            (2, 5)         b"   "      right    (0, 0)
+ *   b"  42 "    right           (0, 4)         b""         any      (0, 0)
+ * Outputs, on the device:
+ *   d_rows int32[n][1][2]   8-byte aligned
+ *   d_prefix int64[n + 1]   (may be NULL) the values 0 .. n: the identity CSR of the rows over the texts, so that rows
+ *                           and prefix go into mrx_gather_spans_*, mrx_parse_spans_* and mrx_expand_spans_* as they stand
+ * No totals, no capacity, no scratch and no synchronisation on any form: the call enqueues and returns.  n == 0
+ * enqueues nothing (and writes nothing, d_prefix[0] included).  Spans are int32 (texts of up to 2 GiB - 1).  The _known
+ * form's bounds are not used.  Bytes outside a text never change a row.
+ * One kernel, a lane per text: it walks the aligned 16-byte words of the text in from the front and then from the back
+ * and reads only the words that hold a stripped byte or the first byte that stays.  A text of set bytes alone is walked
+ * whole by its one lane: right, not fast.  Reads as translate.
+ * MRX_E_ARGUMENT, before anything is enqueued: flags with an unknown bit or with none; negative n, end_offset or
+ * max_text_len; a bad pitch; a null d_rows or d_offsets; a d_rows that is not 8-byte aligned. */
+enum { MRX_STRIP_LEFT = 1, MRX_STRIP_RIGHT = 2 };
+int mrx_strip_dev(const uint8_t* set, uint32_t flags, const uint8_t* d_data, const int64_t* d_offsets, int64_t n,
+                  int32_t* d_rows, int64_t* d_prefix, void* stream);
+int mrx_strip_known_dev(const uint8_t* set, uint32_t flags, const uint8_t* d_data, const int64_t* d_offsets, int64_t n,
+                        int64_t end_offset, int64_t max_text_len, int32_t* d_rows, int64_t* d_prefix, void* stream);
+int mrx_strip_strided_dev(const uint8_t* set, uint32_t flags, const uint8_t* d_data, int64_t stride, const int32_t* d_lens,
+                          int32_t len, int64_t n, int32_t* d_rows, int64_t* d_prefix, void* stream);
+
 /* ---- host-buffer convenience wrappers (copy in, run, copy out) -------------- */
+/* mrx_translate_dev on host buffers: out_offsets int64[n + 1], out_data uint8[out_cap], totals int64[2] = {bytes, longest
+ * text} (may be NULL).  The output is packed in both forms: out_offsets begins at 0 (the same-length form's are the
+ * input's, relative to its first text).  out_offsets and totals are always copied out, out_data only when all of it fits
+ * (MRX_E_CAPACITY otherwise). */
+int mrx_translate_batch(const uint8_t* table, const uint8_t* delete_set, const uint8_t* squeeze_set, const uint8_t* data,
+                        const int64_t* offsets, int64_t n, int64_t* out_offsets, uint8_t* out_data, int64_t out_cap,
+                        int64_t* totals);
+/* mrx_strip_dev on host buffers: rows int32[n][2], prefix int64[n + 1] (may be NULL). */
+int mrx_strip_batch(const uint8_t* set, uint32_t flags, const uint8_t* data, const int64_t* offsets, int64_t n, int32_t* rows,
+                    int64_t* prefix);
 /* mrx_fields_dev on host buffers: rows int32[n][f][2], nf int32[n] (may be NULL), prefix int64[n + 1] (may be NULL). */
 int mrx_fields_batch(uint32_t flags, uint8_t delim, const int32_t* columns, int32_t f, const uint8_t* data,
                      const int64_t* offsets, int64_t n, int32_t* rows, int32_t* nf, int64_t* prefix);

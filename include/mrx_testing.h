@@ -225,6 +225,22 @@ void mrx_debug_fields_grid(int workgroups);
  * outputs and return codes as mrx_fields_batch. */
 int mrx_debug_fields_host(uint32_t flags, uint8_t delim, const int32_t* columns, int32_t f, const uint8_t* data,
                           const int64_t* offsets, int64_t n, int32_t* rows, int32_t* nf, int64_t* prefix);
+/* Translate (include/mrx.h): bytes > 0 pins the piece size P of every later call of the packed form (rounded up to a
+ * multiple of 1024, a wavefront's round), 0 restores the default, a negative value changes nothing.  Returns the P in
+ * force: tests place their runs by it.  The passes report themselves as "k_translate_map" (same-length form) and
+ * "k_translate_emit" through mrx_last_kernel_name(), strip as "k_strip".  Results are the same. */
+int64_t mrx_debug_translate_piece(int64_t bytes);
+/* How often mrx_translate_* has synchronised with the device on this process so far: the CSR form's read-back of its two
+ * offsets and every read-back of the totals.  (Strip never does.) */
+int64_t mrx_debug_translate_syncs(void);
+/* Translate and strip on the CPU, for tests without a GPU: the block walks of the kernels, over the same pieces (the
+ * pinned size, else the default), one block after the other, on the texts data[offsets[i], offsets[i + 1]).  Arguments, outputs, capacity rules and return codes as
+ * mrx_translate_batch and mrx_strip_batch. */
+int mrx_debug_translate_host(const uint8_t* table, const uint8_t* delete_set, const uint8_t* squeeze_set, const uint8_t* data,
+                             const int64_t* offsets, int64_t n, int64_t* out_offsets, uint8_t* out_data, int64_t out_cap,
+                             int64_t* totals);
+int mrx_debug_strip_host(const uint8_t* set, uint32_t flags, const uint8_t* data, const int64_t* offsets, int64_t n,
+                         int32_t* rows, int64_t* prefix);
 /* Bytes of device memory the calling thread's scratch arenas hold (see mrx_release_scratch). */
 size_t mrx_debug_scratch_bytes(void);
 /* ... and how many of them are handed out and not yet rewound.  Scratch belongs to the call's scope, so between calls

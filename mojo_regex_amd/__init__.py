@@ -43,6 +43,9 @@ argument meaning, a *batch* of texts instead of one text:
                                                   buffer's bytes as the packed batch of its lines
     (none: text.split()[k] on the host)           fields_of / DeviceBatch.fields / fields_async / cut: the
                                                   columns of every text as span rows, no pattern involved
+    (none: text.lower() / .translate() / .strip() translate_texts / strip_texts / DeviceBatch.translate / lower /
+     on the host)                                 upper / strip and their _async forms: tr, case folding and
+                                                  trimming of every text, no pattern involved
 
 All matching runs in the HIP kernels of libmrx_hip.so.  There is no CPU
 fallback: if the library is missing or no GPU is usable, calls raise.
@@ -85,6 +88,8 @@ from .api import (  # noqa: F401
     search,
     sort_texts,
     split,
+    strip_texts,
     sub,
+    translate_texts,
     value_counts,
 )

@@ -352,6 +352,23 @@ def load_library():
         "mrx_debug_fields_grid": (None, [C.c_int]),
         "mrx_debug_fields_host": (C.c_int, [C.c_uint32, C.c_uint8, i32p, C.c_int32, u8p, i64p, C.c_int64, i32p, i32p,
                                             i64p]),
+        "mrx_translate_dev": (C.c_int, [u8p, u8p, u8p, u8p, i64p, C.c_int64, u8p, C.c_int64, i64p, i64p, C.c_void_p,
+                                        C.c_void_p]),
+        "mrx_translate_known_dev": (C.c_int, [u8p, u8p, u8p, u8p, i64p, C.c_int64, C.c_int64, C.c_int64, u8p, C.c_int64,
+                                              i64p, i64p, C.c_void_p, C.c_void_p]),
+        "mrx_translate_strided_dev": (C.c_int, [u8p, u8p, u8p, u8p, C.c_int64, i32p, C.c_int32, C.c_int64, u8p, C.c_int64,
+                                                i64p, i64p, C.c_void_p, C.c_void_p]),
+        "mrx_translate_batch": (C.c_int, [u8p, u8p, u8p, u8p, i64p, C.c_int64, i64p, u8p, C.c_int64, C.c_void_p]),
+        "mrx_strip_dev": (C.c_int, [u8p, C.c_uint32, u8p, i64p, C.c_int64, i32p, i64p, C.c_void_p]),
+        "mrx_strip_known_dev": (C.c_int, [u8p, C.c_uint32, u8p, i64p, C.c_int64, C.c_int64, C.c_int64, i32p, i64p,
+                                          C.c_void_p]),
+        "mrx_strip_strided_dev": (C.c_int, [u8p, C.c_uint32, u8p, C.c_int64, i32p, C.c_int32, C.c_int64, i32p, i64p,
+                                            C.c_void_p]),
+        "mrx_strip_batch": (C.c_int, [u8p, C.c_uint32, u8p, i64p, C.c_int64, i32p, i64p]),
+        "mrx_debug_translate_piece": (C.c_int64, [C.c_int64]),
+        "mrx_debug_translate_syncs": (C.c_int64, []),
+        "mrx_debug_translate_host": (C.c_int, [u8p, u8p, u8p, u8p, i64p, C.c_int64, i64p, u8p, C.c_int64, C.c_void_p]),
+        "mrx_debug_strip_host": (C.c_int, [u8p, C.c_uint32, u8p, i64p, C.c_int64, i32p, i64p]),
         "mrx_debug_set_route": (None, [C.c_int]),
         "mrx_testing_set_run": (C.c_int, [H, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_int32)]),
     }
@@ -399,6 +416,8 @@ EXPORTED_SYMBOLS = [
     "mrx_kw_filter_known_dev", "mrx_kw_filter_strided_dev", "mrx_kw_findall_batch",
     "mrx_lines_dev", "mrx_lines_known_dev", "mrx_lines_strided_dev", "mrx_lines_batch",
     "mrx_fields_dev", "mrx_fields_known_dev", "mrx_fields_strided_dev", "mrx_fields_batch",
+    "mrx_translate_dev", "mrx_translate_known_dev", "mrx_translate_strided_dev", "mrx_translate_batch",
+    "mrx_strip_dev", "mrx_strip_known_dev", "mrx_strip_strided_dev", "mrx_strip_batch",
 ]
 TESTING_SYMBOLS = [
     "mrx_timing_reset", "mrx_timing_enable", "mrx_timing_scan_ms", "mrx_last_kernel_name",
@@ -414,6 +433,8 @@ TESTING_SYMBOLS = [
     "mrx_debug_kw_piece", "mrx_debug_kw_tier", "mrx_debug_kw_host_findall",
     "mrx_debug_lines_piece", "mrx_debug_lines_syncs", "mrx_debug_lines_host",
     "mrx_debug_fields_group", "mrx_debug_fields_grid", "mrx_debug_fields_host",
+    "mrx_debug_translate_piece", "mrx_debug_translate_syncs", "mrx_debug_translate_host",
+    "mrx_debug_strip_host",
 ]
 # (hooks with a digit in their name, listed apart: the header scan of tests/test_host_tables.py reads [a-z_] names)
 TESTING_SYMBOLS_NUMBERED = ["mrx_debug_rec12", "mrx_testing_rec12_roundtrip"]
@@ -725,6 +746,97 @@ class DeviceBatch:
         stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
         _check(self.call(load_library(), "mrx_fields", (flags, delim_byte, cols.ctypes.data, len(cols)),
                          (_ptr(rows), _ptr(nf), _ptr(prefix), stream)))
+
+    def translate(self, table=None, delete=b"", squeeze=b""):
+        """bytes.translate(table, delete) of every text, then tr -s over the bytes of `squeeze`, as a new batch
+        (include/mrx.h, mrx_translate_dev).  table is 256 bytes or None, the identity.  Without delete and squeeze the
+        result has this batch's layout -- the same offsets tensor, or the same pitch, length and lens -- and its known
+        bounds, and nothing is read back (a CSR batch without known bounds pays the read-back of its first and last
+        offset; the padding of fixed-pitch rows is unspecified in the result).  With delete or squeeze the result is a
+        packed CSR batch with exact known bounds, its bytes and its longest text: this batch's byte count is capacity
+        enough, so the call never retries and reads the two totals back once.  delete together with squeeze is
+        refused: call twice."""
+        import torch
+        dev = self.data.device
+        args = _translate_args(table, delete, squeeze)
+        if not (delete or squeeze):
+            out = torch.empty_like(self.data)
+            self.translate_async((out, None, None), table)
+            if self.offsets is not None:
+                res = DeviceBatch(out, self.offsets)
+                res._end_offset, res._max_len = self._end_offset, self._max_len
+                return res
+            return DeviceBatch(out, None, stride=self.stride, length=self.length, lens=self.lens, n=self.n)
+        cap = int(self.data.numel())
+        out = torch.empty(max(cap, 1), dtype=torch.uint8, device=dev)
+        out_offsets = torch.empty(self.n + 1, dtype=torch.int64, device=dev)
+        d_totals = torch.empty(2, dtype=torch.int64, device=dev)
+        totals = (C.c_int64 * 2)()
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        _check(self.call(load_library(), "mrx_translate", args,
+                         (_ptr(out), cap, _ptr(out_offsets), _ptr(d_totals), C.cast(totals, C.c_void_p), stream)))
+        nb = int(totals[0])
+        res = DeviceBatch(out[:nb].clone() if 4 * nb < cap else out[:nb], out_offsets)
+        res._end_offset, res._max_len = nb, int(totals[1])
+        return res
+
+    def translate_async(self, out, table=None, delete=b"", squeeze=b""):
+        """Enqueue translate() on the current stream without reading its result back.  out = (out_data uint8[out_cap],
+        out_offsets int64[n + 1], totals int64[2]) device tensors of the caller; totals = {bytes, longest text} once
+        the stream has drained, and no byte is written when bytes > out_cap.  Without delete and squeeze out_offsets
+        and totals may be None and are not written: byte p of this batch's data goes to byte p of out_data.  A CSR
+        batch without known bounds still pays the read-back of its first and last offset."""
+        import torch
+        args = _translate_args(table, delete, squeeze)
+        out_data, out_offsets, totals = out
+        if out_data is None or out_data.dtype != torch.uint8 or not out_data.is_contiguous():
+            raise MrxError("out_data must be a contiguous uint8 tensor")
+        for t, need in ((out_offsets, self.n + 1), (totals, 2)):
+            if t is None and not (delete or squeeze):
+                continue
+            if t is None or t.dtype != torch.int64 or not t.is_contiguous() or t.numel() < need:
+                raise MrxError("out needs out_data uint8[out_cap], out_offsets int64[n + 1], totals int64[2]")
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        _check(self.call(load_library(), "mrx_translate", args,
+                         (_ptr(out_data), int(out_data.numel()), _ptr(out_offsets), _ptr(totals), None, stream)))
+
+    def lower(self):
+        """bytes.lower() of every text: the ASCII letters, as Python's (translate with its table)."""
+        return self.translate(_LOWER)
+
+    def upper(self):
+        """bytes.upper() of every text: the ASCII letters, as Python's."""
+        return self.translate(_UPPER)
+
+    def strip(self, chars=None, left: bool = True, right: bool = True, spans: bool = False):
+        """bytes.strip(chars) of every text (lstrip with right=False, rstrip with left=False) as a new packed batch:
+        strip's rows (include/mrx.h, mrx_strip_dev), then gather_spans.  chars=None strips the six whitespace bytes.
+        spans=True returns (prefix int64[n + 1], rows int32[n, 1, 2]) instead, device tensors that go to gather_spans,
+        parse_spans and expand_spans as they stand; that form enqueues and reads nothing back."""
+        import torch
+        dev = self.data.device
+        rows = torch.empty((self.n, 1, 2), dtype=torch.int32, device=dev)
+        # n == 0 enqueues nothing: the one entry of the prefix is the host's to write
+        prefix = torch.empty(self.n + 1, dtype=torch.int64, device=dev) if self.n else torch.zeros(1, dtype=torch.int64, device=dev)
+        self.strip_async((prefix, rows), chars, left, right)
+        if spans:
+            return prefix, rows
+        return self.gather_spans(prefix, rows)[0]
+
+    def strip_async(self, out, chars=None, left: bool = True, right: bool = True):
+        """strip(spans=True) on the caller's tensors out = (prefix int64[n + 1] or None, rows int32[n, 1, 2]): enqueues
+        on the current stream and returns.  Nothing is written for a batch without texts."""
+        import torch
+        prefix, rows = out
+        if rows is None or rows.dtype != torch.int32 or not rows.is_contiguous() or rows.numel() < self.n * 2:
+            raise MrxError("rows must be a contiguous int32[n, 1, 2] tensor")
+        if prefix is not None and (prefix.dtype != torch.int64 or not prefix.is_contiguous() or prefix.numel() < self.n + 1):
+            raise MrxError("prefix must be a contiguous int64[n + 1] tensor")
+        if self.n == 0:   # nothing is enqueued, but the flags are still the C side's to refuse (no rows: no address)
+            rows = torch.empty(2, dtype=torch.int32, device=self.data.device)
+        chars_set = None if chars is None else _byte_set(chars)
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        _check(self.call(load_library(), "mrx_strip", (chars_set, _strip_flags(left, right)), (_ptr(rows), _ptr(prefix), stream)))
 
     def cut(self, columns, delim=None, out_delim=None, end=b"\n"):
         """cut -d<delim> -f<columns>, or awk '{print $a, $b}' with delim=None: one record per text, the named columns
@@ -1130,6 +1242,35 @@ def _lines_flags(sep, keepends: bool, crlf: bool, partial: bool) -> Tuple[int, i
 
 MRX_FIELDS_WHITESPACE, MRX_FIELDS_REST = 1, 2
 MRX_FIELDS_MAX_COLUMNS = 32
+
+
+MRX_STRIP_LEFT, MRX_STRIP_RIGHT = 1, 2
+_LOWER = bytes(range(256)).lower()
+_UPPER = bytes(range(256)).upper()
+
+
+def _byte_set(members) -> bytes:
+    """The 32-byte bitmap of include/mrx.h over the bytes of `members`."""
+    bits = bytearray(32)
+    for c in _b(members):
+        bits[c >> 3] |= 1 << (c & 7)
+    return bytes(bits)
+
+
+def _translate_args(table=None, delete=b"", squeeze=b""):
+    """(table, delete set, squeeze set) of mrx_translate_*, each None where empty.  What the C side refuses too is refused
+    here first, so that the host-list forms say so before they upload."""
+    table = None if table is None else _b(table)
+    if table is not None and len(table) != 256:
+        raise MrxError("table must be 256 bytes (or None, the identity)")
+    if delete and squeeze:
+        raise MrxError("delete and squeeze in one call: translate twice")
+    return table, _byte_set(delete) if delete else None, _byte_set(squeeze) if squeeze else None
+
+
+def _strip_flags(left: bool, right: bool) -> int:
+    """flags of mrx_strip_*; neither side is the C side's to refuse."""
+    return (MRX_STRIP_LEFT if left else 0) | (MRX_STRIP_RIGHT if right else 0)
 
 
 def _fields_args(columns, delim, rest: bool):
@@ -2217,6 +2358,28 @@ def fields_of(texts, columns, delim=None, rest: bool = False):
     _, rows, _ = DeviceBatch.from_texts(bs).fields(columns, delim, rest, counts=False)
     rows = rows.cpu().numpy()
     return [[None if s < 0 else t[s:e] for s, e in rows[i].tolist()] for i, t in enumerate(bs)]
+
+
+def translate_texts(texts, table=None, delete=b"", squeeze=b"") -> List[bytes]:
+    """DeviceBatch.translate of host texts: [t.translate(table, delete) for t in texts], then tr -s over `squeeze`."""
+    bs = [_b(t) for t in texts]
+    _translate_args(table, delete, squeeze)
+    if not bs:
+        return []
+    res = DeviceBatch.from_texts(bs).translate(table, delete, squeeze)
+    raw, off = res.data.cpu().numpy().tobytes(), res.offsets.cpu().numpy()
+    return [raw[off[i]:off[i + 1]] for i in range(len(bs))]
+
+
+def strip_texts(texts, chars=None, left: bool = True, right: bool = True) -> List[bytes]:
+    """DeviceBatch.strip of host texts: [t.strip(chars) for t in texts] (lstrip / rstrip with one side off)."""
+    bs = [_b(t) for t in texts]
+    if not (left or right):
+        raise MrxError("strip needs left, right or both")
+    if not bs:
+        return []
+    _, rows = DeviceBatch.from_texts(bs).strip(chars, left, right, spans=True)
+    return [t[int(a):int(b)] for t, (a, b) in zip(bs, rows.cpu().numpy().reshape(-1, 2))]
 
 
 def build_dictionary(entries) -> Dictionary:

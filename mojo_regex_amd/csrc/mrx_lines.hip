@@ -9,16 +9,8 @@
 //   exclusive_scan        of the lines into d_line_prefix (sum -> d_totals[0]) and of the bytes (sum -> d_totals[1])
 //   k_lines_emit          a wavefront per piece: offsets, owners and the compacted bytes
 //   k_lines_longest(_end) the longest line from the finished offsets -> d_totals[2]
-// Pieces are numbered text-major.  Fixed pitch: every text has ceil(longest / P) of them (1 at least), so piece -> text is
-// a division.  CSR: a search of the texts' first pieces by the whole wavefront; the grid is sized by an upper bound of
-// the piece count (bytes / P + n, the bytes from the caller's known bound or from one read-back of the first and last
-// offset), and the pieces beyond the last text's count nothing.
-//
-// The emit kernel moves no output byte to memory on its own.  A lane drops its kept bytes into its wavefront's LDS
-// stage at the place the wave's prefix sum gives them -- the stage is laid out like the output from the last 16-byte
-// boundary of its ADDRESS on -- and the lanes then store the stage's complete 16-byte blocks, aligned, one a lane.  What
-// is left behind the last complete block stays in the stage for the next round.  Only the two ends of a piece, blocks
-// that it shares with the pieces around it, go out as single bytes, a lane each: no block has two writers of one byte.
+// The text-major pieces, the wavefront's way from a piece to its text and the LDS stage through which the emit kernel's
+// kept bytes leave as aligned 16-byte blocks are in mrx_pieces.hpp, shared with translate.
 // No atomics, no inline assembly, and no wavefront waits for another one: every scan is a launch of its own.
 #include <hip/hip_runtime.h>
 
@@ -33,6 +25,7 @@
 #include "mrx_host_batch.hpp"
 #include "mrx_internal.hpp"
 #include "mrx_lines_bits.hpp"
+#include "mrx_pieces.hpp"
 
 namespace mrx {
 namespace {
@@ -41,7 +34,6 @@ constexpr int kLinesBlock = 256, kLinesWaves = kLinesBlock / 64;
 constexpr unsigned kLinesMaxGrid = 2048;    // 8 workgroups per CU; the kernels stride over what is left
 constexpr int kLinesParts = 1024;           // partial maxima of the longest line
 constexpr int64_t kLinesPieceMax = 1 << 20;
-constexpr int kLinesStage = (int)kLinesRound + 32;   // a round's bytes behind at most 15 held over, in whole blocks
 
 std::atomic<int64_t> g_lines_piece{0};
 std::atomic<int64_t> g_lines_syncs{0};
@@ -51,13 +43,6 @@ int64_t lines_piece() {
   return pinned > 0 ? pinned : kLinesPiece;
 }
 
-// the pieces of a call
-struct LinesPieces {
-  int64_t P;
-  int64_t per_text;       // fixed pitch: pieces of every text
-  const int64_t* first;   // CSR: [n + 1], the first piece of every text
-  int64_t npieces;        // to walk (CSR: an upper bound)
-};
 // what the passes leave for each other (scratch)
 struct LinesWork {
   int64_t* nsep;        // [npieces]
@@ -70,65 +55,6 @@ struct LinesWork {
   int64_t* tails;       // [n]
   int64_t* tbase;       // [n + 1] every text's first output byte
 };
-// bytes [p0, pend) of text `text` (pend == p0: nothing); a: the text's first piece
-struct LinesJob {
-  const uint8_t* tp;
-  int64_t L, p0, pend, text, a;
-};
-
-// gather_last_le(first, 0, n, piece) by a whole wavefront (every lane calls it with the same arguments): each round the
-// lanes probe 64 evenly spaced entries of what is left, so a million texts take four dependent loads, not twenty.  The
-// lanes whose entry is at or below `piece` are a prefix of the wavefront (first[] does not decrease, first[lo] <= piece).
-__device__ __forceinline__ int64_t lines_wave_last_le(const int64_t* __restrict__ first, int64_t n, int64_t piece) {
-  const int lane = (int)threadIdx.x & 63;
-  int64_t lo = 0, hi = n;
-  while (hi - lo > 1) {
-    const int64_t step = (hi - lo + 63) >> 6, idx = lo + lane * step;
-    const unsigned long long at_or_below = __ballot(idx < hi && first[idx] <= piece);
-    const int64_t k = __popcll(at_or_below | 1ull) - 1;
-    lo += k * step;
-    hi = lo + step < hi ? lo + step : hi;
-  }
-  return lo;
-}
-
-__device__ __forceinline__ LinesJob lines_job(const TextBatch& B, int64_t n, const LinesPieces& pc, int64_t piece) {
-  LinesJob j{nullptr, 0, 0, 0, 0, 0};
-  if (piece >= pc.npieces) return j;
-  if (pc.first) {
-    if (piece >= pc.first[n]) return j;
-    j.text = lines_wave_last_le(pc.first, n, piece);   // (empty texts repeat the value: the last one has the piece)
-    j.a = pc.first[j.text];
-  } else {
-    j.text = piece / pc.per_text;
-    j.a = j.text * pc.per_text;
-  }
-  j.tp = lines_text(B, j.text, &j.L);
-  j.p0 = j.pend = (piece - j.a) * pc.P;
-  if (j.p0 < j.L) j.pend = j.p0 + pc.P < j.L ? j.p0 + pc.P : j.L;
-  return j;
-}
-
-__device__ __forceinline__ int wave_sum(int v) {
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
-__device__ __forceinline__ int wave_max(int v) {
-  for (int off = 32; off > 0; off >>= 1) {
-    const int y = __shfl_xor(v, off);
-    v = y > v ? y : v;
-  }
-  return v;
-}
-
-__global__ __launch_bounds__(256) void k_lines_pieces(const TextBatch B, int64_t n, int64_t P, int64_t* __restrict__ per) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    int64_t L;
-    (void)lines_text(B, i, &L);
-    per[i] = lines_pieces_of(L, P);
-  }
-}
-
 __global__ __launch_bounds__(kLinesBlock) void k_lines_count(const TextBatch B, int64_t n, const LinesPieces pc, uint32_t sep,
                                                              uint32_t flags, const LinesWork W) {
   const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
@@ -182,14 +108,6 @@ struct LinesOut {
   int64_t out_cap;
 };
 
-// A stage belongs to one wavefront, whose LDS accesses the hardware serves in program order: what the lanes need between
-// writing the stage and reading it is that the compiler keeps that order, not a barrier of the workgroup.
-__device__ __forceinline__ void lines_wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 __shared__ g_u64x2 s_lines_stage[kLinesWaves][kLinesStage / 16];
 
 __global__ __launch_bounds__(kLinesBlock) void k_lines_emit(const TextBatch B, int64_t n, const LinesPieces pc, uint32_t sep,
@@ -200,7 +118,6 @@ __global__ __launch_bounds__(kLinesBlock) void k_lines_emit(const TextBatch B, i
   const bool drop_tail = (flags & MRX_LINES_DROP_PARTIAL) != 0;
   const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
   g_u64x2* stage16 = s_lines_stage[wave];
-  uint8_t* stage = (uint8_t*)stage16;
   for (int64_t piece = (int64_t)blockIdx.x * kLinesWaves + wave; piece < pc.npieces; piece += (int64_t)gridDim.x * kLinesWaves) {
     const LinesJob job = lines_job(B, n, pc, piece);
     const bool has = job.pend > job.p0;
@@ -210,15 +127,7 @@ __global__ __launch_bounds__(kLinesBlock) void k_lines_emit(const TextBatch B, i
       pos = W.tbase[job.text] + (W.kept_scan[piece] - W.kept_scan[job.a]);
       limit = job.L - (drop_tail ? W.tails[job.text] : 0);
     }
-    // the stage holds the output from the address `ablk` (16-byte aligned) on: [own, fill) are bytes of this piece
-    // that no block has taken yet, [0, own) belong to the piece in front
-    uintptr_t ablk = 0;
-    int fill = 0, own = 0;
-    if (has && move) {
-      const uintptr_t addr = (uintptr_t)O.out + (uintptr_t)pos;
-      ablk = addr & ~(uintptr_t)15;
-      fill = own = (int)(addr & 15);
-    }
+    LinesStage st = lines_stage_open(has && move, O.out, pos);
     for (int64_t q0 = job.p0; q0 < job.pend; q0 += kLinesRound) {   // (a short text's piece ends after its first round)
       const int64_t q = q0 + 16 * lane;
       const LinesBlock b = q < job.pend ? lines_block(job.tp, job.L, q, limit, sep, flags) : lines_no_block();
@@ -237,32 +146,9 @@ __global__ __launch_bounds__(kLinesBlock) void k_lines_emit(const TextBatch B, i
       }
       line += all >> 16;
       pos += K;
-      if (move) {
-        uint8_t* w = stage + fill + kept_before;
-#pragma unroll
-        for (int k = 0; k < 16; ++k)
-          if ((b.keep >> k) & 1u) *w++ = (uint8_t)(b.bytes >> (8 * k));
-        lines_wave_sync();
-        const int have = fill + K, nb = have >> 4, rem = have & 15;
-        if (lane < nb) {
-          if (lane > 0 || own == 0) gather_store16((uint8_t*)(ablk + 16 * (uintptr_t)lane), ((g_u128)stage16[lane].y << 64) | stage16[lane].x);
-        }
-        if (nb > 0 && lane >= own && lane < 16 && own > 0) *(uint8_t*)(ablk + (uintptr_t)lane) = stage[lane];
-        const uint8_t held = lane < rem ? stage[16 * nb + lane] : (uint8_t)0;
-        lines_wave_sync();
-        if (nb > 0) {
-          if (lane < rem) stage[lane] = held;
-          ablk += 16 * (uintptr_t)nb;
-          own = 0;
-        }
-        fill = rem;
-      }
+      if (move) lines_stage_round(st, stage16, lane, b.bytes, b.keep, kept_before, K);
     }
-    if (move) {   // what is left is the piece's share of a block that the next piece goes on with
-      lines_wave_sync();
-      if (lane >= own && lane < fill) *(uint8_t*)(ablk + (uintptr_t)lane) = stage[lane];
-      lines_wave_sync();
-    }
+    if (move) lines_stage_close(st, stage16, lane);
   }
 }
 
@@ -334,30 +220,7 @@ int lines_run(uint32_t flags, uint8_t sep, const TextBatch& b, BatchForm form, i
   LinesPieces pc{lines_piece(), 0, nullptr, 0};
   int64_t* dummy = (int64_t*)scratch_get(sizeof(int64_t) * 2, o.stream);   // the sums of the scans that nobody reads
   if (!dummy) return internal_fail(MRX_E_NO_DEVICE, "scratch allocation failed");
-  if (b.offsets) {
-    int64_t bytes = known_total;
-    if (bytes < 0) {
-      int64_t ends[2] = {0, 0};
-      MRX_HIP_TRY(hipMemcpyAsync(&ends[0], b.offsets, sizeof(int64_t), hipMemcpyDeviceToHost, hs));
-      MRX_HIP_TRY(hipMemcpyAsync(&ends[1], b.offsets + n, sizeof(int64_t), hipMemcpyDeviceToHost, hs));
-      MRX_HIP_TRY(hipStreamSynchronize(hs));   // the piece count sizes the scratch
-      ++g_lines_syncs;
-      if (ends[1] < ends[0]) return internal_fail(MRX_E_ARGUMENT, "offsets must not decrease");
-      bytes = ends[1] - ends[0];
-    }
-    int64_t* per = (int64_t*)scratch_get(sizeof(int64_t) * (size_t)n, o.stream);
-    int64_t* first = (int64_t*)scratch_get(sizeof(int64_t) * (size_t)(n + 1), o.stream);
-    if (!per || !first) return internal_fail(MRX_E_NO_DEVICE, "scratch allocation failed");
-    hipLaunchKernelGGL(k_lines_pieces, dim3(grid_for(n, 256, 4096)), dim3(256), 0, hs, b, n, pc.P, per);
-    MRX_HIP_TRY(hipGetLastError());
-    if (int rc = exclusive_scan(per, n, first, dummy, o.stream)) return rc;
-    pc.first = first;
-    pc.npieces = bytes / pc.P + n;   // ceil(len / P) <= len / P + 1 for every text
-  } else {
-    pc.per_text = lines_pieces_of(b.pitch_longest(), pc.P);
-    if (pc.per_text < 1) pc.per_text = 1;
-    pc.npieces = n * pc.per_text;
-  }
+  if (int rc = lines_pieces_setup(b, n, known_total, dummy, g_lines_syncs, o.stream, &pc)) return rc;
   LinesWork W;
   const size_t np = (size_t)pc.npieces, i64 = sizeof(int64_t);
   W.nsep = (int64_t*)scratch_get(i64 * np, o.stream);
