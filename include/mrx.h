@@ -966,6 +966,79 @@ int mrx_kw_filter_strided_dev(const mrx_kw* k, uint32_t flags, const uint8_t* d_
                               int32_t len, int64_t n, int64_t* d_kept_idx, int64_t* d_out_offsets, uint8_t* d_out_data,
                               int64_t out_cap, int64_t* d_totals, int64_t* totals, void* stream);
 
+/* ---- keywords: leftmost-longest matches and replacement ----
+ * Rewrite by dictionary: redact 10^4 names in every log line, normalise spellings against a vocabulary, entity tables,
+ * sed -f with thousands of s/literal/replacement/g, greedy tokenisation.  (mrx_set_sub_dev has at most 256 members, runs
+ * every member's own findall and resolves equal starts by member order; mrx_kw_findall_dev reports every overlapping and
+ * nested occurrence.)
+ * THE LEFTMOST-LONGEST MATCHES of a keyword set in a text t.  Set pos = 0 and repeat: take the smallest s >= pos at which
+ * some entry occurs; among the entries that occur at s take the longest, [s, e); report it and set pos = e.  Equal
+ * entries stand under their lowest index, as everywhere in a keyword set.  With MRX_KW_IGNORE_CASE entries and text are
+ * compared folded and spans are unchanged.  No entry is empty, so every match has at least one byte.  With count > 0 only
+ * the first `count` matches of each text are kept (count == 0: all).  This is what re.finditer of the escaped entries,
+ * longest first, joined by `|` yields, and aho-corasick's LeftmostLongest.
+ *   leftmost  d_text_prefix int64[n + 1], d_entries int32[total], d_spans int32[total][2] (8-byte aligned,
+ *             text-relative): text i's kept matches are [d_text_prefix[i], d_text_prefix[i + 1]), in ascending start
+ *             order.  The capacity rule is mrx_kw_findall_dev's: total > span_cap is MRX_E_CAPACITY with *total and
+ *             d_text_prefix valid, and nothing is written at or beyond span_cap (retry with *total).  total may be NULL.
+ *             n == 0 gives d_text_prefix = {0}.
+ *   sub       the output is every text with each kept match replaced; every other byte is copied unchanged, also under
+ *             MRX_KW_IGNORE_CASE: only the comparison folds.  The replacements are a CSR batch ON THE DEVICE with r rows
+ *             (row j = d_repl_data[d_repl_offsets[j], d_repl_offsets[j + 1])): r == 1, one replacement for every entry;
+ *             r == m (mrx_kw_size), a match reported under entry j takes row j; any other r is MRX_E_ARGUMENT.  The bytes
+ *             are taken verbatim: there is no template grammar, and a backslash is a byte.  An empty replacement deletes
+ *             the match.  The aligned 16-byte words around a replacement must be readable, as for texts.
+ *             d_out_offsets int64[n + 1] and d_out_data are the output as a packed CSR batch; d_nsub int32[n] (or NULL)
+ *             the replacements made in every text; d_totals int64[3] (device, or NULL) and totals int64[3] (host, or
+ *             NULL) = {output bytes, longest output text, replacements}.  Output bytes > out_cap is MRX_E_CAPACITY:
+ *             nothing is written at or beyond out_cap (no output byte at all), and d_out_offsets, d_nsub and the totals
+ *             are valid for the retry, as mrx_set_sub_dev leaves them.  With totals == NULL the call only enqueues its
+ *             last steps and the verdict is the caller's to read from d_totals.  m == 0 or no match: the output is the
+ *             input.  n == 0 gives d_out_offsets = {0} and totals of 0.
+ * How.  The handle keeps a host copy of its folded entries; the first leftmost / sub call builds the automaton of the
+ * REVERSED entries from it and uploads it, once (the handle stays immutable and thread-safe for its callers).  A reversed
+ * table above 1 GiB is MRX_E_UNSUPPORTED with states and classes in the message, at that call and every later one of
+ * the two; every other operation on the handle still works.  A piece [p, pend) of P bytes (the pieces of findall) is
+ * walked from min(len, pend + Lmax - 1) DOWN to p: after the step that consumes byte q the state's outputs are the
+ * entries that begin at q, the longest first, so every position gives at most one CANDIDATE, and the right-hand
+ * warm-up never leaves the text.  A candidate is a HEAD when every earlier candidate of its text ends at or before its
+ * start; a head is selected whatever came before it, so a lane per piece starts the sequential selection at the first
+ * head of its piece and stops in front of the first head of a later piece (a running maximum of the ends, seeded from
+ * the ceil((Lmax - 1) / P) pieces in front, decides both).  Every flag has exactly one writer: no memory atomics, and
+ * the same bits on every run.  A text with no head behind its first candidate -- `aa` in `aaaa...` -- is walked end to
+ * end by one lane: exact, and as slow as one lane is (profiles/kw_sub.md).  The output of sub is described as rows
+ * (length, source address): per kept match the copied stretch in front of it and its replacement, per text a tail; one
+ * exclusive scan of the lengths gives d_out_offsets, and the bytes are moved by extract's block gather, balanced by
+ * output bytes.
+ * Synchronisation: one for the candidate total, which sizes the scratch; one read-back of the totals at the end (sub
+ * with totals != NULL, leftmost always), behind everything that was enqueued -- the gather checks the capacity on the
+ * device.  A CSR batch without known bounds adds the usual one for its byte count; the _known forms spare it.
+ * Reads: the keywords rule unchanged -- only the aligned 16-byte words that hold a byte of the walked range, and no byte
+ * outside [0, len) of a text reaches a state, a match or the output.
+ * Scratch: 13 bytes per candidate, 24 per output row (2 x candidates + n at most), 36 per piece, 16 per text.
+ * MRX_E_ARGUMENT, before any device call: the argument classes of the other keyword entry points, and negative count or
+ * r, null replacement pointers where r > 0, r neither 1 nor m. */
+int mrx_kw_leftmost_dev(const mrx_kw* k, int64_t count, const uint8_t* d_data, const int64_t* d_offsets, int64_t n,
+                        int64_t* d_text_prefix, int32_t* d_entries, int32_t* d_spans, int64_t span_cap, int64_t* total,
+                        void* stream);
+int mrx_kw_leftmost_known_dev(const mrx_kw* k, int64_t count, const uint8_t* d_data, const int64_t* d_offsets, int64_t n,
+                              int64_t end_offset, int64_t max_text_len, int64_t* d_text_prefix, int32_t* d_entries,
+                              int32_t* d_spans, int64_t span_cap, int64_t* total, void* stream);
+int mrx_kw_leftmost_strided_dev(const mrx_kw* k, int64_t count, const uint8_t* d_data, int64_t stride, const int32_t* d_lens,
+                                int32_t len, int64_t n, int64_t* d_text_prefix, int32_t* d_entries, int32_t* d_spans,
+                                int64_t span_cap, int64_t* total, void* stream);
+int mrx_kw_sub_dev(const mrx_kw* k, const uint8_t* d_repl_data, const int64_t* d_repl_offsets, int64_t r, int64_t count,
+                   const uint8_t* d_data, const int64_t* d_offsets, int64_t n, int64_t* d_out_offsets, uint8_t* d_out_data,
+                   int64_t out_cap, int32_t* d_nsub, int64_t* d_totals, int64_t* totals, void* stream);
+int mrx_kw_sub_known_dev(const mrx_kw* k, const uint8_t* d_repl_data, const int64_t* d_repl_offsets, int64_t r, int64_t count,
+                         const uint8_t* d_data, const int64_t* d_offsets, int64_t n, int64_t end_offset, int64_t max_text_len,
+                         int64_t* d_out_offsets, uint8_t* d_out_data, int64_t out_cap, int32_t* d_nsub, int64_t* d_totals,
+                         int64_t* totals, void* stream);
+int mrx_kw_sub_strided_dev(const mrx_kw* k, const uint8_t* d_repl_data, const int64_t* d_repl_offsets, int64_t r, int64_t count,
+                           const uint8_t* d_data, int64_t stride, const int32_t* d_lens, int32_t len, int64_t n,
+                           int64_t* d_out_offsets, uint8_t* d_out_data, int64_t out_cap, int32_t* d_nsub, int64_t* d_totals,
+                           int64_t* totals, void* stream);
+
 /* ---- lines: a batch's texts cut at one separator byte, as a new packed batch on the device ----
  * The first step of a pipeline over a file: a buffer's bytes (one text, or the texts of a batch) become the batch of lines
  * that every other call takes.  No pattern and no automaton: with `sep` one byte, lines(t) is t.split(sep) with the last
@@ -1204,6 +1277,14 @@ int mrx_lines_batch(uint32_t flags, uint8_t sep, const uint8_t* data, const int6
 /* mrx_kw_findall_dev on host buffers: text_prefix is always copied out, entries and spans only when all hits fit */
 int mrx_kw_findall_batch(const mrx_kw* k, const uint8_t* data, const int64_t* offsets, int64_t n, int64_t* text_prefix,
                          int32_t* entries, int32_t* spans, int64_t span_cap, int64_t* total);
+/* mrx_kw_leftmost_dev on host buffers: text_prefix is always copied out, entries and spans only when all matches fit */
+int mrx_kw_leftmost_batch(const mrx_kw* k, int64_t count, const uint8_t* data, const int64_t* offsets, int64_t n,
+                          int64_t* text_prefix, int32_t* entries, int32_t* spans, int64_t span_cap, int64_t* total);
+/* mrx_kw_sub_dev on host buffers, the replacements included (repl_offsets int64[r + 1]); out_offsets, nsub (may be NULL)
+ * and totals int64[3] (may be NULL) are always copied out, the output's bytes only when they fit */
+int mrx_kw_sub_batch(const mrx_kw* k, const uint8_t* repl_data, const int64_t* repl_offsets, int64_t r, int64_t count,
+                     const uint8_t* data, const int64_t* offsets, int64_t n, int64_t* out_offsets, uint8_t* out_data,
+                     int64_t out_cap, int32_t* nsub, int64_t* totals);
 /* mrx_format_dev on host buffers: the columns' pointers are host pointers (a text column's offsets may begin anywhere
  * and must not decrease); out_offsets int64[n + 1], out_data uint8[out_cap], row_status uint8[n] (may be NULL), totals
  * int64[2] = {n, bytes} (may be NULL).  out_offsets[0, n] and row_status are copied out, out_data only when all of it

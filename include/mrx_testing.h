@@ -198,6 +198,19 @@ void mrx_debug_kw_tier(int on);
 int mrx_debug_kw_host_findall(const uint8_t* entry_data, const int64_t* entry_offsets, int64_t m, uint32_t flags,
                               const uint8_t* data, const int64_t* offsets, int64_t n, int64_t* text_prefix, int32_t* entries,
                               int32_t* spans, int64_t span_cap, int64_t* total, char* describe, size_t describe_cap);
+/* Keywords, leftmost and sub on the CPU, for tests without a GPU: the automaton of the reversed entries is built as the
+ * handle builds it, and the walk back, the selection, the rows and the block fill of the kernels run over the same pieces
+ * (the pinned size of mrx_debug_kw_piece, else the rule), one after the other.  Entries and texts as
+ * mrx_debug_kw_host_findall; outputs, capacity rules and return codes as mrx_kw_leftmost_batch and mrx_kw_sub_batch, the
+ * replacements on the host too.  On the device the operations report themselves as "k_kw_sub_select" and
+ * "k_kw_sub_gather" through mrx_last_kernel_name(). */
+int mrx_debug_kw_host_leftmost(const uint8_t* entry_data, const int64_t* entry_offsets, int64_t m, uint32_t flags, int64_t count,
+                               const uint8_t* data, const int64_t* offsets, int64_t n, int64_t* text_prefix, int32_t* entries,
+                               int32_t* spans, int64_t span_cap, int64_t* total);
+int mrx_debug_kw_host_sub(const uint8_t* entry_data, const int64_t* entry_offsets, int64_t m, uint32_t flags,
+                          const uint8_t* repl_data, const int64_t* repl_offsets, int64_t r, int64_t count, const uint8_t* data,
+                          const int64_t* offsets, int64_t n, int64_t* out_offsets, uint8_t* out_data, int64_t out_cap,
+                          int32_t* nsub, int64_t* totals);
 /* Lines (include/mrx.h): bytes > 0 pins the piece size P of every later call (rounded up to a multiple of 1024, a
  * wavefront's round), 0 restores the default, a negative value changes nothing.  Returns the P in force: tests place
  * their separators by it.  The pass reports itself as "k_lines_emit" through mrx_last_kernel_name().  Results are the

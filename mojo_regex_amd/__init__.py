@@ -39,6 +39,9 @@ argument meaning, a *batch* of texts instead of one text:
                                                   text and number columns as packed records, the report's bytes
     (none: one alternation of literals per call)  Keywords / build_keywords / keywords_filter: which of
                                                   thousands of literals occur inside each text, one pass
+    (none: one re.sub per literal on the host)    Keywords.sub / subn / leftmost / keywords_sub: the
+                                                  leftmost-longest matches of a keyword set, and every text
+                                                  with them replaced, per entry or by one replacement
     (none: text.split("\\n") on the host)         lines_of / DeviceBatch.from_lines / lines / lines_async: a
                                                   buffer's bytes as the packed batch of its lines
     (none: text.split()[k] on the host)           fields_of / DeviceBatch.fields / fields_async / cut: the
@@ -77,6 +80,7 @@ from .api import (  # noqa: F401
     format_records,
     format_records_async,
     keywords_filter,
+    keywords_sub,
     library_path,
     lines_of,
     load_library,

@@ -325,6 +325,28 @@ def load_library():
         "mrx_kw_filter_strided_dev": (C.c_int, [H, C.c_uint32, u8p, C.c_int64, i32p, C.c_int32, C.c_int64, i64p, i64p, u8p,
                                                 C.c_int64, i64p, C.c_void_p, C.c_void_p]),
         "mrx_kw_findall_batch": (C.c_int, [H, u8p, i64p, C.c_int64, i64p, i32p, i32p, C.c_int64, C.POINTER(C.c_int64)]),
+        # leftmost: the handle, count | the batch | findall's tail; sub: the handle, (repl data, offsets, r), count | the
+        # batch | (out_offsets, out_data, out_cap, nsub, d_totals, totals, stream)
+        "mrx_kw_leftmost_dev": (C.c_int, [H, C.c_int64, u8p, i64p, C.c_int64, i64p, i32p, i32p, C.c_int64,
+                                          C.POINTER(C.c_int64), C.c_void_p]),
+        "mrx_kw_leftmost_known_dev": (C.c_int, [H, C.c_int64, u8p, i64p, C.c_int64, C.c_int64, C.c_int64, i64p, i32p, i32p,
+                                                C.c_int64, C.POINTER(C.c_int64), C.c_void_p]),
+        "mrx_kw_leftmost_strided_dev": (C.c_int, [H, C.c_int64, u8p, C.c_int64, i32p, C.c_int32, C.c_int64, i64p, i32p, i32p,
+                                                  C.c_int64, C.POINTER(C.c_int64), C.c_void_p]),
+        "mrx_kw_leftmost_batch": (C.c_int, [H, C.c_int64, u8p, i64p, C.c_int64, i64p, i32p, i32p, C.c_int64,
+                                            C.POINTER(C.c_int64)]),
+        "mrx_kw_sub_dev": (C.c_int, [H, u8p, i64p, C.c_int64, C.c_int64, u8p, i64p, C.c_int64, i64p, u8p, C.c_int64, i32p,
+                                     i64p, C.c_void_p, C.c_void_p]),
+        "mrx_kw_sub_known_dev": (C.c_int, [H, u8p, i64p, C.c_int64, C.c_int64, u8p, i64p, C.c_int64, C.c_int64, C.c_int64,
+                                           i64p, u8p, C.c_int64, i32p, i64p, C.c_void_p, C.c_void_p]),
+        "mrx_kw_sub_strided_dev": (C.c_int, [H, u8p, i64p, C.c_int64, C.c_int64, u8p, C.c_int64, i32p, C.c_int32, C.c_int64,
+                                             i64p, u8p, C.c_int64, i32p, i64p, C.c_void_p, C.c_void_p]),
+        "mrx_kw_sub_batch": (C.c_int, [H, u8p, i64p, C.c_int64, C.c_int64, u8p, i64p, C.c_int64, i64p, u8p, C.c_int64, i32p,
+                                       C.c_void_p]),
+        "mrx_debug_kw_host_leftmost": (C.c_int, [u8p, i64p, C.c_int64, C.c_uint32, C.c_int64, u8p, i64p, C.c_int64, i64p,
+                                                 i32p, i32p, C.c_int64, C.POINTER(C.c_int64)]),
+        "mrx_debug_kw_host_sub": (C.c_int, [u8p, i64p, C.c_int64, C.c_uint32, u8p, i64p, C.c_int64, C.c_int64, u8p, i64p,
+                                            C.c_int64, i64p, u8p, C.c_int64, i32p, C.c_void_p]),
         "mrx_debug_kw_piece": (None, [C.c_int64]),
         "mrx_debug_kw_tier": (None, [C.c_int]),
         "mrx_debug_kw_host_findall": (C.c_int, [u8p, i64p, C.c_int64, C.c_uint32, u8p, i64p, C.c_int64, i64p, i32p, i32p,
@@ -414,6 +436,8 @@ EXPORTED_SYMBOLS = [
     "mrx_kw_contains_dev", "mrx_kw_contains_strided_dev", "mrx_kw_count_dev", "mrx_kw_count_strided_dev",
     "mrx_kw_findall_dev", "mrx_kw_findall_known_dev", "mrx_kw_findall_strided_dev", "mrx_kw_filter_dev",
     "mrx_kw_filter_known_dev", "mrx_kw_filter_strided_dev", "mrx_kw_findall_batch",
+    "mrx_kw_leftmost_dev", "mrx_kw_leftmost_known_dev", "mrx_kw_leftmost_strided_dev", "mrx_kw_leftmost_batch",
+    "mrx_kw_sub_dev", "mrx_kw_sub_known_dev", "mrx_kw_sub_strided_dev", "mrx_kw_sub_batch",
     "mrx_lines_dev", "mrx_lines_known_dev", "mrx_lines_strided_dev", "mrx_lines_batch",
     "mrx_fields_dev", "mrx_fields_known_dev", "mrx_fields_strided_dev", "mrx_fields_batch",
     "mrx_translate_dev", "mrx_translate_known_dev", "mrx_translate_strided_dev", "mrx_translate_batch",
@@ -431,6 +455,7 @@ TESTING_SYMBOLS = [
     "mrx_debug_decode_lean", "mrx_debug_last_decode_lean", "mrx_testing_decode_expand",
     "mrx_debug_format_grid", "mrx_testing_format_one",
     "mrx_debug_kw_piece", "mrx_debug_kw_tier", "mrx_debug_kw_host_findall",
+    "mrx_debug_kw_host_leftmost", "mrx_debug_kw_host_sub",
     "mrx_debug_lines_piece", "mrx_debug_lines_syncs", "mrx_debug_lines_host",
     "mrx_debug_fields_group", "mrx_debug_fields_grid", "mrx_debug_fields_host",
     "mrx_debug_translate_piece", "mrx_debug_translate_syncs", "mrx_debug_translate_host",
@@ -1562,6 +1587,109 @@ class Keywords:
         """filter() enqueued on the current stream without a read-back, as CompiledRegex.filter_async."""
         _filter_async(self._lib, "mrx_kw_filter", self._h, _filter_flags("any", invert), batch, out)
 
+    def leftmost(self, texts, count: int = 0, span_cap: Optional[int] = None):
+        """The leftmost-longest matches of every text (include/mrx.h, mrx_kw_leftmost_dev): the non-overlapping matches
+        that sub replaces, with count > 0 the first `count` of each text.  (text_prefix int64[n+1], entries
+        int32[total], spans int32[total, 2]) in findall's shape, a text's matches in ascending start order; numpy arrays
+        for a list of bytes, device tensors for a DeviceBatch.  Without span_cap the call retries once with the total it
+        needs."""
+        count = int(count)
+        if isinstance(texts, DeviceBatch):
+            import torch
+            batch, dev, n = texts, texts.data.device, texts.n
+            stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+            prefix = torch.empty(n + 1, dtype=torch.int64, device=dev)
+            nbytes = int(batch.data.numel())
+            (ents, spans), total = _grow_call(
+                int(span_cap) if span_cap is not None else self._default_cap(nbytes, n),
+                lambda cap: (torch.empty(max(cap, 1), dtype=torch.int32, device=dev),
+                             torch.empty((max(cap, 1), 2), dtype=torch.int32, device=dev)),
+                lambda es, cap, total: batch.call(self._lib, "mrx_kw_leftmost", (self._h, count),
+                                                  (_ptr(prefix), _ptr(es[0]), _ptr(es[1]), cap, total, stream)),
+                grow=span_cap is None, only_larger=True)
+        else:
+            data, offsets = pack_texts(texts)
+            n, nbytes = len(offsets) - 1, int(offsets[-1])
+            prefix = np.zeros(n + 1, np.int64)
+            (ents, spans), total = _grow_call(
+                int(span_cap) if span_cap is not None else self._default_cap(nbytes, n),
+                lambda cap: (np.empty(max(cap, 1), np.int32), np.empty((max(cap, 1), 2), np.int32)),
+                lambda es, cap, total: self._lib.mrx_kw_leftmost_batch(self._h, count, data.ctypes.data,
+                                                                       offsets.ctypes.data, n, prefix.ctypes.data,
+                                                                       es[0].ctypes.data, es[1].ctypes.data, cap, total),
+                grow=span_cap is None, only_larger=True)
+        return prefix, ents[:total], spans[:total]
+
+    def leftmost_lists(self, texts, count: int = 0) -> List[List[Tuple[int, int, int]]]:
+        """leftmost() as a list per text of (entry, start, end) tuples."""
+        prefix, ents, spans = self.leftmost(texts, count)
+        if not isinstance(prefix, np.ndarray):
+            prefix, ents, spans = prefix.cpu().numpy(), ents.cpu().numpy(), spans.cpu().numpy()
+        return [[(int(ents[q]), int(spans[q, 0]), int(spans[q, 1])) for q in range(prefix[i], prefix[i + 1])]
+                for i in range(len(prefix) - 1)]
+
+    def _repl_batch(self, repl, device) -> "DeviceBatch":
+        """The replacements as a CSR batch on the device with 1 or len(self) rows; a wrong length raises before any
+        call."""
+        m = len(self)
+        if isinstance(repl, DeviceBatch):
+            if repl.offsets is None:
+                raise MrxError("the replacements must be a CSR DeviceBatch")
+            rows = repl
+        else:
+            reps = [_b(repl)] if isinstance(repl, (bytes, bytearray, memoryview, str)) else [_b(r) for r in repl]
+            rows = None
+        k = rows.n if rows is not None else len(reps)
+        if k != 1 and k != m:
+            raise MrxError("sub needs one replacement or one per entry (%d), not %d" % (m, k))
+        if rows is None:
+            import torch
+            data, offsets = pack_texts(reps)
+            d = torch.zeros(len(data) + 16, dtype=torch.uint8, device=device)   # (a pointer even for b"")
+            if len(data):
+                d[:len(data)] = torch.from_numpy(data).to(device)
+            rows = DeviceBatch(d, torch.from_numpy(offsets).to(device))
+        return rows
+
+    def sub(self, repl, texts, count: int = 0, out_cap: Optional[int] = None):
+        """Every text with its leftmost-longest matches replaced (include/mrx.h, mrx_kw_sub_dev), with count > 0 the
+        first `count` of each text; every other byte is copied unchanged.  `repl` is bytes / str (one for all), a
+        sequence of len(self) of them (a match of entry j takes repl[j]) or a CSR DeviceBatch with 1 or len(self) texts;
+        the bytes are taken verbatim.  A list of texts gives List[bytes]; a DeviceBatch gives a CSR DeviceBatch that
+        knows its byte count and longest text, so it feeds the next call without a read-back.  Without out_cap the call
+        retries once with the size it needs."""
+        return self.subn(repl, texts, count, out_cap)[0]
+
+    def subn(self, repl, texts, count: int = 0, out_cap: Optional[int] = None):
+        """sub(), plus the number of replacements in every text: (List[bytes], numpy int32[n]) for a list of texts,
+        (DeviceBatch, int32[n] device tensor) for a DeviceBatch."""
+        import torch
+        host = not isinstance(texts, DeviceBatch)
+        batch = DeviceBatch.from_texts([_b(t) for t in texts]) if host else texts
+        dev, n = batch.data.device, batch.n
+        rows = self._repl_batch(repl, dev)
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        out_off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        nsub = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+        totals = (C.c_int64 * 3)()
+        cap = int(out_cap) if out_cap is not None else int(batch.data.numel()) + int(batch.data.numel()) // 4 + 64
+        while True:
+            out = torch.empty(max(cap, 1), dtype=torch.uint8, device=dev)
+            rc = batch.call(self._lib, "mrx_kw_sub", (self._h, _ptr(rows.data), _ptr(rows.offsets), rows.n, int(count)),
+                            (_ptr(out_off), _ptr(out), cap, _ptr(nsub), None, C.cast(totals, C.c_void_p), stream))
+            if rc == MRX_E_CAPACITY and out_cap is None and int(totals[0]) > cap:
+                cap = int(totals[0])
+                continue
+            _check(rc)
+            break
+        nbytes = int(totals[0])
+        data = out[:nbytes].clone() if 4 * nbytes < cap else out[:nbytes]
+        res = DeviceBatch.csr_known(data, out_off, nbytes, int(totals[1]))
+        if not host:
+            return res, nsub[:n]
+        raw, off = res.data.cpu().numpy().tobytes(), out_off.cpu().numpy()
+        return [raw[off[i]:off[i + 1]] for i in range(n)], nsub[:n].cpu().numpy()
+
 
 class CompiledRegex:
     """Compile once, match many batches (reference: matcher.mojo:929-1163)."""
@@ -2396,6 +2524,12 @@ def keywords_filter(entries, texts, invert: bool = False):
     """The texts in which some entry occurs (with invert, the others): one keyword set for one batch;
     build_keywords keeps it for many."""
     return Keywords(entries).filter(texts, invert)
+
+
+def keywords_sub(entries, repl, texts, ignore_case: bool = False, count: int = 0):
+    """Keywords(entries, ignore_case).sub(repl, texts, count): one keyword set for one batch; build_keywords keeps it for
+    many."""
+    return Keywords(entries, ignore_case).sub(repl, texts, count)
 
 
 def lookup(entries, texts):

@@ -1,6 +1,6 @@
 // Keywords (include/mrx.h, "keywords"): one Aho-Corasick automaton over all entries of a keyword set, one pass over the
-// texts.  The automaton, the piece decomposition and the walk are in mrx_kw_bits.hpp; here are the handle, the launches
-// and the entry points.
+// texts.  The automaton, the piece decomposition and the walk are in mrx_kw_bits.hpp, the handle and what the kernels
+// share with leftmost and sub (mrx_kw_sub.hip) in mrx_kw_dev.hpp; here are the launches and the entry points.
 //
 //   k_kw_pieces    (CSR) ceil(len / P) per text; the existing exclusive scan makes the first piece of every text of it
 //   k_kw_count     a lane walks a piece and writes its hit count
@@ -29,29 +29,12 @@
 #include "mrx_host_batch.hpp"
 #include "mrx_internal.hpp"
 #include "mrx_kw_bits.hpp"
-
-// Immutable once mrx_kw_build* has returned: every call only reads it.
-struct mrx_kw {
-  int64_t m = 0, distinct = 0;
-  int32_t states = 1, ncls = 1, lmax = 0;
-  uint32_t flags = 0;
-  uint32_t* table = nullptr;    // [states * ncls]
-  uint8_t* cls = nullptr;       // [256]
-  mrx::KwMeta* meta = nullptr;  // [states]
-  ~mrx_kw() {
-    if (table) (void)hipFree(table);
-    if (cls) (void)hipFree(cls);
-    if (meta) (void)hipFree(meta);
-  }
-};
+#include "mrx_kw_dev.hpp"
 
 namespace mrx {
 namespace {
 
 constexpr uint32_t kKwFilterFlags = MRX_FILTER_INVERT | MRX_FILTER_ALL;
-constexpr int kKwBlock = 512;
-constexpr int kKwTierWords = 8192;   // 32 KiB of table rows in LDS: four workgroups, 2048 lanes, a CU
-constexpr unsigned kKwMaxGrid = 1024;
 
 std::atomic<int64_t> g_kw_piece{0};
 std::atomic<int> g_kw_lds{1};
@@ -72,51 +55,9 @@ size_t copy_text(const std::string& s, char* buf, size_t cap) {
   return s.size();
 }
 
-// what a walk reads of the handle
-struct KwView {
-  const uint32_t* table;
-  const uint8_t* cls;
-  const KwMeta* meta;
-  int32_t ncls, lmax;
-  uint32_t tier;   // states whose rows the workgroups keep in LDS
-};
-// the pieces of a call
-struct KwPieces {
-  int64_t P;
-  int64_t per_text;       // fixed pitch: pieces of every text
-  const int64_t* first;   // CSR: [n + 1], the first piece of every text
-  int64_t npieces;        // to walk (CSR: an upper bound)
-};
-
-// (at file scope, so that the walk's loads from them are LDS loads by their type, not loads through a generic pointer)
-__shared__ uint32_t s_kw_tab[kKwTierWords];
-__shared__ uint8_t s_kw_cls[256];
-
-struct KwDevTab {
-  const uint32_t* __restrict__ g;
-  int32_t ncls;
-  uint32_t tier;
-  __device__ __forceinline__ uint32_t word(uint32_t st, uint32_t byte) const {
-    // (the global pointer carries its address space: through a generic one the compiler merges the two loads into
-    // one flat load whose address is chosen per lane)
-    typedef const __attribute__((address_space(1))) uint32_t* GlobalWords;
-    const uint32_t i = st * (uint32_t)ncls + s_kw_cls[byte];
-    if (st < tier) return s_kw_tab[i];
-    return ((GlobalWords)g)[i];
-  }
-};
-
 __device__ __forceinline__ KwJob kw_piece_job(const TextBatch& B, int64_t n, const KwPieces& pc, int32_t lmax, int64_t piece) {
-  if (piece >= pc.npieces) return kw_no_job();
   int64_t i, lp;
-  if (pc.first) {
-    if (piece >= pc.first[n]) return kw_no_job();
-    i = gather_last_le(pc.first, 0, n, piece);
-    lp = piece - pc.first[i];
-  } else {
-    i = piece / pc.per_text;
-    lp = piece - i * pc.per_text;
-  }
+  if (!kw_piece_text(pc, n, piece, &i, &lp)) return kw_no_job();
   int32_t L = 0;
   const uint8_t* tp = B.text(i, &L);
   return kw_job(tp, L, lp, pc.P, lmax);
@@ -127,11 +68,7 @@ template <bool EMIT>
 __device__ __forceinline__ void kw_pass(const TextBatch& B, int64_t n, const KwView& V, const KwPieces& pc, int64_t* __restrict__ out,
                                         const int64_t* __restrict__ scan, int32_t* __restrict__ entries, int32_t* __restrict__ spans,
                                         int64_t cap) {
-  const uint32_t tier_words = V.tier * (uint32_t)V.ncls;
-  for (uint32_t k = threadIdx.x; k < tier_words; k += kKwBlock) s_kw_tab[k] = V.table[k];
-  if (threadIdx.x < 256) s_kw_cls[threadIdx.x] = V.cls[threadIdx.x];
-  __syncthreads();
-  const KwDevTab tab{V.table, V.ncls, V.tier};
+  const KwDevTab tab = kw_stage_tier(V);
   const int64_t nthreads = (int64_t)gridDim.x * kKwBlock;
   for (int64_t piece = (int64_t)blockIdx.x * kKwBlock + threadIdx.x; piece < pc.npieces; piece += nthreads) {
     if constexpr (EMIT) {
@@ -208,39 +145,9 @@ struct KwRun {
 // their counts and the scan.  known_total / known_max: a CSR batch's bounds (< 0: read back, one synchronisation).
 int kw_count_pieces(const mrx_kw* k, const TextBatch& b, int64_t n, int64_t known_total, int64_t known_max, KwRun& r, void* st) {
   hipStream_t hs = (hipStream_t)st;
-  int64_t bytes;
-  if (b.offsets) {
-    int64_t km = known_max;
-    bytes = known_total;
-    if (bytes < 0 || km < 0)
-      if (int rc = batch_bounds(b.offsets, n, st, &bytes, &km)) return rc;
-  } else {
-    bytes = n * b.pitch_longest();
-  }
-  const int64_t pinned = g_kw_piece.load();
   KwPieces& pc = r.pc;
-  pc.P = pinned > 0 ? pinned : kw_piece_rule(k->lmax, bytes);
-  pc.first = nullptr;
-  pc.per_text = 0;
-  if (b.offsets) {
-    int64_t* per = (int64_t*)scratch_get(sizeof(int64_t) * (size_t)n, st);
-    int64_t* first = (int64_t*)scratch_get(sizeof(int64_t) * (size_t)(n + 1), st);
-    int64_t* unused = (int64_t*)scratch_get(sizeof(int64_t), st);
-    if (!per || !first || !unused) return internal_fail(MRX_E_NO_DEVICE, "scratch allocation failed");
-    hipLaunchKernelGGL(k_kw_pieces, dim3(grid_for(n, 256, 4096)), dim3(256), 0, hs, b, n, pc.P, per);
-    MRX_HIP_TRY(hipGetLastError());
-    if (int rc = exclusive_scan(per, n, first, unused, st)) return rc;
-    pc.first = first;
-    pc.npieces = bytes / pc.P + n;   // ceil(len / P) <= len / P + 1 for every text
-  } else {
-    pc.per_text = (b.pitch_longest() + pc.P - 1) / pc.P;
-    if (pc.per_text < 1) pc.per_text = 1;
-    pc.npieces = n * pc.per_text;
-  }
-  const int lds = g_kw_lds.load();
-  int64_t tier = lds ? kKwTierWords / k->ncls : 0;
-  if (tier > k->states) tier = k->states;
-  r.view = KwView{k->table, k->cls, k->meta, k->ncls, k->lmax, (uint32_t)tier};
+  if (int rc = kw_plan_pieces(k->lmax, b, n, known_total, known_max, pc, st)) return rc;
+  r.view = kw_view(k->fwd, k->lmax);
   r.grid = grid_for(pc.npieces, kKwBlock, kKwMaxGrid);
   int64_t* cnt = (int64_t*)scratch_get(sizeof(int64_t) * (size_t)pc.npieces, st);
   r.scan = (int64_t*)scratch_get(sizeof(int64_t) * (size_t)(pc.npieces + 1), st);
@@ -325,6 +232,49 @@ int kw_filter(const mrx_kw* k, uint32_t flags, const TextBatch& b, BatchForm for
   return filter_compact(b, n, known_max, FilterWork{klen, keep, pos, rank}, o);
 }
 
+}  // namespace
+
+int64_t kw_pinned_piece() { return g_kw_piece.load(); }
+
+KwView kw_view(const mrx_kw_tables& t, int32_t lmax) {
+  int64_t tier = g_kw_lds.load() ? kKwTierWords / t.ncls : 0;
+  if (tier > t.states) tier = t.states;
+  return KwView{t.table, t.cls, t.meta, t.ncls, lmax, (uint32_t)tier};
+}
+
+int kw_plan_pieces(int32_t lmax, const TextBatch& b, int64_t n, int64_t known_total, int64_t known_max, KwPieces& pc, void* st) {
+  hipStream_t hs = (hipStream_t)st;
+  int64_t bytes;
+  if (b.offsets) {
+    int64_t km = known_max;
+    bytes = known_total;
+    if (bytes < 0 || km < 0)
+      if (int rc = batch_bounds(b.offsets, n, st, &bytes, &km)) return rc;
+  } else {
+    bytes = n * b.pitch_longest();
+  }
+  const int64_t pinned = g_kw_piece.load();
+  pc.P = pinned > 0 ? pinned : kw_piece_rule(lmax, bytes);
+  pc.first = nullptr;
+  pc.per_text = 0;
+  if (b.offsets) {
+    int64_t* per = (int64_t*)scratch_get(sizeof(int64_t) * (size_t)n, st);
+    int64_t* first = (int64_t*)scratch_get(sizeof(int64_t) * (size_t)(n + 1), st);
+    int64_t* unused = (int64_t*)scratch_get(sizeof(int64_t), st);
+    if (!per || !first || !unused) return internal_fail(MRX_E_NO_DEVICE, "scratch allocation failed");
+    hipLaunchKernelGGL(k_kw_pieces, dim3(grid_for(n, 256, 4096)), dim3(256), 0, hs, b, n, pc.P, per);
+    MRX_HIP_TRY(hipGetLastError());
+    if (int rc = exclusive_scan(per, n, first, unused, st)) return rc;
+    pc.first = first;
+    pc.npieces = bytes / pc.P + n;   // ceil(len / P) <= len / P + 1 for every text
+  } else {
+    pc.per_text = (b.pitch_longest() + pc.P - 1) / pc.P;
+    if (pc.per_text < 1) pc.per_text = 1;
+    pc.npieces = n * pc.per_text;
+  }
+  return MRX_OK;
+}
+
 // the checks that both builds share, and the automaton on the host
 int kw_build_host(const uint8_t* data, const int64_t* offsets, int64_t m, uint32_t flags, KwAutomaton* A) {
   std::string err;
@@ -339,7 +289,23 @@ int kw_check_build(int64_t m, uint32_t flags, const void* offsets, const void* o
   return MRX_OK;
 }
 
-int kw_upload(const KwAutomaton& A, void* stream, mrx_kw** out) {
+int kw_upload_tables(const KwAutomaton& A, void* stream, mrx_kw_tables* t) {
+  hipStream_t hs = (hipStream_t)stream;
+  t->states = A.states;
+  t->ncls = A.ncls;
+  MRX_HIP_TRY(hipMalloc((void**)&t->table, sizeof(uint32_t) * A.table.size()));
+  MRX_HIP_TRY(hipMalloc((void**)&t->cls, 256));
+  MRX_HIP_TRY(hipMalloc((void**)&t->meta, sizeof(KwMeta) * A.meta.size()));
+  MRX_HIP_TRY(hipMemcpyAsync(t->table, A.table.data(), sizeof(uint32_t) * A.table.size(), hipMemcpyHostToDevice, hs));
+  MRX_HIP_TRY(hipMemcpyAsync(t->cls, A.cls.data(), 256, hipMemcpyHostToDevice, hs));
+  MRX_HIP_TRY(hipMemcpyAsync(t->meta, A.meta.data(), sizeof(KwMeta) * A.meta.size(), hipMemcpyHostToDevice, hs));
+  return MRX_OK;
+}
+
+namespace {
+
+// the handle of a built automaton; data / offsets: the caller's entries on the host, kept folded for the reversed build
+int kw_upload(const KwAutomaton& A, const uint8_t* data, const int64_t* offsets, void* stream, mrx_kw** out) {
   hipStream_t hs = (hipStream_t)stream;
   mrx_kw* k = new mrx_kw();
   struct Guard {   // the handle goes back on every early way out
@@ -348,16 +314,17 @@ int kw_upload(const KwAutomaton& A, void* stream, mrx_kw** out) {
   } guard{k};
   k->m = A.m;
   k->distinct = A.distinct;
-  k->states = A.states;
-  k->ncls = A.ncls;
   k->lmax = A.lmax;
   k->flags = A.flags;
-  MRX_HIP_TRY(hipMalloc((void**)&k->table, sizeof(uint32_t) * A.table.size()));
-  MRX_HIP_TRY(hipMalloc((void**)&k->cls, 256));
-  MRX_HIP_TRY(hipMalloc((void**)&k->meta, sizeof(KwMeta) * A.meta.size()));
-  MRX_HIP_TRY(hipMemcpyAsync(k->table, A.table.data(), sizeof(uint32_t) * A.table.size(), hipMemcpyHostToDevice, hs));
-  MRX_HIP_TRY(hipMemcpyAsync(k->cls, A.cls.data(), 256, hipMemcpyHostToDevice, hs));
-  MRX_HIP_TRY(hipMemcpyAsync(k->meta, A.meta.data(), sizeof(KwMeta) * A.meta.size(), hipMemcpyHostToDevice, hs));
+  k->entry_off.assign((size_t)A.m + 1, 0);
+  for (int64_t j = 0; j <= A.m && A.m > 0; ++j) k->entry_off[(size_t)j] = offsets[j] - offsets[0];
+  k->entry_data.resize((size_t)k->entry_off[(size_t)A.m]);
+  for (size_t q = 0; q < k->entry_data.size(); ++q) {
+    uint8_t c = data[offsets[0] + (int64_t)q];
+    if ((A.flags & MRX_KW_IGNORE_CASE) && c >= 'A' && c <= 'Z') c |= 0x20;
+    k->entry_data[q] = c;
+  }
+  if (int rc = kw_upload_tables(A, stream, &k->fwd)) return rc;
   MRX_HIP_TRY(hipStreamSynchronize(hs));   // the automaton's host copy goes with this call
   guard.k = nullptr;
   *out = k;
@@ -376,7 +343,7 @@ int mrx_kw_build(const uint8_t* data, const int64_t* offsets, int64_t m, uint32_
   if (m > 0 && offsets[m] > offsets[0] && !data) return internal_fail(MRX_E_ARGUMENT, "null argument");
   KwAutomaton A;
   if (int rc = kw_build_host(data, offsets, m, flags, &A)) return rc;
-  return kw_upload(A, stream, out);
+  return kw_upload(A, data, offsets, stream, out);
 }
 int mrx_kw_build_dev(const uint8_t* d_data, const int64_t* d_offsets, int64_t m, uint32_t flags, void* stream, mrx_kw** out) {
   if (int rc = kw_check_build(m, flags, d_offsets, out)) return rc;
@@ -396,14 +363,14 @@ int mrx_kw_build_dev(const uint8_t* d_data, const int64_t* d_offsets, int64_t m,
   for (int64_t& o : off) o -= base;
   KwAutomaton A;
   if (int rc = kw_build_host(data.data(), off.data(), m, flags, &A)) return rc;
-  return kw_upload(A, stream, out);
+  return kw_upload(A, data.data(), off.data(), stream, out);
 }
 void mrx_kw_free(mrx_kw* k) { delete k; }
 int64_t mrx_kw_size(const mrx_kw* k) { return k ? k->m : 0; }
 int64_t mrx_kw_distinct(const mrx_kw* k) { return k ? k->distinct : 0; }
 size_t mrx_kw_describe(const mrx_kw* k, char* buf, size_t cap) {
   if (!k) return copy_text("keywords: null", buf, cap);
-  return copy_text(kw_describe_text(k->m, k->distinct, k->states, k->ncls, k->lmax, k->flags), buf, cap);
+  return copy_text(kw_describe_text(k->m, k->distinct, k->fwd.states, k->fwd.ncls, k->lmax, k->flags), buf, cap);
 }
 
 int mrx_kw_contains_dev(const mrx_kw* k, const uint8_t* d_data, const int64_t* d_offsets, int64_t n, uint8_t* d_flag,

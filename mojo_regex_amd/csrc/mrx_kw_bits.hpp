@@ -58,6 +58,29 @@ MRX_HD KwJob kw_job(const uint8_t* tp, int64_t L, int64_t lp, int64_t P, int32_t
 }
 MRX_HD KwJob kw_no_job() { return KwJob{nullptr, 0, 0, 0}; }
 
+// The pieces of a call, numbered text-major.  Fixed pitch: every text has per_text of them, so piece -> text is a
+// division.  CSR: first[n + 1] is the first piece of every text and piece -> text a bisection of it; npieces is then an
+// upper bound, and the pieces beyond the last text's do nothing.
+struct KwPieces {
+  int64_t P;
+  int64_t per_text;       // fixed pitch: pieces of every text
+  const int64_t* first;   // CSR: [n + 1], the first piece of every text
+  int64_t npieces;        // to walk (CSR: an upper bound)
+};
+// the text of a piece and the piece's number inside it; false: the piece lies behind the last text's
+MRX_HD bool kw_piece_text(const KwPieces& pc, int64_t n, int64_t piece, int64_t* i, int64_t* lp) {
+  if (piece >= pc.npieces) return false;
+  if (pc.first) {
+    if (piece >= pc.first[n]) return false;
+    *i = gather_last_le(pc.first, 0, n, piece);
+    *lp = piece - pc.first[*i];
+  } else {
+    *i = piece / pc.per_text;
+    *lp = piece - *i * pc.per_text;
+  }
+  return true;
+}
+
 // The piece size without a pin (mrx_debug_kw_piece): the warm-up, Lmax - 1 bytes, is at most an eighth of the piece,
 // and a piece has 1024 bytes at least (measured: 8 % faster than 256 on 1 KiB texts and on texts of 16 MiB alike,
 // profiles/keywords.md) -- unless the batch then has fewer than 2^18 pieces, too few to fill the device: the piece is
