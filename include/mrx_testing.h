@@ -230,6 +230,9 @@ int mrx_debug_lines_host(uint32_t flags, uint8_t sep, const uint8_t* data, const
  * the pin in force (0 = the rule).  The kernel reports itself as "k_fields" through mrx_last_kernel_name().  Results are
  * the same. */
 int mrx_debug_fields_group(int lanes);
+/* Fields: the G, the lanes that shared a text, of the last launch on this process, pinned or chosen by the rule (0 = no
+ * launch yet; a batch without texts launches nothing).  Process-wide, like mrx_last_kernel_name. */
+int mrx_debug_fields_last_group(void);
 /* Fields: `workgroups` > 0 caps the grid, so that a test makes one wavefront run many rounds of texts without millions
  * of them, as mrx_debug_parse_grid does.  0 (default) = no cap of its own.  Results are the same. */
 void mrx_debug_fields_grid(int workgroups);

@@ -371,6 +371,7 @@ def load_library():
                                              C.c_int64, i32p, i32p, i64p, C.c_void_p]),
         "mrx_fields_batch": (C.c_int, [C.c_uint32, C.c_uint8, i32p, C.c_int32, u8p, i64p, C.c_int64, i32p, i32p, i64p]),
         "mrx_debug_fields_group": (C.c_int, [C.c_int]),
+        "mrx_debug_fields_last_group": (C.c_int, []),
         "mrx_debug_fields_grid": (None, [C.c_int]),
         "mrx_debug_fields_host": (C.c_int, [C.c_uint32, C.c_uint8, i32p, C.c_int32, u8p, i64p, C.c_int64, i32p, i32p,
                                             i64p]),
@@ -457,7 +458,7 @@ TESTING_SYMBOLS = [
     "mrx_debug_kw_piece", "mrx_debug_kw_tier", "mrx_debug_kw_host_findall",
     "mrx_debug_kw_host_leftmost", "mrx_debug_kw_host_sub",
     "mrx_debug_lines_piece", "mrx_debug_lines_syncs", "mrx_debug_lines_host",
-    "mrx_debug_fields_group", "mrx_debug_fields_grid", "mrx_debug_fields_host",
+    "mrx_debug_fields_group", "mrx_debug_fields_last_group", "mrx_debug_fields_grid", "mrx_debug_fields_host",
     "mrx_debug_translate_piece", "mrx_debug_translate_syncs", "mrx_debug_translate_host",
     "mrx_debug_strip_host",
 ]
@@ -612,11 +613,14 @@ class DeviceBatch:
             fn_csr, fn_known, fn_strided = fns
         else:
             (fn_csr, fn_strided), fn_known = op, None
+        # texts without a byte: a tensor of no elements has no address, and some entry points refuse a null d_data when
+        # n > 0 (sets, captures_all) where others take it -- every batch passes a pointer, as format's text columns do
+        data = _ptr(self.data) or _ptr(_no_bytes(self.data.device))
         if self.offsets is None:
-            return fn_strided(*head, _ptr(self.data), self.stride, _ptr(self.lens), self.length, self.n, *tail)
+            return fn_strided(*head, data, self.stride, _ptr(self.lens), self.length, self.n, *tail)
         if fn_known is not None and self._end_offset is not None:
-            return fn_known(*head, _ptr(self.data), _ptr(self.offsets), self.n, self._end_offset, self._max_len, *tail)
-        return fn_csr(*head, _ptr(self.data), _ptr(self.offsets), self.n, *tail)
+            return fn_known(*head, data, _ptr(self.offsets), self.n, self._end_offset, self._max_len, *tail)
+        return fn_csr(*head, data, _ptr(self.offsets), self.n, *tail)
 
     def csr_offsets(self):
         """CSR offsets for the generic kernels (built on device for strided batches)."""
@@ -822,8 +826,13 @@ class DeviceBatch:
             if t is None or t.dtype != torch.int64 or not t.is_contiguous() or t.numel() < need:
                 raise MrxError("out needs out_data uint8[out_cap], out_offsets int64[n + 1], totals int64[2]")
         stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        _check(self.call(load_library(), "mrx_translate", args,
-                         (_ptr(out_data), int(out_data.numel()), _ptr(out_offsets), _ptr(totals), None, stream)))
+        src = self
+        if not (delete or squeeze) and self.offsets is not None and (self._end_offset or 0) > self.data.numel():
+            # The same-length form tells from end_offset whether the region fits out_data (include/mrx.h), so a loose
+            # bound would be refused as a capacity; offsets[n] never exceeds the data's size, which is a bound as good.
+            src = DeviceBatch.csr_known(self.data, self.offsets, int(self.data.numel()), self._max_len)
+        _check(src.call(load_library(), "mrx_translate", args,
+                        (_ptr(out_data), int(out_data.numel()), _ptr(out_offsets), _ptr(totals), None, stream)))
 
     def lower(self):
         """bytes.lower() of every text: the ASCII letters, as Python's (translate with its table)."""
@@ -1161,6 +1170,17 @@ def _row_order(values: "DeviceBatch", counts, sort: Optional[str], top: Optional
 
 def _ptr(t) -> int:
     return 0 if t is None else int(t.data_ptr())
+
+
+_NO_BYTES = {}
+
+
+def _no_bytes(device):
+    """16 zero bytes on `device`, allocated once: the data pointer of a batch whose texts hold no byte."""
+    import torch
+    if device not in _NO_BYTES:
+        _NO_BYTES[device] = torch.zeros(16, dtype=torch.uint8, device=device)
+    return _NO_BYTES[device]
 
 
 def _grow_call(cap, alloc, call, grow=True, only_larger=False):

@@ -38,6 +38,7 @@ constexpr size_t kFieldsMaxLds = 32768;     // of row staging per workgroup: mor
 
 std::atomic<int> g_fields_group{0};   // mrx_debug_fields_group(): the pinned G (0 = the rule)
 std::atomic<int> g_fields_grid{0};    // mrx_debug_fields_grid(): workgroups at most (0 = no cap of its own)
+std::atomic<int> g_fields_last_group{0};   // mrx_debug_fields_last_group(): the G of the last launch (0 = none yet)
 
 struct FieldsOut {
   int32_t* rows;
@@ -159,6 +160,7 @@ int launch(const TextBatch& b, int64_t n, const FieldsPlan& p, int g, const Fiel
   }
   MRX_HIP_TRY(hipGetLastError());
   set_last_kernel("k_fields");
+  g_fields_last_group.store(g, std::memory_order_relaxed);
   return MRX_OK;
 }
 
@@ -240,6 +242,7 @@ int mrx_debug_fields_group(int lanes) {
   return g_fields_group.load();
 }
 void mrx_debug_fields_grid(int workgroups) { g_fields_grid = workgroups > 0 ? workgroups : 0; }
+int mrx_debug_fields_last_group(void) { return g_fields_last_group.load(); }
 
 int mrx_debug_fields_host(uint32_t flags, uint8_t delim, const int32_t* columns, int32_t f, const uint8_t* data,
                           const int64_t* offsets, int64_t n, int32_t* rows, int32_t* nf, int64_t* prefix) {
