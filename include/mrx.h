@@ -758,6 +758,62 @@ int mrx_take_strided_dev(const uint8_t* d_data, int64_t stride, const int32_t* d
                          const int64_t* d_index, int64_t k, int64_t* d_out_offsets, uint8_t* d_out_data, int64_t out_cap,
                          int64_t* d_totals, int64_t* totals, void* stream);
 
+/* ---- sorted index: bisect, prefix ranges and the longest prefix against sorted entries ----
+ * bisect.bisect_left / bisect_right on a sorted vocabulary, look prefix file, the merge step of join and comm, a route or
+ * block table by prefix: where sort puts one batch in order, a sorted index answers questions of that order for other
+ * batches.  It is an immutable handle built once from a batch of m texts, the ENTRIES, in any layout, and probed by any
+ * number of later batches, as a dictionary is.  The order is sort's, word for word: bytewise and unsigned, a proper prefix
+ * first ("" < "a" < "a\0" < "aa"), equal entries in ascending original index.  POSITIONS are positions 0..m in that
+ * sorted order; order[p] is the original index of the entry at position p.
+ * Search: d_lo and d_hi are int64[n] on the device, and `mode` is one of
+ *   MRX_SORTED_EQUAL    d_lo[i] = bisect_left(sorted, text i), d_hi[i] = bisect_right(sorted, text i): the entries equal
+ *                       to text i stand at [lo, hi), and lo == hi is the insertion point when there is none
+ *   MRX_SORTED_PREFIX   [d_lo[i], d_hi[i]) is exactly the positions whose entry begins with text i; without one,
+ *                       lo == hi == bisect_left(text i).  The empty text gives [0, m)
+ *   MRX_SORTED_LONGEST  d_lo[i] is the lowest position of the longest entry that is a prefix of text i (an entry equal to
+ *                       the text counts, and so does the empty entry), -1 when no entry is one; d_hi[i] is that
+ *                       entry's length, or -1
+ * and any other value MRX_E_ARGUMENT.  Either output may be NULL, but not both when n > 0.  Exactly [0, n) of a given
+ * array is written; n == 0 writes nothing.  m == 0 is a valid handle: EQUAL and PREFIX answer 0, 0 and LONGEST -1, -1.
+ * mrx_sorted_search_* enqueues one kernel and returns: it needs no scratch, uses no atomics, reads nothing back and never
+ * synchronises.  The result is a pure function of the entries and the text.  The handle is immutable after the build, so
+ * concurrent searches on one handle, from several threads and on several streams, are safe.  A lane takes a probe and
+ * runs about log2(m) dependent comparisons, each from the depth it has already proven against both of its bounds, so a
+ * prefix that the neighbourhood shares is read once; a text of many KiB is compared by its one lane: correct, not fast.
+ * LONGEST repeats a bisect_right on a shrinking prefix of the text until the entry in front of it is a prefix: one to
+ * three rounds for typical tables, at most one per byte of the text.
+ * Build: mrx_sorted_build_* sorts with mrx_sort_dev's own rounds, so it synchronises the stream once per round as that
+ * call does, once more to learn the entries' byte count, which sizes the copy, and once at its end.  The handle owns
+ * plain device memory, not the per-call scratch arena: a packed copy of the entries in sorted order (made with filter's
+ * byte movers, padded as the dictionary's copy is), and PER ENTRY 8 bytes of offsets, 8 bytes of `order` and 9 bytes of
+ * search aid (the entry's first 8 bytes as a big-endian word and how many of them exist), beside 9 KiB of fence posts
+ * (every ceil(m / 1024)-th of those keys).  So the caller's batch may be freed as soon as the build returns.  Scratch:
+ * sort's, then 8 bytes an entry.  m >= 2^31: MRX_E_ARGUMENT, as for sort.  On any error *out is left as it was.
+ * mrx_sorted_free(NULL) is a no-op; a handle must not be freed while a call on it is still running on some stream.
+ * mrx_sorted_size is m, mrx_sorted_distinct the number of different entries (both 0 for NULL).  mrx_sorted_order_dev
+ * copies order, int64[m], into the caller's device array on `stream` (a device-to-device copy, nothing read back).
+ * MRX_E_ARGUMENT, before any device call: negative n or m; a bad pitch; a null handle; a null required pointer
+ * (d_offsets; out for a build; d_order when m > 0; both of d_lo and d_hi when n > 0); an unknown mode.
+ * Reads: as distinct, a text's bytes are fetched as the aligned 16-byte words that hold them, so up to 15 bytes in front
+ * of a text's first byte and behind its last one are read (never used: they are masked before a comparison sees them) and
+ * no word is read for an empty text.  That holds for the probed batch and, during the build, for the entries; the
+ * handle's copy is padded so that the aligned words around its first and last entry are the handle's own. */
+#define MRX_SORTED_EQUAL 0u
+#define MRX_SORTED_PREFIX 1u
+#define MRX_SORTED_LONGEST 2u
+typedef struct mrx_sorted mrx_sorted;
+int mrx_sorted_build_dev(const uint8_t* d_data, const int64_t* d_offsets, int64_t m, void* stream, mrx_sorted** out);
+int mrx_sorted_build_strided_dev(const uint8_t* d_data, int64_t stride, const int32_t* d_lens, int32_t len, int64_t m,
+                                 void* stream, mrx_sorted** out);
+void mrx_sorted_free(mrx_sorted* s);
+int64_t mrx_sorted_size(const mrx_sorted* s);
+int64_t mrx_sorted_distinct(const mrx_sorted* s);
+int mrx_sorted_order_dev(const mrx_sorted* s, int64_t* d_order, void* stream);
+int mrx_sorted_search_dev(const mrx_sorted* s, uint32_t mode, const uint8_t* d_data, const int64_t* d_offsets, int64_t n,
+                          int64_t* d_lo, int64_t* d_hi, void* stream);
+int mrx_sorted_search_strided_dev(const mrx_sorted* s, uint32_t mode, const uint8_t* d_data, int64_t stride,
+                                  const int32_t* d_lens, int32_t len, int64_t n, int64_t* d_lo, int64_t* d_hi, void* stream);
+
 /* ---- numbers: pieces parsed to int64 and float64 on the device ----
  * The step from bytes to numbers: int(piece), int(piece, 16) and float(piece) for every text of a batch, or for the
  * bytes under every span that findall, split or captures_all left on the device -- read where they lie, inside the
@@ -1336,6 +1392,11 @@ int mrx_take_batch(const uint8_t* data, const int64_t* offsets, int64_t n, const
  * texts are copied in, a dictionary is built, probed once and freed; index int64[n] receives the result. */
 int mrx_dict_lookup_batch(const uint8_t* dict_data, const int64_t* dict_offsets, int64_t m, const uint8_t* data,
                           const int64_t* offsets, int64_t n, int64_t* index);
+/* mrx_sorted_build_dev and mrx_sorted_search_dev on host buffers: the entries (entry_data, entry_offsets int64[m + 1]) and
+ * the texts are copied in, an index is built, searched once in `mode` and freed; lo and hi int64[n] receive the result
+ * (either may be NULL, not both when n > 0). */
+int mrx_sorted_search_batch(const uint8_t* entry_data, const int64_t* entry_offsets, int64_t m, uint32_t mode,
+                            const uint8_t* data, const int64_t* offsets, int64_t n, int64_t* lo, int64_t* hi);
 int mrx_match_first_batch(const mrx_handle* h, const uint8_t* data,
                           const int64_t* offsets, int64_t n, int32_t* start,
                           int32_t* end);

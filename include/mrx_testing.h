@@ -168,6 +168,16 @@ void mrx_debug_sort_grid(int workgroups);
 /* Sort: the number of 8-byte refinement rounds, each with one synchronisation of the stream, that the calling thread's
  * last sort call took (0 for a batch without texts, and before any call). */
 int mrx_debug_sort_rounds(void);
+/* Sorted index (include/mrx.h): `workgroups` > 0 caps the grids of its kernels (4 wavefronts each), so that a test makes
+ * a lane search several probes, a grid's stride apart, without a batch of millions of texts.  0 (default) = no cap.  The
+ * search reports itself as "k_sorted_search" through mrx_last_kernel_name().  Results are the same. */
+void mrx_debug_sorted_grid(int workgroups);
+/* Sorted index: which search aids every later search uses, as a mask: 1 = the key array (the entries' first words are
+ * searched with 8-byte loads before any entry's bytes), 2 = the fence posts in LDS above it (they need the keys: 2 alone
+ * is 0).  0 = the plain binary search over the entries' bytes.  -1 restores the default, any other negative value changes
+ * nothing.  Returns the mask in force.  A handle holds both aids whatever the mask was at its build.  Results are the
+ * same (profiles/sorted.md has the times). */
+int mrx_debug_sorted_aids(int mask);
 /* Numbers (include/mrx.h): the one kernel reports itself as "k_parse" through mrx_last_kernel_name().  Its grid is a
  * lane per row, capped as extract's; `workgroups` > 0 caps it further (4 wavefronts each), so that a test makes one
  * wavefront run several rounds of 64 rows without millions of them.  0 (default) = no cap of its own.  Results are the

@@ -33,6 +33,9 @@ argument meaning, a *batch* of texts instead of one text:
     (none: sorted(...) on the host)               sort_texts / DeviceBatch.argsort / take / sort, and sort= /
                                                   top= of value_counts and distinct: the bytewise order of a
                                                   batch's texts, and the texts at given indices as a new batch
+    (none: bisect / startswith on the host)       SortedIndex / build_sorted_index / searchsorted: bisect,
+                                                  the entries that begin with a text and the longest entry
+                                                  that is a prefix of it, against sorted entries
     (none: int(m.get_match_text()) per match)     numbers / parse_numbers / CompiledRegex.numbers /
                                                   DeviceBatch.parse / parse_spans: pieces as int64 / float64
     (none: "%s %d\\n" % row on the host)          format_records / format_numbers / format_records_async:
@@ -63,9 +66,11 @@ from .api import (  # noqa: F401
     MrxError,
     PatternSet,
     RegexSyntaxError,
+    SortedIndex,
     UnsupportedPattern,
     build_dictionary,
     build_keywords,
+    build_sorted_index,
     captures_all,
     clear_regex_cache,
     compile_regex,
@@ -90,6 +95,7 @@ from .api import (  # noqa: F401
     pack_texts,
     parse_numbers,
     search,
+    searchsorted,
     sort_texts,
     split,
     strip_texts,

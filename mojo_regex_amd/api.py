@@ -264,6 +264,19 @@ def load_library():
         "mrx_dict_filter_strided_dev": (C.c_int, [H, C.c_uint32, u8p, C.c_int64, i32p, C.c_int32, C.c_int64, i64p, i64p,
                                                   i64p, u8p, C.c_int64, i64p, C.c_void_p, C.c_void_p]),
         "mrx_dict_lookup_batch": (C.c_int, [u8p, i64p, C.c_int64, u8p, i64p, C.c_int64, i64p]),
+        # sorted index: build as a dictionary's; search: (handle, mode) | the batch | (lo, hi, stream)
+        "mrx_sorted_build_dev": (C.c_int, [u8p, i64p, C.c_int64, C.c_void_p, C.POINTER(H)]),
+        "mrx_sorted_build_strided_dev": (C.c_int, [u8p, C.c_int64, i32p, C.c_int32, C.c_int64, C.c_void_p, C.POINTER(H)]),
+        "mrx_sorted_free": (None, [H]),
+        "mrx_sorted_size": (C.c_int64, [H]),
+        "mrx_sorted_distinct": (C.c_int64, [H]),
+        "mrx_sorted_order_dev": (C.c_int, [H, i64p, C.c_void_p]),
+        "mrx_sorted_search_dev": (C.c_int, [H, C.c_uint32, u8p, i64p, C.c_int64, i64p, i64p, C.c_void_p]),
+        "mrx_sorted_search_strided_dev": (C.c_int, [H, C.c_uint32, u8p, C.c_int64, i32p, C.c_int32, C.c_int64, i64p, i64p,
+                                                    C.c_void_p]),
+        "mrx_sorted_search_batch": (C.c_int, [u8p, i64p, C.c_int64, C.c_uint32, u8p, i64p, C.c_int64, i64p, i64p]),
+        "mrx_debug_sorted_grid": (None, [C.c_int]),
+        "mrx_debug_sorted_aids": (C.c_int, [C.c_int]),
         # sort: the batch | (order, rank, d_totals, stream); take: the batch | (index, k, out_offsets, out_data, out_cap,
         # d_totals, totals, stream)
         "mrx_sort_dev": (C.c_int, [u8p, i64p, C.c_int64, i64p, i64p, i64p, C.c_void_p]),
@@ -431,6 +444,8 @@ EXPORTED_SYMBOLS = [
     "mrx_dict_filter_strided_dev", "mrx_dict_lookup_batch",
     "mrx_sort_dev", "mrx_sort_known_dev", "mrx_sort_strided_dev", "mrx_sort_batch",
     "mrx_take_dev", "mrx_take_known_dev", "mrx_take_strided_dev", "mrx_take_batch",
+    "mrx_sorted_build_dev", "mrx_sorted_build_strided_dev", "mrx_sorted_free", "mrx_sorted_size", "mrx_sorted_distinct",
+    "mrx_sorted_order_dev", "mrx_sorted_search_dev", "mrx_sorted_search_strided_dev", "mrx_sorted_search_batch",
     "mrx_parse_dev", "mrx_parse_strided_dev", "mrx_parse_spans_dev", "mrx_parse_spans_strided_dev", "mrx_parse_batch",
     "mrx_format_dev", "mrx_format_batch",
     "mrx_kw_build", "mrx_kw_build_dev", "mrx_kw_free", "mrx_kw_size", "mrx_kw_distinct", "mrx_kw_describe",
@@ -453,6 +468,7 @@ TESTING_SYMBOLS = [
     "mrx_debug_set_route", "mrx_testing_set_run", "mrx_debug_filter_form", "mrx_debug_extract_grid",
     "mrx_debug_expand_grid", "mrx_debug_distinct_hash_mask", "mrx_debug_distinct_grid",
     "mrx_debug_sort_small", "mrx_debug_sort_grid", "mrx_debug_sort_rounds", "mrx_debug_parse_grid",
+    "mrx_debug_sorted_grid", "mrx_debug_sorted_aids",
     "mrx_debug_decode_lean", "mrx_debug_last_decode_lean", "mrx_testing_decode_expand",
     "mrx_debug_format_grid", "mrx_testing_format_one",
     "mrx_debug_kw_piece", "mrx_debug_kw_tier", "mrx_debug_kw_host_findall",
@@ -1472,6 +1488,122 @@ class Dictionary:
         if index is not None and (index.dtype != torch.int64 or not index.is_contiguous() or index.numel() < batch.n):
             raise MrxError("index must be a contiguous int64[n] tensor")
         _filter_async(self._lib, "mrx_dict_filter", self._h, _filter_flags("any", invert), batch, out, extra=(_ptr(index),))
+
+
+MRX_SORTED_EQUAL = 0
+MRX_SORTED_PREFIX = 1
+MRX_SORTED_LONGEST = 2
+_SORTED_MODES = {"equal": MRX_SORTED_EQUAL, "prefix": MRX_SORTED_PREFIX, "longest": MRX_SORTED_LONGEST}
+
+
+class SortedIndex:
+    """A batch of texts, the entries, kept in sorted order on the device and searched by any number of batches
+    (include/mrx.h, "sorted index"): bisect.bisect_left / bisect_right, the range of entries that begin with a text, and
+    the longest entry that is a prefix of a text.  `entries` is a list of texts or a DeviceBatch in any layout; the
+    handle keeps its own sorted copy.  The order is sort's: bytewise, unsigned, a proper prefix first, equal entries in
+    ascending original index.  Positions are positions 0..len() in that order; order[p] is the original index of the entry
+    at position p.  A DeviceBatch of texts gives device tensors, a list gives numpy arrays."""
+
+    def __init__(self, entries):
+        import torch
+        self._lib = load_library()
+        batch = entries if isinstance(entries, DeviceBatch) else DeviceBatch.from_texts([_b(t) for t in entries])
+        h = C.c_void_p()
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        _check(batch.call(self._lib, (self._lib.mrx_sorted_build_dev, self._lib.mrx_sorted_build_strided_dev), (),
+                          (stream, C.byref(h))))
+        self._h = h
+        self._entries = batch   # for `values` only: the handle searches its own copy
+        self._order = None
+        self._values = None
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None):
+                self._lib.mrx_sorted_free(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+    def __len__(self) -> int:
+        return int(self._lib.mrx_sorted_size(self._h))
+
+    @property
+    def distinct_count(self) -> int:
+        """How many of the entries are different."""
+        return int(self._lib.mrx_sorted_distinct(self._h))
+
+    @property
+    def order(self):
+        """int64[m], a device tensor: order[p] is the original index of the entry at sorted position p (fetched once)."""
+        if self._order is None:
+            import torch
+            order = torch.empty(len(self), dtype=torch.int64, device=self._entries.data.device)
+            stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+            _check(self._lib.mrx_sorted_order_dev(self._h, _ptr(order), stream))
+            self._order = order
+        return self._order
+
+    @property
+    def values(self) -> "DeviceBatch":
+        """The sorted entries as a DeviceBatch: entries.take(order), made on first use."""
+        if self._values is None:
+            self._values = self._entries.take(self.order)
+        return self._values
+
+    def search_async(self, batch: "DeviceBatch", mode, lo, hi):
+        """Enqueue a search on the current stream: mode is "equal", "prefix" or "longest" (or its MRX_SORTED_ value), lo
+        and hi int64[n] device tensors of the caller (either may be None, not both).  Nothing is read back."""
+        import torch
+        for t in (lo, hi):
+            if t is not None and (t.dtype != torch.int64 or not t.is_contiguous() or t.numel() < batch.n):
+                raise MrxError("lo and hi must be contiguous int64[n] tensors")
+        if lo is None and hi is None:
+            raise MrxError("give lo, hi or both")
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        _check(batch.call(self._lib, (self._lib.mrx_sorted_search_dev, self._lib.mrx_sorted_search_strided_dev),
+                          (self._h, int(_SORTED_MODES.get(mode, mode))), (_ptr(lo), _ptr(hi), stream)))
+
+    def _search(self, texts, mode: int, want_lo: bool = True, want_hi: bool = True):
+        import torch
+        if not isinstance(texts, DeviceBatch):
+            got = self._search(DeviceBatch.from_texts([_b(t) for t in texts]), mode, want_lo, want_hi)
+            return tuple(None if t is None else t.cpu().numpy() for t in got)
+        lo = torch.empty(texts.n, dtype=torch.int64, device=texts.data.device) if want_lo else None
+        hi = torch.empty(texts.n, dtype=torch.int64, device=texts.data.device) if want_hi else None
+        self.search_async(texts, mode, lo, hi)
+        return lo, hi
+
+    def searchsorted(self, texts, side: str = "left"):
+        """bisect.bisect_left (side="left") or bisect_right (side="right") of every text among the sorted entries:
+        int64[n]."""
+        if side not in ("left", "right"):
+            raise MrxError("side must be 'left' or 'right'")
+        return self._search(texts, MRX_SORTED_EQUAL, side == "left", side == "right")[side == "right"]
+
+    def equal_range(self, texts):
+        """(lo, hi): the entries equal to text i stand at positions [lo[i], hi[i]); lo == hi is the insertion point."""
+        return self._search(texts, MRX_SORTED_EQUAL)
+
+    def prefix_range(self, texts):
+        """(lo, hi): exactly the positions [lo[i], hi[i]) hold the entries that begin with text i."""
+        return self._search(texts, MRX_SORTED_PREFIX)
+
+    def longest_prefix(self, texts, lengths: bool = False):
+        """The lowest position of the longest entry that is a prefix of text i, or -1; with lengths=True, (positions,
+        lengths of those entries or -1)."""
+        pos, length = self._search(texts, MRX_SORTED_LONGEST, True, lengths)
+        return (pos, length) if lengths else pos
+
+    def index(self, texts):
+        """The lowest original index of an entry equal to text i, or -1: what Dictionary.lookup answers."""
+        import torch
+        if not isinstance(texts, DeviceBatch):
+            return self.index(DeviceBatch.from_texts([_b(t) for t in texts])).cpu().numpy()
+        lo, hi = self.equal_range(texts)
+        if len(self) == 0:
+            return torch.full_like(lo, -1)
+        return torch.where(lo < hi, self.order[lo.clamp(max=len(self) - 1)], torch.full_like(lo, -1))
 
 
 MRX_KW_IGNORE_CASE = 1
@@ -2533,6 +2665,27 @@ def strip_texts(texts, chars=None, left: bool = True, right: bool = True) -> Lis
 def build_dictionary(entries) -> Dictionary:
     """Dictionary(entries): a list of texts or a DeviceBatch."""
     return Dictionary(entries)
+
+
+def build_sorted_index(entries) -> SortedIndex:
+    """SortedIndex(entries): a list of texts or a DeviceBatch."""
+    return SortedIndex(entries)
+
+
+def searchsorted(entries, texts, side: str = "left"):
+    """bisect.bisect_left (or, with side="right", bisect_right) of every text among sorted(entries), through
+    mrx_sorted_search_batch: np.int64[n].  One index for one batch; build_sorted_index keeps it for many."""
+    if side not in ("left", "right"):
+        raise MrxError("side must be 'left' or 'right'")
+    lib = load_library()
+    es, bs = [_b(t) for t in entries], [_b(t) for t in texts]
+    edata, eoff = pack_texts(es)
+    data, off = pack_texts(bs)
+    pos = np.zeros(max(len(bs), 1), np.int64)
+    lo, hi = (pos.ctypes.data, None) if side == "left" else (None, pos.ctypes.data)
+    _check(lib.mrx_sorted_search_batch(edata.ctypes.data, eoff.ctypes.data, len(es), MRX_SORTED_EQUAL, data.ctypes.data,
+                                       off.ctypes.data, len(bs), lo, hi))
+    return pos[:len(bs)].copy()
 
 
 def build_keywords(entries, ignore_case: bool = False) -> Keywords:

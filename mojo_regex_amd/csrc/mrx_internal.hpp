@@ -171,6 +171,11 @@ struct DistinctGroups {
 int distinct_groups(const TextBatch& b, int64_t n, uint64_t mask, const DistinctGroups& g, void* stream);
 uint64_t distinct_hash_mask();                        // mrx_debug_distinct_hash_mask(): all ones unless a test set it
 unsigned distinct_grid(int64_t items, int64_t per);   // workgroups for `items` at `per` a workgroup, capped by the hook
+// mrx_sort.hip: mrx_sort_dev on a batch in either form, for a caller that keeps the order (the sorted index): d_order[n]
+// and d_totals[1] = {different texts}; known_max: the longest text (< 0 = not known).  Checks its arguments as
+// mrx_sort_dev does and synchronises once per round.
+int sort_order_of(const TextBatch& b, BatchForm form, int64_t n, int64_t known_max, int64_t* d_order, int64_t* d_totals,
+                  void* stream);
 // the scan timer of mrx_timing_scan_ms around a launch sequence: begin returns a token for end
 void* scan_timer_begin(void* stream);
 void scan_timer_end(void* token);

@@ -393,6 +393,12 @@ int known_check(int64_t end_offset, int64_t max_text_len) {
 }
 
 }  // namespace
+
+// mrx_internal.hpp: the sorted index's build
+int sort_order_of(const TextBatch& b, BatchForm form, int64_t n, int64_t known_max, int64_t* d_order, int64_t* d_totals,
+                  void* stream) {
+  return sort_run(b, form, n, known_max, d_order, nullptr, d_totals, stream);
+}
 }  // namespace mrx
 
 using namespace mrx;
