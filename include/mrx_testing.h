@@ -110,6 +110,20 @@ int mrx_debug_last_decode_lean(void);
  * negative or an array is NULL. */
 int mrx_testing_decode_expand(int64_t n, const uint32_t* f_even, const uint32_t* f_odd, const int32_t* start, const int32_t* pb,
                               int fixed_len, int32_t* counts, int32_t* spans);
+/* k_decode's tile store loops (the lean pass and the multi-pass loop of every record, slot and task form; not the dense
+ * row windows, not k_decode_rows): 0 = one span per lane and trip, an 8-byte store each (k_decode<..., false> in a kernel
+ * trace), anything else = two spans per lane and trip in one 16-byte store, single spans only at the ends of a
+ * wavefront's range (k_decode<..., true>; default).  Results are the same.  Environment: MRX_DECODE_STORE16=0. */
+void mrx_debug_decode_store16(int mode);
+/* Which of the two the last k_decode launch took (the streaming findall, its split and pieces forms): 1 = 16-byte
+ * stores, 0 = 8-byte stores (switch off, or k_decode_rows ran instead), -1 = no such launch yet.  Process-wide. */
+int mrx_debug_last_decode_store16(void);
+/* The index arithmetic of the 16-byte form on the host (decode_store_plan, csrc/mrx_decode_bits.hpp), for tests without
+ * a GPU.  A wavefront's nspan spans are the span indices pre0 .. pre0 + nspan - 1 of a buffer whose address / 8 has
+ * parity addr_parity; span_cap = capacity of the buffer in spans.  out = {odd, head, npairs, tail, nclip}: span k sits
+ * at tile slot k + odd; nclip spans leave -- span 0 alone when head, then npairs pairs from span `head` on, then one
+ * more span alone when tail.  Returns 0, or -1 when nspan is negative, addr_parity is not 0 or 1, or out is NULL. */
+int mrx_testing_decode_store_plan(int64_t pre0, int addr_parity, int nspan, int64_t span_cap, int32_t out[5]);
 /* include/mrx_comm.h, padded form of mrx_allgatherv_spans: its two device steps on buffers the caller fills as
  * ncclAllGather would have, so that the multi-rank arithmetic can be checked on one GPU.
  * meta_all: meta_stride int64 words per rank -- 2: {texts, spans}; 4: {texts (-1: that rank's arguments were invalid),

@@ -142,6 +142,9 @@ def load_library():
         "mrx_debug_last_decode_lean": (C.c_int, []),
         "mrx_testing_decode_expand": (C.c_int, [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                                 C.c_void_p, C.c_void_p]),
+        "mrx_debug_decode_store16": (None, [C.c_int]),
+        "mrx_debug_last_decode_store16": (C.c_int, []),
+        "mrx_testing_decode_store_plan": (C.c_int, [C.c_int64, C.c_int, C.c_int, C.c_int64, C.POINTER(C.c_int32)]),
         "mrx_release_scratch": (None, []),
         "mrx_debug_scratch_bytes": (C.c_size_t, []),
         "mrx_debug_scratch_in_use": (C.c_size_t, []),
@@ -470,6 +473,7 @@ TESTING_SYMBOLS = [
     "mrx_debug_sort_small", "mrx_debug_sort_grid", "mrx_debug_sort_rounds", "mrx_debug_parse_grid",
     "mrx_debug_sorted_grid", "mrx_debug_sorted_aids",
     "mrx_debug_decode_lean", "mrx_debug_last_decode_lean", "mrx_testing_decode_expand",
+    "mrx_testing_decode_store_plan",
     "mrx_debug_format_grid", "mrx_testing_format_one",
     "mrx_debug_kw_piece", "mrx_debug_kw_tier", "mrx_debug_kw_host_findall",
     "mrx_debug_kw_host_leftmost", "mrx_debug_kw_host_sub",
@@ -479,7 +483,8 @@ TESTING_SYMBOLS = [
     "mrx_debug_strip_host",
 ]
 # (hooks with a digit in their name, listed apart: the header scan of tests/test_host_tables.py reads [a-z_] names)
-TESTING_SYMBOLS_NUMBERED = ["mrx_debug_rec12", "mrx_testing_rec12_roundtrip"]
+TESTING_SYMBOLS_NUMBERED = ["mrx_debug_rec12", "mrx_testing_rec12_roundtrip", "mrx_debug_decode_store16",
+                            "mrx_debug_last_decode_store16"]
 COMM_SYMBOLS = [
     "mrx_comm_unique_id", "mrx_comm_init", "mrx_comm_free", "mrx_comm_rank", "mrx_comm_size",
     "mrx_comm_spans_staging_bytes", "mrx_comm_reserve",

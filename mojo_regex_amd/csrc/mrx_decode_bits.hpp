@@ -80,4 +80,34 @@ MRX_DECODE_HD void decode_expand_record(uint32_t f_even, uint32_t f_odd, int rst
   decode_expand_group<FIXED>(f_odd, pb + 16, rstart, fixed_len, emit);
 }
 
+// ---- the tile's store loop, two spans per lane (k_decode<..., STORE16 = true>) ----
+// A wavefront's spans are the absolute span indices pre0 .. pre0 + nspan - 1 of `spans`, 8 bytes each; the C ABI gives
+// `spans` 8-byte alignment only.  Two consecutive spans leave as one 16-byte store where the first of them lies on a
+// 16-byte boundary, that is where (address of spans / 8 + its index) is even.  odd = parity of that sum for the
+// wavefront's first span; the kernel puts span k at tile slot k + odd, so that the pairs which are aligned in memory are
+// aligned in the tile as well (one ds_read_b64 / ds_read_b128).  With odd the first span is the second half of a pair
+// that belongs to the wavefront in front: it leaves alone (the head), and so does the last span where the count behind
+// the head is odd (the tail).  Capacity is per span: only the nclip spans in front of span_cap leave, so a pair whose
+// second span would sit at span_cap has become the tail.  Nothing at or behind span_cap and nothing in front of pre0 is
+// part of the plan.  A later pass of a multi-pass wavefront calls this with pre0 + tb; TILE is even, so odd is the same
+// in every pass.
+struct DecodeStorePlan {
+  int odd;      // span k of the wavefront sits at tile slot k + odd
+  int nclip;    // spans that leave: min(nspan, span_cap - pre0), at least 0
+  int head;     // 1: span 0 leaves with an 8-byte store (tile slot 1)
+  int npairs;   // pair p = spans head + 2 p and head + 2 p + 1, tile slot odd + head + 2 p (even), one 16-byte store
+  int tail;     // 1: span head + 2 npairs leaves with an 8-byte store
+};
+MRX_DECODE_HD int decode_store_odd(int64_t pre0, int addr_parity) { return (int)((pre0 + addr_parity) & 1); }
+MRX_DECODE_HD DecodeStorePlan decode_store_plan(int64_t pre0, int addr_parity, int nspan, int64_t span_cap) {
+  DecodeStorePlan pl;
+  pl.odd = decode_store_odd(pre0, addr_parity);
+  const int64_t room = span_cap - pre0;
+  pl.nclip = room >= nspan ? nspan : room > 0 ? (int)room : 0;
+  pl.head = pl.odd && pl.nclip > 0 ? 1 : 0;
+  pl.npairs = (pl.nclip - pl.head) >> 1;
+  pl.tail = (pl.nclip - pl.head) & 1;
+  return pl;
+}
+
 }  // namespace mrx

@@ -2970,6 +2970,10 @@ constexpr int kScanTile = kScanBlock * kScanItems;
 // record arrives as three dwords {F even, F odd, meta}; everything behind the unpacking is the REC32 form's.
 // LEAN (PACK16 && REC32, neither VBASE nor DYN): wavefronts whose spans fit one tile take the lean pass (mrx_decode_bits.hpp);
 // the multi-pass and dense paths are the same code either way.  MRX_DECODE_LEAN=0 / mrx_debug_decode_lean(0) launches LEAN = false.
+// STORE16: the tile's store loops (lean and multi-pass) take two spans per lane and trip: one ds_read_b64 (ds_read_b128 with
+// int2 slots) and one 16-byte store (decode_store_tile16 below, decode_store_plan in mrx_decode_bits.hpp).  The tile is two
+// slots longer for the shift that aligns the pairs.  MRX_DECODE_STORE16=0 / mrx_debug_decode_store16(0) launches STORE16 = false,
+// whose code is the one-span loops'.
 template <int G, bool XOR>
 __device__ __forceinline__ int group_scan(int x);   // (DPP inclusive scan, defined with the sub() kernels below)
 
@@ -2984,8 +2988,32 @@ __device__ __forceinline__ int64_t wave_sum64(int64_t v) {
   return (int64_t)((uint64_t)s0 + ((uint64_t)s1 << 16) + ((uint64_t)s2 << 32));
 }
 
+// The spans of a tile pass to memory by plan `pl`: span k of the pass sits at tile slot k + pl.odd and goes to out + 2 k.
+// The head and the tail leave from lanes 0 and 1 in one 8-byte store instruction, the pairs between them two per lane.
+template <bool PACK16, class Slot>
+__device__ __forceinline__ void decode_store_tile16(const Slot* tile, const DecodeStorePlan pl, int32_t* out, int lane) {
+  if (lane < 2) {
+    const int k = lane == 0 ? 0 : pl.head + 2 * pl.npairs;
+    if (lane == 0 ? pl.head : pl.tail) {
+      if constexpr (PACK16) { const uint32_t v = tile[k + pl.odd]; mrx_stg_span(out + 2 * k, (int)(v >> 16), (int)(v & 0xFFFFu)); }
+      else { const int2 v = tile[k + pl.odd]; mrx_stg_span(out + 2 * k, v.x, v.y); }
+    }
+  }
+  const Slot* tp = tile + pl.odd + pl.head;   // an even slot: 8 bytes aligned with 4-byte slots, 16 with 8-byte slots
+  int32_t* op = out + 2 * pl.head;            // 16 bytes aligned
+  for (int p = lane; p < pl.npairs; p += 64) {
+    if constexpr (PACK16) {
+      const uint2 v = *(const uint2*)(tp + 2 * p);
+      mrx_stg_span2(op + 4 * p, (int)(v.x >> 16), (int)(v.x & 0xFFFFu), (int)(v.y >> 16), (int)(v.y & 0xFFFFu));
+    } else {
+      const int4 v = *(const int4*)(tp + 2 * p);
+      mrx_stg_span2(op + 4 * p, v.x, v.y, v.z, v.w);
+    }
+  }
+}
+
 template <bool PACK16, bool VBASE = false, bool REC32 = false, bool DYN = false, int TILE = kDecodeTile, bool REC12 = false,
-          bool LEAN = false>
+          bool LEAN = false, bool STORE16 = false>
 __global__ __launch_bounds__(kBlock) void k_decode(int64_t n, const int32_t* __restrict__ wave_nrecs,
                                                    const EvRec* __restrict__ recs, int64_t rec_row,
                                                    const int64_t* __restrict__ offsets,
@@ -3005,7 +3033,9 @@ __global__ __launch_bounds__(kBlock) void k_decode(int64_t n, const int32_t* __r
   static_assert(!REC12 || (REC32 && PACK16 && !VBASE && !DYN), "12-byte records: short texts at a fixed aligned pitch");
   static_assert(!LEAN || (REC32 && PACK16 && !VBASE && !DYN), "lean pass: two-word records, 16-bit positions, static tasks");
   using Slot = typename std::conditional<PACK16, uint32_t, int2>::type;
-  __shared__ Slot tile_all[kBlock / 64][TILE];
+  static_assert(TILE % 2 == 0, "a pass begins at an even span of its wavefront: one store parity for all passes");
+  __shared__ alignas(STORE16 ? 16 : alignof(Slot)) Slot tile_all[kBlock / 64][TILE + (STORE16 ? 2 : 0)];
+  const int addr_parity = STORE16 ? (int)(((uintptr_t)spans >> 3) & 1) : 0;
   __shared__ int dense_upto[kBlock / 64][64];   // dense path: spans of each of the wavefront's texts expanded so far
   constexpr int kDecodeTile = TILE, kDecodeDirect = 3 * TILE;   // (shadow the file-scope defaults)
   __shared__ int rel_all[DYN ? kBlock / 64 : 1][DYN ? kDynTexts : 1];   // DYN: spans of the task's texts before each text
@@ -3088,6 +3118,7 @@ __global__ __launch_bounds__(kBlock) void k_decode(int64_t n, const int32_t* __r
       }
     }
     const int64_t pre0 = wbase + base0 + wave_sum64(part);
+    const int odd = STORE16 ? decode_store_odd(pre0, addr_parity) : 0;   // (wave uniform) span k of a pass at tile slot k + odd
     int my_rel = 0, total_spans = 0;
     if (DYN) {
       __builtin_amdgcn_wave_barrier();
@@ -3126,6 +3157,7 @@ __global__ __launch_bounds__(kBlock) void k_decode(int64_t n, const int32_t* __r
         // chosen once per wavefront, the start as a max, and the record loads of load_batch above, whose first batch
         // has been under way since the top of the task.
         const int nrec = total_recs, nspan = total_spans;
+        const int my_rel_t = my_rel + odd;   // my text's first slot in the tile
         auto lean_pass = [&](auto fixed_tag) {
           constexpr bool FIXED = decltype(fixed_tag)::value;
           for (int j = 0; j < nrec; j += 64 * kDecodeBatch) {
@@ -3136,7 +3168,7 @@ __global__ __launch_bounds__(kBlock) void k_decode(int64_t n, const int32_t* __r
               const bool mine = j + u * 64 + lane < nrec;
               const uint32_t f_even = mine ? fe[u] : 0u, f_odd = mine ? fo[u] : 0u;
               const uint32_t meta = m3[u];
-              const int rel_t = __shfl(my_rel, (int)(meta >> 26));
+              const int rel_t = __shfl(my_rel_t, (int)(meta >> 26));
               uint32_t* tp = tile + (rel_t + (REC12 ? rec12_before(meta) : (int)(meta & kBefore)));   // the record's first span
               const int pb = REC12 ? 32 * rec12_pair(meta) : (int)(m2[u] >> 16) - kRecPosBias;
               const int rstart = REC12 ? rec12_start(meta) : (int)(m2[u] & 0xFFFFu);
@@ -3150,9 +3182,13 @@ __global__ __launch_bounds__(kBlock) void k_decode(int64_t n, const int32_t* __r
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        if constexpr (STORE16) {
+          decode_store_tile16<true>(tile, decode_store_plan(pre0, addr_parity, nspan, span_cap), spans + 2 * pre0, lane);
+        } else {
         for (int k = lane; k < nspan; k += 64) {
           const int64_t dst = pre0 + k;
           if (dst < span_cap) { const uint32_t v = tile[k]; mrx_stg_span(spans + 2 * dst, (int)(v >> 16), (int)(v & 0xFFFFu)); }
+        }
         }
         __builtin_amdgcn_wave_barrier();
         continue;
@@ -3293,8 +3329,8 @@ __global__ __launch_bounds__(kBlock) void k_decode(int64_t n, const int32_t* __r
               int st = nsb ? pb + ((31 - __builtin_clz(nsb)) >> 1) : rstart;
               if (fixed_len > 0) st = pb + kk - fixed_len;
               if (dst >= 0 && dst < kDecodeTile) {
-                if constexpr (PACK16) tile[dst] = ((uint32_t)st << 16) | (uint32_t)(pb + kk);
-                else tile[dst] = make_int2(st, pb + kk);
+                if constexpr (PACK16) tile[dst + odd] = ((uint32_t)st << 16) | (uint32_t)(pb + kk);
+                else tile[dst + odd] = make_int2(st, pb + kk);
               }
               ++dst;
               em &= em - 1;
@@ -3311,12 +3347,16 @@ __global__ __launch_bounds__(kBlock) void k_decode(int64_t n, const int32_t* __r
       __builtin_amdgcn_wave_barrier();
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
       const int cnt = total_spans - tb < kDecodeTile ? total_spans - tb : kDecodeTile;
+      if constexpr (STORE16) {
+        decode_store_tile16<PACK16>(tile, decode_store_plan(pre0 + tb, addr_parity, cnt, span_cap), spans + 2 * (pre0 + tb), lane);
+      } else {
       for (int k = lane; k < cnt; k += 64) {
         const int64_t dst = pre0 + tb + k;
         if (dst < span_cap) {
           if constexpr (PACK16) { const uint32_t v = tile[k]; mrx_stg_span(spans + 2 * dst, (int)(v >> 16), (int)(v & 0xFFFFu)); }
           else { const int2 v = tile[k]; mrx_stg_span(spans + 2 * dst, v.x, v.y); }
         }
+      }
       }
       __builtin_amdgcn_wave_barrier();
     }
@@ -5410,6 +5450,12 @@ int pieces_prepare(const mrx_handle* h, const Layout& lay, int64_t n, hipStream_
   return MRX_OK;
 }
 
+// k_decode's tile store loops (lean and multi-pass, every record, slot and task form; not the dense row windows): 0 = one
+// span per lane and trip in an 8-byte store, anything else = two in a 16-byte store (k_decode<..., STORE16 = true>,
+// decode_store_plan in mrx_decode_bits.hpp).  MRX_DECODE_STORE16 / mrx_debug_decode_store16
+std::atomic<int> g_decode_store16{env_int("MRX_DECODE_STORE16", 1)};
+std::atomic<int> g_last_decode_store16{-1};   // the last k_decode launch: 1 = STORE16 instantiation, 0 = not, -1 = none yet
+
 // findall over the pieces: scan, prefix sums and decode as for any CSR batch, then the texts'
 // entries of the per-piece prefix sums
 int findall_pieces(const mrx_handle* h, const Pieces& pc, int64_t n, int64_t* d_prefix, int32_t* d_spans,
@@ -5439,6 +5485,13 @@ int findall_pieces(const mrx_handle* h, const Pieces& pc, int64_t n, int64_t* d_
   }
   hipLaunchKernelGGL(k_scan_local<int32_t>, dim3((unsigned)ntiles), dim3(kScanBlock), 0, s, d_nrecs + nw, nw, d_wbase,
                      d_tsum);
+  const bool st16 = g_decode_store16 != 0;
+  g_last_decode_store16 = st16 ? 1 : 0;
+  if (st16)
+    hipLaunchKernelGGL((k_decode<false, true, false, false, kDecodeTile, false, false, true>), dim3(grid_for(nv, kBlock)),
+                       dim3(kBlock), 0, s, nv, d_nrecs, d_recs, (int64_t)0, pc.lay.offsets, d_vcounts, d_wbase, d_tsum,
+                       d_vprefix, d_spans, span_cap, p.st_fixed_len, d_total, pc.vbase);
+  else
   hipLaunchKernelGGL((k_decode<false, true>), dim3(grid_for(nv, kBlock)), dim3(kBlock), 0, s, nv, d_nrecs, d_recs,
                      (int64_t)0, pc.lay.offsets, d_vcounts, d_wbase, d_tsum, d_vprefix, d_spans, span_cap, p.st_fixed_len,
                      d_total, pc.vbase);
@@ -5511,18 +5564,29 @@ static int findall_split(const mrx_handle* h, const Layout& lay, int64_t n, int3
   layB.data = lay.data + nA * lay.stride;
   if (lay.lens) layB.lens = lay.lens + nA;
   EvRec* d_recsB = d_recs + (size_t)rec_row * nA;
+#define MRX_DECODE_HALF_K(KERNEL, STREAM, N, NRECS, RECS, COUNTS, WBASE, TSUM, PREFIX, TOTAL, BASE)                         \
+  hipLaunchKernelGGL(KERNEL, dg_, db_, 0, STREAM, (N), NRECS, RECS, rec_row, (const int64_t*)nullptr, COUNTS, WBASE, TSUM,    \
+                     PREFIX, d_spans, span_cap, p.st_fixed_len, TOTAL, (const int32_t*)nullptr, BASE)
 #define MRX_DECODE_HALF(STREAM, N, NRECS, RECS, COUNTS, WBASE, TSUM, PREFIX, TOTAL, BASE)                                   \
-  do {                                                                                                                     \
+  do {   /* (the tile's store loops by g_decode_store16, as in decode_launch) */                                             \
     const dim3 dg_((unsigned)grid_for((N), kBlock) * (pack16 ? 2 : 1)), db_(kBlock);                                        \
-    if (pack16 && rec32)                                                                                                   \
-      hipLaunchKernelGGL((k_decode<true, false, true>), dg_, db_, 0, STREAM, (N), NRECS, RECS, rec_row, (const int64_t*)nullptr, \
-                         COUNTS, WBASE, TSUM, PREFIX, d_spans, span_cap, p.st_fixed_len, TOTAL, (const int32_t*)nullptr, BASE); \
+    const bool st16_ = g_decode_store16 != 0;                                                                              \
+    g_last_decode_store16 = st16_ ? 1 : 0;                                                                                 \
+    if (pack16 && rec32 && st16_)                                                                                          \
+      MRX_DECODE_HALF_K((k_decode<true, false, true, false, kDecodeTile, false, false, true>), STREAM, N, NRECS, RECS,       \
+                        COUNTS, WBASE, TSUM, PREFIX, TOTAL, BASE);                                                          \
+    else if (pack16 && rec32)                                                                                              \
+      MRX_DECODE_HALF_K((k_decode<true, false, true>), STREAM, N, NRECS, RECS, COUNTS, WBASE, TSUM, PREFIX, TOTAL, BASE);     \
+    else if (pack16 && st16_)                                                                                              \
+      MRX_DECODE_HALF_K((k_decode<true, false, false, false, kDecodeTile, false, false, true>), STREAM, N, NRECS, RECS,      \
+                        COUNTS, WBASE, TSUM, PREFIX, TOTAL, BASE);                                                          \
     else if (pack16)                                                                                                       \
-      hipLaunchKernelGGL(k_decode<true>, dg_, db_, 0, STREAM, (N), NRECS, RECS, rec_row, (const int64_t*)nullptr,            \
-                         COUNTS, WBASE, TSUM, PREFIX, d_spans, span_cap, p.st_fixed_len, TOTAL, (const int32_t*)nullptr, BASE); \
+      MRX_DECODE_HALF_K(k_decode<true>, STREAM, N, NRECS, RECS, COUNTS, WBASE, TSUM, PREFIX, TOTAL, BASE);                   \
+    else if (st16_)                                                                                                        \
+      MRX_DECODE_HALF_K((k_decode<false, false, false, false, kDecodeTile, false, false, true>), STREAM, N, NRECS, RECS,     \
+                        COUNTS, WBASE, TSUM, PREFIX, TOTAL, BASE);                                                          \
     else                                                                                                                   \
-      hipLaunchKernelGGL(k_decode<false>, dg_, db_, 0, STREAM, (N), NRECS, RECS, rec_row, (const int64_t*)nullptr,           \
-                         COUNTS, WBASE, TSUM, PREFIX, d_spans, span_cap, p.st_fixed_len, TOTAL, (const int32_t*)nullptr, BASE); \
+      MRX_DECODE_HALF_K(k_decode<false>, STREAM, N, NRECS, RECS, COUNTS, WBASE, TSUM, PREFIX, TOTAL, BASE);                  \
   } while (0)
   {
     ScanTimer tm(s);
@@ -5546,6 +5610,7 @@ static int findall_split(const mrx_handle* h, const Layout& lay, int64_t n, int3
   HIP_TRY(hipStreamWaitEvent(s, ss->decoded, 0));
   MRX_DECODE_HALF(s, nB, d_nrB, d_recsB, d_counts + nA, d_wbB, d_tsB, d_prefix + nA, d_total, (const int64_t*)d_totA);
 #undef MRX_DECODE_HALF
+#undef MRX_DECODE_HALF_K
   HIP_TRY(hipGetLastError());
   g_last_kernel = "k_stream_findall";
   return MRX_OK;
@@ -5945,6 +6010,13 @@ struct FindallJob {
   // three are the kernel's defaults but for `reverse`
   template <bool PACK16, bool REC32 = false, bool DYN = false, int TILE = kDecodeTile, bool REC12 = false, bool LEAN = false>
   void decode_launch(unsigned grid, const int64_t* d_tsum, int reverse = 0) {
+    const bool st16 = g_decode_store16 != 0;   // the tile's store loops: two spans per lane and trip, or one
+    g_last_decode_store16 = st16 ? 1 : 0;
+    if (st16)
+      hipLaunchKernelGGL((k_decode<PACK16, false, REC32, DYN, TILE, REC12, LEAN, true>), dim3(grid), dim3(kBlock), 0, s, n,
+                         d_nrecs, d_recs, rec_row, lay.offsets, d_counts, d_wbase, d_tsum, d_prefix, d_spans, span_cap,
+                         p.st_fixed_len, d_total, (const int32_t*)nullptr, (const int64_t*)nullptr, reverse);
+    else
     hipLaunchKernelGGL((k_decode<PACK16, false, REC32, DYN, TILE, REC12, LEAN>), dim3(grid), dim3(kBlock), 0, s, n, d_nrecs,
                        d_recs, rec_row, lay.offsets, d_counts, d_wbase, d_tsum, d_prefix, d_spans, span_cap, p.st_fixed_len,
                        d_total, (const int32_t*)nullptr, (const int64_t*)nullptr, reverse);
@@ -5954,6 +6026,7 @@ struct FindallJob {
   int stream_finish() {
     if (rows) {   // offsets from the scan's counts, then a wavefront per text (k_decode_rows)
       g_last_decode_lean = 0;
+      g_last_decode_store16 = 0;
       if (int rc = device_scan<int32_t>(d_counts, n, d_prefix, d_total, s)) return rc;
       // lanes per text by length: a round of 2 G pairs covers 64 G bytes
       const int G = max_text <= 1024 ? 16 : max_text <= 2048 ? 32 : 64;
@@ -8240,6 +8313,14 @@ void mrx_debug_rec_skew(int64_t bytes) { g_rec_skew = bytes < 0 ? 0 : (bytes & ~
 void mrx_debug_rec12(int mode) { g_rec12 = mode != 0; }
 void mrx_debug_decode_lean(int mode) { g_decode_lean = mode != 0; }
 int mrx_debug_last_decode_lean(void) { return g_last_decode_lean; }
+void mrx_debug_decode_store16(int mode) { g_decode_store16 = mode != 0; }
+int mrx_debug_last_decode_store16(void) { return g_last_decode_store16; }
+int mrx_testing_decode_store_plan(int64_t pre0, int addr_parity, int nspan, int64_t span_cap, int32_t out[5]) {
+  if (nspan < 0 || (addr_parity != 0 && addr_parity != 1) || !out) return -1;
+  const DecodeStorePlan pl = decode_store_plan(pre0, addr_parity, nspan, span_cap);
+  out[0] = pl.odd; out[1] = pl.head; out[2] = pl.npairs; out[3] = pl.tail; out[4] = pl.nclip;
+  return 0;
+}
 int mrx_testing_decode_expand(int64_t n, const uint32_t* f_even, const uint32_t* f_odd, const int32_t* start, const int32_t* pb,
                               int fixed_len, int32_t* counts, int32_t* spans) {
   if (n < 0 || fixed_len < 0 || (n > 0 && (!f_even || !f_odd || !start || !pb || !counts || !spans))) return -1;

@@ -38,6 +38,17 @@ __device__ __forceinline__ void mrx_stg_span(int32_t* p, int a, int b) {
   *(int2*)p = make_int2(a, b);
 #endif
 }
+typedef int mrx_i32x4 __attribute__((ext_vector_type(4)));
+// two consecutive spans {s0, e0, s1, e1} in one 16-byte store; p is 16-byte aligned (decode_store_plan in
+// mrx_decode_bits.hpp is what makes it so)
+__device__ __forceinline__ void mrx_stg_span2(int32_t* p, int s0, int e0, int s1, int e1) {
+#if MRX_NT_LOADS
+  mrx_i32x4 v; v.x = s0; v.y = e0; v.z = s1; v.w = e1;
+  __builtin_nontemporal_store(v, (mrx_i32x4*)p);
+#else
+  *(int4*)p = make_int4(s0, e0, s1, e1);
+#endif
+}
 
 
 
