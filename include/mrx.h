@@ -1216,6 +1216,53 @@ int mrx_fields_strided_dev(uint32_t flags, uint8_t delim, const int32_t* columns
                            int64_t stride, const int32_t* d_lens, int32_t len, int64_t n, int32_t* d_rows, int32_t* d_nf,
                            int64_t* d_prefix, void* stream);
 
+/* ---- quoted fields: CSV and log-line quoting in fields, on the device ----
+ * fields with one more input, `quote` (one byte Q), and one more optional output, d_quoted: x,"Doe, Jane",42 is three
+ * cells, and the request and the agent of a combined-format access log line are one column each.  flags are fields':
+ * MRX_FIELDS_WHITESPACE and MRX_FIELDS_REST.  mrx_fields_* itself is unchanged, and knows no quote.
+ *   inside           byte p of a text t is inside when the number of Q bytes in t[0..p], p included, is odd.  An opening
+ *                    quote is inside, a closing one is not.  "" within a quoted stretch closes and opens again with
+ *                    nothing between, so doubled quotes need no rule of their own.
+ *   delimiter mode   a delimiter byte separates only when it is not inside.  The rest is fields': nf is the number of
+ *                    separating delimiters plus 1, columns count from 1 or from -1, MRX_FIELDS_REST lets column cmax
+ *                    run to L after cmax - 1 separations, and the empty text has one empty field.
+ *   whitespace mode  a whitespace byte that is inside counts as a byte that is no whitespace.  Starts, ends and nf are
+ *                    whitespace mode's own rules over that mask.
+ *   content          let a part be [s, e) as above.  If e - s >= 2, t[s] == Q and t[e - 1] == Q, the pair written is
+ *                    (s + 1, e - 1) and d_quoted[i][j] = 1.  Otherwise the pair is (s, e) and the byte is 0.  A part
+ *                    that does not exist is (-1, -1) and 0.  d_quoted is uint8[n][f] and may be NULL.
+ *   decoded cell     (documented, not computed by this call) the content with every leftmost non-overlapping QQ
+ *                    replaced by Q: what mrx_kw_sub_* does with the one entry QQ and the replacement Q.
+ * For every row that Python's csv.writer produces with QUOTE_MINIMAL or QUOTE_ALL from cells without \r and \n, the
+ * decoded cells are csv.reader's.  Malformed input is defined by the rules above, not by csv:
+ *   text           call                           rows                            quoted
+ *   a,"b,c",d      ",", {1, 2, 3}                 (0,1) (3,6) (8,9)               0 1 0
+ *   a,"b""c",d     ",", {2}                       (3,7): content b""c             1
+ *   x,"",y         ",", {2}                       (3,3)                           1
+ *   "a,b           ",", {1, 2}                    (0,4) (-1,-1)                   0 0
+ *   a"b,c"d        ",", {1}                       (0,7): csv says two cells       0
+ *   "ab"cd,e       ",", {1, 2}                    (0,6) (7,8)                     0 0
+ *   "              ",", {1}                       (0,1)                           0
+ *   a "b c"  d     whitespace, {1, 2, 3, -1}      (0,1) (3,6) (9,10) (9,10)       0 1 0 0
+ *   a,"b,c",d      ",", rest, {2}                 (2,9)                           0
+ * Bytes outside a text never make, open or close a quote: every walk of a text begins outside.  Reads are as for fields,
+ * and t[s] and t[e - 1] of every part that exists are read once more.  The early stop stays where the results cannot
+ * differ: under MRX_FIELDS_REST, and when d_nf is NULL and no column is negative.  No scratch, no atomics, nothing read
+ * back, the same bits on every run, and no synchronisation on any form.  n == 0 enqueues nothing.
+ * MRX_E_ARGUMENT, before anything is enqueued: everything mrx_fields_* refuses; quote == delim in delimiter mode; a quote
+ * that is one of the six whitespace bytes in whitespace mode; a d_quoted given with d_rows NULL.
+ * Forms: CSR and fixed pitch.  There is no form that takes a CSR batch's known bounds: the CSR form cannot know the mean
+ * text length and shares a text among the default number of lanes (2), the fixed-pitch form routes by its pitch or length
+ * as mrx_fields_strided_dev does.
+ * Not here: an escape byte (\"), open / close pairs such as [ ... ], records with a newline inside quotes (mrx_lines_*
+ * knows no quote), and a CSV writer. */
+int mrx_fields_quoted_dev(uint32_t flags, uint8_t delim, uint8_t quote, const int32_t* columns, int32_t f, const uint8_t* d_data,
+                          const int64_t* d_offsets, int64_t n, int32_t* d_rows, int32_t* d_nf, uint8_t* d_quoted,
+                          int64_t* d_prefix, void* stream);
+int mrx_fields_quoted_strided_dev(uint32_t flags, uint8_t delim, uint8_t quote, const int32_t* columns, int32_t f,
+                                  const uint8_t* d_data, int64_t stride, const int32_t* d_lens, int32_t len, int64_t n,
+                                  int32_t* d_rows, int32_t* d_nf, uint8_t* d_quoted, int64_t* d_prefix, void* stream);
+
 /* ---- translate: bytes.translate and tr -s for every text, as a new batch on the device ----
  * The step that normalises bytes: tr A-Z a-z, tr -d '\r"', tr '\t' ' ', tr -s ' ', sed y/../../.  No pattern and no
  * automaton.  For every text t of the batch:
@@ -1324,6 +1371,9 @@ int mrx_strip_batch(const uint8_t* set, uint32_t flags, const uint8_t* data, con
 /* mrx_fields_dev on host buffers: rows int32[n][f][2], nf int32[n] (may be NULL), prefix int64[n + 1] (may be NULL). */
 int mrx_fields_batch(uint32_t flags, uint8_t delim, const int32_t* columns, int32_t f, const uint8_t* data,
                      const int64_t* offsets, int64_t n, int32_t* rows, int32_t* nf, int64_t* prefix);
+/* mrx_fields_quoted_dev on host buffers: as mrx_fields_batch, and quoted uint8[n][f] (may be NULL). */
+int mrx_fields_quoted_batch(uint32_t flags, uint8_t delim, uint8_t quote, const int32_t* columns, int32_t f, const uint8_t* data,
+                            const int64_t* offsets, int64_t n, int32_t* rows, int32_t* nf, uint8_t* quoted, int64_t* prefix);
 /* mrx_lines_dev on host buffers: line_prefix int64[n + 1], owner int64[piece_cap], out_offsets int64[piece_cap + 1],
  * out_data uint8[out_cap], totals int64[4] (may be NULL).  line_prefix is always copied out, owner[0, lines) and
  * out_offsets[0, lines] when the lines fit, out_data only when the bytes fit too (MRX_E_CAPACITY otherwise). */

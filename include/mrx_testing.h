@@ -265,6 +265,12 @@ void mrx_debug_fields_grid(int workgroups);
  * outputs and return codes as mrx_fields_batch. */
 int mrx_debug_fields_host(uint32_t flags, uint8_t delim, const int32_t* columns, int32_t f, const uint8_t* data,
                           const int64_t* offsets, int64_t n, int32_t* rows, int32_t* nf, int64_t* prefix);
+/* Quoted fields on the CPU: mrx_debug_fields_host with the quote, over the same groups and rounds as the kernel and with
+ * the same parity arithmetic (the ballot of a group's lanes is put together lane by lane).  The buffer that the walk
+ * reads holds quote bytes around the texts.  Arguments, outputs and return codes as mrx_fields_quoted_batch. */
+int mrx_debug_fields_quoted_host(uint32_t flags, uint8_t delim, uint8_t quote, const int32_t* columns, int32_t f,
+                                 const uint8_t* data, const int64_t* offsets, int64_t n, int32_t* rows, int32_t* nf,
+                                 uint8_t* quoted, int64_t* prefix);
 /* Translate (include/mrx.h): bytes > 0 pins the piece size P of every later call of the packed form (rounded up to a
  * multiple of 1024, a wavefront's round), 0 restores the default, a negative value changes nothing.  Returns the P in
  * force: tests place their runs by it.  The passes report themselves as "k_translate_map" (same-length form) and

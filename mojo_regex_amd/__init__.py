@@ -49,6 +49,8 @@ argument meaning, a *batch* of texts instead of one text:
                                                   buffer's bytes as the packed batch of its lines
     (none: text.split()[k] on the host)           fields_of / DeviceBatch.fields / fields_async / cut: the
                                                   columns of every text as span rows, no pattern involved
+    (none: csv.reader on the host)                csv_of / csv_columns / DeviceBatch.fields(quote=): quoted
+                                                  CSV cells and quoted log-line columns
     (none: text.lower() / .translate() / .strip() translate_texts / strip_texts / DeviceBatch.translate / lower /
      on the host)                                 upper / strip and their _async forms: tr, case folding and
                                                   trimming of every text, no pattern involved
@@ -75,6 +77,8 @@ from .api import (  # noqa: F401
     clear_regex_cache,
     compile_regex,
     compile_set,
+    csv_columns,
+    csv_of,
     distinct,
     expand,
     fields_of,

@@ -386,6 +386,14 @@ def load_library():
         "mrx_fields_strided_dev": (C.c_int, [C.c_uint32, C.c_uint8, i32p, C.c_int32, u8p, C.c_int64, i32p, C.c_int32,
                                              C.c_int64, i32p, i32p, i64p, C.c_void_p]),
         "mrx_fields_batch": (C.c_int, [C.c_uint32, C.c_uint8, i32p, C.c_int32, u8p, i64p, C.c_int64, i32p, i32p, i64p]),
+        "mrx_fields_quoted_dev": (C.c_int, [C.c_uint32, C.c_uint8, C.c_uint8, i32p, C.c_int32, u8p, i64p, C.c_int64, i32p,
+                                            i32p, u8p, i64p, C.c_void_p]),
+        "mrx_fields_quoted_strided_dev": (C.c_int, [C.c_uint32, C.c_uint8, C.c_uint8, i32p, C.c_int32, u8p, C.c_int64, i32p,
+                                                    C.c_int32, C.c_int64, i32p, i32p, u8p, i64p, C.c_void_p]),
+        "mrx_fields_quoted_batch": (C.c_int, [C.c_uint32, C.c_uint8, C.c_uint8, i32p, C.c_int32, u8p, i64p, C.c_int64, i32p,
+                                              i32p, u8p, i64p]),
+        "mrx_debug_fields_quoted_host": (C.c_int, [C.c_uint32, C.c_uint8, C.c_uint8, i32p, C.c_int32, u8p, i64p, C.c_int64,
+                                                   i32p, i32p, u8p, i64p]),
         "mrx_debug_fields_group": (C.c_int, [C.c_int]),
         "mrx_debug_fields_last_group": (C.c_int, []),
         "mrx_debug_fields_grid": (None, [C.c_int]),
@@ -459,6 +467,7 @@ EXPORTED_SYMBOLS = [
     "mrx_kw_sub_dev", "mrx_kw_sub_known_dev", "mrx_kw_sub_strided_dev", "mrx_kw_sub_batch",
     "mrx_lines_dev", "mrx_lines_known_dev", "mrx_lines_strided_dev", "mrx_lines_batch",
     "mrx_fields_dev", "mrx_fields_known_dev", "mrx_fields_strided_dev", "mrx_fields_batch",
+    "mrx_fields_quoted_dev", "mrx_fields_quoted_strided_dev", "mrx_fields_quoted_batch",
     "mrx_translate_dev", "mrx_translate_known_dev", "mrx_translate_strided_dev", "mrx_translate_batch",
     "mrx_strip_dev", "mrx_strip_known_dev", "mrx_strip_strided_dev", "mrx_strip_batch",
 ]
@@ -479,6 +488,7 @@ TESTING_SYMBOLS = [
     "mrx_debug_kw_host_leftmost", "mrx_debug_kw_host_sub",
     "mrx_debug_lines_piece", "mrx_debug_lines_syncs", "mrx_debug_lines_host",
     "mrx_debug_fields_group", "mrx_debug_fields_last_group", "mrx_debug_fields_grid", "mrx_debug_fields_host",
+    "mrx_debug_fields_quoted_host",
     "mrx_debug_translate_piece", "mrx_debug_translate_syncs", "mrx_debug_translate_host",
     "mrx_debug_strip_host",
 ]
@@ -761,7 +771,7 @@ class DeviceBatch:
                          (_ptr(prefix), _ptr(owner), _ptr(out_offsets), int(owner.numel()), _ptr(out_data),
                           int(out_data.numel()), _ptr(totals), None, stream)))
 
-    def fields(self, columns, delim=None, rest: bool = False, counts: bool = True):
+    def fields(self, columns, delim=None, rest: bool = False, counts: bool = True, quote=None):
         """The columns of every text as span rows (include/mrx.h, mrx_fields_dev): (prefix int64[n + 1], rows
         int32[n, f, 2], nf int32[n]), device tensors.  delim=None is whitespace mode, bytes.split() of every text; delim
         one byte is t.split(delim).  columns count from 1 as cut and awk do, or from -1 at the end ($NF); rest=True
@@ -769,22 +779,38 @@ class DeviceBatch:
         (-1, -1) where the text has no such part; nf[i] is the field count (None with counts=False, which lets the
         kernel stop reading a text behind its largest column).  prefix is the identity CSR 0 .. n: prefix and rows go
         to gather_spans(pair=j), parse_spans(pair=j) and expand_spans as they stand.  A batch with known bounds passes
-        them on.  The call enqueues on the current stream and reads nothing back."""
+        them on.  The call enqueues on the current stream and reads nothing back.
+        With quote (one byte, include/mrx.h, mrx_fields_quoted_dev) a delimiter or whitespace byte between quotes
+        separates nothing, a part that begins and ends with the quote is given without both, and the result has a
+        fourth value: (prefix, rows, nf, quoted uint8[n, f]), quoted[i, j] = 1 where the outer quotes were taken off.
+        Doubled quotes stay in the content; csv_columns(batch, ...) takes them out."""
         import torch
         dev, f = self.data.device, len(columns)
         rows = torch.empty((self.n, f, 2), dtype=torch.int32, device=dev)
         nf = torch.empty(self.n, dtype=torch.int32, device=dev) if counts else None
         # n == 0 enqueues nothing: the one entry of the prefix is the host's to write
         prefix = torch.empty(self.n + 1, dtype=torch.int64, device=dev) if self.n else torch.zeros(1, dtype=torch.int64, device=dev)
+        if quote is not None:
+            quoted = torch.empty((self.n, f), dtype=torch.uint8, device=dev)
+            self.fields_async((prefix, rows, nf, quoted), columns, delim, rest, quote)
+            return prefix, rows, nf, quoted
         self.fields_async((prefix, rows, nf), columns, delim, rest)
         return prefix, rows, nf
 
-    def fields_async(self, out, columns, delim=None, rest: bool = False):
+    def fields_async(self, out, columns, delim=None, rest: bool = False, quote=None):
         """fields() on the caller's tensors out = (prefix int64[n + 1] or None, rows int32[n, f, 2], nf int32[n] or
-        None): enqueues on the current stream and returns.  Nothing is written for a batch without texts."""
+        None), with quote out = (prefix, rows, nf, quoted uint8[n, f] or None): enqueues on the current stream and
+        returns.  Nothing is written for a batch without texts."""
         import torch
         flags, delim_byte, cols = _fields_args(columns, delim, rest)
-        prefix, rows, nf = out
+        quoted = None
+        if quote is not None:
+            quote_byte = _quote_byte(quote)
+            prefix, rows, nf, quoted = out
+            if quoted is not None and (quoted.dtype != torch.uint8 or not quoted.is_contiguous() or quoted.numel() < self.n * len(cols)):
+                raise MrxError("quoted must be a contiguous uint8[n, f] tensor")
+        else:
+            prefix, rows, nf = out
         if rows is None or rows.dtype != torch.int32 or not rows.is_contiguous() or rows.numel() < self.n * len(cols) * 2:
             raise MrxError("rows must be a contiguous int32[n, f, 2] tensor")
         if nf is not None and (nf.dtype != torch.int32 or not nf.is_contiguous() or nf.numel() < self.n):
@@ -794,6 +820,10 @@ class DeviceBatch:
         if self.n == 0:   # nothing is enqueued, but the columns are still the C side's to refuse (no rows: no address)
             rows = torch.empty(2, dtype=torch.int32, device=self.data.device)
         stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        if quote is not None:
+            _check(self.call(load_library(), "mrx_fields_quoted", (flags, delim_byte, quote_byte, cols.ctypes.data, len(cols)),
+                             (_ptr(rows), _ptr(nf), _ptr(quoted), _ptr(prefix), stream)))
+            return
         _check(self.call(load_library(), "mrx_fields", (flags, delim_byte, cols.ctypes.data, len(cols)),
                          (_ptr(rows), _ptr(nf), _ptr(prefix), stream)))
 
@@ -893,19 +923,20 @@ class DeviceBatch:
         stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
         _check(self.call(load_library(), "mrx_strip", (chars_set, _strip_flags(left, right)), (_ptr(rows), _ptr(prefix), stream)))
 
-    def cut(self, columns, delim=None, out_delim=None, end=b"\n"):
+    def cut(self, columns, delim=None, out_delim=None, end=b"\n", quote=None):
         """cut -d<delim> -f<columns>, or awk '{print $a, $b}' with delim=None: one record per text, the named columns
         joined by out_delim (default: delim, or one space in whitespace mode) and closed by `end`, as a new packed
         batch: (records DeviceBatch, owner int64[n]).  This is fields() followed by expand_spans() with the template
         \\1<out_delim>\\2...<end>, so a column that a text does not have contributes nothing, and at most 9 columns
-        can be named: expand's templates know \\1 .. \\9 only."""
+        can be named: expand's templates know \\1 .. \\9 only.  With quote the columns are those of fields(quote=)
+        and the records hold their contents: outer quotes taken off, doubled quotes as they stand."""
         if len(columns) > 9:
             raise MrxError("cut takes at most 9 columns: it runs expand_spans, whose templates know \\1 .. \\9 only "
                            "(fields() itself takes %d)" % MRX_FIELDS_MAX_COLUMNS)
         sep = _b(out_delim) if out_delim is not None else (_b(delim) if delim is not None else b" ")
         template = sep.join(b"\\" + str(j + 1).encode() for j in range(len(columns))) + _b(end)
         # expand takes a row's last pair for the whole match, which no reference names: one more pair stands there
-        prefix, rows, _ = self.fields(list(columns) + [1], delim, counts=False)
+        prefix, rows = self.fields(list(columns) + [1], delim, counts=False, quote=quote)[:2]
         return self.expand_spans(template, prefix, rows)
 
     def gather_spans(self, prefix, spans, pair: int = 0, piece_cap: Optional[int] = None, out_cap: Optional[int] = None):
@@ -1354,6 +1385,14 @@ def _fields_args(columns, delim, rest: bool):
     if any(not -(1 << 31) <= c < (1 << 31) for c in cols):
         raise MrxError("a column must fit an int32")
     return flags, delim_byte, np.array(cols, dtype=np.int32)
+
+
+def _quote_byte(quote) -> int:
+    """The quote byte of mrx_fields_quoted_*; which bytes a mode refuses is the C side's to say."""
+    quote = _b(quote)
+    if len(quote) != 1:
+        raise MrxError("quote must be a single byte")
+    return quote[0]
 
 
 def _filter_flags(mode: str = "any", invert: bool = False) -> int:
@@ -2633,16 +2672,56 @@ def lines_of(texts, sep=b"\n", keepends: bool = False, crlf: bool = False, parti
     return out[0] if single else out
 
 
-def fields_of(texts, columns, delim=None, rest: bool = False):
+def fields_of(texts, columns, delim=None, rest: bool = False, quote=None):
     """The columns of host texts (DeviceBatch.fields): List[List[Optional[bytes]]], one list per text with the bytes of
-    every requested column, None for a part that the text does not have."""
+    every requested column, None for a part that the text does not have.  With quote: the contents of quoted fields."""
     bs = [_b(t) for t in texts]
     _fields_args(columns, delim, rest)
+    if quote is not None:
+        _quote_byte(quote)
     if not bs:
         return []
-    _, rows, _ = DeviceBatch.from_texts(bs).fields(columns, delim, rest, counts=False)
+    rows = DeviceBatch.from_texts(bs).fields(columns, delim, rest, counts=False, quote=quote)[1]
     rows = rows.cpu().numpy()
     return [[None if s < 0 else t[s:e] for s, e in rows[i].tolist()] for i, t in enumerate(bs)]
+
+
+_unescape_keywords = {}   # csv_columns(): the one-entry keyword set QQ per quote byte, built once
+
+
+def csv_columns(batch: "DeviceBatch", columns, delim=b",", quote=b'"', unescape: bool = True):
+    """The cells of the named columns of every text of a DeviceBatch as CSV understands them: one packed DeviceBatch of
+    n texts per column.  fields(quote=) gives the contents, gather_spans(pair=j) packs them (a column that a text does
+    not have is an empty text), and with unescape every doubled quote becomes one: Keywords([QQ]).sub(Q, ...), leftmost
+    and non-overlapping.  For rows that csv.writer wrote (QUOTE_MINIMAL or QUOTE_ALL, cells without \\r and \\n) these
+    are csv.reader's cells; what malformed rows give is include/mrx.h's to say ("quoted fields")."""
+    q = bytes([_quote_byte(quote)])
+    prefix, rows, _, _ = batch.fields(columns, delim, counts=False, quote=q)
+    out = []
+    for j in range(len(columns)):
+        cells = batch.gather_spans(prefix, rows, pair=j)[0]
+        if unescape:
+            kw = _unescape_keywords.get(q)
+            if kw is None:
+                kw = _unescape_keywords[q] = Keywords([q + q])
+            cells = kw.sub(q, cells)
+        out.append(cells)
+    return out
+
+
+def csv_of(texts, columns, delim=b",", quote=b'"') -> List[List[bytes]]:
+    """csv_columns of host texts: one list per text with the decoded cell of every requested column, b""
+    for a column that the text does not have."""
+    bs = [_b(t) for t in texts]
+    _fields_args(columns, delim, False)
+    _quote_byte(quote)
+    if not bs:
+        return []
+    cols = []
+    for cells in csv_columns(DeviceBatch.from_texts(bs), columns, delim, quote):
+        raw, off = cells.data.cpu().numpy().tobytes(), cells.offsets.cpu().numpy()
+        cols.append([raw[off[i]:off[i + 1]] for i in range(len(bs))])
+    return [list(cell) for cell in zip(*cols)]
 
 
 def translate_texts(texts, table=None, delete=b"", squeeze=b"") -> List[bytes]:

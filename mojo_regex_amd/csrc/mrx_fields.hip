@@ -16,6 +16,11 @@
 // G is chosen per call from the mean text length where the call knows it (fields_group_rule, from the sweep of
 // profiles/fields.md: 1, 2 or 4 lanes for texts of up to 16 KiB); a text takes as many rounds of 16 G bytes as it is
 // long.  One text of many MiB is answered by a single group: right, not fast.
+//
+// Quoted fields (mrx_fields_quoted_*) are the same kernel with QUOTED = true: the quote bits of the word a lane holds,
+// their prefix-xor, one ballot a round for the parity of the lanes in front within the group and one carried bit make
+// the inside mask; the outer quotes of a pair are decided where the pairs leave the stage.  The instances with
+// QUOTED = false are the code they were.
 #include <hip/hip_runtime.h>
 
 #include <atomic>
@@ -45,6 +50,12 @@ struct FieldsOut {
   int32_t* nf;
   int64_t* prefix;
 };
+// quoted fields: the quote byte and the quoted bytes uint8[n][f] (may be null).  The last kernel argument, so that the
+// arguments in front of it lie where they lay; the instances without quotes never read it
+struct FieldsQuote {
+  uint8_t* quoted;
+  uint32_t quote;
+};
 
 // LDS writes of one lane are read by another lane of the same wavefront behind this
 __device__ __forceinline__ void fields_wave_sync() {
@@ -53,8 +64,9 @@ __device__ __forceinline__ void fields_wave_sync() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-template <int G>
-__global__ __launch_bounds__(kFieldsBlock) void k_fields(const TextBatch B, int64_t n, const FieldsPlan P, const FieldsOut O) {
+template <int G, bool QUOTED>
+__global__ __launch_bounds__(kFieldsBlock) void k_fields(const TextBatch B, int64_t n, const FieldsPlan P, const FieldsOut O,
+                                                         const FieldsQuote Q) {
   extern __shared__ __align__(8) int32_t fields_lds[];
   constexpr int T = 64 / G;   // texts of a wavefront's round
   const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
@@ -86,6 +98,7 @@ __global__ __launch_bounds__(kFieldsBlock) void k_fields(const TextBatch B, int6
       fields_wave_sync();
       int64_t ra = 0, rb = 0;   // the events of the text in front of the round
       uint32_t carry = 0;
+      uint32_t parity = 0;   // QUOTED: the quotes of the text in front of the round are odd; every walk begins outside
       bool done = false;
       for (int64_t w0 = 0;; w0 += G) {
         if (!negative && P.stop && fields_done(P, ra, rb)) done = true;
@@ -93,7 +106,21 @@ __global__ __launch_bounds__(kFieldsBlock) void k_fields(const TextBatch B, int6
         if (!__any(more)) break;
         const int64_t wi = w0 + gl;
         uint32_t m = 0;
-        if (more && wi < nwords) m = fields_word_mask(P, gather_window(base + 16 * wi, 16), fields_valid(head, L, wi));
+        if constexpr (QUOTED) {
+          g_u128 word = 0;
+          uint32_t valid = 0;
+          if (more && wi < nwords) {
+            word = gather_window(base + 16 * wi, 16);
+            valid = fields_valid(head, L, wi);
+          }
+          const uint32_t q = lines_eq16(word, Q.quote) & valid;
+          // one ballot: the lanes whose word holds an odd number of quotes.  The walk is uniform, all lanes are here
+          const uint64_t mine = fields_group_bits(__ballot(lines_popc(q) & 1), t, G);
+          m = fields_word_mask_quoted(P, word, valid, fields_inside(q, fields_parity_front(mine, gl) ^ parity));
+          parity ^= fields_parity_all(mine);
+        } else {
+          if (more && wi < nwords) m = fields_word_mask(P, gather_window(base + 16 * wi, 16), fields_valid(head, L, wi));
+        }
         uint32_t a = m, b = m;
         if (ws) {
           const uint32_t up = (uint32_t)__shfl_up((int)m, 1, G);
@@ -122,10 +149,28 @@ __global__ __launch_bounds__(kFieldsBlock) void k_fields(const TextBatch B, int6
     const int64_t texts = t_end - i0 < T ? t_end - i0 : T;
     const int pairs = (int)texts * P.f;
     int32_t* out = O.rows + 2 * (i0 * P.f);
-    for (int p = lane; p < pairs; p += 64) {
-      int2 v = *(const int2*)(tile + 2 * p);
-      fields_finish(&v.x, &v.y);
-      *(int2*)(out + 2 * p) = v;
+    if constexpr (QUOTED) {
+      // the outer quotes are decided here: the lane that stores pair p reads t[s] and t[e - 1] of that pair's text,
+      // whose address the first lane of its group holds.  Uniform trips, so that every source lane is there
+      const uint32_t tp_lo = (uint32_t)(uintptr_t)tp, tp_hi = (uint32_t)((uintptr_t)tp >> 32);
+      for (int p0 = 0; p0 < pairs; p0 += 64) {
+        const int p = p0 + lane;
+        const int src = (p < pairs ? p / P.f : 0) * G;
+        const uint32_t lo = (uint32_t)__shfl((int)tp_lo, src), hi = (uint32_t)__shfl((int)tp_hi, src);
+        if (p < pairs) {
+          int2 v = *(const int2*)(tile + 2 * p);
+          fields_finish(&v.x, &v.y);
+          const uint8_t was = fields_unquote((const uint8_t*)(((uintptr_t)hi << 32) | lo), Q.quote, &v.x, &v.y);
+          *(int2*)(out + 2 * p) = v;
+          if (Q.quoted) Q.quoted[i0 * P.f + p] = was;
+        }
+      }
+    } else {
+      for (int p = lane; p < pairs; p += 64) {
+        int2 v = *(const int2*)(tile + 2 * p);
+        fields_finish(&v.x, &v.y);
+        *(int2*)(out + 2 * p) = v;
+      }
     }
     if (live && gl == 0) {
       if (O.nf) O.nf[i] = nf;
@@ -142,7 +187,7 @@ int pinned_or(int rule) {
   return g > 0 ? g : rule;
 }
 
-int launch(const TextBatch& b, int64_t n, const FieldsPlan& p, int g, const FieldsOut& o, void* stream) {
+int launch(const TextBatch& b, int64_t n, const FieldsPlan& p, int g, const FieldsOut& o, int quote, uint8_t* d_quoted, void* stream) {
   const int texts_per_wave = 64 / g;
   int block = kFieldsBlock;
   const size_t per_wave = (size_t)texts_per_wave * (size_t)p.f * 8;
@@ -150,9 +195,13 @@ int launch(const TextBatch& b, int64_t n, const FieldsPlan& p, int g, const Fiel
   const size_t lds = per_wave * (size_t)(block / 64);
   const unsigned grid = grid_for(n, (int64_t)texts_per_wave * (block / 64), kFieldsMaxGrid, g_fields_grid.load(std::memory_order_relaxed));
   hipStream_t hs = (hipStream_t)stream;
+  const FieldsQuote q{d_quoted, quote >= 0 ? (uint32_t)quote : 0u};
   switch (g) {
-#define MRX_FIELDS_CASE(GG) \
-  case GG: hipLaunchKernelGGL(k_fields<GG>, dim3(grid), dim3(block), lds, hs, b, n, p, o); break;
+#define MRX_FIELDS_CASE(GG)                                                                                     \
+  case GG:                                                                                                      \
+    if (quote >= 0) hipLaunchKernelGGL((k_fields<GG, true>), dim3(grid), dim3(block), lds, hs, b, n, p, o, q);  \
+    else hipLaunchKernelGGL((k_fields<GG, false>), dim3(grid), dim3(block), lds, hs, b, n, p, o, q);            \
+    break;
     MRX_FIELDS_CASE(1) MRX_FIELDS_CASE(2) MRX_FIELDS_CASE(4) MRX_FIELDS_CASE(8) MRX_FIELDS_CASE(16) MRX_FIELDS_CASE(32)
     MRX_FIELDS_CASE(64)
 #undef MRX_FIELDS_CASE
@@ -173,18 +222,87 @@ struct FieldsCall {
   int32_t* d_nf;
   int64_t* d_prefix;
   void* stream;
+  int quote = -1;   // >= 0: quoted fields with that quote byte
+  uint8_t* d_quoted = nullptr;
 };
 
 // argument errors: nothing has touched the device when one of them returns.  mean_len < 0: not known
 int fields_run(const TextBatch& b, BatchForm form, int64_t n, int64_t mean_len, const FieldsCall& c) {
   FieldsPlan p;
   if (const char* msg = fields_plan(c.flags, c.delim, c.columns, c.f, c.d_nf != nullptr, &p)) return internal_fail(MRX_E_ARGUMENT, msg);
+  if (c.quote >= 0)
+    if (const char* msg = fields_quote_check(c.flags, c.delim, (uint8_t)c.quote)) return internal_fail(MRX_E_ARGUMENT, msg);
   if (n < 0) return internal_fail(MRX_E_ARGUMENT, "n must be >= 0");
   if (int rc = check_batch(b, form)) return rc;
-  if (!c.d_rows) return internal_fail(MRX_E_ARGUMENT, "null argument");
+  if (!c.d_rows) return internal_fail(MRX_E_ARGUMENT, c.d_quoted ? "d_quoted needs d_rows" : "null argument");
   if ((uintptr_t)c.d_rows & 7) return internal_fail(MRX_E_ARGUMENT, "d_rows must be 8-byte aligned");
   if (n == 0) return MRX_OK;
-  return launch(b, n, p, pinned_or(fields_group_rule(mean_len)), FieldsOut{c.d_rows, c.d_nf, c.d_prefix}, c.stream);
+  return launch(b, n, p, pinned_or(fields_group_rule(mean_len)), FieldsOut{c.d_rows, c.d_nf, c.d_prefix}, c.quote, c.d_quoted, c.stream);
+}
+
+// mrx_fields_batch and mrx_fields_quoted_batch (quote >= 0; quoted may be null)
+int fields_batch(uint32_t flags, uint8_t delim, int quote, const int32_t* columns, int32_t f, const uint8_t* data, const int64_t* offsets,
+                 int64_t n, int32_t* rows, int32_t* nf, uint8_t* quoted, int64_t* prefix) {
+  FieldsPlan p;
+  if (const char* msg = fields_plan(flags, delim, columns, f, nf != nullptr, &p)) return internal_fail(MRX_E_ARGUMENT, msg);
+  if (quote >= 0)
+    if (const char* msg = fields_quote_check(flags, delim, (uint8_t)quote)) return internal_fail(MRX_E_ARGUMENT, msg);
+  if (n < 0) return internal_fail(MRX_E_ARGUMENT, "n must be >= 0");
+  if (quoted && !rows) return internal_fail(MRX_E_ARGUMENT, "d_quoted needs d_rows");
+  if (!offsets || !rows) return internal_fail(MRX_E_ARGUMENT, "null argument");
+  DevBatch b; DevBuf<int32_t> dr, dn; DevBuf<int64_t> dp; DevBuf<uint8_t> dq;
+  if (int rc = b.measure(offsets, n)) return rc;
+  if (b.nbytes < 0) return internal_fail(MRX_E_ARGUMENT, "offsets must not decrease");
+  if (b.nbytes > 0 && !data) return internal_fail(MRX_E_ARGUMENT, "null argument");
+  if (n == 0) return MRX_OK;
+  if (int rc = b.upload(data, offsets, n)) return rc;
+  if (int rc = dr.alloc((size_t)n * (size_t)f * 2)) return rc;
+  if (nf) if (int rc = dn.alloc((size_t)n)) return rc;
+  if (prefix) if (int rc = dp.alloc((size_t)n + 1)) return rc;
+  if (quoted) if (int rc = dq.alloc((size_t)n * (size_t)f)) return rc;
+  FieldsCall c{flags, delim, columns, f, dr.p, nf ? dn.p : nullptr, prefix ? dp.p : nullptr, nullptr};
+  c.quote = quote;
+  c.d_quoted = quoted ? dq.p : nullptr;
+  if (int rc = fields_run(csr(b.data, b.offsets), BATCH_CSR, n, b.nbytes / n, c)) return rc;
+  MRX_HIP_TRY(hipMemcpy(rows, dr.p, sizeof(int32_t) * (size_t)n * (size_t)f * 2, hipMemcpyDeviceToHost));
+  if (nf) MRX_HIP_TRY(hipMemcpy(nf, dn.p, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost));
+  if (quoted) MRX_HIP_TRY(hipMemcpy(quoted, dq.p, (size_t)n * (size_t)f, hipMemcpyDeviceToHost));
+  if (prefix) MRX_HIP_TRY(hipMemcpy(prefix, dp.p, sizeof(int64_t) * ((size_t)n + 1), hipMemcpyDeviceToHost));
+  return MRX_OK;
+}
+
+// mrx_debug_fields_host and mrx_debug_fields_quoted_host (quote >= 0; quoted may be null)
+int fields_host(uint32_t flags, uint8_t delim, int quote, const int32_t* columns, int32_t f, const uint8_t* data, const int64_t* offsets,
+                int64_t n, int32_t* rows, int32_t* nf, uint8_t* quoted, int64_t* prefix) {
+  FieldsPlan p;
+  if (const char* msg = fields_plan(flags, delim, columns, f, nf != nullptr, &p)) return internal_fail(MRX_E_ARGUMENT, msg);
+  if (quote >= 0)
+    if (const char* msg = fields_quote_check(flags, delim, (uint8_t)quote)) return internal_fail(MRX_E_ARGUMENT, msg);
+  if (n < 0) return internal_fail(MRX_E_ARGUMENT, "n must be >= 0");
+  if (quoted && !rows) return internal_fail(MRX_E_ARGUMENT, "d_quoted needs d_rows");
+  if (!offsets || !rows) return internal_fail(MRX_E_ARGUMENT, "null argument");
+  for (int64_t i = 0; i < n; ++i)
+    if (offsets[i + 1] < offsets[i]) return internal_fail(MRX_E_ARGUMENT, "offsets must not decrease");
+  if (n == 0) return MRX_OK;
+  if (offsets[n] > offsets[0] && !data) return internal_fail(MRX_E_ARGUMENT, "null argument");
+  const int g = pinned_or(fields_group_rule((offsets[n] - offsets[0]) / n));
+  // the texts in a buffer of its own, at their alignment, with whole words around them: the walk loads aligned words
+  const int64_t lo = offsets[0], nbytes = offsets[n] - lo;
+  const int skew = (int)((uintptr_t)(data + lo) & 15);
+  std::vector<uint8_t> store((size_t)nbytes + 48);
+  for (size_t k = 0; k < store.size(); ++k) store[k] = k % 3 == 0 ? delim : k % 3 == 1 ? (uint8_t)' ' : (uint8_t)'q';
+  if (quote >= 0)   // quote bytes around the texts too: an odd number in front of the first one
+    for (size_t k = 0; k < store.size(); k += 2) store[k] = (uint8_t)quote;
+  uint8_t* at = store.data() + ((16 - ((uintptr_t)store.data() & 15)) & 15) + skew;
+  for (int64_t k = 0; k < nbytes; ++k) at[k] = data[lo + k];
+  for (int64_t i = 0; i < n; ++i) {
+    int32_t one = 0;
+    fields_host_text(p, g, at + (offsets[i] - lo), offsets[i + 1] - offsets[i], rows + 2 * i * f, &one, quote, quoted ? quoted + i * f : nullptr);
+    if (nf) nf[i] = one;
+    if (prefix) prefix[i] = i;
+  }
+  if (prefix) prefix[n] = n;
+  return MRX_OK;
 }
 
 }  // namespace
@@ -212,28 +330,33 @@ int mrx_fields_strided_dev(uint32_t flags, uint8_t delim, const int32_t* columns
                     FieldsCall{flags, delim, columns, f, d_rows, d_nf, d_prefix, stream});
 }
 
+static FieldsCall quoted_call(uint32_t flags, uint8_t delim, uint8_t quote, const int32_t* columns, int32_t f, int32_t* d_rows,
+                              int32_t* d_nf, uint8_t* d_quoted, int64_t* d_prefix, void* stream) {
+  FieldsCall c{flags, delim, columns, f, d_rows, d_nf, d_prefix, stream};
+  c.quote = quote;
+  c.d_quoted = d_quoted;
+  return c;
+}
+int mrx_fields_quoted_dev(uint32_t flags, uint8_t delim, uint8_t quote, const int32_t* columns, int32_t f, const uint8_t* d_data,
+                          const int64_t* d_offsets, int64_t n, int32_t* d_rows, int32_t* d_nf, uint8_t* d_quoted,
+                          int64_t* d_prefix, void* stream) {
+  return fields_run(csr(d_data, d_offsets), BATCH_CSR, n, -1,
+                    quoted_call(flags, delim, quote, columns, f, d_rows, d_nf, d_quoted, d_prefix, stream));
+}
+int mrx_fields_quoted_strided_dev(uint32_t flags, uint8_t delim, uint8_t quote, const int32_t* columns, int32_t f,
+                                  const uint8_t* d_data, int64_t stride, const int32_t* d_lens, int32_t len, int64_t n,
+                                  int32_t* d_rows, int32_t* d_nf, uint8_t* d_quoted, int64_t* d_prefix, void* stream) {
+  return fields_run(strided(d_data, stride, d_lens, len), BATCH_PITCH, n, d_lens ? stride : (int64_t)len,
+                    quoted_call(flags, delim, quote, columns, f, d_rows, d_nf, d_quoted, d_prefix, stream));
+}
+
 int mrx_fields_batch(uint32_t flags, uint8_t delim, const int32_t* columns, int32_t f, const uint8_t* data,
                      const int64_t* offsets, int64_t n, int32_t* rows, int32_t* nf, int64_t* prefix) {
-  FieldsPlan p;
-  if (const char* msg = fields_plan(flags, delim, columns, f, nf != nullptr, &p)) return internal_fail(MRX_E_ARGUMENT, msg);
-  if (n < 0) return internal_fail(MRX_E_ARGUMENT, "n must be >= 0");
-  if (!offsets || !rows) return internal_fail(MRX_E_ARGUMENT, "null argument");
-  DevBatch b; DevBuf<int32_t> dr, dn; DevBuf<int64_t> dp;
-  if (int rc = b.measure(offsets, n)) return rc;
-  if (b.nbytes < 0) return internal_fail(MRX_E_ARGUMENT, "offsets must not decrease");
-  if (b.nbytes > 0 && !data) return internal_fail(MRX_E_ARGUMENT, "null argument");
-  if (n == 0) return MRX_OK;
-  if (int rc = b.upload(data, offsets, n)) return rc;
-  if (int rc = dr.alloc((size_t)n * (size_t)f * 2)) return rc;
-  if (nf) if (int rc = dn.alloc((size_t)n)) return rc;
-  if (prefix) if (int rc = dp.alloc((size_t)n + 1)) return rc;
-  if (int rc = mrx_fields_known_dev(flags, delim, columns, f, b.data, b.offsets, n, b.nbytes, b.longest, dr.p, nf ? dn.p : nullptr,
-                                    prefix ? dp.p : nullptr, nullptr))
-    return rc;
-  MRX_HIP_TRY(hipMemcpy(rows, dr.p, sizeof(int32_t) * (size_t)n * (size_t)f * 2, hipMemcpyDeviceToHost));
-  if (nf) MRX_HIP_TRY(hipMemcpy(nf, dn.p, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost));
-  if (prefix) MRX_HIP_TRY(hipMemcpy(prefix, dp.p, sizeof(int64_t) * ((size_t)n + 1), hipMemcpyDeviceToHost));
-  return MRX_OK;
+  return fields_batch(flags, delim, -1, columns, f, data, offsets, n, rows, nf, nullptr, prefix);
+}
+int mrx_fields_quoted_batch(uint32_t flags, uint8_t delim, uint8_t quote, const int32_t* columns, int32_t f, const uint8_t* data,
+                            const int64_t* offsets, int64_t n, int32_t* rows, int32_t* nf, uint8_t* quoted, int64_t* prefix) {
+  return fields_batch(flags, delim, quote, columns, f, data, offsets, n, rows, nf, quoted, prefix);
 }
 
 int mrx_debug_fields_group(int lanes) {
@@ -246,30 +369,12 @@ int mrx_debug_fields_last_group(void) { return g_fields_last_group.load(); }
 
 int mrx_debug_fields_host(uint32_t flags, uint8_t delim, const int32_t* columns, int32_t f, const uint8_t* data,
                           const int64_t* offsets, int64_t n, int32_t* rows, int32_t* nf, int64_t* prefix) {
-  FieldsPlan p;
-  if (const char* msg = fields_plan(flags, delim, columns, f, nf != nullptr, &p)) return internal_fail(MRX_E_ARGUMENT, msg);
-  if (n < 0) return internal_fail(MRX_E_ARGUMENT, "n must be >= 0");
-  if (!offsets || !rows) return internal_fail(MRX_E_ARGUMENT, "null argument");
-  for (int64_t i = 0; i < n; ++i)
-    if (offsets[i + 1] < offsets[i]) return internal_fail(MRX_E_ARGUMENT, "offsets must not decrease");
-  if (n == 0) return MRX_OK;
-  if (offsets[n] > offsets[0] && !data) return internal_fail(MRX_E_ARGUMENT, "null argument");
-  const int g = pinned_or(fields_group_rule((offsets[n] - offsets[0]) / n));
-  // the texts in a buffer of its own, at their alignment, with whole words around them: the walk loads aligned words
-  const int64_t lo = offsets[0], nbytes = offsets[n] - lo;
-  const int skew = (int)((uintptr_t)(data + lo) & 15);
-  std::vector<uint8_t> store((size_t)nbytes + 48);
-  for (size_t k = 0; k < store.size(); ++k) store[k] = k % 3 == 0 ? delim : k % 3 == 1 ? (uint8_t)' ' : (uint8_t)'q';
-  uint8_t* at = store.data() + ((16 - ((uintptr_t)store.data() & 15)) & 15) + skew;
-  for (int64_t k = 0; k < nbytes; ++k) at[k] = data[lo + k];
-  for (int64_t i = 0; i < n; ++i) {
-    int32_t one = 0;
-    fields_host_text(p, g, at + (offsets[i] - lo), offsets[i + 1] - offsets[i], rows + 2 * i * f, &one);
-    if (nf) nf[i] = one;
-    if (prefix) prefix[i] = i;
-  }
-  if (prefix) prefix[n] = n;
-  return MRX_OK;
+  return fields_host(flags, delim, -1, columns, f, data, offsets, n, rows, nf, nullptr, prefix);
+}
+int mrx_debug_fields_quoted_host(uint32_t flags, uint8_t delim, uint8_t quote, const int32_t* columns, int32_t f,
+                                 const uint8_t* data, const int64_t* offsets, int64_t n, int32_t* rows, int32_t* nf,
+                                 uint8_t* quoted, int64_t* prefix) {
+  return fields_host(flags, delim, quote, columns, f, data, offsets, n, rows, nf, quoted, prefix);
 }
 
 }  // extern "C"

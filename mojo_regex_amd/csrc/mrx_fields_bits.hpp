@@ -15,6 +15,8 @@
 // So a pair is two ranks in two sequences of set bits, and a missing end is L.  A group of G lanes takes G words a
 // round, ranks them with a prefix sum of popcounts, and the lane whose word holds a wanted rank writes the position.
 // Under MRX_FIELDS_REST the largest column has no end to find: it stays L.
+// Quoted fields (include/mrx.h, "quoted fields") change the masks and nothing behind them: a delimiter between quotes is
+// no event, a whitespace byte between quotes counts as a byte that is none, and a finished pair loses its outer quotes.
 #pragma once
 #include <cstdint>
 
@@ -114,6 +116,50 @@ MRX_HD uint32_t fields_word_mask(const FieldsPlan& P, g_u128 word, uint32_t vali
 MRX_HD uint32_t fields_starts(uint32_t m, uint32_t carry) { return m & ~((m << 1) | carry) & 0xffffu; }
 MRX_HD uint32_t fields_ends(uint32_t m, uint32_t carry) { return ~m & ((m << 1) | carry) & 0xffffu; }
 
+// ---- quoted fields (include/mrx.h, "quoted fields") ---------------------------------------------------------------------
+// Byte p of a text is inside when the quote bytes in t[0..p], p included, are odd in number: an opening quote is
+// inside, a closing one is not.  A word's inside mask is the inclusive prefix-xor of its quote bits, turned over when
+// the quotes of the text in front of the word are odd.  Within a round that parity comes from one ballot of the lanes'
+// quote parities, cut to the lanes of the group in front of this one, and over the rounds it is carried as one bit.
+MRX_HD bool fields_quote_ok_byte(uint32_t q) { return !((q >= 9 && q <= 13) || q == 32); }
+// MRX_E_ARGUMENT's message for a quote that the mode cannot take, or nullptr
+inline const char* fields_quote_check(uint32_t flags, uint8_t delim, uint8_t quote) {
+  if (flags & ~kFieldsFlags) return nullptr;   // the plan refuses it by its own name
+  if (flags & MRX_FIELDS_WHITESPACE) return fields_quote_ok_byte(quote) ? nullptr : "quote must not be a whitespace byte in whitespace mode";
+  return quote != delim ? nullptr : "quote must differ from delim";
+}
+MRX_HD int fields_popc64(uint64_t m) { return lines_popc((uint32_t)m) + lines_popc((uint32_t)(m >> 32)); }
+// bit k: the bits 0 .. k of q are odd in number (q: 16 bits)
+MRX_HD uint32_t fields_prefix_xor16(uint32_t q) {
+  q ^= q << 1;
+  q ^= q << 2;
+  q ^= q << 4;
+  q ^= q << 8;
+  return q & 0xffffu;
+}
+// a word's inside mask from its quote bits and the parity (0 or 1) of the quotes in front of it
+MRX_HD uint32_t fields_inside(uint32_t q, uint32_t parity) { return (fields_prefix_xor16(q) ^ (0u - parity)) & 0xffffu; }
+// the bits of group t's G lanes in a wavefront's ballot, lane 0 of the group at bit 0
+MRX_HD uint64_t fields_group_bits(uint64_t ballot, int t, int G) {
+  return G >= 64 ? ballot : (ballot >> (t * G)) & ((1ull << G) - 1ull);
+}
+// the parity of the group's lanes in front of lane gl, and of all of them
+MRX_HD uint32_t fields_parity_front(uint64_t group_bits, int gl) { return (uint32_t)fields_popc64(group_bits & ((1ull << gl) - 1ull)) & 1u; }
+MRX_HD uint32_t fields_parity_all(uint64_t group_bits) { return (uint32_t)fields_popc64(group_bits) & 1u; }
+// fields_word_mask under quotes: a delimiter that is inside separates nothing; a whitespace byte that is inside counts
+// as a byte that is none
+MRX_HD uint32_t fields_word_mask_quoted(const FieldsPlan& P, g_u128 word, uint32_t valid, uint32_t inside) {
+  return fields_ws_mode(P) ? (~fields_ws16(word) | inside) & valid : lines_eq16(word, P.delim) & ~inside & valid;
+}
+// A finished pair's content: a part of two bytes or more that begins and ends with the quote loses both.  tp: the
+// text's first byte; only t[s] and t[e - 1] are read, and only of a part that exists.  Returns the quoted byte.
+MRX_HD uint8_t fields_unquote(const uint8_t* tp, uint32_t quote, int32_t* s, int32_t* e) {
+  if (*s < 0 || *e - *s < 2 || tp[*s] != quote || tp[*e - 1] != quote) return 0;
+  *s += 1;
+  *e -= 1;
+  return 1;
+}
+
 // the position of set bit r of m (0 <= r < popcount(m))
 MRX_HD int fields_kth(uint32_t m, int r) {
   for (; r > 0; --r) m &= m - 1;
@@ -166,8 +212,10 @@ MRX_HD int32_t fields_count(const FieldsPlan& P, int64_t ra) {
 MRX_HD void fields_finish(int32_t* s, int32_t* e) { if (*s < 0) *e = -1; }
 
 // ---- host only: one text, as a group of G lanes walks it ---------------------------------------------------------------
-// The aligned 16-byte words around the text must be readable.  row: int32[f][2].
-inline void fields_host_text(const FieldsPlan& P, int G, const uint8_t* tp, int64_t L, int32_t* row, int32_t* nf_out) {
+// The aligned 16-byte words around the text must be readable.  row: int32[f][2].  quote >= 0: quoted fields with that
+// quote byte, and quoted (uint8[f], may be null) takes the row's quoted bytes.
+inline void fields_host_text(const FieldsPlan& P, int G, const uint8_t* tp, int64_t L, int32_t* row, int32_t* nf_out,
+                             int quote = -1, uint8_t* quoted = nullptr) {
   const int head = (int)((uintptr_t)tp & 15);
   const uint8_t* base = tp - head;
   const int64_t nwords = fields_words(head, L);
@@ -176,14 +224,27 @@ inline void fields_host_text(const FieldsPlan& P, int G, const uint8_t* tp, int6
     const bool negative = pass == 1;
     for (int l = 0; l < G; ++l) fields_row_init(P, negative, nf, (int32_t)L, row, l, G);
     int64_t ra = 0, rb = 0;
-    uint32_t carry = 0;
+    uint32_t carry = 0, parity = 0;   // every walk begins outside
     for (int64_t w0 = 0; w0 < nwords; w0 += G) {
       if (!negative && P.stop && fields_done(P, ra, rb)) break;
       int64_t ea = ra, eb = rb;   // the running prefix over the lanes of the round
+      uint64_t ballot = 0;        // the group's lanes whose word holds an odd number of quotes
+      if (quote >= 0)
+        for (int l = 0; l < G && w0 + l < nwords; ++l) {
+          const uint32_t q = lines_eq16(gather_window(base + 16 * (w0 + l), 16), (uint32_t)quote) & fields_valid(head, L, w0 + l);
+          ballot |= (uint64_t)(lines_popc(q) & 1) << l;
+        }
       for (int l = 0; l < G && w0 + l < nwords; ++l) {
         const int64_t w = w0 + l;
         const g_u128 word = gather_window(base + 16 * w, 16);
-        const uint32_t m = fields_word_mask(P, word, fields_valid(head, L, w));
+        const uint32_t valid = fields_valid(head, L, w);
+        uint32_t m;
+        if (quote >= 0) {
+          const uint32_t q = lines_eq16(word, (uint32_t)quote) & valid;
+          m = fields_word_mask_quoted(P, word, valid, fields_inside(q, fields_parity_front(fields_group_bits(ballot, 0, G), l) ^ parity));
+        } else {
+          m = fields_word_mask(P, word, valid);
+        }
         uint32_t a = m, b = m;
         if (fields_ws_mode(P)) {
           a = fields_starts(m, carry);
@@ -196,10 +257,17 @@ inline void fields_host_text(const FieldsPlan& P, int G, const uint8_t* tp, int6
       }
       ra = ea;
       rb = eb;
+      parity ^= fields_parity_all(fields_group_bits(ballot, 0, G));
     }
     if (!negative) nf = fields_count(P, ra);
   }
-  for (int j = 0; j < P.f; ++j) fields_finish(&row[2 * j], &row[2 * j + 1]);
+  for (int j = 0; j < P.f; ++j) {
+    fields_finish(&row[2 * j], &row[2 * j + 1]);
+    if (quote >= 0) {
+      const uint8_t was = fields_unquote(tp, (uint32_t)quote, &row[2 * j], &row[2 * j + 1]);
+      if (quoted) quoted[j] = was;
+    }
+  }
   if (nf_out) *nf_out = nf;
 }
 
