@@ -1,4 +1,4 @@
-// Device-side matching semantics shared by every kernel in mrx_kernels.hip.
+// Device-side matching semantics shared by the regex kernels of mrx_kernels.hip, mrx_sub.hip and mrx_capall.hip.
 //
 // One wavefront lane owns one text.  The functions below restate, per lane, the
 // reference's matching control flow so that every (pattern, text) pair yields the

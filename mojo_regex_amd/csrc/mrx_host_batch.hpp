@@ -1,7 +1,7 @@
 // Host code that the entry points share.  The packed-output tail of the byte movers: the n == 0 result, the read-back
 // of {rows, bytes} with the capacity verdict, and the workgroup count.  Host-buffer staging of the mrx_*_batch wrappers
-// (mrx_kernels.hip, mrx_set.hip): a CSR batch copied to the device with offsets made relative to its first byte, and
-// device buffers for the outputs, all freed on every way out.
+// (mrx_kernels.hip, mrx_sub.hip, mrx_capall.hip, mrx_split.hip, mrx_set.hip): a CSR batch copied to the device with
+// offsets made relative to its first byte, and device buffers for the outputs, all freed on every way out.
 #pragma once
 #include <hip/hip_runtime.h>
 

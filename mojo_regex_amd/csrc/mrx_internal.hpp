@@ -19,7 +19,7 @@ int internal_fail(int code, const std::string& msg);
 
 // ---- where the texts of a batch live: the one form that entry points, host code and kernels pass on ------------
 // CSR (offsets != nullptr: text i is data[offsets[i], offsets[i + 1])) or fixed pitch (text i begins at data + i * stride
-// and is lens[i], or without lens `len`, bytes long).  The kernels' Layout (mrx_kernels.hip) begins with these fields.
+// and is lens[i], or without lens `len`, bytes long).  The kernels' Layout (mrx_core.hpp) begins with these fields.
 struct TextBatch {
   const uint8_t* data = nullptr;
   const int64_t* offsets = nullptr;

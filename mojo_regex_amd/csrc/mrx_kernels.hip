@@ -1,17 +1,21 @@
-// HIP kernels (gfx950 / CDNA4) and the C ABI of libmrx_hip.so.
+// The core of libmrx_hip.so (gfx950 / CDNA4): the regex kernels, the handle and the entry points of match, search,
+// findall and count.  sub (mrx_sub.hip), captures_all (mrx_capall.hip) and split (mrx_split.hip) launch what is here
+// through mrx_core.hpp.
 //
 // Kernels
 //   k_match<OP>        one lane per text: match_first / search / is_match / captures
 //   k_findall<MODE>    one lane per text: count, or emit spans at a CSR offset
+//   k_wstep, k_mwalk, k_req_wave ...  the stepper family
 //   k_stream_findall   the streaming scan: texts at a fixed pitch, a wavefront
 //                      stages 64 texts x CHUNK bytes through LDS with coalesced
 //                      16-byte loads, each lane then walks its own text in lockstep
 //                      through a register-indexed search automaton (no per-byte
 //                      dependent memory access); match events go to per-text records
 //   k_decode           event records -> CSR spans
-//   k_sub<MODE>        output sizes / output bytes of sub()
 //   k_scan_*           exclusive prefix sums (counts -> CSR offsets)
 // All tables are staged from the plan blob into LDS once per workgroup.
+// Host side: the scratch arena, the prefix sums, the debug switches, the calling thread's state (last error, last
+// kernel, timing) and the definitions of everything mrx_core.hpp and mrx_internal.hpp declare of the core.
 #include <hip/hip_runtime.h>
 #include <atomic>
 #include <map>
@@ -28,12 +32,11 @@
 
 #include "../../include/mrx.h"
 #include "../../include/mrx_testing.h"
-#include "mrx_device.hpp"
-#include "mrx_host_batch.hpp"
-#include "mrx_internal.hpp"
+#include "mrx_core.hpp"
 #include "mrx_lookback.hpp"
 #include "mrx_rec12.hpp"
 #include "mrx_decode_bits.hpp"
+#include "mrx_wave_bits.hpp"
 
 using namespace mrx;
 
@@ -41,86 +44,6 @@ using namespace mrx;
 // device side
 // ============================================================================
 namespace {
-
-constexpr int kBlock = 256;  // 4 wavefronts
-
-struct Layout : TextBatch {  // where text i lives (TextBatch: data, offsets, stride, lens, len), and what kernels add
-  Layout() = default;
-  Layout(const TextBatch& b) : TextBatch(b) {}
-  // Stepper kernels only (ragged batches with a few very long texts): k_wstep leaves texts of at least
-  // `split` bytes to k_req_wave, which in turn skips the shorter ones; 0 = no split
-  int32_t split = 0;
-  // k_wstep / k_req_wave<STEP_SLOTS / STEP_EMIT> and k_slots_gather_wide: slot rows sized by the text
-  // (len / 4 + 32 spans, see slot_row()) instead of kStepSlots, so that long texts rarely need the second walk
-  int32_t wide_slots = 0;
-  // Views (the `start` argument, mrx_*_at_*): with offsets != nullptr, text i is the vlen[i] bytes at
-  // data + offsets[i] (offsets need not be contiguous); nullptr = plain CSR
-  const int32_t* vlen = nullptr;
-  const uint32_t* vskip = nullptr;   // with vlen: the per-text word k_stream_findall's VIRT form expects
-  // k_mwalk<STEP_SLOTS / STEP_EMIT> only: text i is a piece of a longer text and its spans are reported as positions
-  // of that text, vbase[i] + position in the piece (FindallJob::step_scan's pieces); nullptr = as found
-  const int32_t* vbase = nullptr;
-  // per text: first occurrence of the backtracking matcher's literal, last occurrence << 1 | has-newline
-  // (k_litscan in front of the lane-per-text kernels, see bt_prepass()); nullptr = not computed
-  const int2* pre = nullptr;
-  // marks of the positions at which a match begins (k_backscan -> k_wstep<., 0, 0, 0, 1>): one bit per byte of the
-  // text's FRAME (the 16-byte blocks that hold it: bit f = frame position f, the text begins at f = address & 15),
-  // text i's words from bm_row(i) on -- a multiple of four, so that the four words of a 128-byte window are one
-  // aligned 16-byte load; bm_cnt[i] = how many marks text i has
-  const uint32_t* bm = nullptr;
-  const int32_t* bm_cnt = nullptr;
-  __host__ __device__ __forceinline__ int64_t bm_row(int64_t i) const {
-    return 4 * (offsets ? (offsets[i] >> 7) + 2 * i : i * ((stride >> 7) + 2));
-  }
-  // first slot of text i's row and the row's capacity (wide rows)
-  __device__ __forceinline__ int64_t slot_row(int64_t i, int* cap) const {
-    if (offsets) {
-      const int64_t a = (offsets[i] >> 2) + 32 * i, b = (offsets[i + 1] >> 2) + 32 * (i + 1);
-      *cap = (int)(b - a);
-      return a;
-    }
-    const int64_t row = (int64_t)((lens ? stride : (int64_t)len) >> 2) + 32;
-    *cap = (int)row;
-    return i * row;
-  }
-  __device__ __forceinline__ Text text(int64_t i) const {
-    Text t = offsets ? Text(data + offsets[i], vlen ? vlen[i] : (int)(offsets[i + 1] - offsets[i]))
-                     : Text(data + i * stride, lens ? lens[i] : len);
-    if (pre) { const int2 v = pre[i]; t.pre_first = v.x; t.pre_last_nl = v.y; }
-    return t;
-  }
-};
-// every kernel's argument block holds a Layout: its size and field offsets are part of the device code
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Winvalid-offsetof"
-static_assert(sizeof(Layout) == 96 && offsetof(Layout, data) == 0 && offsetof(Layout, len) == 32 &&
-                  offsetof(Layout, split) == 36 && offsetof(Layout, bm_cnt) == 88,
-              "Layout must keep its layout");
-#pragma clang diagnostic pop
-
-__device__ __forceinline__ Ctx stage_tables(const DevPlan& p, const uint8_t* __restrict__ blob,
-                                            uint8_t* lds) {
-  // cooperative 4-byte copy of the plan blob into LDS
-  const uint32_t* src = (const uint32_t*)blob;
-  uint32_t* dst = (uint32_t*)lds;
-  const int words = p.blob_bytes >> 2;
-  for (int i = threadIdx.x; i < words; i += blockDim.x) dst[i] = src[i];
-  __syncthreads();
-  Ctx c;
-  c.p = p;
-  c.cls = lds + p.off_cls;
-  c.first = lds + p.off_first;
-  c.trans = (const uint16_t*)(lds + p.off_trans);
-  c.lit = lds + p.off_lit;
-  c.pre = lds + p.off_pre;
-  c.bs_cls = lds + p.off_bs_cls;
-  c.bs_mask = (const uint64_t*)(lds + p.off_bs_mask);
-  c.bs_follow = (const uint64_t*)(lds + p.off_bs_follow);
-  c.bt_items = (const BtItem*)(lds + (p.off_bt_items >= 0 ? p.off_bt_items : 0));
-  c.bt_tbl = lds + (p.off_bt_tbl >= 0 ? p.off_bt_tbl : 0);
-  c.bt_lit = lds + (p.off_bt_lit >= 0 ? p.off_bt_lit : 0);
-  return c;
-}
 
 enum { OP_MATCH_FIRST = 0, OP_SEARCH = 1, OP_IS_MATCH = 2, OP_CAPTURES = 3 };
 
@@ -1477,7 +1400,6 @@ __global__ __launch_bounds__(kBlock) void k_slots_gather(int64_t n, const int32_
   }
 }
 
-
 // The stepper's two routes for long texts: one WAVEFRONT per text instead of one lane per text.
 // ROUTE 1 (required byte):
 // In HybridMatcher._match_all_required_byte (matcher.mojo:864-898) the attempt made at a hit --
@@ -1707,7 +1629,6 @@ __global__ __launch_bounds__(kBlock) void k_slots_gather_wide(Layout lay, int64_
       if (w + j < span_cap) *(int2*)(spans + 2 * (w + j)) = *(const int2*)(slots + 2 * (row + j));
   }
 }
-
 
 template <int MODE, int BT = 0>
 __global__ __launch_bounds__(kBlock) void k_findall(DevPlan p, const uint8_t* __restrict__ blob,
@@ -2974,20 +2895,6 @@ constexpr int kScanTile = kScanBlock * kScanItems;
 // int2 slots) and one 16-byte store (decode_store_tile16 below, decode_store_plan in mrx_decode_bits.hpp).  The tile is two
 // slots longer for the shift that aligns the pairs.  MRX_DECODE_STORE16=0 / mrx_debug_decode_store16(0) launches STORE16 = false,
 // whose code is the one-span loops'.
-template <int G, bool XOR>
-__device__ __forceinline__ int group_scan(int x);   // (DPP inclusive scan, defined with the sub() kernels below)
-
-// Sum over the wavefront of one 64-bit value per lane -- none negative, the total below 2^63 -- as a wave-uniform
-// value: three 32-bit DPP scans (the low word as two 16-bit halves, which 64 lanes cannot overflow, and the high
-// word) whose last lane is read into SGPRs.  No LDS round trip.
-__device__ __forceinline__ int64_t wave_sum64(int64_t v) {
-  const uint32_t lo = (uint32_t)v, hi = (uint32_t)((uint64_t)v >> 32);
-  const uint32_t s0 = (uint32_t)__builtin_amdgcn_readlane(group_scan<64, false>((int)(lo & 0xFFFFu)), 63);
-  const uint32_t s1 = (uint32_t)__builtin_amdgcn_readlane(group_scan<64, false>((int)(lo >> 16)), 63);
-  const uint32_t s2 = (uint32_t)__builtin_amdgcn_readlane(group_scan<64, false>((int)hi), 63);
-  return (int64_t)((uint64_t)s0 + ((uint64_t)s1 << 16) + ((uint64_t)s2 << 32));
-}
-
 // The spans of a tile pass to memory by plan `pl`: span k of the pass sits at tile slot k + pl.odd and goes to out + 2 k.
 // The head and the tail leave from lanes 0 and 1 in one 8-byte store instruction, the pairs between them two per lane.
 template <bool PACK16, class Slot>
@@ -3764,595 +3671,6 @@ __global__ __launch_bounds__(kBlock) void k_max_len(const int64_t* __restrict__ 
   }
 }
 
-// ---- sub() -------------------------------------------------------------------------
-struct SizeSink {
-  int64_t n = 0;
-  __device__ __forceinline__ void bytes(const uint8_t*, int k) { n += k; }
-};
-struct WriteSink {
-  uint8_t* out;
-  int64_t pos, cap;
-  __device__ __forceinline__ void bytes(const uint8_t* src, int k) {
-    if (pos + k > cap || k < 24) {   // clipped at the buffer's end, or short: byte by byte
-      for (int j = 0; j < k; ++j)
-        if (pos + j < cap) out[pos + j] = src[j];
-      pos += k;
-      return;
-    }
-    // A long piece (the text between two matches): aligned 8-byte stores; the source word for each is put
-    // together from the two aligned words that hold its bytes (every word read holds at least one byte of the piece)
-    uint8_t* d = out + pos;
-    int j = 0;
-    while ((uintptr_t)(d + j) & 7) { d[j] = src[j]; ++j; }
-    const uintptr_t sa = (uintptr_t)(src + j);
-    const uint64_t* sp = (const uint64_t*)(sa & ~(uintptr_t)7);
-    const int sh = (int)(sa & 7) * 8;
-    if (sh) {
-      uint64_t lo = *sp;
-      for (; j + 8 <= k; j += 8) {
-        const uint64_t hi = *++sp;   // (holds the chunk's last sh / 8 bytes)
-        *(uint64_t*)(d + j) = (lo >> sh) | (hi << (64 - sh));
-        lo = hi;
-      }
-    } else {
-      for (; j + 8 <= k; j += 8) *(uint64_t*)(d + j) = *sp++;
-    }
-    for (; j < k; ++j) d[j] = src[j];
-    pos += k;
-  }
-};
-
-// Inclusive scan over the G lanes of a group (16, 32 or 64: groups are aligned rows of 16 lanes) on the
-// DPP path: row_shr 1 / 2 / 4 / 8 inside a row, row_bcast:15 into rows 1 and 3, row_bcast:31 into rows 2
-// and 3 -- one VALU instruction per step where __shfl_up costs a ds_bpermute round trip and a select.
-template <int G, bool XOR>
-__device__ __forceinline__ int group_scan(int x) {
-#define MRX_DPP_STEP(CTRL, ROWS)                                                      \
-  do {                                                                                \
-    const int y = __builtin_amdgcn_update_dpp(0, x, CTRL, ROWS, 0xF, false);          \
-    x = XOR ? (x ^ y) : (x + y);                                                      \
-  } while (0)
-  MRX_DPP_STEP(0x111, 0xF);   // row_shr:1
-  MRX_DPP_STEP(0x112, 0xF);   // row_shr:2
-  MRX_DPP_STEP(0x114, 0xF);   // row_shr:4
-  MRX_DPP_STEP(0x118, 0xF);   // row_shr:8
-  if (G >= 32) MRX_DPP_STEP(0x142, 0xA);   // row_bcast:15 -> rows 1, 3
-  if (G >= 64) MRX_DPP_STEP(0x143, 0xC);   // row_bcast:31 -> rows 2, 3
-#undef MRX_DPP_STEP
-  return x;
-}
-
-// ---- sub() from findall spans (streamable plans) -----------------------------------------
-// For plans whose findall runs on the streaming kernel, regex.sub is assembled from the CSR spans:
-// the first `count` matches of a text (all when count == 0) are replaced, matches are never empty,
-// and the replacement has a fixed length R (literal, or template over fixed-width groups), so
-//   out position of replacement m:  rstart(m) = s_m - cum_m + m * R     (cum_m = matched bytes before m)
-// k_subs_sizes: one lane per text -> output length and cum_m per span.
-__global__ __launch_bounds__(kBlock) void k_subs_sizes(int64_t n, const int64_t* __restrict__ offsets,
-                                                       const int64_t* __restrict__ prefix,
-                                                       const int32_t* __restrict__ spans, long long count,
-                                                       int R, int64_t* __restrict__ sizes,
-                                                       int32_t* __restrict__ cum, int64_t span_cap,
-                                                       const int32_t* __restrict__ left) {
-  // 16 lanes per text: coalesced span loads, prefix sum of the match lengths inside the group
-  if (prefix[n] > span_cap) return;   // the findall in front did not have room for its spans: the host retries
-  if (left && *left == 0) return;     // cum[] is wanted for the texts k_subs_wave left over: there are none
-  constexpr int G = 16;
-  const int lane = threadIdx.x & (G - 1);
-  const int64_t ngroups = (int64_t)gridDim.x * (blockDim.x / G);
-  for (int64_t i = (int64_t)blockIdx.x * (blockDim.x / G) + (threadIdx.x / G); i < n; i += ngroups) {
-    const int64_t a = prefix[i];
-    int64_t k = prefix[i + 1] - a;
-    if (count > 0 && k > count) k = count;
-    int carry = 0;
-    for (int64_t m0 = 0; m0 < k; m0 += G) {
-      const int64_t m = m0 + lane;
-      int len = 0;
-      if (m < k) {
-        const int2 sp = *(const int2*)(spans + 2 * (a + m));
-        len = sp.y - sp.x;
-      }
-      int incl = len;
-#pragma unroll
-      for (int d = 1; d < G; d <<= 1) {
-        const int v = __shfl_up(incl, d, G);
-        if (lane >= d) incl += v;
-      }
-      if (m < k) cum[a + m] = carry + incl - len;
-      carry += __shfl(incl, G - 1, G);
-    }
-    if (lane == 0 && sizes) sizes[i] = (offsets[i + 1] - offsets[i]) - carry + k * (int64_t)R;
-  }
-}
-
-// k_subs_sizes_flat (count == 0: every match is replaced): output length of every text without a dependent
-// round trip per text.  A wavefront owns 64 consecutive texts, whose spans are one contiguous range of the
-// CSR; it streams that range 256 spans at a time, keeps the running sum of the match lengths, and lane t
-// picks the sum's value at its text's first and one-past-last span as they pass (two cross-lane reads per
-// 64 spans).  cum[] -- matched bytes before each match, which only k_subs_emit reads -- is not written here.
-__global__ __launch_bounds__(kBlock) void k_subs_sizes_flat(int64_t n, const int64_t* __restrict__ offsets,
-                                                            const int64_t* __restrict__ prefix,
-                                                            const int32_t* __restrict__ spans, int R,
-                                                            int64_t* __restrict__ sizes, int64_t span_cap) {
-  if (prefix[n] > span_cap) return;   // as k_subs_sizes
-  const int lane = threadIdx.x & 63;
-  const int64_t nw = (n + 63) / 64;
-  for (int64_t w = (int64_t)blockIdx.x * (kBlock / 64) + threadIdx.x / 64; w < nw; w += (int64_t)gridDim.x * (kBlock / 64)) {
-    const int64_t i = w * 64 + lane;
-    const bool live = i < n;
-    const int64_t pa = live ? prefix[i] : 0, pb = live ? prefix[i + 1] : 0;
-    const int64_t tbytes = live ? offsets[i + 1] - offsets[i] : 0;
-    const int64_t i_last = (w * 64 + 64 < n ? w * 64 + 64 : n);
-    const int64_t A = __shfl(pa, 0), B = prefix[i_last];
-    int run = 0;                 // matched bytes of spans [A, c), modulo 2^32 (differences are what is used)
-    int at_a = 0, at_b = 0;      // the running sum in front of span pa / pb (both 0 while pa == A / pb == A)
-    for (int64_t c = A; c < B; c += 256) {
-      int len[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int64_t m = c + 64 * j + lane;
-        int2 sp = make_int2(0, 0);
-        if (m < B) sp = *(const int2*)(spans + 2 * m);
-        len[j] = sp.y - sp.x;
-      }
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int64_t c0 = c + 64 * j;
-        const int incl = (int)((uint32_t)run + (uint32_t)group_scan<64, false>(len[j]));   // sum of spans [A, c0 + lane]
-        // the sum in front of span x, x in (c0, c0 + 64]: lane x - 1 - c0 holds it
-        const int64_t ja = pa - 1 - c0, jb = pb - 1 - c0;
-        const int va = __shfl(incl, (int)(ja & 63)), vb = __shfl(incl, (int)(jb & 63));
-        if (ja >= 0 && ja < 64) at_a = va;
-        if (jb >= 0 && jb < 64) at_b = vb;
-        run = __shfl(incl, 63);
-      }
-    }
-    if (live) sizes[i] = tbytes - (int64_t)((uint32_t)at_b - (uint32_t)at_a) + (pb - pa) * (int64_t)R;
-  }
-}
-
-// k_subs_emit: one wavefront per text, output centric.  Each lane produces one 16-byte block of
-// the output (aligned on the output ADDRESS, so full blocks are single coalesced 16-byte stores),
-// finds by binary search which replacement precedes its first byte and then walks: replacement
-// bytes come from rmap (literal byte, or 0x8000 | offset into the match for a group byte), kept
-// bytes from the input through an 8-byte register window.
-constexpr int kSubsStage = 128;  // replacements per text staged in LDS (more: read from global)
-constexpr int kSubsLanes = 16;   // lanes that share one text in k_subs_emit
-
-// bytes src .. src+15 of a text as two little-endian u64 (bytes past the text are unspecified but
-// never fetched from beyond the aligned word that holds the text's last byte)
-__device__ __forceinline__ void load16(const uint8_t* base, int len, int src, uint64_t& lo, uint64_t& hi) {
-  const uintptr_t addr = (uintptr_t)(base + src);
-  const uint64_t* w = (const uint64_t*)(addr & ~(uintptr_t)7);
-  const uint64_t* last = (const uint64_t*)(((uintptr_t)(base + len - 1)) & ~(uintptr_t)7);  // len > 0
-  const uint64_t w0 = w <= last ? w[0] : 0, w1 = w + 1 <= last ? w[1] : 0, w2 = w + 2 <= last ? w[2] : 0;
-  const int sh = (int)(addr & 7) * 8;
-  if (sh == 0) { lo = w0; hi = w1; }
-  else { lo = (w0 >> sh) | (w1 << (64 - sh)); hi = (w1 >> sh) | (w2 << (64 - sh)); }
-}
-
-// G = 16: 16 lanes share a text and its replacements are staged whole (up to kSubsStage, more: read
-// from global).  G = kBlock (long texts): a whole workgroup shares a text, and every round -- G output
-// blocks = 4 KiB of output -- stages the window of replacements that can touch it (the last one
-// starting at or before the round's first byte, and the kSubsWindow - 1 after it).
-constexpr int kSubsWindow = 512;
-// texts k_subs_wave<G> takes (the rest is k_subs_emit's): frame and output fit the group's LDS tiles
-__host__ __device__ inline bool subs_wave_takes(int G, int tlen, int mis, int olen, int head) {
-  return tlen + mis <= 32 * G + 16 && olen + head <= 64 * G;
-}
-template <int G>
-__global__ __launch_bounds__(kBlock) void k_subs_emit(int64_t n, const uint8_t* __restrict__ data,
-                                                      const int64_t* __restrict__ offsets,
-                                                      const int64_t* __restrict__ prefix,
-                                                      const int32_t* __restrict__ spans,
-                                                      const int32_t* __restrict__ cum, long long count,
-                                                      int R, const uint16_t* __restrict__ rmap,
-                                                      const int64_t* __restrict__ out_off,
-                                                      uint8_t* __restrict__ out, int skip_g,
-                                                      const int32_t* __restrict__ left) {
-  // `left`: k_subs_wave<skip_g> in front took every text (skip_g != 0), or the host's go-ahead behind the totals
-  // (k_subs_gate: the kernel is enqueued before the host has seen them) says no
-  if (left && *left == 0) return;
-  // kSubsLanes lanes share one text (4 texts per wavefront): a 1 KiB text has ~70 output blocks,
-  // which 64 lanes cover in two half-empty rounds; 16 lanes cover them in five full ones, and the
-  // four texts' dependent round trips (offsets -> spans -> bytes) overlap.
-  constexpr bool WIN = G != kSubsLanes;
-  constexpr int STAGE = WIN ? kSubsWindow : kSubsStage;
-  static_assert(G == kSubsLanes || G == kBlock, "a group is 16 lanes or the workgroup");
-  __shared__ int3 stage_all[kBlock / G][STAGE];  // {rstart, match start, match end}
-  extern __shared__ __align__(16) uint8_t subs_dyn[];   // the replacement map (R u16 entries)
-  uint16_t* rmap_lds = (uint16_t*)subs_dyn;
-  for (int r = threadIdx.x; r < R; r += blockDim.x) rmap_lds[r] = rmap[r];
-  __syncthreads();
-  auto group_sync = [&]() {
-    if (WIN) __syncthreads();
-    else {
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    }
-  };
-  const int lane = threadIdx.x & (G - 1);   // lane within the group that owns the text
-  int3* stage = stage_all[threadIdx.x / G];
-  const int64_t ngroups = (int64_t)gridDim.x * (blockDim.x / G);
-  for (int64_t i = (int64_t)blockIdx.x * (blockDim.x / G) + (threadIdx.x / G); i < n; i += ngroups) {
-    const int64_t ibase = offsets[i];
-    const uint8_t* tptr = data + ibase;
-    const int tlen = (int)(offsets[i + 1] - ibase);
-    const int64_t a = prefix[i];
-    int64_t k64 = prefix[i + 1] - a;
-    if (count > 0 && k64 > count) k64 = count;
-    const int k = (int)k64;
-    const int64_t obase = out_off[i];
-    const int olen = (int)(out_off[i + 1] - obase);
-    if (olen <= 0) continue;
-    if (skip_g && subs_wave_takes(skip_g, tlen, (int)((uintptr_t)tptr & 15), olen, (int)((uintptr_t)(out + obase) & 15)))
-      continue;   // k_subs_wave<skip_g> wrote this text
-    const int32_t* sp = spans + 2 * a;
-    const int32_t* cm = cum + a;
-    const bool staged = !WIN && k <= STAGE;
-    auto repl_global = [&](int m) {  // {rstart, match start, match end} of replacement m
-      const int2 se = *(const int2*)(sp + 2 * m);
-      return make_int3(se.x - cm[m] + m * R, se.x, se.y);
-    };
-    group_sync();
-    if (staged) {
-      for (int m = lane; m < k; m += G) stage[m] = repl_global(m);
-      group_sync();
-    }
-    int wbase = 0, wcnt = 0;   // WIN: replacements [wbase, wbase + wcnt) are staged
-    auto repl_at = [&](int m) {
-      if (staged) return stage[m];
-      if (WIN && m >= wbase && m < wbase + wcnt) return stage[m - wbase];
-      return repl_global(m);
-    };
-    const int head = (int)((uintptr_t)(out + obase) & 15);  // output starts `head` bytes into its first 16-byte block
-    for (int blk = 0; blk * 16 < head + olen; blk += G) {
-      if (WIN) {
-        group_sync();   // everyone is done with the previous window
-        const int w_lo = blk * 16 - head < 0 ? 0 : blk * 16 - head;   // first output position of this round
-        int lo = -1, hi = k;
-        while (hi - lo > 1) {   // same addresses in every lane: one broadcast load per step
-          const int mid = (lo + hi) >> 1;
-          if (repl_global(mid).x <= w_lo) lo = mid; else hi = mid;
-        }
-        wbase = lo < 0 ? 0 : lo;
-        wcnt = k - wbase < STAGE ? k - wbase : STAGE;
-        for (int m = lane; m < wcnt; m += G) stage[m] = repl_global(wbase + m);
-        group_sync();
-      }
-      const int p_lo = (blk + lane) * 16 - head;   // first output position of my block (may be < 0)
-      int p = p_lo < 0 ? 0 : p_lo;
-      const int p_hi = p_lo + 16 < olen ? p_lo + 16 : olen;
-      if (p >= p_hi) continue;
-      // j = last replacement with rstart(j) <= p, or -1
-      int lo = -1, hi = k;
-      while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (repl_at(mid).x <= p) lo = mid; else hi = mid;
-      }
-      int j = lo;
-      int3 cur = j >= 0 ? repl_at(j) : make_int3(0, 0, 0);
-      int nxt = j + 1 < k ? repl_at(j + 1).x : 0x7FFFFFFF;
-      uint64_t wlo = 0, whi = 0;   // the 16 output bytes
-      // OR `cnt` (1..16) bytes of (vlo, vhi) into the block at byte offset q
-      auto put = [&](uint64_t vlo, uint64_t vhi, int q, int cnt) {
-        if (cnt < 8) { vlo &= (1ull << (cnt * 8)) - 1; vhi = 0; }
-        else if (cnt < 16) { vhi &= (cnt == 8) ? 0ull : ((1ull << ((cnt - 8) * 8)) - 1); }
-        if (q == 0) { wlo |= vlo; whi |= vhi; }
-        else if (q < 8) { wlo |= vlo << (q * 8); whi |= (vhi << (q * 8)) | (vlo >> (64 - q * 8)); }
-        else if (q == 8) { whi |= vlo; }
-        else { whi |= vlo << ((q - 8) * 8); }
-      };
-      while (p < p_hi) {
-        while (p == nxt) {   // several replacements can start here when R == 0 and matches touch
-          ++j;
-          cur = repl_at(j);
-          nxt = j + 1 < k ? repl_at(j + 1).x : 0x7FFFFFFF;
-        }
-        if (j >= 0 && p < cur.x + R) {   // replacement bytes: literal, or group bytes of the match
-          int stop = cur.x + R < p_hi ? cur.x + R : p_hi;
-          if (nxt < stop) stop = nxt;
-          uint64_t mlo, mhi;
-          load16(tptr, tlen, cur.y, mlo, mhi);   // the first 16 bytes of the match
-          for (; p < stop; ++p) {
-            const uint32_t r = rmap_lds[p - cur.x];
-            int b = (int)r;
-            if (r & 0x8000u) {
-              const int o = (int)(r & 0x7FFFu);
-              b = o < 16 ? (int)(((o < 8 ? mlo : mhi) >> ((o & 7) * 8)) & 0xFFu) : (int)tptr[cur.y + o];
-            }
-            put((uint64_t)(uint32_t)b, 0, p - p_lo, 1);
-          }
-        } else {                          // kept input bytes up to the next replacement: one 16-byte fetch
-          const int src = j >= 0 ? p - (cur.x + R) + cur.z : p;
-          const int stop = nxt < p_hi ? nxt : p_hi;
-          uint64_t vlo, vhi;
-          load16(tptr, tlen, src, vlo, vhi);
-          put(vlo, vhi, p - p_lo, stop - p);
-          p = stop;
-        }
-      }
-      uint8_t* dst = out + (obase + p_lo);
-      if (p_lo >= 0 && p_lo + 16 <= olen) {
-        *(uint4*)dst = make_uint4((uint32_t)wlo, (uint32_t)(wlo >> 32), (uint32_t)whi, (uint32_t)(whi >> 32));
-      } else {  // block shared with a neighbouring text: byte stores only
-        for (int q = (p_lo < 0 ? -p_lo : 0); q < p_hi - p_lo; ++q)
-          dst[q] = (uint8_t)((q < 8 ? wlo : whi) >> ((q & 7) * 8));
-      }
-    }
-    group_sync();
-  }
-}
-
-// k_subs_wave<G>: G lanes (a wavefront, half or quarter of one) assemble one text's output in LDS without a
-// search and without a per-byte branch.  Text positions are kept in the frame of the 16-byte blocks that
-// hold the text (mis = address & 15), the output tile in the frame of the output address (head).
-//   matches, one lane each:  the start and end position of every replaced match set a bit in two LDS
-//     bitmaps; matched bytes before the match come from a prefix sum over the lanes' match lengths, so the
-//     replacement's R bytes go straight to  head + start - matched_before + m R  in the output tile;
-//   frame blocks, one lane each:  T = starts ^ ends of the block; "inside a match" at byte t is the parity
-//     of the T bits at or below t (matches are non-empty and do not overlap; an end that is the next
-//     match's start cancels), carried across lanes by a prefix sum that also gives the kept bytes and the
-//     match starts before the block, i.e. where the block's first kept byte goes; the 16 bytes are then
-//     placed with predicated byte writes;
-//   output blocks, one lane each:  16-byte stores (byte stores where a block is shared with a neighbour).
-// Texts whose frame or output exceeds the tiles (32 G + 16 / 64 G bytes) are left to k_subs_emit.
-template <int G>
-__global__ __launch_bounds__(kBlock) void k_subs_wave(int64_t n, const uint8_t* __restrict__ data,
-                                                      const int64_t* __restrict__ offsets,
-                                                      const int64_t* __restrict__ prefix,
-                                                      const int32_t* __restrict__ spans, long long count,
-                                                      int R, const uint16_t* __restrict__ rmap,
-                                                      const int64_t* __restrict__ out_off,
-                                                      uint8_t* __restrict__ out, int32_t* __restrict__ left,
-                                                      const int32_t* __restrict__ go, int dbg) {
-  if (*go == 0) return;   // k_subs_gate: the spans or the output do not fit (the host finds out behind this launch)
-  constexpr int NG = kBlock / G, F = 32 * G + 16, O = 64 * G, BW = F / 32 + 1;
-  static_assert(G == 256 || G == 64 || G == 32 || G == 16, "group = workgroup, wavefront, half or quarter of one");
-  constexpr bool BLK = G > 64;   // the workgroup shares one text: barriers instead of wavefront order, prefix
-                                 // sums carried across its four wavefronts through LDS
-  static_assert(!BLK || G == kBlock, "a group beyond a wavefront is the whole workgroup");
-  __shared__ __align__(16) uint8_t text_all[NG][F];
-  __shared__ __align__(16) uint8_t out_all[NG][O];
-  __shared__ uint32_t sbits_all[NG][BW], ebits_all[NG][BW];
-  __shared__ uint32_t spare_all[kBlock];
-  __shared__ int xw_all[3][BLK ? kBlock / 64 : 1];   // BLK: per-wavefront totals of the three prefix sums
-  extern __shared__ __align__(16) uint8_t subs_dyn[];   // the replacement map (R u16 entries)
-  uint16_t* rmap_lds = (uint16_t*)subs_dyn;
-  for (int r = threadIdx.x; r < R + 8; r += blockDim.x) rmap_lds[r] = r < R ? rmap[r] : (uint16_t)0;
-  __syncthreads();
-  auto group_sync = [&]() {
-    if (BLK) { __syncthreads(); return; }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  };
-  // inclusive prefix over the group's lanes and the group's total (xw: one of the three LDS rows; a row is
-  // used once per round, and the rounds are separated by the barriers of the other two)
-  auto scan_add = [&](int x, int* xw, int& total) {
-    if constexpr (!BLK) {
-      const int incl = group_scan<BLK ? 64 : G, false>(x);
-      total = __shfl(incl, G - 1, G);
-      return incl;
-    }
-    int incl = group_scan<64, false>(x);
-    const int wv = threadIdx.x >> 6;
-    __syncthreads();   // the row's previous readers are done
-    if ((threadIdx.x & 63) == 63) xw[wv] = incl;
-    __syncthreads();
-    int before = 0, tot = 0;
-#pragma unroll
-    for (int q = 0; q < kBlock / 64; ++q) { const int v = xw[q]; tot += v; if (q < wv) before += v; }
-    total = tot;
-    return incl + before;
-  };
-  auto scan_xor = [&](int x, int* xw, int& total) {
-    if constexpr (!BLK) {
-      const int incl = group_scan<BLK ? 64 : G, true>(x);
-      total = __shfl(incl, G - 1, G);
-      return incl;
-    }
-    int incl = group_scan<64, true>(x);
-    const int wv = threadIdx.x >> 6;
-    __syncthreads();
-    if ((threadIdx.x & 63) == 63) xw[wv] = incl;
-    __syncthreads();
-    int before = 0, tot = 0;
-#pragma unroll
-    for (int q = 0; q < kBlock / 64; ++q) { const int v = xw[q]; tot ^= v; if (q < wv) before ^= v; }
-    total = tot;
-    return incl ^ before;
-  };
-  const int lane = threadIdx.x & (G - 1), grp = threadIdx.x / G;
-  uint8_t* text = text_all[grp];
-  uint8_t* otile = out_all[grp];
-  uint32_t* sbits = sbits_all[grp];
-  uint32_t* ebits = ebits_all[grp];
-  const int64_t ngroups = (int64_t)gridDim.x * NG;
-  // Two texts ahead: the descriptor (offsets, prefix, out_off: one round trip); one text ahead: its frame
-  // blocks and its first G spans, in registers -- the global round trips of text i + 1 run under the LDS
-  // phases of text i.
-  struct Desc { int64_t ibase, a, obase; int tlen, k, olen; };
-  auto load_desc = [&](int64_t i) {
-    Desc d{0, 0, 0, 0, 0, 0};
-    if (i < n) {
-      d.ibase = offsets[i];
-      d.tlen = (int)(offsets[i + 1] - d.ibase);
-      d.a = prefix[i];
-      int64_t k64 = prefix[i + 1] - d.a;
-      if (count > 0 && k64 > count) k64 = count;
-      d.k = (int)k64;
-      d.obase = out_off[i];
-      d.olen = (int)(out_off[i + 1] - d.obase);
-    }
-    return d;
-  };
-  uint4 tx[3];
-  int2 sp_first;
-  auto issue = [&](const Desc& d) {
-    const uint8_t* tptr = data + d.ibase;
-    const int mis = (int)((uintptr_t)tptr & 15);
-    const uint8_t* fptr = tptr - mis;
-    int nfb = d.olen > 0 ? (mis + d.tlen + 15) >> 4 : 0;
-    if (nfb > 2 * G + 1) nfb = 2 * G + 1;   // a longer text is not this kernel's
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-      const int b = lane + r * G;
-      tx[r] = b < nfb ? MRX_LDG((const uint4*)(fptr + 16 * b)) : make_uint4(0, 0, 0, 0);
-    }
-    sp_first = (d.olen > 0 && lane < d.k) ? *(const int2*)(spans + 2 * (d.a + lane)) : make_int2(0, 0);
-  };
-  int64_t i = (int64_t)blockIdx.x * NG + grp;
-  Desc d0 = load_desc(i), d1 = load_desc(i + ngroups);
-  issue(d0);
-  for (; i < n; i += ngroups) {
-    const Desc d = d0;
-    d0 = d1;
-    d1 = load_desc(i + 2 * ngroups);
-    const uint8_t* tptr = data + d.ibase;
-    const int tlen = d.tlen, k = d.k, olen = d.olen;
-    const int64_t a = d.a, obase = d.obase;
-    const int mis = (int)((uintptr_t)tptr & 15), head = (int)((uintptr_t)(out + obase) & 15);
-    if (olen <= 0 || !subs_wave_takes(G, tlen, mis, olen, head)) {
-      if (olen > 0 && lane == 0) *left = 1;   // k_subs_emit, launched behind this kernel, looks
-      issue(d0);
-      continue;
-    }
-    const int nfb = (mis + tlen + 15) >> 4;
-    group_sync();   // the previous text's tiles are free
-    for (int w = lane; w < BW; w += G) { sbits[w] = 0; ebits[w] = 0; }
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-      if (lane + r * G < nfb) *(uint4*)(text + 16 * (lane + r * G)) = tx[r];
-    const int2 sp_cur = sp_first;
-    issue(d0);
-    group_sync();
-    // ---- matches: boundary bits, replacement bytes
-    int carry = 0;
-    for (int m0 = 0; m0 < ((dbg & 16) ? 0 : k); m0 += G) {
-      const int m = m0 + lane;
-      int ms = 0, me = 0;
-      if (m < k) {
-        const int2 sp = m0 == 0 ? sp_cur : *(const int2*)(spans + 2 * (a + m));
-        ms = sp.x; me = sp.y;
-      }
-      const int len = me - ms;
-      int round_total;
-      const int incl = scan_add(len, xw_all[0], round_total);
-      const int before = carry + incl - len;
-      carry += round_total;
-      if (m < k) {
-        atomicOr(&sbits[(mis + ms) >> 5], 1u << ((mis + ms) & 31));
-        atomicOr(&ebits[(mis + me) >> 5], 1u << ((mis + me) & 31));
-        uint8_t* dst = otile + (head + ms - before + m * R);
-        const uint8_t* msrc = text + mis + ms;
-        // four bytes a round: the map entries (one address for every lane) and the match bytes they name are read
-        // together -- a byte at a time the loop waits for two dependent LDS reads per replacement byte
-        for (int t = 0; t < ((dbg & 1) ? 0 : R); t += 4) {
-          uint32_t r[4], v[4];
-#pragma unroll
-          for (int q = 0; q < 4; ++q) r[q] = rmap_lds[t + q];   // (the map is padded with eight zero entries)
-#pragma unroll
-          for (int q = 0; q < 4; ++q) v[q] = msrc[(r[q] & 0x8000u) ? (r[q] & 0x7FFFu) : 0u];
-#pragma unroll
-          for (int q = 0; q < 4; ++q)
-            if (t + q < R) dst[t + q] = (r[q] & 0x8000u) ? (uint8_t)v[q] : (uint8_t)r[q];
-        }
-      }
-    }
-    group_sync();
-    // ---- frame blocks: kept bytes
-    int kept_carry = 0, starts_carry = 0, inside_carry = 0;
-    for (int b0 = 0; b0 < ((dbg & 8) ? 0 : nfb); b0 += G) {
-      const int b = b0 + lane;
-      uint32_t S = 0, T = 0, valid = 0;
-      uint4 bx = make_uint4(0, 0, 0, 0);
-      if (b < nfb) {
-        const int sh = (b & 1) * 16;
-        S = (sbits[b >> 1] >> sh) & 0xFFFFu;
-        T = S ^ ((ebits[b >> 1] >> sh) & 0xFFFFu);
-        const int lo = b == 0 ? mis : 0;
-        const int hi = mis + tlen - 16 * b < 16 ? mis + tlen - 16 * b : 16;
-        valid = ((1u << hi) - 1u) & ~((1u << lo) - 1u);
-        bx = *(const uint4*)(text + 16 * b);
-      }
-      uint32_t P = T;   // P bit t = parity of the T bits at or below t
-      P ^= P << 1; P ^= P << 2; P ^= P << 4; P ^= P << 8;
-      P &= 0xFFFFu;
-      const uint32_t keep0 = valid & ~P, keep1 = valid & P;   // kept bytes if the block begins outside / inside a match
-      // kept bytes | match starts << 12 | parity << 24, for both entry states the counts differ: scan the
-      // parity first (it decides which), then the counts
-      const int par = (int)(P >> 15);
-      int par_total;
-      const int pin = scan_xor(par, xw_all[1], par_total);
-      const int inside = inside_carry ^ pin ^ par;   // state on entry to my block
-      inside_carry ^= par_total;
-      const uint32_t keep = inside ? keep1 : keep0;
-      const int cnt = __popc(keep) | (__popc(S) << 16);   // kept bytes (<= 16 G) | match starts
-      int tot;
-      const int cin = scan_add(cnt, xw_all[2], tot);
-      const int ex = cin - cnt;
-      int po = head + kept_carry + (ex & 0xFFFF) + (starts_carry + (ex >> 16)) * R;
-      kept_carry += tot & 0xFFFF;
-      starts_carry += tot >> 16;
-      // 16 unconditional byte writes: a byte that is not kept goes to the lane's own spare word (a select costs
-      // less than an execution-mask round trip per byte); a wavefront without any kept byte skips them
-      if (__builtin_amdgcn_ballot_w64(keep != 0) == 0 || (dbg & 2)) continue;
-      const uint32_t wv[4] = {bx.x, bx.y, bx.z, bx.w};
-      uint8_t* const spare = (uint8_t*)&spare_all[threadIdx.x];
-      const int Rs = S ? R : 0;
-#pragma unroll
-      for (int t = 0; t < 16; ++t) {
-        po += (int)((S >> t) & 1u) * Rs;
-        const uint32_t kb = (keep >> t) & 1u;
-        uint8_t* const wp = kb ? otile + po : spare;
-        *wp = (uint8_t)(wv[t >> 2] >> ((t & 3) * 8));
-        po += (int)kb;
-      }
-    }
-    group_sync();
-    // ---- output blocks
-    uint8_t* dst0 = out + obase - head;
-    const int nob = (dbg & 4) ? 0 : (head + olen + 15) >> 4;
-    for (int b = lane; b < nob; b += G) {
-      if (16 * b >= head && 16 * b + 16 <= head + olen) {
-        *(uint4*)(dst0 + 16 * b) = *(const uint4*)(otile + 16 * b);
-      } else {   // block shared with a neighbouring text
-        const int q1 = 16 * b + 16 < head + olen ? 16 * b + 16 : head + olen;
-        for (int q = 16 * b < head ? head : 16 * b; q < q1; ++q) dst0[q] = otile[q];
-      }
-    }
-  }
-}
-
-enum { SUB_SIZE = 0, SUB_EMIT = 1 };
-
-template <int MODE, int BT = 0>
-__global__ __launch_bounds__(kBlock) void k_sub(DevPlan p, const uint8_t* __restrict__ blob,
-                                                Layout lay, int64_t n,
-                                                const uint8_t* __restrict__ repl, int repl_len,
-                                                int use_groups, const ReplSeg* __restrict__ tpl,
-                                                int ntpl, long long count,
-                                                int64_t* __restrict__ sizes,
-                                                const int64_t* __restrict__ out_off,
-                                                uint8_t* __restrict__ out, int64_t out_cap) {
-  extern __shared__ __align__(16) uint8_t lds[];
-  const Ctx c = stage_tables(p, blob, lds);
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += (int64_t)gridDim.x * blockDim.x) {
-    const Text t = lay.text(i);
-    if (MODE == SUB_SIZE) {
-      SizeSink s;
-      sub_text<BT>(c, t, repl, repl_len, use_groups, tpl, ntpl, count, s);
-      sizes[i] = s.n;
-    } else {
-      WriteSink s{out, out_off[i], out_cap};
-      sub_text<BT>(c, t, repl, repl_len, use_groups, tpl, ntpl, count, s);
-    }
-  }
-}
-
 // ---- exclusive scan (counts -> CSR offsets) ---------------------------------------
 template <class T>
 __global__ __launch_bounds__(kScanBlock) void k_scan_local(const T* __restrict__ in, int64_t n,
@@ -4437,46 +3755,6 @@ __global__ __launch_bounds__(kScanBlock) void k_scan_add(int64_t* __restrict__ o
 // ============================================================================
 // host side
 // ============================================================================
-// The compiled tables live once per device that has used the handle (uploaded on first use there,
-// never freed or replaced before mrx_free): concurrent calls on one handle from threads bound to
-// different GPUs each see their own device's copy.
-constexpr int kMaxDevices = 64;
-struct mrx_handle {
-  HostPlan hp;
-  std::atomic<uint8_t*> d_blobs[kMaxDevices];
-  std::mutex mu;   // serialises the first upload per device
-  std::string describe_cache;
-  // sub: matches per KiB of input the last batch held (0 = nothing seen yet): sizes the span buffer of the next
-  // call so that a dense batch (more than one match per eight bytes) does not scan twice every time
-  mutable std::atomic<int64_t> sub_matches_per_kib{0};
-  // findall of a required-byte plan on long texts: the wavefront-per-text kernel or pieces on the multi-walk kernel?
-  // Neither candidate density nor batch shape predicts it (profiles/r04_suite_routes.md), so the first two calls of a
-  // batch shape try each route (see ReqTune) and the faster one is kept.
-  // Four measured calls per batch shape: each route once untimed (its scratch gets allocated), then each route timed --
-  // two HIP events on the caller's stream around the call's work, read by a LATER call of the shape once the last pair
-  // has completed: no call ever waits for the tuner, and callers that enqueue back to back are served as well.
-  struct ReqTune {
-    int issued = 0, choice = 0;   // calls measured so far (0..4); choice: 1 wavefront kernel, 2 pieces
-    bool probed = false;
-    float ms_wave = 0, ms_pieces = 0;
-    hipEvent_t ev[4][2] = {{nullptr, nullptr}, {nullptr, nullptr}, {nullptr, nullptr}, {nullptr, nullptr}};
-    int dev = 0;                  // device the events belong to (part of the key)
-  };
-  mutable std::mutex tune_mu;
-  mutable std::map<uint32_t, ReqTune> req_tune;
-  // findall on texts FULL of matches (config 5: a match every six bytes): event rows instead of records (ST_ROWS,
-  // k_decode_rows).  How full a batch is, the handle's previous eligible call tells: its total travels to pinned host
-  // memory behind the call's work and is looked at by the next call if it has arrived -- no call waits for it.
-  struct DenseProbe {
-    int64_t* host_total = nullptr;   // pinned
-    hipEvent_t ev = nullptr;
-    bool pending = false;
-    int64_t bytes = 0;               // of the batch the pending total belongs to
-    int dev = 0, dense = 0;          // dense: 1 = the last batch seen held at least one match per kDenseBytesPerSpan bytes
-  };
-  mutable DenseProbe dense_probe;    // (under tune_mu)
-  mrx_handle() { for (auto& b : d_blobs) b.store(nullptr, std::memory_order_relaxed); }
-};
 
 namespace {
 
@@ -4503,8 +3781,10 @@ int fail(int code, const std::string& msg) {
 }
 
 }  // namespace
-namespace mrx {   // mrx_internal.hpp
+namespace mrx {   // mrx_internal.hpp, mrx_core.hpp
 int internal_fail(int code, const std::string& msg) { return fail(code, msg); }
+int force_generic() { return g_force_generic; }
+int long_text_mode() { return g_long_text_mode; }
 int check_batch(const TextBatch& b, BatchForm form) {
   if (form == BATCH_CSR) return b.offsets ? MRX_OK : fail(MRX_E_ARGUMENT, "null offsets");
   if (b.offsets) return MRX_OK;
@@ -4580,13 +3860,12 @@ hipError_t scratch_alloc(void** out, size_t bytes, hipStream_t s) {
   *out = p;
   return hipSuccess;
 }
-// A phase that began with nothing in use (the head of a call) hands its bytes to what follows: the next phase
-// allocates where it lay.  Further inside a call -- something is held at the mark -- the bytes stay until the scope
-// closes, so that what follows lies where it always lay.
-void scratch_reuse_from(hipStream_t s, const mrx::ScratchMark& m) {
+}  // namespace
+void mrx::scratch_reuse_from(hipStream_t s, const ScratchMark& m) {   // (mrx_core.hpp)
   for (size_t u : m.used) if (u) return;
-  mrx::scratch_rewind(s, m);
+  scratch_rewind(s, m);
 }
+namespace {
 size_t scratch_bytes_reserved() {   // testing: total bytes held by the calling thread's arenas
   size_t t = 0;
   for (auto& kv : g_scratch) for (auto& c : kv.second.chunks) t += c.cap;
@@ -4609,10 +3888,11 @@ void scratch_release_all() {
   g_scratch.clear();
 }
 
-// The calling thread's current device, set by ensure_device() at the start of every entry point;
-// H_BLOB(h) is the handle's table copy on that device.
+// The calling thread's current device, set by ensure_device() at the start of every entry point
 thread_local int t_dev = 0;
-#define H_BLOB(h) ((h)->d_blobs[t_dev].load(std::memory_order_acquire))
+}  // namespace
+namespace mrx {   // mrx_core.hpp
+int current_device() { return t_dev; }
 
 int ensure_device(const mrx_handle* hc) {
   mrx_handle* h = const_cast<mrx_handle*>(hc);
@@ -4644,14 +3924,16 @@ int grid_cap() {
   return c * 8;
 }
 
-int grid_for(int64_t n, int block) {
+int device_grid(int64_t n, int block) {
   int64_t g = (n + block - 1) / block;
   if (g < 1) g = 1;
   const int64_t cap = grid_cap();
   return (int)(g < cap ? g : cap);
 }
+}  // namespace mrx
+namespace {
 // one lane per text in workgroups of `waves` wavefronts: at least one workgroup, at most what fills the device
-int wave_grid(int64_t n, int waves) { return grid_for((n + 63) / 64, waves); }
+int wave_grid(int64_t n, int waves) { return device_grid((n + 63) / 64, waves); }
 int wstep_grid(int64_t n) { return wave_grid(n, kWsWaves); }
 
 // Which form of the stepper family a findall / count call launches (wstep_launch / reqwave_launch).  Filled in one
@@ -4863,13 +4145,14 @@ int bscan_fixed(const mrx_handle* h, const Layout& lay, int64_t n, int mode, hip
 
 // byte count and longest text of a CSR batch: both live on the device (one small kernel, one sync).  At the head of
 // a call the word it reads back through is handed back at once (scratch_reuse_from()).
-int csr_stats(const Layout& lay, int64_t n, hipStream_t s, int64_t* total, int64_t* max_len) {
+}  // namespace
+int mrx::csr_stats(const Layout& lay, int64_t n, hipStream_t s, int64_t* total, int64_t* max_len) {
   const ScratchMark mark = scratch_mark(s);
   int32_t* d_max = nullptr;
   int32_t m = 0;
   HIP_TRY(scratch_alloc((void**)&d_max, sizeof(int32_t), s));
   HIP_TRY(hipMemsetAsync(d_max, 0, sizeof(int32_t), s));
-  hipLaunchKernelGGL(k_max_len, dim3(grid_for(n, kBlock * 8)), dim3(kBlock), 0, s, lay.offsets, n, d_max);
+  hipLaunchKernelGGL(k_max_len, dim3(device_grid(n, kBlock * 8)), dim3(kBlock), 0, s, lay.offsets, n, d_max);
   HIP_TRY(hipMemcpyAsync(&m, d_max, sizeof m, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipMemcpyAsync(total, lay.offsets + n, sizeof *total, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
@@ -4877,6 +4160,7 @@ int csr_stats(const Layout& lay, int64_t n, hipStream_t s, int64_t* total, int64
   *max_len = m;
   return MRX_OK;
 }
+namespace {
 // bytes the batch holds: a CSR batch's count lives on the device (one 8-byte read-back and one synchronisation); at a
 // fixed pitch n texts of `per_text` bytes (the pitch where the rows' span is meant, pitch_longest() for the texts' own bytes)
 int batch_bytes(const Layout& lay, int64_t n, int64_t per_text, hipStream_t s, int64_t* bytes) {
@@ -4946,25 +4230,22 @@ void reqwave_launch(const StepRoute& r, const mrx_handle* h, const Layout& lay, 
                        spans, cap, (int32_t*)nullptr, (int32_t*)nullptr);
 }
 
-struct ScanTimer {  // HIP events around the dominant scan kernel, on its own stream
-  hipEvent_t a = nullptr, b = nullptr;
-  hipStream_t s;
-  bool on;
-  explicit ScanTimer(hipStream_t st, bool enable = true) : s(st), on(g_timing && enable) {
-    if (on) { (void)hipEventCreate(&a); (void)hipEventCreate(&b); (void)hipEventRecord(a, s); }
-  }
-  void stop() {
-    if (!on) return;
-    (void)hipEventRecord(b, s);
-    (void)hipEventSynchronize(b);
-    float ms = 0;
-    (void)hipEventElapsedTime(&ms, a, b);
-    g_scan_ms += ms;
-    g_scan_launches += 1;
-    (void)hipEventDestroy(a); (void)hipEventDestroy(b);
-    on = false;
-  }
-};
+}  // namespace
+namespace mrx {   // mrx_core.hpp
+ScanTimer::ScanTimer(hipStream_t st, bool enable) : s(st), on(g_timing && enable) {
+  if (on) { (void)hipEventCreate(&a); (void)hipEventCreate(&b); (void)hipEventRecord(a, s); }
+}
+void ScanTimer::stop() {
+  if (!on) return;
+  (void)hipEventRecord(b, s);
+  (void)hipEventSynchronize(b);
+  float ms = 0;
+  (void)hipEventElapsedTime(&ms, a, b);
+  g_scan_ms += ms;
+  g_scan_launches += 1;
+  (void)hipEventDestroy(a); (void)hipEventDestroy(b);
+  on = false;
+}
 
 int check_search_supported(const mrx_handle* h) {
   if (!h->hp.why_no_search.empty()) return fail(MRX_E_UNSUPPORTED, h->hp.why_no_search);
@@ -4985,6 +4266,8 @@ int device_scan(const T* d_in, int64_t n, int64_t* d_prefix, int64_t* d_total, h
   HIP_TRY(hipGetLastError());
   return MRX_OK;
 }
+template int device_scan<int32_t>(const int32_t*, int64_t, int64_t*, int64_t*, hipStream_t);
+template int device_scan<int64_t>(const int64_t*, int64_t, int64_t*, int64_t*, hipStream_t);
 
 size_t lds_for(const mrx_handle* h) { return (size_t)h->hp.dev.blob_bytes; }
 
@@ -4994,22 +4277,6 @@ int check_lds(const mrx_handle* h) {
   return MRX_OK;
 }
 
-// plans with a backtracker route take the kernel instantiations that carry its interpreter (k_match<., true> ...)
-static bool plan_uses_backtracker(const mrx_handle* h) {
-  return (h->hp.dev.flags & (PF_BT_FIRST | PF_BT_SEARCH)) != 0 && h->hp.dev.bt_nitems > 0;
-}
-// ... 2: the lean instantiation for deterministic chains (DevPlan::bt_flags bit 5: no choice stack), 1: the full one
-static int bt_kernel_kind(const mrx_handle* h, bool wanted) {
-  static const bool full_only = getenv("MRX_BT_FULL") && getenv("MRX_BT_FULL")[0] == '1';   // A/B: chains on the full interpreter
-  if (!wanted) return 0;
-  return ((h->hp.dev.bt_flags & 32) && !full_only) ? 2 : 1;
-}
-#define MRX_BT_DISPATCH(KIND, LAUNCH)        \
-  do {                                       \
-    if ((KIND) == 2) { LAUNCH(2); }          \
-    else if ((KIND) == 1) { LAUNCH(1); }     \
-    else { LAUNCH(0); }                      \
-  } while (0)
 // NFAEngine's literal prefilter (nfa.mojo:86-143, 391-498, 169-340) in front of the lane-per-text kernels:
 // every backtracker-routed search starts with String.find(literal) -- and, on the '.*' fast paths, with a
 // look for a newline and String.rfind(literal) -- over the WHOLE text, per lane and byte by byte in the
@@ -5044,11 +4311,11 @@ int bt_prepass(const mrx_handle* h, const Layout& lay, int64_t n, hipStream_t s,
     HIP_TRY(scratch_alloc((void**)&d_cnt, sizeof(int32_t) * n, s));
     HIP_TRY(scratch_alloc((void**)&d_vfirst, sizeof(int64_t) * (n + 1), s));
     HIP_TRY(scratch_alloc((void**)&d_acc, sizeof(int4) * n, s));
-    hipLaunchKernelGGL(k_litscan_pieces, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, s, lay, n, C, d_cnt, d_acc);
+    hipLaunchKernelGGL(k_litscan_pieces, dim3(device_grid(n, kBlock)), dim3(kBlock), 0, s, lay, n, C, d_cnt, d_acc);
     if (int rc = device_scan<int32_t>(d_cnt, n, d_vfirst, d_tot, s)) return rc;
     hipLaunchKernelGGL((k_litscan<true, true>), dim3((unsigned)grid_cap()), dim3(64 * kWsWaves), 0, s, H_BLOB(h) + p.off_bt_lit,
                        p.bt_lit_len, H_BLOB(h), lay, n, (int32_t*)nullptr, (int2*)nullptr, d_vfirst, C, d_acc);
-    hipLaunchKernelGGL(k_litscan_join, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, s, n, d_acc, d_pre);
+    hipLaunchKernelGGL(k_litscan_join, dim3(device_grid(n, kBlock)), dim3(kBlock), 0, s, n, d_acc, d_pre);
   } else if (p.bt_flags & (4 | 8))
     hipLaunchKernelGGL(k_litscan<true>, dim3((unsigned)g), dim3(64 * kWsWaves), 0, s, H_BLOB(h) + p.off_bt_lit, p.bt_lit_len,
                        H_BLOB(h), lay, n, (int32_t*)nullptr, d_pre);
@@ -5059,6 +4326,8 @@ int bt_prepass(const mrx_handle* h, const Layout& lay, int64_t n, hipStream_t s,
   out->pre = d_pre;
   return MRX_OK;
 }
+}  // namespace mrx
+namespace {
 
 template <int OP>
 int run_match(const mrx_handle* h, const Layout& lay, int64_t n, int32_t* d_s, int32_t* d_e,
@@ -5124,7 +4393,7 @@ int run_match(const mrx_handle* h, const Layout& lay, int64_t n, int32_t* d_s, i
       }
     } else
     if (big && !wave) {   // many short texts: the literal restatement, one lane per text
-      hipLaunchKernelGGL((k_match<OP, 0>), dim3(grid_for(n, kBlock)), dim3(kBlock), lds_for(h), s, h->hp.dev,
+      hipLaunchKernelGGL((k_match<OP, 0>), dim3(device_grid(n, kBlock)), dim3(kBlock), lds_for(h), s, h->hp.dev,
                          H_BLOB(h), lay, n, d_s, d_e, d_flag);   // (a stepper plan: no backtracker route)
       g_last_kernel = "k_match";
     } else if (big) {
@@ -5161,7 +4430,7 @@ int run_match(const mrx_handle* h, const Layout& lay, int64_t n, int32_t* d_s, i
     Layout layp = lay;
     if ((OP == OP_SEARCH && (h->hp.dev.flags & PF_BT_SEARCH)) || (OP == OP_CAPTURES && h->hp.fixed_total < 0))
       if (int rc = bt_prepass(h, lay, n, s, &layp)) return rc;
-#define MRX_L(B) hipLaunchKernelGGL((k_match<OP, B>), dim3(grid_for(n, kBlock)), dim3(kBlock), lds_for(h), s, h->hp.dev, \
+#define MRX_L(B) hipLaunchKernelGGL((k_match<OP, B>), dim3(device_grid(n, kBlock)), dim3(kBlock), lds_for(h), s, h->hp.dev, \
                                    H_BLOB(h), layp, n, d_s, d_e, d_flag)
     MRX_BT_DISPATCH(bt_kernel_kind(h, plan_uses_backtracker(h) || (OP == OP_CAPTURES && h->hp.fixed_total < 0)), MRX_L);
 #undef MRX_L
@@ -5317,20 +4586,16 @@ void launch_stream_dyn(const mrx_handle* h, const Layout& lay, int64_t n, int32_
 #undef MRX_DYN_R
 }
 
+}  // namespace
+namespace mrx {   // mrx_core.hpp
 // (a named function, not a lambda: hipcc gave two namespace-scope lambdas of this shape ONE body -- the second
-// variable was initialised by the first one's getenv -- see env_int's other user, g_subs_group)
-static int env_int(const char* name, int dflt) {
+// variable was initialised by the first one's getenv -- see env_int's other user, g_subs_group in mrx_sub.hip)
+int env_int(const char* name, int dflt) {
   const char* e = getenv(name);
   return e ? atoi(e) : dflt;
 }
 // Measurement knobs of the call path, read from the environment ONCE (at the first call that looks): no getenv per call.
-struct EnvKnobs {
-  int decode_grid, decode_reverse, piece_c, fused_skew, fused_debug;
-  int subc_debug;   // k_subc_sizes / k_subc_emit with phases left out (timing only): 1 no walk, 2 no bitmaps, 4 no per-match store; 8 no gap copies, 32 no replacement bytes, 64 no stores
-  int subs_debug;   // k_subs_wave with phases left out (timing only, the output is wrong): 1 replacement bytes, 2 kept bytes, 4 stores, 8 frame phase, 16 match phase
-  bool piece_c_set;
-};
-static const EnvKnobs& env_knobs() {
+const EnvKnobs& env_knobs() {
   static const EnvKnobs k = [] {
     EnvKnobs e;
     e.decode_grid = env_int("MRX_DECODE_GRID", 0);
@@ -5345,6 +4610,8 @@ static const EnvKnobs& env_knobs() {
   }();
   return k;
 }
+}  // namespace mrx
+namespace {
 
 // Long texts on the streaming kernels: cut into pieces at synchronising bytes when one lane per text
 // would leave most of the device idle.
@@ -5416,13 +4683,13 @@ int pieces_prepare(const mrx_handle* h, const Layout& lay, int64_t n, hipStream_
   if (!lay.offsets && !lay.lens) {   // one length: nothing to count, nothing to read back
     const int64_t cpt = (max_len + C - 1) / C;
     nv = n * cpt;
-    hipLaunchKernelGGL(k_virt_uniform, dim3(grid_for(n + 1, kBlock)), dim3(kBlock), 0, s, n, cpt, pc->vfirst);
+    hipLaunchKernelGGL(k_virt_uniform, dim3(device_grid(n + 1, kBlock)), dim3(kBlock), 0, s, n, cpt, pc->vfirst);
   } else {
     int32_t* d_cnt = nullptr;
     int64_t* d_tot = nullptr;
     HIP_TRY(scratch_alloc((void**)&d_cnt, sizeof(int32_t) * n, s));
     HIP_TRY(scratch_alloc((void**)&d_tot, sizeof(int64_t), s));
-    hipLaunchKernelGGL(k_virt_count, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, s, lay, n, C, d_cnt);
+    hipLaunchKernelGGL(k_virt_count, dim3(device_grid(n, kBlock)), dim3(kBlock), 0, s, lay, n, C, d_cnt);
     if (int rc = device_scan<int32_t>(d_cnt, n, pc->vfirst, d_tot, s)) return rc;
     HIP_TRY(hipMemcpyAsync(&nv, d_tot, sizeof nv, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
@@ -5439,9 +4706,9 @@ int pieces_prepare(const mrx_handle* h, const Layout& lay, int64_t n, hipStream_
   HIP_TRY(scratch_alloc((void**)&pc->vbase, sizeof(int32_t) * pc->nv, s));
   HIP_TRY(scratch_alloc((void**)&pc->back, sizeof(int32_t) * pc->nv, s));
   const uint8_t* sync = H_BLOB(h) + p.off_st_sync;
-  hipLaunchKernelGGL(k_virt_check, dim3(grid_for(pc->nv, kBlock)), dim3(kBlock), 0, s, lay, n, pc->vfirst, pc->nv, C, sync,
+  hipLaunchKernelGGL(k_virt_check, dim3(device_grid(pc->nv, kBlock)), dim3(kBlock), 0, s, lay, n, pc->vfirst, pc->nv, C, sync,
                      pc->back);
-  hipLaunchKernelGGL(k_virt_fill, dim3(grid_for(pc->nv, kBlock)), dim3(kBlock), 0, s, lay, n, pc->vfirst, pc->nv, C,
+  hipLaunchKernelGGL(k_virt_fill, dim3(device_grid(pc->nv, kBlock)), dim3(kBlock), 0, s, lay, n, pc->vfirst, pc->nv, C,
                      pc->back, pc->vstart, pc->vlen, pc->vskip, pc->vbase, disjoint ? 1 : 0);
   HIP_TRY(hipGetLastError());
   pc->lay = csr(lay.data, pc->vstart);
@@ -5488,14 +4755,14 @@ int findall_pieces(const mrx_handle* h, const Pieces& pc, int64_t n, int64_t* d_
   const bool st16 = g_decode_store16 != 0;
   g_last_decode_store16 = st16 ? 1 : 0;
   if (st16)
-    hipLaunchKernelGGL((k_decode<false, true, false, false, kDecodeTile, false, false, true>), dim3(grid_for(nv, kBlock)),
+    hipLaunchKernelGGL((k_decode<false, true, false, false, kDecodeTile, false, false, true>), dim3(device_grid(nv, kBlock)),
                        dim3(kBlock), 0, s, nv, d_nrecs, d_recs, (int64_t)0, pc.lay.offsets, d_vcounts, d_wbase, d_tsum,
                        d_vprefix, d_spans, span_cap, p.st_fixed_len, d_total, pc.vbase);
   else
-  hipLaunchKernelGGL((k_decode<false, true>), dim3(grid_for(nv, kBlock)), dim3(kBlock), 0, s, nv, d_nrecs, d_recs,
+  hipLaunchKernelGGL((k_decode<false, true>), dim3(device_grid(nv, kBlock)), dim3(kBlock), 0, s, nv, d_nrecs, d_recs,
                      (int64_t)0, pc.lay.offsets, d_vcounts, d_wbase, d_tsum, d_vprefix, d_spans, span_cap, p.st_fixed_len,
                      d_total, pc.vbase);
-  hipLaunchKernelGGL(k_virt_prefix, dim3(grid_for(n + 1, kBlock)), dim3(kBlock), 0, s, n, pc.vfirst, d_vprefix, d_prefix);
+  hipLaunchKernelGGL(k_virt_prefix, dim3(device_grid(n + 1, kBlock)), dim3(kBlock), 0, s, n, pc.vfirst, d_vprefix, d_prefix);
   HIP_TRY(hipGetLastError());
   return MRX_OK;
 }
@@ -5569,7 +4836,7 @@ static int findall_split(const mrx_handle* h, const Layout& lay, int64_t n, int3
                      PREFIX, d_spans, span_cap, p.st_fixed_len, TOTAL, (const int32_t*)nullptr, BASE)
 #define MRX_DECODE_HALF(STREAM, N, NRECS, RECS, COUNTS, WBASE, TSUM, PREFIX, TOTAL, BASE)                                   \
   do {   /* (the tile's store loops by g_decode_store16, as in decode_launch) */                                             \
-    const dim3 dg_((unsigned)grid_for((N), kBlock) * (pack16 ? 2 : 1)), db_(kBlock);                                        \
+    const dim3 dg_((unsigned)device_grid((N), kBlock) * (pack16 ? 2 : 1)), db_(kBlock);                                        \
     const bool st16_ = g_decode_store16 != 0;                                                                              \
     g_last_decode_store16 = st16_ ? 1 : 0;                                                                                 \
     if (pack16 && rec32 && st16_)                                                                                          \
@@ -5679,8 +4946,6 @@ static int sync_bytes_frequent(const mrx_handle* h, const Layout& lay, int64_t n
   return MRX_OK;
 }
 
-int run_findall(const mrx_handle* h, const Layout& lay, int64_t n, int64_t* d_prefix, int32_t* d_spans, int64_t span_cap,
-                int64_t* total, void* stream, bool match_next_sequence = false, int64_t known_total = -1, int64_t known_max = -1);
 int run_count_any(const mrx_handle* h, const Layout& lay, int64_t n, int32_t* counts, void* st, int64_t known_total = -1,
                   int64_t known_max = -1);
 
@@ -5773,7 +5038,7 @@ static int anchored_counts(const mrx_handle* h, const Layout& lay, int64_t n, hi
   launch_stream<ST_FIRST>(h, lay, n, nullptr, nullptr, nullptr, 0, *d_se, *d_se + n, s, lay.vlen, lay.vskip);
   HIP_TRY(hipGetLastError());
   tm.stop();
-  hipLaunchKernelGGL(k_first_to_counts, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, s, n, *d_se, counts);
+  hipLaunchKernelGGL(k_first_to_counts, dim3(device_grid(n, kBlock)), dim3(kBlock), 0, s, n, *d_se, counts);
   return MRX_OK;
 }
 
@@ -5885,7 +5150,7 @@ struct FindallJob {
     if (int rc = anchored_counts(h, lay, n, s, d_counts, &d_se)) return rc;
     if (int rc = device_scan<int32_t>(d_counts, n, d_prefix, d_total, s)) return rc;
     if (span_cap > 0)
-      hipLaunchKernelGGL(k_first_to_spans, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, s, n, d_se, d_se + n, d_prefix, d_spans,
+      hipLaunchKernelGGL(k_first_to_spans, dim3(device_grid(n, kBlock)), dim3(kBlock), 0, s, n, d_se, d_se + n, d_prefix, d_spans,
                          span_cap);
     HIP_TRY(hipGetLastError());
     g_last_kernel = "k_stream_first_findall";
@@ -6054,11 +5319,11 @@ struct FindallJob {
     // one k_decode per record form; texts of 768 bytes and more take the 3072-span tile, and only they the grid and
     // reverse knobs (MRX_DECODE_GRID, MRX_DECODE_REVERSE)
     const bool big = max_text >= 768, lean = pack16 && rec32 && g_decode_lean != 0;
-    const unsigned g2 = (unsigned)grid_for(n, kBlock) * 2;
+    const unsigned g2 = (unsigned)device_grid(n, kBlock) * 2;
     const unsigned gbig = env_knobs().decode_grid > 0 ? (unsigned)env_knobs().decode_grid : g2;
     const int rev = env_knobs().decode_reverse;
     if (dyn) {
-      const unsigned gd = (unsigned)grid_for(nw * 64, kBlock) * 2;
+      const unsigned gd = (unsigned)device_grid(nw * 64, kBlock) * 2;
       if (pack16 && rec32) decode_launch<true, true, true, MRX_DYN_DECODE_TILE>(gd, d_tsum);
       else if (pack16) decode_launch<true, false, true>(gd, d_tsum);
       else decode_launch<false, false, true>(gd, d_tsum);
@@ -6072,7 +5337,7 @@ struct FindallJob {
     else if (pack16 && rec32 && big) decode_launch<true, true, false, 3072>(gbig, d_tsum, rev);
     else if (pack16 && rec32) decode_launch<true, true>(g2, d_tsum);
     else if (pack16) decode_launch<true>(g2, d_tsum);
-    else decode_launch<false>((unsigned)grid_for(n, kBlock), d_tsum);
+    else decode_launch<false>((unsigned)device_grid(n, kBlock), d_tsum);
     g_last_decode_lean = !dyn && lean ? 1 : 0;
     HIP_TRY(hipGetLastError());
     return MRX_OK;
@@ -6133,7 +5398,7 @@ struct FindallJob {
     t_piece_tries = -1;
     if (rc != MRX_OK) return rc;
     const std::string inner = g_last_kernel;
-    hipLaunchKernelGGL(k_virt_prefix, dim3(grid_for(n + 1, kBlock)), dim3(kBlock), 0, s, n, spc.vfirst, d_vprefix, d_prefix);
+    hipLaunchKernelGGL(k_virt_prefix, dim3(device_grid(n + 1, kBlock)), dim3(kBlock), 0, s, n, spc.vfirst, d_vprefix, d_prefix);
     if (!t_piece_base_applied)
       hipLaunchKernelGGL(k_virt_add_base, dim3(grid_cap()), dim3(kBlock), 0, s, spc.nv, d_vprefix, spc.vbase,
                          d_spans, span_cap);
@@ -6154,7 +5419,7 @@ struct FindallJob {
     t_in_pieces = false;
     t_piece_tries = -1;
     if (rc != MRX_OK) return rc;
-    hipLaunchKernelGGL(k_virt_sum, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, s, n, spc.vfirst, d_vcounts, d_counts);
+    hipLaunchKernelGGL(k_virt_sum, dim3(device_grid(n, kBlock)), dim3(kBlock), 0, s, n, spc.vfirst, d_vcounts, d_counts);
     HIP_TRY(hipGetLastError());
     return MRX_OK;
   }
@@ -6280,7 +5545,7 @@ struct FindallJob {
     } else {
       if (p.flags & PF_BT_SEARCH)
         if (int rc = bt_prepass(h, lay, n, s, &lay_pre)) return rc;
-  #define MRX_L(B) hipLaunchKernelGGL((k_findall<FA_COUNT, B>), dim3(grid_for(n, kBlock)), dim3(kBlock), lds_for(h), s, \
+  #define MRX_L(B) hipLaunchKernelGGL((k_findall<FA_COUNT, B>), dim3(device_grid(n, kBlock)), dim3(kBlock), lds_for(h), s, \
                                  p, H_BLOB(h), lay_pre, n, d_counts, (const int64_t*)nullptr, (int32_t*)nullptr, (int64_t)0)
       MRX_BT_DISPATCH(bt_kernel_kind(h, plan_uses_backtracker(h)), MRX_L);
   #undef MRX_L
@@ -6295,7 +5560,7 @@ struct FindallJob {
   // ... second stage, behind the prefix sums: spans to their CSR place
   int step_finish() {
   if (bits_fixed && bits_fixed_slots) {
-      hipLaunchKernelGGL(k_slots_gather_wide, dim3(grid_for(n * 64, kBlock)), dim3(kBlock), 0, s, lay2, n, d_counts,
+      hipLaunchKernelGGL(k_slots_gather_wide, dim3(device_grid(n * 64, kBlock)), dim3(kBlock), 0, s, lay2, n, d_counts,
                          d_prefix, d_slots, d_spans, span_cap);
     } else if (bits_fixed) {   // the union pass once more, texts that hold a match: spans straight to their CSR place
       if (int rc = bscan_fixed(h, lay, n, 3, s, d_counts, d_spans, d_prefix, span_cap)) return rc;
@@ -6309,10 +5574,10 @@ struct FindallJob {
                        lay2, n, (int32_t*)nullptr, d_prefix, d_spans, span_cap, (int32_t*)nullptr, (int32_t*)nullptr);
     } else if (step_ok) {
       if (lay2.wide_slots)
-        hipLaunchKernelGGL(k_slots_gather_wide, dim3(grid_for(n * 64, kBlock)), dim3(kBlock), 0, s, lay2, n, d_counts,
+        hipLaunchKernelGGL(k_slots_gather_wide, dim3(device_grid(n * 64, kBlock)), dim3(kBlock), 0, s, lay2, n, d_counts,
                            d_prefix, d_slots, d_spans, span_cap);
       else
-      hipLaunchKernelGGL(k_slots_gather, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, s, n, d_counts, d_prefix,
+      hipLaunchKernelGGL(k_slots_gather, dim3(device_grid(n, kBlock)), dim3(kBlock), 0, s, n, d_counts, d_prefix,
                          d_slots, d_spans, span_cap);
       // wavefronts without an overflowing text leave at once
       if (req_wave)
@@ -6324,7 +5589,7 @@ struct FindallJob {
       if (step_split > 0) reqwave_launch<STEP_EMIT>(rt, h, lay2, n, d_counts, d_prefix, d_spans, span_cap, s);
       }
     } else
-  #define MRX_L(B) hipLaunchKernelGGL((k_findall<FA_EMIT, B>), dim3(grid_for(n, kBlock)), dim3(kBlock), lds_for(h), s, p, \
+  #define MRX_L(B) hipLaunchKernelGGL((k_findall<FA_EMIT, B>), dim3(device_grid(n, kBlock)), dim3(kBlock), lds_for(h), s, p, \
                                  H_BLOB(h), lay_pre, n, (int32_t*)nullptr, d_prefix, d_spans, span_cap)
       MRX_BT_DISPATCH(bt_kernel_kind(h, plan_uses_backtracker(h)), MRX_L);
   #undef MRX_L
@@ -6415,8 +5680,9 @@ struct FindallJob {
   }
 };
 
-int run_findall(const mrx_handle* h, const Layout& lay, int64_t n, int64_t* d_prefix, int32_t* d_spans, int64_t span_cap,
-                int64_t* total, void* stream, bool match_next_sequence, int64_t known_total, int64_t known_max) {
+}  // namespace
+int mrx::run_findall(const mrx_handle* h, const Layout& lay, int64_t n, int64_t* d_prefix, int32_t* d_spans, int64_t span_cap,
+                     int64_t* total, void* stream, bool match_next_sequence, int64_t known_total, int64_t known_max) {
   ScratchScope scratch_scope_((hipStream_t)stream);
   if (!h) return fail(MRX_E_ARGUMENT, "null handle");
   if (n < 0 || span_cap < 0) return fail(MRX_E_ARGUMENT, "negative size");
@@ -6427,6 +5693,7 @@ int run_findall(const mrx_handle* h, const Layout& lay, int64_t n, int64_t* d_pr
   FindallJob job(h, lay, n, d_prefix, d_spans, span_cap, total, (hipStream_t)stream, match_next_sequence, known_total, known_max);
   return job.run();
 }
+namespace {
 
 // count for any layout: the anchored automaton, the streaming scan, or the stepper family through FindallJob's
 // counts-only mode.  known_total / known_max: csr_stats() of a CSR batch when the caller has them already (< 0: not;
@@ -6455,7 +5722,7 @@ int run_count_any(const mrx_handle* h, const Layout& lay, int64_t n, int32_t* co
       int32_t* d_vcounts = nullptr;
       HIP_TRY(scratch_alloc((void**)&d_vcounts, sizeof(int32_t) * pc.nv, s));
       launch_stream<ST_COUNT>(h, pc.lay, pc.nv, d_vcounts, nullptr, nullptr, 0, nullptr, nullptr, s, pc.vlen, pc.vskip);
-      hipLaunchKernelGGL(k_virt_sum, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, s, n, pc.vfirst, d_vcounts, counts);
+      hipLaunchKernelGGL(k_virt_sum, dim3(device_grid(n, kBlock)), dim3(kBlock), 0, s, n, pc.vfirst, d_vcounts, counts);
       HIP_TRY(hipGetLastError());
       g_last_kernel = "k_stream_count_pieces";
     } else if (dyn_ok(h, lay, n)) {
@@ -6478,622 +5745,6 @@ int run_count_any(const mrx_handle* h, const Layout& lay, int64_t n, int32_t* co
 }
 
 }  // namespace
-
-namespace {
-// mrx_debug_subs_group(): lanes per text in k_subs_wave (16 / 32 / 64), 0 = k_subs_emit only, -1 = by text length
-std::atomic<int> g_subs_group{env_int("MRX_SUBS_G", -1)};
-// regex.sub for streamable plans: streaming findall -> sizes -> prefix sums -> emit (see k_subs_*)
-// A replacement that copies a fixed-width group copies text[match start + offset ...] whatever the match looked like
-// (_apply_template_fixed, matcher.mojo:1592-1621; the widths come from the pattern text, quantifiers ignored:
-// 'x(\\d)?' has its group at offset 1 even when the match is "x").  A match close to the end of its text can thus
-// reach behind the text -- upstream reads those bytes unchecked; the oracle's slice and sub_text() stop at the end of
-// the text, so the replacement is shorter than R bytes there.  The spans route has one R for every match: it
-// looks at the LAST match of each text (the one that reaches furthest) and hands the call back
-// (kSubsRetryGeneric) when any reaches behind its text.
-constexpr int kSubsRetryGeneric = 1 << 20;
-__global__ __launch_bounds__(kBlock) void k_subs_reach(int64_t n, const int64_t* __restrict__ offsets,
-                                                       const int64_t* __restrict__ prefix, const int32_t* __restrict__ spans,
-                                                       int64_t span_cap, int reach, int32_t* __restrict__ over) {
-  if (prefix[n] > span_cap) return;   // the spans are incomplete: the caller repeats the findall
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t a = prefix[i], b = prefix[i + 1];
-    if (b > a && (int64_t)spans[2 * (b - 1)] + reach > offsets[i + 1] - offsets[i]) *over = 1;
-  }
-}
-// go = 1 when the assembly may run: every span had room, the output fits, there is output, no group reaches behind its text
-__global__ void k_subs_gate(const int64_t* __restrict__ matches, int64_t span_cap, const int64_t* __restrict__ out_bytes,
-                            int64_t out_cap, const int32_t* __restrict__ over, int32_t* __restrict__ go) {
-  *go = (*matches <= span_cap && *out_bytes <= out_cap && *out_bytes > 0 && !(over && *over)) ? 1 : 0;
-}
-int sub_from_spans(const mrx_handle* h, const Layout& lay, int64_t n, const std::vector<uint16_t>& rmap,
-                   int64_t count, int64_t* out_off, uint8_t* out, int64_t out_cap, int64_t* total_bytes,
-                   hipStream_t s, int group_reach = 0, int64_t known_bytes = -1, int64_t known_max = -1) {
-  // Two host synchronisations per call: the batch's byte count and longest text (sizes the span buffer
-  // and, handed on, spares findall its own look; none when the caller knows them: rows at a fixed pitch), and the
-  // two totals -- matches and output bytes -- behind findall, sizes and prefix sums, all enqueued without waiting.
-  int64_t in_bytes = known_bytes, max_len = known_max;
-  if (known_bytes < 0 || known_max < 0)
-    if (int rc0 = csr_stats(lay, n, s, &in_bytes, &max_len)) return rc0;
-  if (in_bytes < 0) return fail(MRX_E_ARGUMENT, "offsets[n] is negative");
-  const int R = (int)rmap.size();
-  int64_t* d_prefix = nullptr;
-  int32_t* d_spans = nullptr;
-  uint16_t* d_rmap = nullptr;
-  int32_t* d_cum = nullptr;
-  int64_t *d_sizes = nullptr, *d_total = nullptr;
-  int32_t* d_left = nullptr;
-  int32_t* d_go = nullptr;
-  int32_t* d_over = nullptr;
-  int32_t over = 0;
-  HIP_TRY(scratch_alloc((void**)&d_over, sizeof(int32_t), s));
-  if (group_reach > 0) HIP_TRY(hipMemsetAsync(d_over, 0, sizeof(int32_t), s));
-  HIP_TRY(scratch_alloc((void**)&d_prefix, sizeof(int64_t) * (n + 1), s));
-  HIP_TRY(scratch_alloc((void**)&d_rmap, sizeof(uint16_t) * (R + 8), s));
-  HIP_TRY(scratch_alloc((void**)&d_sizes, sizeof(int64_t) * n, s));
-  HIP_TRY(scratch_alloc((void**)&d_total, sizeof(int64_t), s));
-  HIP_TRY(scratch_alloc((void**)&d_left, sizeof(int32_t), s));
-  HIP_TRY(scratch_alloc((void**)&d_go, sizeof(int32_t), s));
-  if (R) HIP_TRY(hipMemcpyAsync(d_rmap, rmap.data(), sizeof(uint16_t) * R, hipMemcpyHostToDevice, s));
-  int64_t cap = in_bytes / 8 + n + 64, nm = 0, tot = 0;
-  if (const int64_t seen = h->sub_matches_per_kib.load(std::memory_order_relaxed); seen > 128) {
-    const int64_t by_hint = (in_bytes >> 10) * (seen + seen / 8 + 1) + n + 64;   // the last batch's density + 1/8
-    if (by_hint > cap) cap = by_hint < in_bytes + n + 64 ? by_hint : in_bytes + n + 64;
-  }
-  int rc = MRX_OK;
-  bool cum_later = false;
-  int G = 0;
-  for (int attempt = 0; attempt < 2; ++attempt) {
-    HIP_TRY(scratch_alloc((void**)&d_spans, sizeof(int32_t) * 2 * (size_t)cap, s));
-    HIP_TRY(scratch_alloc((void**)&d_cum, sizeof(int32_t) * (size_t)(cap + 1), s));
-    rc = run_findall(h, lay, n, d_prefix, d_spans, cap, nullptr, s, /*match_next_sequence=*/true, in_bytes, max_len);
-    if (rc != MRX_OK) return rc;
-    const int64_t avg0 = in_bytes / (n > 0 ? n : 1);
-    // lanes per text in k_subs_wave by average text length (1 KiB texts: 32 lanes 1.41 ms, 64 lanes 1.56 ms);
-    // 0 = k_subs_emit alone: long replacement templates (one lane writes a replacement), forced, or texts
-    // beyond the workgroup form's tiles, which take k_subs_emit<kBlock>
-    const bool long_texts = (g_long_text_mode == 1 || g_long_text_mode == 3 || avg0 > 6144) && g_long_text_mode != 2;
-    const int force_g = g_subs_group;
-    G = force_g >= 0 ? force_g : (avg0 > 2048 ? 256 : avg0 > 1024 ? 64 : avg0 > 224 ? 32 : 16);
-    if (R > 1024 || long_texts) G = 0;
-    // cum[] (matched bytes before each match) is k_subs_emit's: when k_subs_wave runs in front of it, it is
-    // only computed if that kernel leaves texts over (cum_later)
-    cum_later = count == 0 && G != 0;
-    if (cum_later) {
-      const int64_t blocks = ((n + 63) / 64 + (kBlock / 64) - 1) / (kBlock / 64);
-      hipLaunchKernelGGL(k_subs_sizes_flat, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(kBlock), 0, s,
-                         n, lay.offsets, d_prefix, d_spans, R, d_sizes, cap);
-    } else {
-      const int64_t blocks = (n + (kBlock / 16) - 1) / (kBlock / 16);
-      hipLaunchKernelGGL(k_subs_sizes, dim3((unsigned)(blocks < 65536 * 4 ? blocks : 65536 * 4)), dim3(kBlock), 0, s,
-                         n, lay.offsets, d_prefix, d_spans, (long long)count, R, d_sizes, d_cum, cap, (const int32_t*)nullptr);
-    }
-    HIP_TRY(hipGetLastError());
-    rc = device_scan<int64_t>(d_sizes, n, out_off, d_total, s);
-    if (rc != MRX_OK) return rc;
-    if (group_reach > 0)
-      hipLaunchKernelGGL(k_subs_reach, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, s, n, lay.offsets, d_prefix, d_spans, cap,
-                         group_reach, d_over);
-    // The assembly is enqueued BEHIND a device-side go-ahead and BEFORE the host has seen the totals: the stream does
-    // not run dry while they travel (63 us of 1.7 ms on config 4).  When the go-ahead says no, the kernels return at
-    // once and the host, which reads the same numbers below, retries or reports.
-    hipLaunchKernelGGL(k_subs_gate, dim3(1), dim3(1), 0, s, d_prefix + n, cap, d_total, out_cap,
-                       group_reach > 0 ? (const int32_t*)d_over : (const int32_t*)nullptr, d_go);
-    if (G == 0 && (g_long_text_mode == 1 || g_long_text_mode == 3 || in_bytes / n >= 4096) && g_long_text_mode != 2) {   // long texts: a workgroup per text
-      hipLaunchKernelGGL(k_subs_emit<kBlock>, dim3((unsigned)(n < 4096 ? n : 4096)), dim3(kBlock),
-                         (size_t)(2 * R + 16), s, n, lay.data, lay.offsets, d_prefix, d_spans, d_cum, (long long)count, R,
-                         d_rmap, out_off, out, 0, (const int32_t*)d_go);
-      g_last_kernel = "k_subs_emit_long";
-    } else {
-      // short texts: G lanes assemble a text in LDS (k_subs_wave); what does not fit its tiles is left to
-      // k_subs_emit, which returns at once when nothing was left
-      HIP_TRY(hipMemsetAsync(d_left, 0, sizeof(int32_t), s));
-#define MRX_SUBS_WAVE(GG)                                                                                        \
-  do {                                                                                                           \
-    const int64_t blocks = (n + (kBlock / GG) - 1) / (kBlock / GG);                                              \
-    hipLaunchKernelGGL(k_subs_wave<GG>, dim3((unsigned)(blocks < grid_cap() ? blocks : grid_cap())), dim3(kBlock), \
-                       (size_t)(2 * R + 16), s, n, lay.data, lay.offsets, d_prefix, d_spans, (long long)count, R,   \
-                       d_rmap, out_off, out, d_left, (const int32_t*)d_go, env_knobs().subs_debug);              \
-  } while (0)
-      if (G == 256) MRX_SUBS_WAVE(256);
-      else if (G == 64) MRX_SUBS_WAVE(64);
-      else if (G == 32) MRX_SUBS_WAVE(32);
-      else if (G == 16) MRX_SUBS_WAVE(16);
-#undef MRX_SUBS_WAVE
-      HIP_TRY(hipGetLastError());
-      const int64_t blocks = (n + (kBlock / kSubsLanes) - 1) / (kBlock / kSubsLanes);
-      if (cum_later)
-        hipLaunchKernelGGL(k_subs_sizes, dim3((unsigned)(blocks < grid_cap() ? blocks : grid_cap())), dim3(kBlock), 0, s,
-                           n, lay.offsets, d_prefix, d_spans, (long long)count, R, (int64_t*)nullptr, d_cum, cap,
-                           (const int32_t*)d_left);
-      // (behind k_subs_wave: the texts it left over -- none when the go-ahead stopped it; alone: the go-ahead itself)
-      hipLaunchKernelGGL(k_subs_emit<kSubsLanes>, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(kBlock),
-                         (size_t)(2 * R + 16), s, n, lay.data, lay.offsets, d_prefix, d_spans, d_cum, (long long)count, R,
-                         d_rmap, out_off, out, G, G ? (const int32_t*)d_left : (const int32_t*)d_go);
-      g_last_kernel = G ? "k_subs_wave" : "k_subs_emit";
-    }
-    HIP_TRY(hipGetLastError());   // the output bytes are complete when `s` reaches this point, as with every _dev call
-    if (group_reach > 0) HIP_TRY(hipMemcpyAsync(&over, d_over, sizeof over, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(&nm, d_prefix + n, sizeof nm, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(&tot, d_total, sizeof tot, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    h->sub_matches_per_kib.store(in_bytes >= 1024 ? nm / (in_bytes >> 10) : 0, std::memory_order_relaxed);
-    if (nm <= cap) break;
-    if (attempt == 1) return fail(MRX_E_NO_DEVICE, "sub: match count changed between two passes");
-    // more matches than one per eight bytes: once more with room for all of them.  The second attempt's buffers lie
-    // behind the first's, which stay where they are until the call returns (a dense batch sizes its next call's
-    // first attempt by sub_matches_per_kib, so this is paid once).
-    cap = nm;
-  }
-  if (over) {
-    rc = kSubsRetryGeneric;
-  } else {
-    if (total_bytes) *total_bytes = tot;
-    if (tot > out_cap) rc = fail(MRX_E_CAPACITY, "output buffer too small: need " + std::to_string(tot));
-  }
-  return rc;
-}
-}  // namespace
-
-static int g_chain_sub_general = 0;   // mrx_debug_chain_sub_general
-// ---- sub() with \1..\9 on a deterministic chain (HostPlan::chain) -----------------------------------------
-// The matches are the plain search's spans (run_findall, match_next_sequence); a wavefront takes a text: every byte's
-// leaf mask (bit l: leaf l takes the byte) in an LDS tile, a lane per match finds the leaves' boundaries as runs of
-// mask bits, four bytes a step; from them the groups and the replacement's length.  k_subc_sizes: output length per
-// text and, per match, the bytes the output has gained in front of it; k_subc_emit<TILE>: gaps and replacements into
-// an output tile, the tile out in 16-byte stores.  A text or an output beyond 4 KiB: the call is the lane-per-text
-// interpreter's (k_sub).
-namespace {
-constexpr int kSubcLeaves = 8, kSubcTpl = 8, kSubcRepl = 256;   // (loops over leaves and segments are unrolled: the kernel
-                                                                   // arguments they index stay in scalar registers)
-struct ChainDev {
-  int nleaf, ntpl;
-  int lmax[kSubcLeaves];
-  int lfix[kSubcLeaves];   // width of a leaf with a fixed count, else 0
-  int need;                // bit l: leaf l's runs are looked at (variable count, not the last leaf): its bitmap is built
-  ReplSeg tpl[kSubcTpl];   // (as sub_chain_from_spans rewrites them: a group's segment names its two boundaries)
-};
-// One text's descriptor, loaded two texts ahead; its blocks, first spans and first gains one text ahead: the global
-// round trips of text i + 1 run under the LDS phases of text i (as in k_subs_wave).
-struct SubcDesc { int64_t ibase, a, obase; int tlen, k, olen; };
-template <bool EMIT>
-__device__ __forceinline__ SubcDesc subc_desc(int64_t i, int64_t n, const int64_t* offsets, const int64_t* prefix,
-                                              const int64_t* out_off, long long count) {
-  SubcDesc d{0, 0, 0, 0, 0, 0};
-  if (i < n) {
-    d.ibase = offsets[i];
-    d.tlen = (int)(offsets[i + 1] - d.ibase);
-    d.a = prefix[i];
-    int64_t k64 = prefix[i + 1] - d.a;
-    if (count > 0 && k64 > count) k64 = count;
-    d.k = (int)k64;
-    if constexpr (EMIT) {
-      d.obase = out_off[i];
-      d.olen = (int)(out_off[i + 1] - d.obase);
-    }
-  }
-  return d;
-}
-// blocks in registers -> per-leaf bitmaps (bm[l * ROW + b] bit j: leaf l takes byte 16 b + j of the frame) and, when wanted,
-// the text tile; frame of the blocks: the text begins at [address & 15]
-template <int NB, int ROW, bool TEXT>
-__device__ __forceinline__ void subc_store(const uint4 (&tx)[NB], uint16_t* bm, uint8_t* tile, const uint8_t* mask, int need,
-                                           int nfb, int lane) {
-#pragma unroll
-  for (int r = 0; r < NB; ++r) {
-    const int b = lane + 64 * r;
-    if (b < nfb) {
-      const uint4 v = tx[r];
-      if constexpr (TEXT) *(uint4*)(tile + 16 * b) = v;
-      const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-      uint32_t o[4];
-#pragma unroll
-      for (int q = 0; q < 4; ++q)
-        o[q] = (uint32_t)mask[w[q] & 255] | ((uint32_t)mask[(w[q] >> 8) & 255] << 8) |
-               ((uint32_t)mask[(w[q] >> 16) & 255] << 16) | ((uint32_t)mask[w[q] >> 24] << 24);
-#pragma unroll
-      for (int l = 0; l < kSubcLeaves; ++l) {
-        if (!((need >> l) & 1)) continue;
-        uint32_t bits = 0;
-#pragma unroll
-        for (int q = 0; q < 4; ++q)   // bit l of four bytes -> four adjacent bits (the products' other terms stay below bit 24)
-          bits |= (((((o[q] >> l) & 0x01010101u) * 0x01020408u) >> 24) & 15u) << (4 * q);
-        bm[l * ROW + b] = (uint16_t)bits;
-      }
-    }
-  }
-}
-// boundaries of the leaves of the match [ms, me) -> bnd[0 .. nleaf] (the lane's row); positions relative to the text, which
-// begins at frame position mis; a leaf's run: trailing ones of its bitmap from the position on, 32 positions a step
-template <int ROW>
-__device__ __forceinline__ void subc_walk(const ChainDev& cd, const uint16_t* bm, int mis, uint16_t* bnd, int ms, int me) {
-  int pos = ms;
-#pragma unroll
-  for (int l = 0; l < kSubcLeaves; ++l) {
-    if (l >= cd.nleaf) break;
-    bnd[l] = (uint16_t)pos;
-    if (l == cd.nleaf - 1) { pos = me; break; }          // the last leaf ends with the match
-    if (cd.lfix[l]) { pos += cd.lfix[l]; continue; }     // a fixed count: nothing to look at (the match is the table walk's)
-    const int lm = cd.lmax[l];
-    const int stop = lm < 0 || pos + lm > me ? me : pos + lm;
-    const uint16_t* row = bm + l * ROW;
-    while (pos < stop) {
-      const int f = mis + pos;
-      const uint16_t* w = row + (f >> 4);
-      const uint32_t lo = (uint32_t)w[0] | ((uint32_t)w[1] << 16), hi = w[2];
-      const uint32_t miss = ~__funnelshift_r(lo, hi, f & 15);
-      int k = miss ? __ffs((int)miss) - 1 : 32;
-      if (k > stop - pos) k = stop - pos;
-      pos += k;
-      if (k < 32) break;
-    }
-  }
-  bnd[cd.nleaf] = (uint16_t)pos;
-}
-// (ChainDev::tpl as the host rewrote it: group_ref != 0: bytes between the boundaries `start` and `length`; else literal)
-__device__ __forceinline__ int subc_repl_len(const ChainDev& cd, const uint16_t* bnd) {
-  int rl = 0;
-#pragma unroll
-  for (int k = 0; k < kSubcTpl; ++k) {
-    if (k >= cd.ntpl) break;
-    const ReplSeg sg = cd.tpl[k];
-    rl += sg.group_ref ? (int)bnd[sg.length] - (int)bnd[sg.start] : sg.length;
-  }
-  return rl;
-}
-// n bytes src -> dst (LDS, one lane), four reads in flight
-__device__ __forceinline__ void subc_copy(uint8_t* dst, const uint8_t* src, int n) {
-  for (int j = 0; j < n; j += 4) {
-    const uint8_t b0 = src[j], b1 = src[j + 1], b2 = src[j + 2], b3 = src[j + 3];   // (the tiles are padded)
-    dst[j] = b0;
-    if (j + 1 < n) dst[j + 1] = b1;
-    if (j + 2 < n) dst[j + 2] = b2;
-    if (j + 3 < n) dst[j + 3] = b3;
-  }
-}
-#define MRX_SUBC_WAVE_SYNC()                                      \
-  do {                                                            \
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");        \
-    __builtin_amdgcn_wave_barrier();                              \
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");        \
-  } while (0)
-template <int TILE>
-__global__ __launch_bounds__(kBlock) void k_subc_sizes(ChainDev cd, int64_t n, const uint8_t* __restrict__ data,
-                                                       const int64_t* __restrict__ offsets,
-                                                       const int64_t* __restrict__ prefix, const int32_t* __restrict__ spans,
-                                                       long long count, const uint8_t* __restrict__ g_mask,
-                                                       int64_t* __restrict__ sizes, int32_t* __restrict__ dcum,
-                                                       int32_t* __restrict__ longest, int64_t span_cap, int dbg) {
-  if (prefix[n] > span_cap) return;   // the findall in front did not have room for its spans: the host retries
-  constexpr int NB = TILE / 1024 + 1;
-  constexpr int ROW = TILE / 16 + 4;
-  __shared__ uint16_t bm_all[kBlock / 64][kSubcLeaves * ROW];
-  __shared__ uint16_t bnd_all[kBlock / 64][64 * (kSubcLeaves + 1)];
-  __shared__ uint8_t mask[256];
-  for (int c = threadIdx.x; c < 256; c += blockDim.x) mask[c] = g_mask[c];
-  __syncthreads();
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  uint16_t* bm = bm_all[wv];
-  uint16_t* bnd = bnd_all[wv] + lane * (kSubcLeaves + 1);
-  int worst = 0;
-  const int64_t nw = (int64_t)gridDim.x * (kBlock / 64);
-  uint4 tx[NB];
-  int2 sp_first;
-  auto issue = [&](const SubcDesc& d) {
-    const uint8_t* tptr = data + d.ibase;
-    const int mis = (int)((uintptr_t)tptr & 15);
-    const uint8_t* fptr = tptr - mis;
-    const int nfb = d.k > 0 && d.tlen <= TILE ? (mis + d.tlen + 15) >> 4 : 0;
-#pragma unroll
-    for (int r = 0; r < NB; ++r) {
-      const int b = lane + 64 * r;
-      tx[r] = b < nfb ? *(const uint4*)(fptr + 16 * b) : make_uint4(0, 0, 0, 0);
-    }
-    sp_first = lane < d.k ? *(const int2*)(spans + 2 * (d.a + lane)) : make_int2(0, 0);
-  };
-  int64_t i = (int64_t)blockIdx.x * (kBlock / 64) + wv;
-  SubcDesc d0 = subc_desc<false>(i, n, offsets, prefix, nullptr, count), d1 = subc_desc<false>(i + nw, n, offsets, prefix, nullptr, count);
-  issue(d0);
-  for (; i < n; i += nw) {
-    const SubcDesc d = d0;
-    d0 = d1;
-    d1 = subc_desc<false>(i + 2 * nw, n, offsets, prefix, nullptr, count);
-    const int tlen = d.tlen, k = d.k;
-    const int64_t a = d.a;
-    if (tlen > TILE) {   // (the host has looked at the longest text already: not reached)
-      if (lane == 0) sizes[i] = 0;
-      worst = 0x7FFFFFFF;
-      issue(d0);
-      continue;
-    }
-    const int mis = (int)((uintptr_t)(data + d.ibase) & 15);
-    MRX_SUBC_WAVE_SYNC();
-    if (k > 0 && !(dbg & 2)) subc_store<NB, ROW, false>(tx, bm, nullptr, mask, cd.need, (mis + tlen + 15) >> 4, lane);
-    const int2 sp_cur = sp_first;
-    issue(d0);
-    MRX_SUBC_WAVE_SYNC();
-    int carry = 0;
-    for (int m0 = 0; m0 < k; m0 += 64) {
-      const int m = m0 + lane;
-      int delta = 0;
-      if (m < k) {
-        const int2 sp = m0 == 0 ? sp_cur : *(const int2*)(spans + 2 * (a + m));
-        if (!(dbg & 1)) {
-          subc_walk<ROW>(cd, bm, mis, bnd, sp.x, sp.y);
-          delta = subc_repl_len(cd, bnd) - (sp.y - sp.x);
-        }
-      }
-      const int incl = group_scan<64, false>(delta);
-      if (m < k && !(dbg & 4)) dcum[a + m] = carry + incl - delta;
-      carry += __shfl(incl, 63, 64);
-    }
-    if (lane == 0) sizes[i] = (int64_t)tlen + carry;
-    if (tlen + carry > worst) worst = tlen + carry;
-  }
-  if (lane == 0 && worst > 0) atomicMax(longest, worst);
-}
-// Every match's replacement differs from the match by the same number of bytes (each leaf of variable width lies in
-// exactly one referenced group -- a template that reorders the groups): no walk for the sizes, a lane per text.
-__global__ __launch_bounds__(kBlock) void k_subc_sizes_const(int64_t n, const int64_t* __restrict__ offsets,
-                                                             const int64_t* __restrict__ prefix, long long count, int delta,
-                                                             int64_t* __restrict__ sizes, int32_t* __restrict__ longest,
-                                                             int64_t span_cap) {
-  if (prefix[n] > span_cap) return;
-  int worst = 0;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t tlen = offsets[i + 1] - offsets[i];
-    int64_t k = prefix[i + 1] - prefix[i];
-    if (count > 0 && k > count) k = count;
-    const int64_t olen = tlen + k * delta;
-    sizes[i] = olen;
-    const int w = tlen > 0x7FFFFFFF || olen > 0x7FFFFFFF ? 0x7FFFFFFF : (int)(tlen > olen ? tlen : olen);
-    if (w > worst) worst = w;
-  }
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) { const int o = __shfl_xor(worst, d, 64); if (o > worst) worst = o; }
-  if ((threadIdx.x & 63) == 0 && worst > 0) atomicMax(longest, worst);
-}
-template <int TILE>
-__global__ __launch_bounds__(kBlock) void k_subc_emit(ChainDev cd, int64_t n, const uint8_t* __restrict__ data,
-                                                      const int64_t* __restrict__ offsets,
-                                                      const int64_t* __restrict__ prefix, const int32_t* __restrict__ spans,
-                                                      long long count, const uint8_t* __restrict__ g_mask,
-                                                      const uint8_t* __restrict__ g_repl, int repl_len,
-                                                      const int32_t* __restrict__ dcum, const int64_t* __restrict__ out_off,
-                                                      uint8_t* __restrict__ out, int cdelta, int dbg) {
-  // dbg (MRX_SUBC_DEBUG, timing only): 8 no gap copies, 32 no replacement bytes, 64 no stores
-  // dcum == nullptr: every match gains cdelta bytes (k_subc_sizes_const)
-  constexpr int NB = TILE / 1024 + 1;
-  constexpr int ROW = TILE / 16 + 4;
-  __shared__ uint16_t bm_all[kBlock / 64][kSubcLeaves * ROW];
-  __shared__ __align__(16) uint8_t text_all[kBlock / 64][TILE + 32];
-  __shared__ __align__(16) uint8_t otile_all[kBlock / 64][TILE + 32];
-  __shared__ uint16_t bnd_all[kBlock / 64][64 * (kSubcLeaves + 1)];
-  __shared__ uint8_t mask[256];
-  __shared__ uint8_t repl[kSubcRepl + 8];
-  for (int c = threadIdx.x; c < 256; c += blockDim.x) mask[c] = g_mask[c];
-  for (int c = threadIdx.x; c < repl_len; c += blockDim.x) repl[c] = g_repl[c];
-  __syncthreads();
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  uint16_t* bm = bm_all[wv];
-  uint8_t* tile = text_all[wv];
-  uint8_t* otile = otile_all[wv];
-  uint16_t* bnd = bnd_all[wv] + lane * (kSubcLeaves + 1);
-  const int64_t nw = (int64_t)gridDim.x * (kBlock / 64);
-  uint4 tx[NB];
-  int2 sp_first;
-  int dc_first;
-  auto takes = [&](const SubcDesc& d) { return d.olen > 0 && d.olen <= TILE && d.tlen <= TILE; };   // (else: not launched)
-  auto issue = [&](const SubcDesc& d) {
-    const uint8_t* tptr = data + d.ibase;
-    const int mis = (int)((uintptr_t)tptr & 15);
-    const uint8_t* fptr = tptr - mis;
-    const int nfb = takes(d) ? (mis + d.tlen + 15) >> 4 : 0;
-#pragma unroll
-    for (int r = 0; r < NB; ++r) {
-      const int b = lane + 64 * r;
-      tx[r] = b < nfb ? *(const uint4*)(fptr + 16 * b) : make_uint4(0, 0, 0, 0);
-    }
-    const bool have = takes(d) && lane < d.k;
-    sp_first = have ? *(const int2*)(spans + 2 * (d.a + lane)) : make_int2(0, 0);
-    dc_first = have && dcum ? dcum[d.a + lane] : lane * cdelta;
-  };
-  int64_t i = (int64_t)blockIdx.x * (kBlock / 64) + wv;
-  SubcDesc d0 = subc_desc<true>(i, n, offsets, prefix, out_off, count), d1 = subc_desc<true>(i + nw, n, offsets, prefix, out_off, count);
-  issue(d0);
-  for (; i < n; i += nw) {
-    const SubcDesc d = d0;
-    d0 = d1;
-    d1 = subc_desc<true>(i + 2 * nw, n, offsets, prefix, out_off, count);
-    const int tlen = d.tlen, k = d.k, olen = d.olen;
-    const int64_t a = d.a, obase = d.obase;
-    if (!takes(d)) { issue(d0); continue; }
-    const int mis = (int)((uintptr_t)(data + d.ibase) & 15), head = (int)((uintptr_t)(out + obase) & 15);
-    MRX_SUBC_WAVE_SYNC();   // the previous text's tiles are free
-    subc_store<NB, ROW, true>(tx, bm, tile, mask, cd.need, (mis + tlen + 15) >> 4, lane);
-    const int2 sp_cur = sp_first;
-    const int dc_cur = dc_first;
-    issue(d0);
-    MRX_SUBC_WAVE_SYNC();
-    const uint8_t* txt = tile + mis;
-    uint8_t* o = otile + head;
-    // the whole wavefront copies text[src, src + len) to o[dst ..]
-    auto copy_all = [&](int src, int len, int dst) {
-      for (int j = lane; j < len; j += 64) o[dst + j] = txt[src + j];
-    };
-    int prev_end = 0;   // end of the match in front of this round's first
-    for (int m0 = 0; m0 < k; m0 += 64) {
-      const int m = m0 + lane;
-      const bool live = m < k;
-      int ms = 0, me = 0, before = 0;
-      if (live) {
-        const int2 sp = m0 == 0 ? sp_cur : *(const int2*)(spans + 2 * (a + m));
-        ms = sp.x; me = sp.y;
-        before = m0 == 0 ? dc_cur : dcum ? dcum[a + m] : m * cdelta;
-      }
-      int pe = __shfl_up(me, 1, 64);
-      if (lane == 0) pe = prev_end;
-      const int nlive = k - m0 < 64 ? k - m0 : 64;
-      prev_end = __shfl(me, nlive - 1, 64);
-      // the kept bytes in front of the match: short gaps by the lane, long ones by the wavefront
-      const int gap = live ? ms - pe : 0;
-      if (gap <= 24 && !(dbg & 8)) subc_copy(o + pe + before, txt + pe, gap);
-      uint64_t wide = __ballot(gap > 24);
-      while (wide) {
-        const int src_lane = __ffsll((unsigned long long)wide) - 1;
-        wide &= wide - 1;
-        copy_all(__shfl(pe, src_lane, 64), __shfl(gap, src_lane, 64), __shfl(pe + before, src_lane, 64));
-      }
-      if (live) {
-        subc_walk<ROW>(cd, bm, mis, bnd, ms, me);
-        uint8_t* dst = o + ms + before;
-        if (!(dbg & 32))
-#pragma unroll
-        for (int q = 0; q < kSubcTpl; ++q) {
-          if (q >= cd.ntpl) break;
-          const ReplSeg sg = cd.tpl[q];
-          if (sg.group_ref) {
-            const int gs = bnd[sg.start], gl = (int)bnd[sg.length] - gs;
-            subc_copy(dst, txt + gs, gl);
-            dst += gl;
-          } else {
-            subc_copy(dst, repl + sg.start, sg.length);
-            dst += sg.length;
-          }
-        }
-      }
-    }
-    copy_all(prev_end, tlen - prev_end, prev_end + (olen - tlen));   // behind the last replaced match
-    MRX_SUBC_WAVE_SYNC();
-    // the tile out: whole 16-byte blocks where the block is the text's alone, bytes at the two ends
-    uint8_t* oframe = out + obase - head;
-    const int nob = (head + olen + 15) >> 4;
-    for (int b = lane; b < ((dbg & 64) ? 0 : nob); b += 64) {
-      const int lo = 16 * b, hi = lo + 16;
-      if (lo >= head && hi <= head + olen) {
-        *(uint4*)(oframe + lo) = *(const uint4*)(otile + lo);
-      } else {
-        const int from = lo > head ? lo : head, to = hi < head + olen ? hi : head + olen;
-        for (int j = from; j < to; ++j) oframe[j] = otile[j];
-      }
-    }
-  }
-}
-#undef MRX_SUBC_WAVE_SYNC
-
-int sub_chain_from_spans(const mrx_handle* h, const Layout& lay, int64_t n, const std::string& r,
-                         const std::vector<ReplSeg>& tpl, int64_t count, int64_t* out_off, uint8_t* out, int64_t out_cap,
-                         int64_t* total_bytes, hipStream_t s, int64_t known_bytes, int64_t known_max) {
-  const ChainGroups& cg = h->hp.chain;
-  if (cg.nleaf > kSubcLeaves || (int)tpl.size() > kSubcTpl || (int)r.size() > kSubcRepl) return kSubsRetryGeneric;
-  int64_t in_bytes = known_bytes, max_len = known_max;
-  if (known_bytes < 0 || known_max < 0)
-    if (int rc0 = csr_stats(lay, n, s, &in_bytes, &max_len)) return rc0;
-  if (in_bytes < 0) return fail(MRX_E_ARGUMENT, "offsets[n] is negative");
-  if (max_len > 4096) return kSubsRetryGeneric;
-  ChainDev cd{};
-  cd.nleaf = cg.nleaf; cd.ntpl = (int)tpl.size();
-  for (int l = 0; l < kSubcLeaves; ++l) { cd.lmax[l] = cg.lmax[l]; cd.lfix[l] = l < cg.nleaf && cg.lmin[l] == cg.lmax[l] ? cg.lmin[l] : 0; }
-  for (int l = 0; l + 1 < cg.nleaf; ++l) if (!cd.lfix[l]) cd.need |= 1 << l;
-  cd.ntpl = 0;
-  for (const ReplSeg& sg : tpl) {   // a group's segment: the two boundaries it lies between (a group the pattern lacks: nothing)
-    if (sg.group_ref > 0) {
-      if (sg.group_ref <= 9 && cg.gopen[sg.group_ref] >= 0) cd.tpl[cd.ntpl++] = ReplSeg{1, cg.gopen[sg.group_ref], cg.gclose[sg.group_ref]};
-    } else if (sg.length > 0) {
-      cd.tpl[cd.ntpl++] = sg;
-    }
-  }
-  uint8_t mask8[256];
-  for (int c = 0; c < 256; ++c) mask8[c] = (uint8_t)cg.mask[c];
-  // does every match gain the same number of bytes?  (literal bytes + fixed-width leaves counted by the groups that hold
-  // them - their own width; a leaf of variable width must lie in exactly one referenced group)
-  bool const_delta = true;
-  int cdelta = 0;
-  {
-    int covers[kSubcLeaves] = {0};
-    for (int k = 0; k < cd.ntpl; ++k) {
-      if (cd.tpl[k].group_ref) for (int l = cd.tpl[k].start; l < cd.tpl[k].length; ++l) ++covers[l];
-      else cdelta += cd.tpl[k].length;
-    }
-    for (int l = 0; l < cg.nleaf; ++l) {
-      if (cg.lmin[l] == cg.lmax[l]) cdelta += (covers[l] - 1) * cg.lmin[l];
-      else if (covers[l] != 1) const_delta = false;
-    }
-    if (g_chain_sub_general) const_delta = false;   // (mrx_debug_chain_sub_general: the general form, for A/B runs and tests)
-  }
-  int64_t *d_prefix = nullptr, *d_sizes = nullptr, *d_total = nullptr;
-  int32_t *d_spans = nullptr, *d_dcum = nullptr, *d_longest = nullptr;
-  uint8_t *d_mask = nullptr, *d_repl = nullptr;
-  HIP_TRY(scratch_alloc((void**)&d_prefix, sizeof(int64_t) * (n + 1), s));
-  HIP_TRY(scratch_alloc((void**)&d_sizes, sizeof(int64_t) * n, s));
-  // (output total, longest output, match total: three words side by side, one copy to the host)
-  HIP_TRY(scratch_alloc((void**)&d_total, 3 * sizeof(int64_t), s));
-  d_longest = (int32_t*)(d_total + 1);
-  HIP_TRY(scratch_alloc((void**)&d_mask, 256, s));
-  HIP_TRY(scratch_alloc((void**)&d_repl, r.size() + 16, s));
-  HIP_TRY(hipMemcpyAsync(d_mask, mask8, 256, hipMemcpyHostToDevice, s));   // (pageable source: copied before the call returns)
-  if (!r.empty()) HIP_TRY(hipMemcpyAsync(d_repl, r.data(), r.size(), hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemsetAsync(d_total, 0, 3 * sizeof(int64_t), s));
-  int64_t cap = in_bytes / 8 + n + 64, nm = 0, tot = 0;
-  if (const int64_t seen = h->sub_matches_per_kib.load(std::memory_order_relaxed); seen > 128) {
-    const int64_t by_hint = (in_bytes >> 10) * (seen + seen / 8 + 1) + n + 64;
-    if (by_hint > cap) cap = by_hint < in_bytes + n + 64 ? by_hint : in_bytes + n + 64;
-  }
-  int32_t longest = 0;
-  const int subc_dbg = env_knobs().subc_debug;   // (ablation runs: wrong results)
-  const int64_t blocks = (n + (kBlock / 64) - 1) / (kBlock / 64);
-  const unsigned grid = (unsigned)(blocks < grid_cap() ? blocks : grid_cap());
-  int rc = MRX_OK;
-  // (one host synchronisation: the match total, which sizes the spans; the output total and the longest output, which
-  // picks the emit kernel's tile)
-  for (int attempt = 0; attempt < 2; ++attempt) {
-    HIP_TRY(scratch_alloc((void**)&d_spans, sizeof(int32_t) * 2 * (size_t)cap, s));
-    HIP_TRY(scratch_alloc((void**)&d_dcum, sizeof(int32_t) * (size_t)(cap + 1), s));
-    rc = run_findall(h, lay, n, d_prefix, d_spans, cap, nullptr, s, /*match_next_sequence=*/true, in_bytes, max_len);
-    if (rc != MRX_OK) return rc;
-    // (sizes behind the spans without waiting: when the spans did not fit it returns at once)
-    if (const_delta)
-      hipLaunchKernelGGL(k_subc_sizes_const, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, s, n, lay.offsets, d_prefix,
-                         (long long)count, cdelta, d_sizes, d_longest, cap);
-    else if (max_len <= 2048)
-      hipLaunchKernelGGL(k_subc_sizes<2048>, dim3(grid), dim3(kBlock), 0, s, cd, n, lay.data, lay.offsets, d_prefix, d_spans,
-                         (long long)count, d_mask, d_sizes, d_dcum, d_longest, cap, subc_dbg);
-    else
-      hipLaunchKernelGGL(k_subc_sizes<4096>, dim3(grid), dim3(kBlock), 0, s, cd, n, lay.data, lay.offsets, d_prefix, d_spans,
-                         (long long)count, d_mask, d_sizes, d_dcum, d_longest, cap, subc_dbg);
-    HIP_TRY(hipGetLastError());
-    rc = device_scan<int64_t>(d_sizes, n, out_off, d_total, s);
-    if (rc != MRX_OK) return rc;
-    int64_t h3[3] = {0, 0, 0};
-    HIP_TRY(hipMemcpyAsync(d_total + 2, d_prefix + n, sizeof(int64_t), hipMemcpyDeviceToDevice, s));
-    HIP_TRY(hipMemcpyAsync(h3, d_total, sizeof h3, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    tot = h3[0]; longest = (int32_t)(h3[1] & 0xFFFFFFFF); nm = h3[2];
-    h->sub_matches_per_kib.store(in_bytes >= 1024 ? nm / (in_bytes >> 10) : 0, std::memory_order_relaxed);
-    if (nm <= cap) break;
-    if (attempt == 1) return fail(MRX_E_NO_DEVICE, "sub: match count changed between two passes");
-    cap = nm;   // (as in sub_from_spans(): the second attempt's buffers lie behind the first's)
-  }
-  if (longest > 4096) {
-    rc = kSubsRetryGeneric;
-  } else {
-    if (total_bytes) *total_bytes = tot;
-    if (tot > out_cap) {
-      rc = fail(MRX_E_CAPACITY, "output buffer too small: need " + std::to_string(tot));
-    } else if (tot > 0) {
-#define MRX_SUBC_EMIT(TT)                                                                                              \
-  hipLaunchKernelGGL(k_subc_emit<TT>, dim3(grid), dim3(kBlock), 0, s, cd, n, lay.data, lay.offsets, d_prefix, d_spans, \
-                     (long long)count, d_mask, d_repl, (int)r.size(), const_delta ? (const int32_t*)nullptr : d_dcum, out_off, out, cdelta, subc_dbg)
-      if (longest <= 2048 && max_len <= 2048) MRX_SUBC_EMIT(2048);
-      else MRX_SUBC_EMIT(4096);
-#undef MRX_SUBC_EMIT
-      HIP_TRY(hipGetLastError());
-      g_last_kernel = "k_subc_emit";
-    }
-  }
-  return rc;
-}
-}  // namespace
-
 extern "C" {
 
 int mrx_compile(const char* pattern, size_t pattern_len, mrx_handle** out) {
@@ -7166,29 +5817,6 @@ int mrx_num_groups(const mrx_handle* h) {
 }
 const char* mrx_version(void) { return "mrx-hip 0.1 (gfx950)"; }
 
-// captures_all's route for a CSR batch with no text beyond the chain kernel's tile (4096 bytes), from the plan alone:
-// the rows of a deterministic chain from findall's spans (k_capall_chain), the fixed-width windows from findall's spans
-// (k_capall_fixed), or sub_text()'s loop, a lane per text (k_capall_emit).  force_generic: mrx_debug_force_generic's level.
-enum CapallRoute { CAPALL_GENERAL, CAPALL_FIXED, CAPALL_CHAIN };
-static CapallRoute capall_route(const mrx_handle* h, int force_generic) {
-  const HostPlan& hp = h->hp;
-  const uint32_t sfl = hp.dev.flags;
-  const bool general = hp.fixed_total < 0;
-  const ChainGroups& cg = hp.chain;
-  bool chain_ok = general && cg.ok && !force_generic && (sfl & (PF_STREAM_SEARCH | PF_STEP_SEARCH)) &&
-                  hp.why_no_search.empty() && cg.nleaf <= kSubcLeaves && hp.bt.ngroups <= 9;
-  for (int j = 1; chain_ok && j <= hp.bt.ngroups; ++j) chain_ok = cg.gopen[j] >= 0;
-  if (chain_ok) return CAPALL_CHAIN;
-  // (as sub_any's spans route: not with a memchr prefilter, not for exact literals, not for the whole-text shortcut of
-  // "concat" patterns that are not purely groups)
-  const bool spans_ok = !(sfl & PF_EXACT_LITERAL) &&
-                        ((!force_generic && (sfl & PF_STREAM_SEARCH)) ||
-                         (force_generic < 2 && (sfl & PF_STEP_SEARCH) && !(sfl & PF_PREFILTER)));
-  const bool shortcut_differs = hp.fixed_concat && !hp.fixed_pure;
-  if (spans_ok && !general && !shortcut_differs && hp.fixed_total < 0x7FFF) return CAPALL_FIXED;
-  return CAPALL_GENERAL;
-}
-
 size_t mrx_describe(const mrx_handle* h, char* buf, size_t cap) {
   if (!h) return 0;
   std::string s = describe_plan(h->hp);
@@ -7196,8 +5824,7 @@ size_t mrx_describe(const mrx_handle* h, char* buf, size_t cap) {
   const bool refused = mrx::captures_all_refusal(h) != MRX_OK;
   g_err = err;
   if (!refused) {   // (no route for a handle that captures_all refuses)
-    const CapallRoute r = capall_route(h, 0);
-    s += std::string("device.capall=") + (r == CAPALL_CHAIN ? "chain" : r == CAPALL_FIXED ? "fixed" : "general") + "\n";
+    s += std::string("device.capall=") + capall_route_name(h) + "\n";
   }
   if (buf && cap) {
     const size_t k = s.size() < cap - 1 ? s.size() : cap - 1;
@@ -7245,7 +5872,7 @@ static int run_search_any(const mrx_handle* h, const Layout& lay, int64_t n, int
     HIP_TRY(scratch_alloc((void**)&vskip, sizeof(uint32_t) * n, s));
     hipLaunchKernelGGL(k_litscan<false>, dim3(wstep_grid(n)), dim3(64 * kWsWaves), 0, s, H_BLOB(h) + p.off_pre, p.pre_len, H_BLOB(h), lay, n,
                        d_cand, (int2*)nullptr);
-    hipLaunchKernelGGL(k_view_build, dim3(grid_for(n + 1, kBlock)), dim3(kBlock), 0, s, lay, n, 0, d_cand, vstart, vlen, vskip, 0);
+    hipLaunchKernelGGL(k_view_build, dim3(device_grid(n + 1, kBlock)), dim3(kBlock), 0, s, lay, n, 0, d_cand, vstart, vlen, vskip, 0);
     HIP_TRY(hipGetLastError());
     Layout view{csr(lay.data, vstart)};
     view.vlen = vlen;
@@ -7254,7 +5881,7 @@ static int run_search_any(const mrx_handle* h, const Layout& lay, int64_t n, int
     const int rc = run_search_any(h, view, n, ds, de, st);
     t_prefilter_done = false;
     if (rc != MRX_OK) return rc;
-    hipLaunchKernelGGL(k_view_fix, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, s, lay, n, 0, d_cand, 0, ds, de, (uint8_t*)nullptr);
+    hipLaunchKernelGGL(k_view_fix, dim3(device_grid(n, kBlock)), dim3(kBlock), 0, s, lay, n, 0, d_cand, 0, ds, de, (uint8_t*)nullptr);
     HIP_TRY(hipGetLastError());
     return MRX_OK;
   }
@@ -7273,7 +5900,7 @@ static int run_search_any(const mrx_handle* h, const Layout& lay, int64_t n, int
     ScanTimer tm(s);
     launch_stream<ST_SEARCH>(h, pc.lay, pc.nv, nullptr, nullptr, nullptr, 0, d_vs, d_vs + pc.nv, s, pc.vlen, pc.vskip);
     tm.stop();
-    hipLaunchKernelGGL(k_virt_first, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, s, n, pc.vfirst, d_vs, d_vs + pc.nv,
+    hipLaunchKernelGGL(k_virt_first, dim3(device_grid(n, kBlock)), dim3(kBlock), 0, s, n, pc.vfirst, d_vs, d_vs + pc.nv,
                        pc.vbase, ds, de);
     HIP_TRY(hipGetLastError());
     g_last_kernel = "k_stream_search_pieces";
@@ -7308,7 +5935,7 @@ static int run_first_any(const mrx_handle* h, const Layout& lay, int64_t n, int3
   if (p.off_fa_run >= 0 && !lay.offsets && !lay.vlen && g_long_text_mode != 2 &&
       (g_long_text_mode == 1 || g_long_text_mode == 3 || (lay.pitch_longest() >= 2048 && n <= 131072))) {
     ScanTimer tm(s);
-    hipLaunchKernelGGL(k_first_run, dim3(grid_for(n * 64, kBlock)), dim3(kBlock), 0, s, p, H_BLOB(h), lay, n, ds, de);
+    hipLaunchKernelGGL(k_first_run, dim3(device_grid(n * 64, kBlock)), dim3(kBlock), 0, s, p, H_BLOB(h), lay, n, ds, de);
     g_last_kernel = "k_first_run";
     HIP_TRY(hipGetLastError());
     tm.stop();
@@ -7354,7 +5981,7 @@ static int run_is_match_any(const mrx_handle* h, const Layout& lay, int64_t n, u
     // the first-byte quirk (A.6 #8): no walk at all
     if (int rc = ensure_device(h)) return rc;
     hipStream_t s = (hipStream_t)st;
-    hipLaunchKernelGGL(k_is_match_byte, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, s, lay, n, H_BLOB(h) + h->hp.dev.off_first,
+    hipLaunchKernelGGL(k_is_match_byte, dim3(device_grid(n, kBlock)), dim3(kBlock), 0, s, lay, n, H_BLOB(h) + h->hp.dev.off_first,
                        (h->hp.dev.flags & PF_START_ACCEPTING) ? 1 : 0, f);
     g_last_kernel = "k_is_match_byte";
     HIP_TRY(hipGetLastError());
@@ -7372,7 +5999,7 @@ static int run_is_match_any(const mrx_handle* h, const Layout& lay, int64_t n, u
     HIP_TRY(scratch_alloc((void**)&tmp, sizeof(int32_t) * 2 * n, s));
     int rc = run_first_any(h, lay, n, tmp, tmp + n, st);
     if (rc == MRX_OK) {
-      hipLaunchKernelGGL(k_span_to_flag, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, s, n, tmp, f);
+      hipLaunchKernelGGL(k_span_to_flag, dim3(device_grid(n, kBlock)), dim3(kBlock), 0, s, n, tmp, f);
       HIP_TRY(hipGetLastError());
     }
     return rc;
@@ -7427,7 +6054,7 @@ static int run_at(int op, const mrx_handle* h, const Layout& lay, int64_t n, int
   // NFAEngine.match_first (is_match = bool of it) at start > len: the program decides -- zero repetitions and
   // groups pass, bytes and '$' do not ('[^0-9]{0,2}$' at len + 1: None; 'x?' there: the empty match)
   const bool bt_first = op != AT_SEARCH && (h->hp.dev.flags & PF_BT_FIRST) && plan_uses_backtracker(h);
-  hipLaunchKernelGGL(k_view_build, dim3(grid_for(n + 1, kBlock)), dim3(kBlock), 0, s, lay, n, start, d_starts, vstart, vlen, vskip,
+  hipLaunchKernelGGL(k_view_build, dim3(device_grid(n + 1, kBlock)), dim3(kBlock), 0, s, lay, n, start, d_starts, vstart, vlen, vskip,
                      bt_first ? 1 : 0);
   Layout view{csr(lay.data, vstart)};
   view.vlen = vlen;
@@ -7452,7 +6079,7 @@ static int run_at(int op, const mrx_handle* h, const Layout& lay, int64_t n, int
   else if (op == AT_SEARCH) { rules &= ~2; rc = run_search_any(h, view, n, ds, de, st); }
   else { rules |= 8; rc = run_is_match_any(h, view, n, flag, st); }
   if (rc == MRX_OK) {
-    hipLaunchKernelGGL(k_view_fix, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, s, lay, n, start, d_starts, rules, ds, de, flag);
+    hipLaunchKernelGGL(k_view_fix, dim3(device_grid(n, kBlock)), dim3(kBlock), 0, s, lay, n, start, d_starts, rules, ds, de, flag);
     HIP_TRY(hipGetLastError());
   }
   return rc;
@@ -7510,7 +6137,7 @@ static int run_captures_any(const mrx_handle* h, const Layout& lay, int64_t n, i
   HIP_TRY(scratch_alloc((void**)&tmp, sizeof(int32_t) * 2 * n, s));
   int rc = run_search_any(h, lay, n, tmp, tmp + n, st);
   if (rc == MRX_OK) {
-    hipLaunchKernelGGL(k_expand_captures, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, s, h->hp.dev, n, tmp,
+    hipLaunchKernelGGL(k_expand_captures, dim3(device_grid(n, kBlock)), dim3(kBlock), 0, s, h->hp.dev, n, tmp,
                        tmp + n, spans);
     HIP_TRY(hipGetLastError());
   }
@@ -7545,112 +6172,6 @@ int mrx_findall_strided_dev(const mrx_handle* h, const uint8_t* d, int64_t strid
   return run_findall(h, b, n, prefix, spans, cap, total, st);
 }
 
-}  // extern "C"
-namespace {
-// ---- regex.split (matcher.mojo:1357-1393): the text between successive findall matches ------------------------
-// kept[i] = min(matches of text i, maxsplit) (all of them for maxsplit == 0, none for a negative maxsplit)
-__global__ __launch_bounds__(kBlock) void k_split_kept(int64_t n, const int64_t* __restrict__ prefix, int64_t maxsplit,
-                                                       int32_t* __restrict__ kept) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t c = prefix[i + 1] - prefix[i];
-    kept[i] = (int32_t)(maxsplit == 0 ? c : maxsplit < 0 ? 0 : (c < maxsplit ? c : maxsplit));
-  }
-}
-// piece_prefix[i] = (kept matches of the texts before i) + i: text i yields kept[i] + 1 pieces
-__global__ __launch_bounds__(kBlock) void k_split_prefix(int64_t n, const int64_t* __restrict__ kept_prefix,
-                                                         int64_t* __restrict__ piece_prefix, int64_t* __restrict__ total) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i <= n; i += (int64_t)gridDim.x * blockDim.x) {
-    piece_prefix[i] = kept_prefix[i] + i;
-    if (i == n && total) *total = kept_prefix[n] + n;
-  }
-}
-// one lane per PIECE: piece q of text i is [end of match q - 1 (0 for q = 0), start of match q (the text's end behind the
-// last kept match)); its text is found by bisection of the piece offsets (coalesced stores whatever the texts hold)
-__global__ __launch_bounds__(kBlock) void k_split_pieces(Layout lay, int64_t n, const int64_t* __restrict__ prefix,
-                                                         const int32_t* __restrict__ spans, const int64_t* __restrict__ piece_prefix,
-                                                         int32_t* __restrict__ pieces, int64_t piece_cap) {
-  const int64_t total = piece_prefix[n] < piece_cap ? piece_prefix[n] : piece_cap;
-  for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < total; j += (int64_t)gridDim.x * blockDim.x) {
-    int64_t lo = 0, hi = n;   // the last i with piece_prefix[i] <= j
-    while (hi - lo > 1) {
-      const int64_t mid = (lo + hi) >> 1;
-      if (piece_prefix[mid] <= j) lo = mid; else hi = mid;
-    }
-    const int64_t i = lo, q = j - piece_prefix[i];
-    const int64_t kept = piece_prefix[i + 1] - piece_prefix[i] - 1;
-    const int32_t* sp = spans + 2 * prefix[i];
-    const int a = q == 0 ? 0 : sp[2 * (q - 1) + 1];
-    const int b = q < kept ? sp[2 * q] : lay.text(i).len;
-    // exact-literal plans return overlapping spans (findall of a self-overlapping literal), so match q may begin
-    // before match q-1 ends: that piece is empty, [a, a), never a reversed range
-    *(int2*)(pieces + 2 * j) = make_int2(a, b > a ? b : a);
-  }
-}
-
-int run_split(const mrx_handle* h, const Layout& lay, int64_t n, int64_t maxsplit, int64_t* d_piece_prefix, int32_t* d_pieces,
-              int64_t piece_cap, int64_t* total, void* st) {
-  hipStream_t s = (hipStream_t)st;
-  ScratchScope scratch_scope_(s);
-  if (!h) return fail(MRX_E_ARGUMENT, "null handle");
-  if (n < 0 || piece_cap < 0 || !d_piece_prefix || (!d_pieces && piece_cap > 0)) return fail(MRX_E_ARGUMENT, "bad arguments");
-  if ((uintptr_t)d_pieces & 7) return fail(MRX_E_ARGUMENT, "d_pieces must be 8-byte aligned");
-  // findall into scratch: every piece but a text's last ends at a match, so piece_cap holds the spans of any result
-  // that fits (maxsplit == 0: pieces = spans + n)
-  int64_t* d_prefix = nullptr;
-  int32_t* d_spans = nullptr;
-  int32_t* d_kept = nullptr;
-  int64_t* d_kprefix = nullptr;
-  int64_t* d_tot = nullptr;
-  const int64_t span_cap = piece_cap > n ? piece_cap : n + 1;
-  HIP_TRY(scratch_alloc((void**)&d_prefix, sizeof(int64_t) * (n + 1), s));
-  HIP_TRY(scratch_alloc((void**)&d_spans, sizeof(int32_t) * 2 * (size_t)span_cap, s));
-  HIP_TRY(scratch_alloc((void**)&d_kept, sizeof(int32_t) * (n > 0 ? n : 1), s));
-  HIP_TRY(scratch_alloc((void**)&d_kprefix, sizeof(int64_t) * (n + 1), s));
-  HIP_TRY(scratch_alloc((void**)&d_tot, sizeof(int64_t) * 2, s));
-  int64_t nspans = 0;
-  int rc_f = run_findall(h, lay, n, d_prefix, d_spans, span_cap, &nspans, s);
-  if (rc_f == MRX_E_CAPACITY && maxsplit == 0) {   // pieces = matches + n: the need is known
-    if (total) *total = nspans + n;
-    return fail(MRX_E_CAPACITY, "piece buffer too small: need " + std::to_string(nspans + n));
-  }
-  if (rc_f == MRX_E_CAPACITY) {   // a limit is on: the pieces may well fit although the matches did not -- once more, all of them
-    HIP_TRY(scratch_alloc((void**)&d_spans, sizeof(int32_t) * 2 * (size_t)nspans, s));
-    rc_f = run_findall(h, lay, n, d_prefix, d_spans, nspans, &nspans, s);
-  }
-  if (rc_f != MRX_OK) return rc_f;
-  const char* scanned = g_last_kernel;
-  if (n > 0) {
-    hipLaunchKernelGGL(k_split_kept, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, s, n, d_prefix, maxsplit, d_kept);
-    if (int rc = device_scan<int32_t>(d_kept, n, d_kprefix, d_tot, s)) return rc;
-  } else {
-    HIP_TRY(hipMemsetAsync(d_kprefix, 0, sizeof(int64_t), s));
-  }
-  hipLaunchKernelGGL(k_split_prefix, dim3(grid_for(n + 1, kBlock)), dim3(kBlock), 0, s, n, d_kprefix, d_piece_prefix, d_tot + 1);
-  int64_t pieces_total = 0;
-  HIP_TRY(hipMemcpyAsync(&pieces_total, d_tot + 1, sizeof pieces_total, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  if (total) *total = pieces_total;
-  if (piece_cap > 0 && n > 0)
-    hipLaunchKernelGGL(k_split_pieces, dim3(grid_for(pieces_total < piece_cap ? pieces_total : piece_cap, kBlock)), dim3(kBlock), 0, s,
-                       lay, n, d_prefix, d_spans, d_piece_prefix, d_pieces, piece_cap);
-  HIP_TRY(hipGetLastError());
-  g_last_kernel = scanned;   // (the scan that found the separators)
-  if (pieces_total > piece_cap) return fail(MRX_E_CAPACITY, "piece buffer too small: need " + std::to_string(pieces_total));
-  return MRX_OK;
-}
-}  // namespace
-extern "C" {
-int mrx_split_dev(const mrx_handle* h, const uint8_t* d, const int64_t* off, int64_t n, int64_t maxsplit,
-                  int64_t* d_piece_prefix, int32_t* d_pieces, int64_t piece_cap, int64_t* total, void* st) {
-  return run_split(h, csr(d, off), n, maxsplit, d_piece_prefix, d_pieces, piece_cap, total, st);
-}
-int mrx_split_strided_dev(const mrx_handle* h, const uint8_t* d, int64_t stride, const int32_t* lens, int32_t len, int64_t n,
-                          int64_t maxsplit, int64_t* d_piece_prefix, int32_t* d_pieces, int64_t piece_cap, int64_t* total, void* st) {
-  const TextBatch b = strided(d, stride, lens, len);
-  if (int rc = check_batch(b, BATCH_PITCH)) return rc;
-  return run_split(h, b, n, maxsplit, d_piece_prefix, d_pieces, piece_cap, total, st);
-}
-
 int mrx_count_dev(const mrx_handle* h, const uint8_t* d, const int64_t* off, int64_t n,
                   int32_t* counts, void* st) {
   const TextBatch b = csr(d, off);
@@ -7664,553 +6185,6 @@ int mrx_count_strided_dev(const mrx_handle* h, const uint8_t* d, int64_t stride,
   return run_count_any(h, b, n, counts, st);
 }
 
-}  // extern "C"
-namespace {
-__global__ __launch_bounds__(kBlock) void k_pitch_offsets(int64_t n, int64_t stride, int64_t* __restrict__ off) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i <= n; i += (int64_t)gridDim.x * blockDim.x) off[i] = i * stride;
-}
-}  // namespace
-static int sub_any(const mrx_handle* h, const char* repl, size_t repl_len, int64_t count, const Layout& lay_in,
-                   int64_t n, int64_t* out_off, uint8_t* out, int64_t out_cap, int64_t* total_bytes, void* st,
-                   int64_t known_bytes = -1, int64_t known_max = -1);   // (byte count and longest text, when the caller has them)
-extern "C" {
-int mrx_sub_dev(const mrx_handle* h, const char* repl, size_t repl_len, int64_t count,
-                const uint8_t* d, const int64_t* off, int64_t n, int64_t* out_off, uint8_t* out,
-                int64_t out_cap, int64_t* total_bytes, void* st) {
-  return sub_any(h, repl, repl_len, count, csr(d, off), n, out_off, out, out_cap, total_bytes, st);
-}
-int mrx_sub_known_dev(const mrx_handle* h, const char* repl, size_t repl_len, int64_t count,
-                      const uint8_t* d, const int64_t* off, int64_t n, int64_t end_offset, int64_t max_text_len,
-                      int64_t* out_off, uint8_t* out, int64_t out_cap, int64_t* total_bytes, void* st) {
-  if (end_offset < 0 || max_text_len < 0) return fail(MRX_E_ARGUMENT, "negative end offset / text length");
-  return sub_any(h, repl, repl_len, count, csr(d, off), n, out_off, out, out_cap, total_bytes, st,
-                 end_offset, max_text_len);
-}
-// Texts at a fixed pitch.  Rows without padding (len == stride, no per-text lengths) are a CSR batch whose offsets
-// are i * stride: they are written once on the device and the call takes every fast path of mrx_sub_dev; padded
-// rows run on the lane-per-text kernels (the spans route assembles its output from CSR offsets).
-int mrx_sub_strided_dev(const mrx_handle* h, const char* repl, size_t repl_len, int64_t count,
-                        const uint8_t* d, int64_t stride, const int32_t* d_lens, int32_t len, int64_t n,
-                        int64_t* out_off, uint8_t* out, int64_t out_cap, int64_t* total_bytes, void* st) {
-  // (`len` is ignored when d_lens is given, as in every other strided entry point)
-  const TextBatch b = strided(d, stride, d_lens, len);
-  if (int rc = check_batch(b, BATCH_PITCH_TERSE)) return rc;
-  if (!d_lens && (int64_t)len == stride && n > 0) {
-    ScratchScope scope_((hipStream_t)st);
-    int64_t* d_off = nullptr;
-    HIP_TRY(scratch_alloc((void**)&d_off, sizeof(int64_t) * (n + 1), (hipStream_t)st));
-    hipLaunchKernelGGL(k_pitch_offsets, dim3(grid_for(n + 1, kBlock)), dim3(kBlock), 0, (hipStream_t)st, n, stride, d_off);
-    HIP_TRY(hipGetLastError());
-    return sub_any(h, repl, repl_len, count, csr(d, d_off), n, out_off, out, out_cap, total_bytes, st,
-                   n * stride, stride);
-  }
-  return sub_any(h, repl, repl_len, count, b, n, out_off, out, out_cap, total_bytes, st);
-}
-}  // extern "C"
-static int sub_any(const mrx_handle* h, const char* repl, size_t repl_len, int64_t count, const Layout& lay_in,
-                   int64_t n, int64_t* out_off, uint8_t* out, int64_t out_cap, int64_t* total_bytes, void* st,
-                   int64_t known_bytes, int64_t known_max) {
-  const uint8_t* d = lay_in.data;
-  const int64_t* off = lay_in.offsets;
-  ScratchScope scratch_scope_((hipStream_t)st);
-  if (!h) return fail(MRX_E_ARGUMENT, "null handle");
-  if (n < 0) return fail(MRX_E_ARGUMENT, "negative batch size");
-  const std::string r(repl ? repl : "", repl_len);
-  const bool groups = repl_has_group_refs(r);
-  // group references on a pattern outside the fixed-width form: every match comes from
-  // NFAEngine.match_next_with_groups (matcher.mojo:1781-1822), not from the search engines
-  const bool general_groups = groups && h->hp.fixed_total < 0;
-  std::vector<ReplSeg> tpl;
-  if (general_groups) {
-    if (!h->hp.bt.ok)
-      return fail(MRX_E_UNSUPPORTED,
-                  "sub() with \\1..\\9 on this pattern uses NFAEngine.match_next_with_groups (recursive "
-                  "backtracking matcher, nfa.mojo:500-574); its flat-program form does not cover: " +
-                      (h->hp.bt.why_not.empty() ? std::string("'.*'") : h->hp.bt.why_not));
-  } else if (int rc = check_search_supported(h)) {
-    return rc;
-  }
-  if (groups) tpl = parse_repl_template(r);
-  if (int rc = check_lds(h)) return rc;
-  if (int rc = ensure_device(h)) return rc;
-  hipStream_t s = (hipStream_t)st;
-  // a spans route that hands the call back (kSubsRetryGeneric) has enqueued its work; the lane-per-text form below
-  // runs behind it on the same stream and takes over its bytes (not behind mrx_sub_strided_dev's offsets: they stay)
-  const ScratchMark before_spans = scratch_mark(s);
-  // \1..\9 on a deterministic chain whose matches are the table walk's: spans of the plain search, groups from the
-  // leaves' runs (k_subc_sizes / k_subc_emit); batches with a text or an output beyond the tiles stay the interpreter's
-  if (general_groups && h->hp.chain.ok && !g_force_generic && n > 0 && off && count >= 0 &&
-      (h->hp.dev.flags & (PF_STREAM_SEARCH | PF_STEP_SEARCH)) && h->hp.why_no_search.empty()) {
-    const int rc = sub_chain_from_spans(h, csr(d, off), n, r, tpl, count, out_off, out, out_cap,
-                                        total_bytes, s, known_bytes, known_max);
-    if (rc != kSubsRetryGeneric) return rc;
-    scratch_reuse_from(s, before_spans);
-  }
-  // sub() iterates match_next from the previous match end; on the plain route that is exactly the
-  // findall sequence, so the spans of the streaming kernel or of the windowed stepper serve it.
-  // (Not with a memchr prefilter, which only match_next consults; not for exact literals, whose
-  // findall spans overlap while sub's own search loop does not.)
-  const uint32_t sfl = h->hp.dev.flags;
-  const bool spans_ok = !(sfl & PF_EXACT_LITERAL) &&
-                        ((!g_force_generic && (sfl & PF_STREAM_SEARCH)) ||
-                         (g_force_generic < 2 && (sfl & PF_STEP_SEARCH) && !(sfl & PF_PREFILTER)));
-  // (group templates of "concat" patterns that are not purely groups: texts of exactly fixed_total bytes take the
-  // whole-text shortcut, which only sub_text() has)
-  const bool shortcut_differs = groups && h->hp.fixed_concat && !h->hp.fixed_pure;
-  if (spans_ok && !general_groups && !shortcut_differs && n > 0 && off) {
-    // replacement as a fixed-length byte map
-    std::vector<uint16_t> rmap;
-    int group_reach = 0;   // how far behind a match's start the template reads
-    if (groups) {
-      for (const ReplSeg& sg : tpl) {
-        if (sg.group_ref > 0 && sg.group_ref <= h->hp.fixed_ngroups) {
-          for (int j = 0; j < h->hp.fixed_w[sg.group_ref]; ++j)
-            rmap.push_back((uint16_t)(0x8000 | (h->hp.fixed_off[sg.group_ref] + j)));
-          group_reach = std::max(group_reach, h->hp.fixed_off[sg.group_ref] + h->hp.fixed_w[sg.group_ref]);
-        }
-        else
-          for (int j = 0; j < sg.length; ++j) rmap.push_back((uint8_t)r[sg.start + j]);
-      }
-    } else {
-      for (unsigned char ch : r) rmap.push_back(ch);
-    }
-    // (nothing but (\d{N}) groups: every match is fixed_total bytes long and holds all its windows)
-    if (h->hp.fixed_pure) group_reach = 0;
-    if (rmap.size() <= 4096 && h->hp.fixed_total < 0x7FFF) {
-      const int rc = sub_from_spans(h, csr(d, off), n, rmap, count, out_off, out, out_cap,
-                                    total_bytes, s, group_reach, known_bytes, known_max);
-      if (rc != kSubsRetryGeneric) return rc;   // else: a group reaches behind its text, the lane-per-text form cuts it
-      scratch_reuse_from(s, before_spans);
-    }
-  }
-  uint8_t* d_repl = nullptr;
-  ReplSeg* d_tpl = nullptr;
-  int64_t *d_sizes = nullptr, *d_total = nullptr;
-  HIP_TRY(scratch_alloc((void**)&d_repl, r.size() + 16, s));
-  HIP_TRY(scratch_alloc((void**)&d_tpl, sizeof(ReplSeg) * (tpl.size() + 1), s));
-  HIP_TRY(scratch_alloc((void**)&d_sizes, sizeof(int64_t) * (n > 0 ? n : 1), s));
-  HIP_TRY(scratch_alloc((void**)&d_total, sizeof(int64_t), s));
-  if (!r.empty()) HIP_TRY(hipMemcpyAsync(d_repl, r.data(), r.size(), hipMemcpyHostToDevice, s));
-  if (!tpl.empty())
-    HIP_TRY(hipMemcpyAsync(d_tpl, tpl.data(), sizeof(ReplSeg) * tpl.size(), hipMemcpyHostToDevice, s));
-  Layout lay = lay_in;
-  const bool sub_bt = plan_uses_backtracker(h) || general_groups;
-  if ((h->hp.dev.flags & PF_BT_SEARCH) || general_groups) {
-    const Layout plain = lay;
-    if (int rc = bt_prepass(h, plain, n, s, &lay)) return rc;
-  }
-  if (n > 0) {
-    ScanTimer tm(s);
-#define MRX_L(B) hipLaunchKernelGGL((k_sub<SUB_SIZE, B>), dim3(grid_for(n, kBlock)), dim3(kBlock), lds_for(h), s,                     \
-                                   h->hp.dev, H_BLOB(h), lay, n, d_repl, (int)r.size(), general_groups ? 2 : groups ? 1 : 0, d_tpl, \
-                                   (int)tpl.size(), (long long)count, d_sizes, (const int64_t*)nullptr, (uint8_t*)nullptr, (int64_t)0)
-    MRX_BT_DISPATCH(bt_kernel_kind(h, sub_bt), MRX_L);
-#undef MRX_L
-    g_last_kernel = "k_sub_size";
-    HIP_TRY(hipGetLastError());
-    tm.stop();
-  }
-  if (int rc = device_scan<int64_t>(d_sizes, n, out_off, d_total, s)) return rc;
-  int64_t tot = 0;
-  HIP_TRY(hipMemcpyAsync(&tot, d_total, sizeof tot, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  if (total_bytes) *total_bytes = tot;
-  int rc = MRX_OK;
-  if (tot > out_cap) {
-    rc = fail(MRX_E_CAPACITY, "output buffer too small: need " + std::to_string(tot));
-  } else if (n > 0 && tot > 0) {
-#define MRX_L(B) hipLaunchKernelGGL((k_sub<SUB_EMIT, B>), dim3(grid_for(n, kBlock)), dim3(kBlock), lds_for(h), s,                     \
-                                   h->hp.dev, H_BLOB(h), lay, n, d_repl, (int)r.size(), general_groups ? 2 : groups ? 1 : 0, d_tpl, \
-                                   (int)tpl.size(), (long long)count, (int64_t*)nullptr, out_off, out, out_cap)
-    MRX_BT_DISPATCH(bt_kernel_kind(h, sub_bt), MRX_L);
-#undef MRX_L
-    HIP_TRY(hipGetLastError());
-  }
-  return rc;
-}
-
-// ---- captures_all: every match of sub()'s loop with a group template, and the groups that loop reads ----------------
-// Three routes, chosen as sub_any() chooses them for a group template:
-//   fixed-width groups on span-capable plans: findall's spans -> clamped counts -> k_scan_* -> k_capall_fixed;
-//   deterministic chains: the plain search's spans -> k_capall_chain (the leaves' boundaries, as in k_subc_sizes);
-//   everything else: sub_text()'s loop a lane per text, k_capall<CA_COUNT> -> k_scan_* -> k_capall<CA_EMIT>.
-// A row is g + 1 int2: groups 1..g, then group 0; no row at or beyond match_cap is ever written.
-namespace {
-enum { CA_COUNT = 0, CA_EMIT = 1 };
-// sub_text()'s loop without a byte sink: emit(k, ms, me, caps) for the k-th match; returns the number of matches.
-// general: groups from NFAEngine.match_next_with_groups (caps), else the fixed-width form (caps unused).
-template <int BT, class F>
-__device__ inline int capall_text(const Ctx& c, const Text& t, bool general, long long count, F&& emit) {
-  if (t.len == 0) return 0;
-  int k = 0, pos = 0, ms, me;
-  BtCaps caps;
-  if constexpr (BT) if (general) {
-    while (pos <= t.len) {
-      if (!bt_match_next_with_groups<BT == 1>(c, t, pos, ms, me, caps)) break;
-      if ((me == ms ? me + 1 : me) <= pos) break;   // a match in front of pos ends the list, as in sub_text()
-      emit(k, ms, me, caps);
-      ++k;
-      pos = me == ms ? me + 1 : me;
-      if (count > 0 && k >= count) break;
-    }
-    return k;
-  }
-  if (c.p.fixed_concat && t.len == c.p.fixed_total) {   // matcher.mojo:1726-1744: the whole text, if all digits
-    for (int i = 0; i < c.p.fixed_total; ++i) {
-      const int b = t.at(i);
-      if (b < '0' || b > '9') return 0;
-    }
-    emit(0, 0, c.p.fixed_total, caps);
-    return 1;
-  }
-  while (pos <= t.len) {
-    if (!hybrid_match_next<BT>(c, t, pos, ms, me)) break;
-    if ((me == ms ? me + 1 : me) <= pos) break;
-    emit(k, ms, me, caps);
-    ++k;
-    pos = me == ms ? me + 1 : me;
-    if (count > 0 && k >= count) break;
-  }
-  return k;
-}
-template <int MODE, int BT = 0>
-__global__ __launch_bounds__(kBlock) void k_capall(DevPlan p, const uint8_t* __restrict__ blob, Layout lay, int64_t n,
-                                                   int general, long long count, int32_t* __restrict__ counts,
-                                                   const int64_t* __restrict__ prefix, int32_t* __restrict__ groups,
-                                                   int64_t match_cap) {
-  extern __shared__ __align__(16) uint8_t lds[];
-  const Ctx c = stage_tables(p, blob, lds);
-  const int g = general ? p.bt_ngroups : p.fixed_ngroups;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const Text t = lay.text(i);
-    if (MODE == CA_COUNT) {
-      counts[i] = capall_text<BT>(c, t, general != 0, count, [](int, int, int, const BtCaps&) {});
-    } else {
-      const int64_t base = prefix[i];
-      capall_text<BT>(c, t, general != 0, count, [&](int k, int ms, int me, const BtCaps& caps) {
-        const int64_t row = base + k;
-        if (row >= match_cap) return;
-        int2* o = (int2*)(groups + row * (int64_t)(g + 1) * 2);
-        for (int j = 1; j <= g; ++j)
-          o[j - 1] = general ? make_int2(caps.gs(j), caps.ge(j))
-                             : make_int2(ms + p.fixed_off[j], ms + p.fixed_off[j] + p.fixed_w[j]);
-        o[g] = make_int2(ms, me);
-      });
-    }
-  }
-}
-// matches kept per text: findall's, at most `count` (> 0), none in an empty text (sub_text() returns at once there)
-__global__ __launch_bounds__(kBlock) void k_capall_clamp(int64_t n, const int64_t* __restrict__ offsets,
-                                                         const int64_t* __restrict__ fprefix, long long count,
-                                                         int32_t* __restrict__ counts) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    int64_t k = offsets[i + 1] > offsets[i] ? fprefix[i + 1] - fprefix[i] : 0;
-    if (count > 0 && k > count) k = count;
-    counts[i] = (int32_t)k;
-  }
-}
-// a wavefront per text; its lanes take the text's rows pair by pair, so the stores of a wavefront are one run
-__global__ __launch_bounds__(kBlock) void k_capall_fixed(DevPlan p, int64_t n, const int64_t* __restrict__ fprefix,
-                                                         const int32_t* __restrict__ spans, int64_t span_cap,
-                                                         const int64_t* __restrict__ prefix, int32_t* __restrict__ groups,
-                                                         int64_t match_cap) {
-  if (fprefix[n] > span_cap) return;   // the spans are incomplete: the host repeats the findall
-  const int g1 = p.fixed_ngroups + 1;
-  const int lane = threadIdx.x & 63;
-  const int64_t nw = (int64_t)gridDim.x * (kBlock / 64);
-  for (int64_t i = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6); i < n; i += nw) {
-    const int64_t a = prefix[i], sa = fprefix[i];
-    int64_t kept = prefix[i + 1] - a;
-    if (a + kept > match_cap) kept = match_cap > a ? match_cap - a : 0;
-    const int64_t npairs = kept * g1;
-    int2* o = (int2*)groups + a * g1;
-    for (int64_t q = lane; q < npairs; q += 64) {
-      const int64_t k = q / g1;
-      const int j = (int)(q - k * g1);
-      const int2 sp = *(const int2*)(spans + 2 * (sa + k));
-      o[q] = j == g1 - 1 ? sp : make_int2(sp.x + p.fixed_off[j + 1], sp.x + p.fixed_off[j + 1] + p.fixed_w[j + 1]);
-    }
-  }
-}
-// the groups of a deterministic chain: a wavefront per text builds the leaves' bitmaps (subc_store), a lane per match
-// finds the boundaries (subc_walk); group j lies between boundaries gb[j].x and gb[j].y
-#define MRX_CAPALL_WAVE_SYNC()                                    \
-  do {                                                            \
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");        \
-    __builtin_amdgcn_wave_barrier();                              \
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");        \
-  } while (0)
-struct CapChainDev {
-  ChainDev cd;
-  int g;
-  int2 gb[10];
-};
-template <int TILE>
-__global__ __launch_bounds__(kBlock) void k_capall_chain(CapChainDev cc, int64_t n, const uint8_t* __restrict__ data,
-                                                         const int64_t* __restrict__ offsets,
-                                                         const int64_t* __restrict__ fprefix, const int32_t* __restrict__ spans,
-                                                         int64_t span_cap, const uint8_t* __restrict__ g_mask,
-                                                         const int64_t* __restrict__ prefix, int32_t* __restrict__ groups,
-                                                         int64_t match_cap) {
-  if (fprefix[n] > span_cap) return;
-  constexpr int NB = TILE / 1024 + 1;
-  constexpr int ROW = TILE / 16 + 4;
-  __shared__ uint16_t bm_all[kBlock / 64][kSubcLeaves * ROW];
-  __shared__ uint16_t bnd_all[kBlock / 64][64 * (kSubcLeaves + 1)];
-  __shared__ uint8_t mask[256];
-  for (int c = threadIdx.x; c < 256; c += blockDim.x) mask[c] = g_mask[c];
-  __syncthreads();
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  uint16_t* bm = bm_all[wv];
-  uint16_t* bnd = bnd_all[wv] + lane * (kSubcLeaves + 1);
-  const int g1 = cc.g + 1;
-  const int64_t nw = (int64_t)gridDim.x * (kBlock / 64);
-  for (int64_t i = (int64_t)blockIdx.x * (kBlock / 64) + wv; i < n; i += nw) {
-    const int64_t a = prefix[i], sa = fprefix[i];
-    int64_t kept = prefix[i + 1] - a;
-    if (a + kept > match_cap) kept = match_cap > a ? match_cap - a : 0;
-    const int64_t ibase = offsets[i];
-    const int tlen = (int)(offsets[i + 1] - ibase);
-    if (kept <= 0 || tlen > TILE) continue;   // (the host sends no text beyond the tile)
-    const int k = (int)kept;
-    const uint8_t* tptr = data + ibase;
-    const int mis = (int)((uintptr_t)tptr & 15);
-    const uint8_t* fptr = tptr - mis;
-    const int nfb = (mis + tlen + 15) >> 4;
-    uint4 tx[NB];
-#pragma unroll
-    for (int r = 0; r < NB; ++r) {
-      const int b = lane + 64 * r;
-      tx[r] = b < nfb ? *(const uint4*)(fptr + 16 * b) : make_uint4(0, 0, 0, 0);
-    }
-    MRX_CAPALL_WAVE_SYNC();   // (the previous text's walks are done with the bitmaps)
-    subc_store<NB, ROW, false>(tx, bm, nullptr, mask, cc.cd.need, nfb, lane);
-    MRX_CAPALL_WAVE_SYNC();
-    for (int m = lane; m < k; m += 64) {
-      const int2 sp = *(const int2*)(spans + 2 * (sa + m));
-      subc_walk<ROW>(cc.cd, bm, mis, bnd, sp.x, sp.y);
-      int2* o = (int2*)groups + (a + m) * g1;
-#pragma unroll
-      for (int j = 1; j <= 9; ++j) {
-        if (j > cc.g) break;
-        o[j - 1] = make_int2((int)bnd[cc.gb[j].x], (int)bnd[cc.gb[j].y]);
-      }
-      o[cc.g] = sp;
-    }
-  }
-}
-#undef MRX_CAPALL_WAVE_SYNC
-}  // namespace
-
-static int capall_counts_to_prefix(const Layout& lay, int64_t n, const int64_t* d_fprefix, int64_t count,
-                                   int32_t* d_counts, int64_t* d_prefix, int64_t* d_total, hipStream_t s) {
-  hipLaunchKernelGGL(k_capall_clamp, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, s, n, lay.offsets, d_fprefix,
-                     (long long)count, d_counts);
-  HIP_TRY(hipGetLastError());
-  return device_scan<int32_t>(d_counts, n, d_prefix, d_total, s);
-}
-
-// routes 1 and 2: the spans of findall's match_next sequence, then the rows.  kSubsRetryGeneric: the batch is route 3's.
-static int capall_from_spans(const mrx_handle* h, const Layout& lay, int64_t n, int64_t count, bool chain,
-                             int64_t* d_prefix, int32_t* d_groups, int64_t match_cap, int64_t* total, hipStream_t s,
-                             int64_t known_bytes, int64_t known_max) {
-  int64_t in_bytes = known_bytes, max_len = known_max;
-  if (known_bytes < 0 || known_max < 0)
-    if (int rc0 = csr_stats(lay, n, s, &in_bytes, &max_len)) return rc0;
-  if (in_bytes < 0) return fail(MRX_E_ARGUMENT, "offsets[n] is negative");
-  CapChainDev cc{};
-  uint8_t mask8[256];
-  if (chain) {
-    const ChainGroups& cg = h->hp.chain;
-    if (max_len > 4096) return kSubsRetryGeneric;   // (as sub_chain_from_spans: beyond the tile, the interpreter's)
-    cc.cd.nleaf = cg.nleaf;
-    for (int l = 0; l < kSubcLeaves; ++l) { cc.cd.lmax[l] = cg.lmax[l]; cc.cd.lfix[l] = l < cg.nleaf && cg.lmin[l] == cg.lmax[l] ? cg.lmin[l] : 0; }
-    for (int l = 0; l + 1 < cg.nleaf; ++l) if (!cc.cd.lfix[l]) cc.cd.need |= 1 << l;
-    cc.g = h->hp.bt.ngroups;
-    for (int j = 1; j <= cc.g; ++j) cc.gb[j] = make_int2(cg.gopen[j], cg.gclose[j]);
-    for (int c = 0; c < 256; ++c) mask8[c] = (uint8_t)cg.mask[c];
-  }
-  int64_t* d_fprefix = nullptr;
-  int32_t *d_spans = nullptr, *d_counts = nullptr;
-  int64_t* d_tot2 = nullptr;   // (kept rows, findall's spans: one copy to the host)
-  uint8_t* d_mask = nullptr;
-  HIP_TRY(scratch_alloc((void**)&d_fprefix, sizeof(int64_t) * (n + 1), s));
-  HIP_TRY(scratch_alloc((void**)&d_counts, sizeof(int32_t) * n, s));
-  HIP_TRY(scratch_alloc((void**)&d_tot2, 2 * sizeof(int64_t), s));
-  if (chain) {
-    HIP_TRY(scratch_alloc((void**)&d_mask, 256, s));
-    HIP_TRY(hipMemcpyAsync(d_mask, mask8, 256, hipMemcpyHostToDevice, s));   // (pageable source: copied before the call returns)
-  }
-  int64_t cap = in_bytes / 8 + n + 64;
-  if (const int64_t seen = h->sub_matches_per_kib.load(std::memory_order_relaxed); seen > 128) {
-    const int64_t by_hint = (in_bytes >> 10) * (seen + seen / 8 + 1) + n + 64;
-    if (by_hint > cap) cap = by_hint < in_bytes + n + 64 ? by_hint : in_bytes + n + 64;
-  }
-  int64_t h2[2] = {0, 0};
-  const int64_t waves = (n + (kBlock / 64) - 1) / (kBlock / 64);
-  const unsigned grid = (unsigned)(waves < grid_cap() ? waves : grid_cap());
-  for (int attempt = 0; attempt < 2; ++attempt) {
-    HIP_TRY(scratch_alloc((void**)&d_spans, sizeof(int32_t) * 2 * (size_t)cap, s));
-    if (int rc = run_findall(h, lay, n, d_fprefix, d_spans, cap, nullptr, s, /*match_next_sequence=*/true, in_bytes, max_len))
-      return rc;
-    if (int rc = capall_counts_to_prefix(lay, n, d_fprefix, count, d_counts, d_prefix, d_tot2, s)) return rc;
-    // (the rows behind the spans without waiting: when the spans did not fit, the kernels return at once)
-    if (!chain) {
-      hipLaunchKernelGGL(k_capall_fixed, dim3(grid), dim3(kBlock), 0, s, h->hp.dev, n, d_fprefix, d_spans, cap, d_prefix,
-                         d_groups, match_cap);
-      g_last_kernel = "k_capall_fixed";
-    } else if (max_len <= 2048) {
-      hipLaunchKernelGGL(k_capall_chain<2048>, dim3(grid), dim3(kBlock), 0, s, cc, n, lay.data, lay.offsets, d_fprefix,
-                         d_spans, cap, d_mask, d_prefix, d_groups, match_cap);
-      g_last_kernel = "k_capall_chain";
-    } else {
-      hipLaunchKernelGGL(k_capall_chain<4096>, dim3(grid), dim3(kBlock), 0, s, cc, n, lay.data, lay.offsets, d_fprefix,
-                         d_spans, cap, d_mask, d_prefix, d_groups, match_cap);
-      g_last_kernel = "k_capall_chain";
-    }
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(d_tot2 + 1, d_fprefix + n, sizeof(int64_t), hipMemcpyDeviceToDevice, s));
-    HIP_TRY(hipMemcpyAsync(h2, d_tot2, sizeof h2, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    h->sub_matches_per_kib.store(in_bytes >= 1024 ? h2[1] / (in_bytes >> 10) : 0, std::memory_order_relaxed);
-    if (h2[1] <= cap) break;
-    if (attempt == 1) return fail(MRX_E_NO_DEVICE, "captures_all: match count changed between two passes");
-    cap = h2[1];   // more matches than the first guess: once more with room for all of them (behind the first attempt's)
-  }
-  *total = h2[0];
-  if (h2[0] > match_cap) return fail(MRX_E_CAPACITY, "group rows buffer too small: need " + std::to_string(h2[0]));
-  return MRX_OK;
-}
-
-// (mrx_internal.hpp) what captures_all refuses, for the calls that put it in front of their own work (expand)
-int mrx::captures_all_refusal(const mrx_handle* h) {
-  // the groups sub() reads for a template such as "\\1": the general form unless the pattern has the fixed-width one
-  if (h->hp.fixed_total < 0) {
-    if (!h->hp.bt.ok)
-      return fail(MRX_E_UNSUPPORTED,
-                  "sub() with \\1..\\9 on this pattern uses NFAEngine.match_next_with_groups (recursive "
-                  "backtracking matcher, nfa.mojo:500-574); its flat-program form does not cover: " +
-                      (h->hp.bt.why_not.empty() ? std::string("'.*'") : h->hp.bt.why_not));
-  } else if (int rc = check_search_supported(h)) {
-    return rc;
-  }
-  return check_lds(h);
-}
-
-static int captures_all_any(const mrx_handle* h, int64_t count, const Layout& lay_in, int64_t n, int64_t* d_prefix,
-                            int32_t* d_groups, int64_t match_cap, int64_t* total, void* st, int64_t known_bytes = -1,
-                            int64_t known_max = -1) {
-  ScratchScope scratch_scope_((hipStream_t)st);
-  if (!h) return fail(MRX_E_ARGUMENT, "null handle");
-  if (!total) return fail(MRX_E_ARGUMENT, "null total");
-  *total = 0;
-  if (n < 0) return fail(MRX_E_ARGUMENT, "negative batch size");
-  if (count < 0) return fail(MRX_E_ARGUMENT, "negative count");
-  if (match_cap < 0) return fail(MRX_E_ARGUMENT, "negative match_cap");
-  if (!d_prefix || (!d_groups && match_cap > 0)) return fail(MRX_E_ARGUMENT, "null output buffer");
-  if ((!lay_in.data && n > 0) || (!lay_in.offsets && lay_in.stride <= 0)) return fail(MRX_E_ARGUMENT, "null batch");
-  if (int rc = mrx::captures_all_refusal(h)) return rc;
-  const bool general = h->hp.fixed_total < 0;
-  if (int rc = ensure_device(h)) return rc;
-  hipStream_t s = (hipStream_t)st;
-  const int64_t* off = lay_in.offsets;
-  const uint32_t sfl = h->hp.dev.flags;
-  // (the spans routes take CSR batches; a chain batch with a text beyond the tile comes back for route 3)
-  const CapallRoute route = n > 0 && off ? capall_route(h, g_force_generic) : CAPALL_GENERAL;
-  if (route == CAPALL_CHAIN) {
-    const int rc = capall_from_spans(h, csr(lay_in.data, off), n, count, true, d_prefix, d_groups,
-                                     match_cap, total, s, known_bytes, known_max);
-    if (rc != kSubsRetryGeneric) return rc;
-  }
-  if (route == CAPALL_FIXED)
-    return capall_from_spans(h, csr(lay_in.data, off), n, count, false, d_prefix, d_groups, match_cap,
-                             total, s, known_bytes, known_max);
-  // route 3: sub_text()'s loop, a lane per text
-  Layout lay = lay_in;
-  if ((sfl & PF_BT_SEARCH) || general) {
-    const Layout plain = lay;
-    if (int rc = bt_prepass(h, plain, n, s, &lay)) return rc;
-  }
-  const bool use_bt = plan_uses_backtracker(h) || general;
-  int32_t* d_counts = nullptr;
-  int64_t* d_total = nullptr;
-  HIP_TRY(scratch_alloc((void**)&d_counts, sizeof(int32_t) * (n > 0 ? n : 1), s));
-  HIP_TRY(scratch_alloc((void**)&d_total, sizeof(int64_t), s));
-  if (n > 0) {
-    ScanTimer tm(s);
-#define MRX_L(B) hipLaunchKernelGGL((k_capall<CA_COUNT, B>), dim3(grid_for(n, kBlock)), dim3(kBlock), lds_for(h), s, h->hp.dev, \
-                                   H_BLOB(h), lay, n, general ? 1 : 0, (long long)count, d_counts, (const int64_t*)nullptr,    \
-                                   (int32_t*)nullptr, (int64_t)0)
-    MRX_BT_DISPATCH(bt_kernel_kind(h, use_bt), MRX_L);
-#undef MRX_L
-    g_last_kernel = "k_capall_count";
-    HIP_TRY(hipGetLastError());
-    tm.stop();
-  }
-  if (int rc = device_scan<int32_t>(d_counts, n, d_prefix, d_total, s)) return rc;
-  if (n > 0 && match_cap > 0) {   // (enqueued before the total is known: rows at or beyond match_cap are not written)
-#define MRX_L(B) hipLaunchKernelGGL((k_capall<CA_EMIT, B>), dim3(grid_for(n, kBlock)), dim3(kBlock), lds_for(h), s, h->hp.dev, \
-                                   H_BLOB(h), lay, n, general ? 1 : 0, (long long)count, (int32_t*)nullptr, d_prefix,        \
-                                   d_groups, match_cap)
-    MRX_BT_DISPATCH(bt_kernel_kind(h, use_bt), MRX_L);
-#undef MRX_L
-    g_last_kernel = "k_capall_emit";
-    HIP_TRY(hipGetLastError());
-  }
-  int64_t tot = 0;
-  HIP_TRY(hipMemcpyAsync(&tot, d_total, sizeof tot, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  *total = tot;
-  if (tot > match_cap) return fail(MRX_E_CAPACITY, "group rows buffer too small: need " + std::to_string(tot));
-  return MRX_OK;
-}
-
-extern "C" {
-int mrx_captures_all_dev(const mrx_handle* h, const uint8_t* d, const int64_t* off, int64_t n, int64_t count,
-                         int64_t* d_match_prefix, int32_t* d_groups, int64_t match_cap, int64_t* total, void* st) {
-  const TextBatch b = csr(d, off);
-  if (int rc = check_batch(b, BATCH_CSR)) return rc;
-  return captures_all_any(h, count, b, n, d_match_prefix, d_groups, match_cap, total, st);
-}
-// Texts at a fixed pitch, as mrx_sub_strided_dev: rows without padding are a CSR batch (offsets i * stride written on the
-// device) and take every route; padded rows take the lane-per-text kernels.
-int mrx_captures_all_strided_dev(const mrx_handle* h, const uint8_t* d, int64_t stride, const int32_t* d_lens, int32_t len,
-                                 int64_t n, int64_t count, int64_t* d_match_prefix, int32_t* d_groups, int64_t match_cap,
-                                 int64_t* total, void* st) {
-  const TextBatch b = strided(d, stride, d_lens, len);
-  if (int rc = check_batch(b, BATCH_PITCH_TERSE)) return rc;
-  if (h && total && n > 0 && count >= 0 && !d_lens && (int64_t)len == stride) {
-    ScratchScope scope_((hipStream_t)st);
-    int64_t* d_off = nullptr;
-    HIP_TRY(scratch_alloc((void**)&d_off, sizeof(int64_t) * (n + 1), (hipStream_t)st));
-    hipLaunchKernelGGL(k_pitch_offsets, dim3(grid_for(n + 1, kBlock)), dim3(kBlock), 0, (hipStream_t)st, n, stride, d_off);
-    HIP_TRY(hipGetLastError());
-    return captures_all_any(h, count, csr(d, d_off), n, d_match_prefix, d_groups, match_cap, total, st,
-                            n * stride, stride);
-  }
-  return captures_all_any(h, count, b, n, d_match_prefix, d_groups, match_cap,
-                          total, st);
-}
-int mrx_captures_all_batch(const mrx_handle* h, const uint8_t* data, const int64_t* off, int64_t n, int64_t count,
-                           int64_t* match_prefix, int32_t* groups, int64_t match_cap, int64_t* total) {
-  if (!h || !total || !match_prefix || (!groups && match_cap > 0)) return fail(MRX_E_ARGUMENT, "null argument");
-  if (match_cap < 0) return fail(MRX_E_ARGUMENT, "negative match_cap");
-  DevBatch b; DevBuf<int64_t> pre; DevBuf<int32_t> gr;
-  if (int rc = b.upload(data, off, n)) return rc;
-  if (int rc = pre.alloc(n + 1)) return rc;
-  const size_t per = (size_t)(mrx_num_groups(h) + 1) * 2;
-  if (int rc = gr.alloc(per * (size_t)match_cap)) return rc;
-  int64_t tot = 0;
-  const int rc = mrx_captures_all_dev(h, b.data, b.offsets, n, count, pre.p, gr.p, match_cap, &tot, nullptr);
-  *total = tot;
-  if (rc != MRX_OK && rc != MRX_E_CAPACITY) return rc;
-  HIP_TRY(hipMemcpy(match_prefix, pre.p, sizeof(int64_t) * (n + 1), hipMemcpyDeviceToHost));
-  if (rc == MRX_OK && tot > 0) HIP_TRY(hipMemcpy(groups, gr.p, sizeof(int32_t) * per * (size_t)tot, hipMemcpyDeviceToHost));
-  return rc;
-}
-}  // extern "C"
-
-extern "C" {
 // ---- host-buffer wrappers -----------------------------------------------------------
 
 int mrx_match_first_batch(const mrx_handle* h, const uint8_t* data, const int64_t* off, int64_t n,
@@ -8259,20 +6233,6 @@ int mrx_findall_batch(const mrx_handle* h, const uint8_t* data, const int64_t* o
     HIP_TRY(hipMemcpy(spans, sp.p, sizeof(int32_t) * 2 * tot, hipMemcpyDeviceToHost));
   return rc;
 }
-int mrx_split_batch(const mrx_handle* h, const uint8_t* data, const int64_t* off, int64_t n, int64_t maxsplit,
-                    int64_t* piece_prefix, int32_t* pieces, int64_t piece_cap, int64_t* total) {
-  DevBatch b; DevBuf<int64_t> pre; DevBuf<int32_t> pc;
-  if (int rc = b.upload(data, off, n)) return rc;
-  if (int rc = pre.alloc(n + 1)) return rc;
-  if (int rc = pc.alloc(2 * (size_t)(piece_cap > 0 ? piece_cap : 1))) return rc;
-  int64_t tot = 0;
-  const int rc = mrx_split_dev(h, b.data, b.offsets, n, maxsplit, pre.p, pc.p, piece_cap, &tot, nullptr);
-  if (total) *total = tot;
-  if (rc != MRX_OK) return rc;
-  HIP_TRY(hipMemcpy(piece_prefix, pre.p, sizeof(int64_t) * (n + 1), hipMemcpyDeviceToHost));
-  if (tot > 0) HIP_TRY(hipMemcpy(pieces, pc.p, sizeof(int32_t) * 2 * tot, hipMemcpyDeviceToHost));
-  return MRX_OK;
-}
 int mrx_captures_batch(const mrx_handle* h, const uint8_t* data, const int64_t* off, int64_t n,
                        int32_t* spans) {
   DevBatch b; DevBuf<int32_t> sp;
@@ -8282,22 +6242,6 @@ int mrx_captures_batch(const mrx_handle* h, const uint8_t* data, const int64_t* 
   if (int rc = mrx_captures_dev(h, b.data, b.offsets, n, sp.p, nullptr)) return rc;
   HIP_TRY(hipMemcpy(spans, sp.p, sizeof(int32_t) * per * n, hipMemcpyDeviceToHost));
   return MRX_OK;
-}
-int mrx_sub_batch(const mrx_handle* h, const char* repl, size_t repl_len, int64_t count,
-                  const uint8_t* data, const int64_t* off, int64_t n, int64_t* out_offsets,
-                  uint8_t* out_data, int64_t out_cap, int64_t* total_bytes) {
-  DevBatch b; DevBuf<int64_t> oo; DevBuf<uint8_t> od;
-  if (int rc = b.upload(data, off, n)) return rc;
-  if (int rc = oo.alloc(n + 1)) return rc;
-  if (int rc = od.alloc((size_t)out_cap)) return rc;
-  int64_t tot = 0;
-  const int rc = mrx_sub_dev(h, repl, repl_len, count, b.data, b.offsets, n, oo.p, od.p, out_cap,
-                             &tot, nullptr);
-  if (total_bytes) *total_bytes = tot;
-  if (rc != MRX_OK && rc != MRX_E_CAPACITY) return rc;
-  HIP_TRY(hipMemcpy(out_offsets, oo.p, sizeof(int64_t) * (n + 1), hipMemcpyDeviceToHost));
-  if (rc == MRX_OK && tot > 0) HIP_TRY(hipMemcpy(out_data, od.p, (size_t)tot, hipMemcpyDeviceToHost));
-  return rc;
 }
 
 void mrx_timing_reset(void) { g_scan_ms = 0; g_scan_launches = 0; }
@@ -8349,14 +6293,12 @@ void mrx_debug_dynamic_texts(int mode) { g_dyn_mode = mode < 0 ? 0 : mode > 2 ? 
 void mrx_debug_split_findall(int on) { g_split_findall = on ? 1 : 0; }
 void mrx_debug_dense_rows(int mode) { g_dense_rows = mode; }
 void mrx_debug_tries_always(int on) { g_tries_always = on ? 1 : 0; }
-void mrx_debug_chain_sub_general(int on) { g_chain_sub_general = on ? 1 : 0; }
 int mrx_testing_emptywalk_findall(const mrx_handle* h, const uint8_t* text, int len, int32_t* spans, int cap) {
   if (!h || !h->hp.ew2_ok || len < 0) return -1;
   const std::vector<std::pair<int, int>> v = emptywalk2_run(h->hp.ew2, text, len);
   for (size_t k = 0; k < v.size() && (int)k < cap; ++k) { spans[2 * k] = v[k].first; spans[2 * k + 1] = v[k].second; }
   return (int)v.size();
 }
-void mrx_debug_subs_group(int g) { g_subs_group = (g == 0 || g == 16 || g == 32 || g == 64 || g == 256) ? g : -1; }
 void mrx_debug_litscan_pieces(int mode) { g_litscan_pieces = (mode == 0 || mode == 1) ? mode : 2; }
 void mrx_debug_multiwalk(int mode) { g_mwalk_mode = mode == 2 ? 2 : 0; g_mwalk_pk = mode == 3 ? 0 : 1; }
 void mrx_release_scratch(void) { scratch_release_all(); }

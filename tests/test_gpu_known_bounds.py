@@ -30,23 +30,24 @@ CORPORA = {"base": CC.BASE, "short": CC.SHORT}
 CONSUMER = {c.name: c for c in CC.CONSUMERS}
 
 # The limits with which the host code compares max_text_len (the value just above each is passed where it is a legal
-# bound).  Line numbers are those of mojo_regex_amd/csrc at the time of writing.
+# bound).  The core's limits are named by function and constant (mrx_kernels.hip, mrx_sub.hip, mrx_capall.hip); line
+# numbers elsewhere are those of mojo_regex_amd/csrc at the time of writing.
 FINDALL_MAX = (
     1024,     # mrx_stream_bits.hip:425   stream_bits_eligible: max_len > 1024 (fixed pitch only; a CSR batch must not care)
-    2048,     # mrx_kernels.hip:5369      pieces_prepare: the piece size C is at least 2048, C >= max_len cuts nothing
-    4095,     # mrx_kernels.hip:5355      pieces_prepare: max_len < 4096, nothing long enough to cut
-    65300,    # mrx_kernels.hip:1798/5844 rec32 = max_text <= kRec32MaxLen: 16-bit positions in the event records
-)             # (mrx_kernels.hip:5846 dyn: 1 << kDynShift and :5163 kStreamMaxText = 1 << 26 lie above 65537 and size scratch)
+    2048,     # pieces_prepare            the piece size C is at least 2048, C >= max_len cuts nothing
+    4095,     # pieces_prepare            max_len < 4096, nothing long enough to cut
+    65300,    # kRec32MaxLen              FindallJob's rec32 = max_text <= kRec32MaxLen: 16-bit positions in the event records
+)             # (FindallJob's dyn: 1 << kDynShift and kStreamMaxText = 1 << 26 lie above 65537 and size scratch)
 SUB_MAX = FINDALL_MAX + (
-    2048,     # mrx_kernels.hip:6984/7013/7989  the group-template forms: tiles of 2048 or 4096 positions
-    4096,     # mrx_kernels.hip:6919/7952       max_len > 4096: beyond the tile, the generic form
+    2048,     # sub_chain_from_spans' and capall_from_spans' tile: the group-template forms take 2048 or 4096 positions
+    4096,     # sub_chain_from_spans, capall_from_spans: max_len > 4096 is beyond the tile, the generic form
 )
 SET_SUB_MAX = FINDALL_MAX + (
     1472,     # mrx_set.hip:1093          the window W = min(kSetSubMaxW = 1536, longest + 1 rounded up to 64)
 )
 FILTER_MAX = (
     4096,     # mrx_filter.hip:55/161     kFilterTextMax: the text form of the byte mover up to here, the block form above
-    4095,     # mrx_kernels.hip:5355      the search in front of it: pieces_prepare as findall
+    4095,     # pieces_prepare            the search in front of it, as findall
 )
 MOVER_MAX = (4096,)   # mrx_filter.hip:161 alone: dict filter (mrx_lookup.hip:276), take (mrx_sort.hip:384), distinct (mrx_distinct.hip:331)
 SORT_MAX = (

@@ -1,4 +1,5 @@
-"""The planner's flag families that the stepper's route decision (FindallJob::choose_route, csrc/mrx_kernels.hip) relies on,
+"""The planner's flag families that the stepper's route decision (FindallJob::choose_route in csrc/mrx_kernels.hip, the
+core that sub, captures_all and split reach through csrc/mrx_core.hpp) relies on,
 checked without a GPU on the route cases' patterns, the parity corpus, the empty-match, bitset and '$' lists and the
 reference's benchmark patterns: which flags never meet on one plan."""
 import os

@@ -2,20 +2,18 @@
 # Ablation of the streaming scan kernel on the real bench workload: builds variants of
 # libmrx_hip.so with pieces of k_stream_findall switched off (MRX_ABLATE, see mrx_kernels.hip)
 # and prints the scan kernel's time for each.  Variant results are wrong by design; only the
-# timings mean anything.  Build here (cross-compile), run on the GPU box:
-#   tools/ablate.sh build            (in the container)
-#   gpurun -- tools/ablate.sh run    (on the box)
+# timings mean anything.
+#   tools/ablate.sh build    (cross-compiles: no GPU needed)
+#   tools/ablate.sh run      (on a machine with the GPU)
 R=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$R/tools/ablate_libs
 VARIANTS="0 1 2 3 4 5 7 16 18 23"
 if [ "$1" = build ]; then
   mkdir -p $OUT
-  for v in $VARIANTS; do
-    (cd $R/mojo_regex_amd/csrc && /opt/rocm/bin/hipcc -O3 --offload-arch=gfx950 -std=c++17 -fPIC -shared \
-      -Wno-unused-function -DMRX_ABLATE=$v -o $OUT/libmrx_hip_$v.so mrx_frontend.cpp mrx_analysis.cpp \
-      mrx_dfa_build.cpp mrx_nfa_build.cpp mrx_plan.cpp mrx_kernels.hip) &
+  for v in $VARIANTS; do   # (one after the other: build_library compiles a variant's units a few at a time)
+    (cd $R && python3 -c 'import sys, __graft_entry__ as g; g.build_library(extra_flags=sys.argv[2:], out=sys.argv[1])' \
+      $OUT/libmrx_hip_$v.so -DMRX_ABLATE=$v) || exit 1
   done
-  wait
   ls -la $OUT
 else
   for v in $VARIANTS; do

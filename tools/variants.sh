@@ -1,18 +1,16 @@
 #!/bin/bash
 # Build variants of libmrx_hip.so with extra -D flags and time the bench step with each.
-#   VARIANTS="base: b16:-DMRX_DECODE_BATCH=16" tools/variants.sh build     (in the container)
-#   gpurun -- tools/variants.sh run                                          (on the box)
+#   VARIANTS="base: b16:-DMRX_DECODE_BATCH=16" tools/variants.sh build     (cross-compiles: no GPU needed)
+#   tools/variants.sh run                                                    (on a machine with the GPU)
 R=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$R/tools/variant_libs
 if [ "$1" = build ]; then
   rm -rf $OUT; mkdir -p $OUT
-  for v in $VARIANTS; do
+  for v in $VARIANTS; do   # (one after the other: build_library compiles a variant's units a few at a time)
     name=${v%%:*}; flags=${v#*:}; flags=${flags//,/ }
-    (cd $R/mojo_regex_amd/csrc && /opt/rocm/bin/hipcc -O3 --offload-arch=gfx950 -std=c++17 -fPIC -shared \
-      -Wno-unused-function $flags -o $OUT/libmrx_hip_$name.so mrx_frontend.cpp mrx_analysis.cpp \
-      mrx_dfa_build.cpp mrx_nfa_build.cpp mrx_plan.cpp mrx_kernels.hip) &
+    (cd $R && python3 -c 'import sys, __graft_entry__ as g; g.build_library(extra_flags=sys.argv[2:], out=sys.argv[1])' \
+      $OUT/libmrx_hip_$name.so $flags) || exit 1
   done
-  wait
   ls -la $OUT
 elif [ "$1" = cmd ]; then
   # tools/variants.sh cmd <command...>: run the command once per variant with MRX_LIB set
